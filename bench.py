@@ -15,7 +15,10 @@ ranks itself (a child `python -m torch.distributed.run`, never an exec; the pare
 GPU), relays rank 0's JSON line and exits with the children's status.  Under an external torchrun
 (WORLD_SIZE set) the process is a rank.
 
-Prints ONE JSON line (see the driver contract): metric trajectories/sec, plus
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, runs W untimed and K timed steps, optionally
+writes the last timed step's results (`--dump-outputs DIR`, below) and prints ONE JSON line (see the driver contract):
+metric trajectories/sec (`value`), `ms_per_step`, iteration and status counts of the batch.  Everything else is measured
+only with `--full`, after the timed steps and outside them:
   roofline      -- whole Gauss-Newton pass (linearize + assemble + solve; the finish of a step is part of the next
                    linearization for fixed-base arms, a kernel of its own otherwise), SURVEY.md 8(d)'s
                    638 048 algorithmic bytes per trajectory-iteration / the summed average launch
@@ -25,7 +28,14 @@ Prints ONE JSON line (see the driver contract): metric trajectories/sec, plus
                    time vs the fp64 matrix peak; per-kernel averages next to it
   cpu_baseline  -- the CPU oracle (a port of the reference algorithm; the reference itself needs
                    GTSAM and cannot be built here) timed on this box's host cores on a bounded
-                   sample: all host threads, and a single thread (what the reference is)
+                   sample: all host threads, and a single thread (what the reference is), parity-gated against
+                   the GPU results of the same restarts
+  pcie_inclusive_value, variants (LM / Dogleg on the same restarts), windows (BASELINE config 4 beside the headline)
+
+--dump-outputs DIR writes what the timed path returned in its last step -- traj, iters, status and final_error, the
+per-trajectory results gpmp2mi_plan_get_result hands a caller, over the whole (gathered) batch -- as DIR/<name>.npy in
+float64 (not the error trace: its entries past a trajectory's last iteration are NaN by contract).  The inputs are generated from fixed seeds, so two builds run with the same arguments can be compared output
+for output.  Above 64 MB in all, a fixed, seeded sample of trajectories is written instead (DIR/sample_index.npy).
 """
 from __future__ import annotations
 
@@ -59,10 +69,18 @@ def parse(argv=None):
     ap.add_argument("--workload", default="restarts", choices=["restarts", "windows"],
                     help="restarts = BASELINE config 3 (default, the metric's config); windows = config 4 "
                          "(receding-horizon windows warm-started from the solved trajectory, 3 fixed GN iterations)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the LM / Dogleg sub-results")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="restarts in the CPU sample (0 = auto)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event sampling and the roofline, "
+                         "the host-buffer rate, the LM / Dogleg variants, the config-4 windows, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the LM / Dogleg and windows sub-results")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="with --full: restarts in the CPU sample (0 = auto)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher
@@ -203,6 +221,23 @@ def pmc_traffic():
     return None, None, None, None
 
 
+def dump_outputs(directory, arrays, limit=64_000_000, seed=0):
+    """Writes every per-trajectory array (leading dimension = the batch) as DIR/<name>.npy in float64.  When they
+    would exceed `limit` bytes together, the same fixed, seeded sample of trajectories is taken from each and its
+    indices are written as DIR/sample_index.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row = sum(a.nbytes for a in arrays.values()) // n
+    if n * row > limit:
+        keep = max(1, (limit - 4096) // (row + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def status_hist(status):
     return {STATUS_NAMES.get(int(k), str(int(k))): int(v) for k, v in zip(*np.unique(status, return_counts=True))}
 
@@ -325,7 +360,7 @@ def main():
         return float(every[:, 0].max()), [float(x) for x in every[:, 0]], float(every[:, 1].max())
 
     step, gather_events = make_step(plan, out_traj, gathered, B)
-    dt_local, kern, sampled = timed_region(plan, step, args.steps, args.warmup)
+    dt_local, kern, sampled = timed_region(plan, step, args.steps, args.warmup, events=args.full)
     dt, rank_dts, gather_ms = over_ranks(dt_local, gather_events)
     iters, status, ferr = plan.result_counts()
     passes_local = int(np.sum(iters + 1))                 # linearize+solve passes per step on this rank
@@ -339,10 +374,19 @@ def main():
     else:
         passes_all, hist_all, it_all = passes_local, hist_local, iters
 
+    if args.dump_outputs:       # what the last timed step returned, over the whole batch (every rank joins the gather)
+        res = plan.result()
+        fields = {k: res[k] for k in ("traj", "iters", "status", "final_error")}
+        if world > 1:
+            fields = {k: sharding.gather_results(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(cdev),
+                                                 B * world).cpu().numpy() for k, v in fields.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, fields)
+
     # the boundary handing over HOST buffers (gpmp2mi_plan_set_problem / get_result): same work plus the
     # PCIe copies, reported next to `value`, never as `value`
     host_rate = None
-    if world == 1:
+    if world == 1 and args.full:
         plan.enable_timing(False)
         h_in = [np.ascontiguousarray(a[lo:hi]) for a in (p.start_conf, p.start_vel, p.end_conf, p.end_vel, p.init)]
         reps = max(3, min(args.steps, 10))
@@ -359,7 +403,7 @@ def main():
     # LM / Dogleg on the same restarts (the optimizers the reference's WAM scripts use), measured in the same
     # run OUTSIDE the timed Gauss-Newton region
     variants = None
-    if world == 1 and args.workload == "restarts" and args.opt == "GN" and not args.no_variants:
+    if world == 1 and args.full and args.workload == "restarts" and args.opt == "GN" and not args.no_variants:
         variants = {}
         for opt in ("LM", "DOGLEG"):
             pv = problems.wam_restarts(B=B, opt=opt)
@@ -383,7 +427,7 @@ def main():
     # windows per GPU, warm-started from the solved restart-0 trajectory, 3 fixed Gauss-Newton iterations, the final
     # gather inside the timed step; measured in the same run OUTSIDE the timed region of `value`.
     windows = None
-    if args.workload == "restarts" and args.opt == "GN" and not args.no_variants:
+    if args.full and args.workload == "restarts" and args.opt == "GN" and not args.no_variants:
         WB = int(os.environ.get("GPMP2MI_BENCH_WINDOWS", "128"))
         base = problems.wam_restarts(B=1, opt="GN")
         sol = eng.batch_optimize(r, s, base.setting, base.start_conf, base.start_vel, base.end_conf, base.end_vel,
@@ -483,7 +527,9 @@ def main():
                    rolled_back_share=float(hist.get("rolled_back", 0)) / max(n_all, 1),
                    status_note=("rolled_back = the last iteration increased the error, so gpmp2::optimize returns the values "
                                 "before it (planner/BatchTrajOptimizer.cpp:297-307); iters-to-tol counts that last iteration"),
-                   roofline=roof)
+                   full=args.full)
+        if args.full:
+            out["roofline"] = roof
         if host_rate is not None:
             out["pcie_inclusive_value"] = host_rate
         if variants:
@@ -493,7 +539,7 @@ def main():
         out["rank_ms_per_step"] = [x / args.steps * 1e3 for x in rank_dts]
         out["rank_ms_spread"] = (max(rank_dts) - min(rank_dts)) / args.steps * 1e3
         out["gather_ms_per_step"] = gather_ms
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             threads = max(1, min(os.cpu_count() or 1, 64))
             sample = args.cpu_sample or min(B, max(8, threads))
             sample = min(sample, 256)

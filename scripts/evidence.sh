@@ -8,15 +8,15 @@ mkdir -p $O
 export TMPDIR=/tmp
 source scripts/lib_run.sh
 COMMIT=$(cat .evidence_commit 2>/dev/null || echo unknown)
-BENCH="python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-variants"
-timeout -k 10 500 python3 bench.py > $O/${R}_bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+BENCH="python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-variants"
+timeout -k 10 500 python3 bench.py --full > $O/${R}_bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 tail -c 400 $O/${R}_bench.json; echo
 if [ "$2" != "quick" ]; then
-timeout -k 10 200 python3 bench.py --batch 1024 --steps 10 --no-cpu-baseline --no-variants > $O/${R}_bench_b1024.json 2>> $O/bench.err || exit 1
+timeout -k 10 200 python3 bench.py --batch 1024 --steps 10 --full --no-cpu-baseline --no-variants > $O/${R}_bench_b1024.json 2>> $O/bench.err || exit 1
 # config 4 with its CPU leg: every sampled window is compared with the oracle before the timing counts
-timeout -k 10 300 python3 bench.py --workload windows --batch 128 --cpu-sample 128 > $O/${R}_bench_windows128.json 2>> $O/bench.err || exit 1
-timeout -k 10 200 python3 bench.py --opt LM --steps 10 --no-cpu-baseline > $O/${R}_bench_lm.json 2>> $O/bench.err || exit 1
-timeout -k 10 200 python3 bench.py --opt DOGLEG --steps 10 --no-cpu-baseline > $O/${R}_bench_dogleg.json 2>> $O/bench.err || exit 1
+timeout -k 10 300 python3 bench.py --workload windows --batch 128 --full --cpu-sample 128 > $O/${R}_bench_windows128.json 2>> $O/bench.err || exit 1
+timeout -k 10 200 python3 bench.py --opt LM --steps 10 --full --no-cpu-baseline > $O/${R}_bench_lm.json 2>> $O/bench.err || exit 1
+timeout -k 10 200 python3 bench.py --opt DOGLEG --steps 10 --full --no-cpu-baseline > $O/${R}_bench_dogleg.json 2>> $O/bench.err || exit 1
 echo "bench lines done"
 fi
 run ks 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- $BENCH || exit 1
@@ -30,7 +30,7 @@ run sq_b 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS 
 run sq_c 300 rocprofv3 --pmc SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_LDS_IDX_ACTIVE --output-format csv -d $O/sq_c -o c -- $BENCH && SQ="$SQ $O/sq_c"
 [ -n "$SQ" ] && python3 scripts/pmc_sq_to_json.py $O/${R}_pmc_sq.json $SQ
 if [ "$2" != "quick" ]; then
-B1K="python3 bench.py --batch 1024 --steps 3 --warmup 1 --no-cpu-baseline --no-variants"
+B1K="python3 bench.py --batch 1024 --steps 3 --warmup 1 --full --no-cpu-baseline --no-variants"
 SQ=""
 run sq_a_b1024 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU --output-format csv -d $O/sq_a_b1024 -o a -- $B1K && SQ="$O/sq_a_b1024"
 run ks_b1024 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_b1024 -o ks -- $B1K || exit 1

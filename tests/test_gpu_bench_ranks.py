@@ -21,7 +21,7 @@ def test_bench_spawns_its_ranks_and_gathers_the_hip_results(engine, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(GPMP2MI_BENCH_REHEARSAL="1", GPMP2MI_BENCH_DUMP=dump, OMP_NUM_THREADS="2", GPMP2MI_BENCH_WINDOWS="6")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "4", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          "--batch", "4", "--full", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
