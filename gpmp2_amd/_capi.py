@@ -67,6 +67,20 @@ class GraphOpts(C.Structure):
                 ("self_collision", (C.c_double * 4) * MAX_SELF_COLLISION_PAIRS)]
 
 
+class DebugForms(C.Structure):
+    """gpmp2mi_debug_forms (include/gpmp2mi_debug.h): kernel forms forced on a plan; all zero = the plan's own choice."""
+    _fields_ = [("lin_split", C.c_int), ("no_fused_finish", C.c_int), ("generic_gn", C.c_int), ("wide_dense", C.c_int),
+                ("fail_alloc_at", C.c_int)]
+
+
+def make_debug_forms(forms):
+    """DebugForms from a dict such as {"lin_split": 2}; an unknown name raises."""
+    unknown = set(forms) - {name for name, _ in DebugForms._fields_}
+    if unknown:
+        raise ValueError(f"unknown plan forms: {sorted(unknown)}")
+    return DebugForms(**{k: int(v) for k, v in forms.items()})
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

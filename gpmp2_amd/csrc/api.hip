@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/gpmp2mi_debug.h"
 #include "launch.h"
 #include "plan.h"
 
@@ -287,22 +288,76 @@ static void chunk_release(void* q, int device) {
 // live-resource counters for the lifetime tests (gpmp2mi_debug_resource_counts)
 static std::atomic<long> g_live_chunks{0}, g_live_flagbufs{0}, g_leaked_plans{0};
 
+// The kernel forms of a plan, chosen once at creation (choose_forms).  The int fields go to PlanParams (plan.h), where
+// the kernels read them; `dense` and `generic_gn` are host-only choices of the drivers in plan_run_impl.
+struct PlanForms {
+  int wide = 0, split_back = 0, wide_h0 = 2, lin_split = 1, fuse_finish = 0, spart_groups = 0;
+  bool dense = false;        // dense normal equations + cyclic reduction over dense blocks: dof 12..18, or forced for 8..11
+  bool generic_gn = false;   // forced: the plan's Gauss-Newton optimize runs through the trial-step driver
+  // Gauss-Newton takes the fast driver (3 launches per pass) on every plan that is not wide; a forced generic GN sends
+  // only the plan's own optimize through the trial-step driver, not plan_update
+  bool gn_fast(bool update) const { return !wide && (update || !generic_gn); }
+  // trial-step driver, LM / GN (Dogleg's step kernel does the whole back-substitution): k_finish_trial(_wide) finishes
+  // the step, or the trial linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
+  bool finish_trial(int opt) const { return split_back && opt != GPMP2MI_OPT_DOGLEG && !fuse_finish; }
+  bool trial_lin_steps(int opt) const { return fuse_finish && opt != GPMP2MI_OPT_DOGLEG; }
+};
+
+// The one place where a plan's forms are decided.  `force` (gpmp2mi_debug_plan_create, NULL: none) overrides the choice;
+// a forced form the plan cannot take is refused.
+static int choose_forms(const RobotDev& h, const gpmp2mi_settings& s, int B, const gpmp2mi_debug_forms* force,
+                        PlanForms* out) {
+  const gpmp2mi_debug_forms f = force ? *force : gpmp2mi_debug_forms{};
+  const int D = h.dof, N = s.total_step, I = s.obs_check_inter;
+  const bool fixed_arm = h.kind == GPMP2MI_ROBOT_ARM;
+  G2_CHECK(f.lin_split == 0 || f.lin_split == 1 || (fixed_arm && (f.lin_split == 2 || f.lin_split == 4)), GPMP2MI_ERR_UNSUPPORTED,
+           "forced lin_split: 1, or 2 / 4 on a fixed-base arm");
+  // (the four-wavefront form keeps the <= 24 states of a chunk in LDS: two or more sub-steps per interval)
+  G2_CHECK(f.lin_split != 4 || I >= 2, GPMP2MI_ERR_UNSUPPORTED, "forced lin_split 4: needs obs_check_inter >= 2");
+  PlanForms F;
+  F.wide = 2 * D > 15;
+  G2_CHECK(!f.wide_dense || F.wide, GPMP2MI_ERR_UNSUPPORTED, "forced wide_dense: the plan has no wide blocks (dof < 8)");
+  F.dense = D > 11 || f.wide_dense;
+  F.split_back = !F.dense && N >= 16;   // the finish kernels take groups of 8 blocks (levels 4, 2, 1)
+  // wide blocks: the first forward levels (2, 4) run chip-wide when they are not among the last two of the tree (up to
+  // level 8; 16 measured: see DESIGN)
+  while (F.wide && F.wide_h0 < 8 && 4 * F.wide_h0 <= N) F.wide_h0 *= 2;
+  // sphere-split linearization for fixed-base arms: four wavefronts per 64 points sharing one walk of the chain
+  // (k_linearize_arm), or two wavefronts that each walk it (k_linearize NSPLIT = 2).  Alone, the four-wavefront form wins
+  // up to 256 trajectories (round 3: 14.4 / 16.8 / 22.5 / 35.5 / 59.3 us against 17.6 / 18.7 / 24.2 / 35.6 / 58.1 us at
+  // 32 / 64 / 128 / 256 / 512); with the fused finish, which only it has, it wins the Gauss-Newton pass at every size
+  // (195.3 / 226.9 / 224.8 k against 193.4 / 225.1 / 218.6 k traj/s at 256 / 512 / 1 024), and the LM pass too, if barely
+  // (97.7 / 102.0 k against 96.6 / 101.3 k at 512 / 1 024).  So: Gauss-Newton and LM plans always, Dogleg plans (no fusion
+  // there) up to 256 trajectories.
+  const bool four = B <= 256 || s.opt_type != GPMP2MI_OPT_DOGLEG;
+  F.lin_split = (fixed_arm && h.nr_spheres >= 2) ? (four ? 4 : 2) : 1;
+  if (F.lin_split == 4 && I < 2) F.lin_split = 2;
+  if (f.lin_split) F.lin_split = f.lin_split;
+  // fused finish (k_linearize_arm applies the step: GN fast path, LM / GN trial steps); the trial-step shares then come
+  // per chunk of 64 of the 1 + N (I + 1) evaluation points instead of per group of 8 blocks (k_finish_trial)
+  F.fuse_finish = F.lin_split == 4 && F.split_back && !F.wide && !f.no_fused_finish;
+  F.spart_groups = F.fuse_finish ? (1 + N * (I + 1) + 63) / 64 : (N + 8) / 8;
+  F.generic_gn = f.generic_gn != 0;
+  *out = F;
+  return GPMP2MI_OK;
+}
+
 struct gpmp2mi_plan {
   const gpmp2mi_robot* robot = nullptr;
   const gpmp2mi_sdf* sdf = nullptr;
   PlanParams hp;
+  PlanForms forms;             // the kernel forms chosen at creation (choose_forms); hp carries the device-visible ones
   PlanBuffers pb;
   std::vector<void*> allocs;   // arena chunks (plan_alloc)
   std::vector<size_t> alloc_bytes;
   char* arena_cur = nullptr;   // bump pointer into the newest chunk
   size_t arena_left = 0;
-  int alloc_calls = 0;         // plan_alloc calls so far (GPMP2MI_FAIL_ALLOC_AT injects a failure at the k-th)
+  int alloc_calls = 0;         // plan_alloc calls so far
+  int fail_alloc_at = 0;       // gpmp2mi_debug_forms::fail_alloc_at: the k-th plan_alloc call fails (0: none)
   int device = -1;             // the device the plan was created on: its chunks / flags go back to that device's pools
   FlagBuf flagbuf;
   int* h_flags = nullptr;    // pinned + device-mapped [n_active_len]: per-pass active count, -1 = not yet known
   KernelTimer timer;
-  bool wide_dense = false;   // GPMP2MI_WIDE_DENSE=1: 8..11-dof plans through the dense block solver (A/B, fallback)
-  bool generic_gn = false;   // GPMP2MI_GENERIC_GN=1: run GaussNewton through the LM/Dogleg machinery
   int n_active_len = 0;
   std::vector<int> h_xp_n;   // host mirror of the extra-prior counts
   PlanExtras ex;             // extra factors carried as data (host copy of the specs + device workspace)
@@ -354,7 +409,7 @@ struct gpmp2mi_plan {
   }
 };
 
-static int plan_run(gpmp2mi_plan* p, hipStream_t st, const double* start);
+static int plan_run(gpmp2mi_plan* p, hipStream_t st, const double* start, bool update);
 
 // linearize `traj` into record buffer `bufsel` of every (active) trajectory: the fused obstacle / GP-prior kernel,
 // then -- only for plans that carry extra factors -- the workspace / self-collision factor kernels on the support
@@ -382,18 +437,13 @@ static int plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const
   return launch_extra_accumulate(P, p->pb, ex, L, S, bufsel, active, st);
 }
 
-// GPMP2MI_FAIL_ALLOC_AT=k (tests): the k-th plan_alloc call of every plan creation fails as if the device were out
-// of memory, so that the half-built plan's release path can be exercised
-static int fail_alloc_at() {
-  const char* e = getenv("GPMP2MI_FAIL_ALLOC_AT");
-  return e ? atoi(e) : 0;
-}
 template <class T>
 static int plan_alloc(gpmp2mi_plan* p, T** ptr, size_t count) {
   constexpr size_t ALIGN = 256, CHUNK = ARENA_CHUNK;
   const size_t bytes = (std::max<size_t>(count, 1) * sizeof(T) + ALIGN - 1) / ALIGN * ALIGN;
-  if (++p->alloc_calls == fail_alloc_at()) {
-    set_error("hipMalloc: injected failure (GPMP2MI_FAIL_ALLOC_AT)");
+  // fail_alloc_at (tests): fails as if the device were out of memory, so that the half-built plan's release path runs
+  if (++p->alloc_calls == p->fail_alloc_at) {
+    set_error("hipMalloc: injected failure (gpmp2mi_debug_forms::fail_alloc_at)");
     return GPMP2MI_ERR_ALLOC;
   }
   if (bytes > p->arena_left) {
@@ -984,7 +1034,13 @@ int gpmp2mi_block_tridiag_solve(int B, int nblk, int n, const double* Hd, const 
 
 // -------------------------------------------------------------------------------------------- plan
 int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const gpmp2mi_settings* s,
-                        const gpmp2mi_graph_opts* o_in, int B, gpmp2mi_plan** out) {
+                        const gpmp2mi_graph_opts* o, int B, gpmp2mi_plan** out) {
+  return gpmp2mi_debug_plan_create(robot, sdf, s, o, B, nullptr, out);
+}
+
+int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const gpmp2mi_settings* s,
+                              const gpmp2mi_graph_opts* o_in, int B, const gpmp2mi_debug_forms* forms,
+                              gpmp2mi_plan** out) {
   G2_CHECK(robot && sdf && s && out, GPMP2MI_ERR_INVALID, "null argument");
   *out = nullptr;
   gpmp2mi_graph_opts o;
@@ -1001,14 +1057,14 @@ int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, cons
   // fail inside optimize
   G2_CHECK(D <= 11 || D == 17 || D == 18, GPMP2MI_ERR_UNSUPPORTED,
            "plans are instantiated for dof <= 11 and for dof 17 / 18 (SE(2) base [+ lift] + two 7-joint arms)");
-  const bool wide = 2 * D > 15;  // blocks wider than one 16x16 tile: 2x2-tile cyclic reduction (dof <= 11)
-  const bool dense_only = D > 11; // 12 <= dof <= 18 (PR2): dense normal equations + cyclic reduction over dense blocks
+  PlanForms F;
+  G2_TRY(choose_forms(robot->h, *s, B, forms, &F));
   {
     // the assembler stages an interval with at most NLD2 16-B loads per lane (assembler.h: 6, 9 on the wide path)
     const int nd = D * (D + 1) / 2 + D + 1 + ((robot->h.base_dof == 3 && s->obs_check_inter > 0) ? 36 : 0);
     const int gpr = 2 * D + 1 + (robot->h.base_dof == 3 ? 18 : 0);
     const int nds = (nd + 1) & ~1, gps = (gpr + 1) & ~1;
-    G2_CHECK((s->obs_check_inter + 1) * nds + gps + 24 * s->obs_check_inter <= 2 * 64 * (dense_only ? 14 : wide ? 9 : 6), GPMP2MI_ERR_UNSUPPORTED,
+    G2_CHECK((s->obs_check_inter + 1) * nds + gps + 24 * s->obs_check_inter <= 2 * 64 * (D > 11 ? 14 : F.wide ? 9 : 6), GPMP2MI_ERR_UNSUPPORTED,
              "obs_check_inter too large for the staged assembly");
   }
   G2_CHECK(s->opt_type >= GPMP2MI_OPT_GAUSS_NEWTON && s->opt_type <= GPMP2MI_OPT_DOGLEG, GPMP2MI_ERR_INVALID,
@@ -1023,6 +1079,8 @@ int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, cons
   auto p = std::make_unique<gpmp2mi_plan>();   // ~gpmp2mi_plan returns whatever has been allocated if anything below fails
   p->robot = robot;
   p->sdf = sdf;
+  p->forms = F;
+  p->fail_alloc_at = forms ? forms->fail_alloc_at : 0;
   G2_HIP(hipGetDevice(&p->device));
   PlanParams& P = p->hp;
   std::memset(&P, 0, sizeof(P));
@@ -1037,19 +1095,8 @@ int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, cons
   P.REC = P.NG + D + 1 + ((robot->h.base_dof == 3 && P.I > 0) ? 36 : 0);
   P.Npad = (P.N + 1 + 63) / 64 * 64;
   P.lie = robot->h.base_dof == 3 ? 1 : 0;
-  P.wide = wide ? 1 : 0;
-  const char* wd_env = getenv("GPMP2MI_WIDE_DENSE");
-  const bool dense_path = dense_only || (wide && wd_env && wd_env[0] == '1');   // dense block solver: no split tail
-  P.split_back = (!dense_path && P.N >= 16) ? 1 : 0;   // the finish kernels take groups of 8 blocks (levels 4, 2, 1)
-  if (const char* e = getenv("GPMP2MI_SPLIT_BACK")) if (e[0] == '0') P.split_back = 0;   // A/B: whole back-substitution in the step kernel
-  P.spart_groups = (P.N + 8) / 8;
-  // wide blocks: the first forward levels (2, 4) run chip-wide when they are not among the last two of the tree
-  P.wide_h0 = 2;
-  if (wide) {
-    const char* e = getenv("GPMP2MI_WIDE_H0");
-    const int want = e ? atoi(e) : 8;   // (16 measured: see DESIGN)
-    while (P.wide_h0 < want && 4 * P.wide_h0 <= P.N) P.wide_h0 *= 2;
-  }
+  P.wide = F.wide; P.split_back = F.split_back; P.spart_groups = F.spart_groups;
+  P.wide_h0 = F.wide_h0; P.lin_split = F.lin_split; P.fuse_finish = F.fuse_finish;
   P.GPREC = P.n + 1 + (P.lie ? 18 : 0);
   P.RECS = (P.REC + 1) & ~1;
   P.GPS = (P.GPREC + 1) & ~1;
@@ -1061,25 +1108,6 @@ int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, cons
   P.no_increase = s->final_iter_no_increase;
   P.fixed_iters = o.fixed_iterations;
   P.end_conf_prior_off = o.end_conf_prior_off ? 1 : 0;
-  {
-    // sphere-split linearization for fixed-base arms: four wavefronts per 64 points sharing one walk of the chain
-    // (k_linearize_arm), or two wavefronts that each walk it (k_linearize NSPLIT = 2).  Alone, the four-wavefront form wins
-    // up to 256 trajectories (scripts/probes/split_sweep.sh, round 3: 14.4 / 16.8 / 22.5 / 35.5 / 59.3 us against 17.6 / 18.7 /
-    // 24.2 / 35.6 / 58.1 us at 32 / 64 / 128 / 256 / 512); with the fused finish, which only it has, it wins the Gauss-Newton
-    // pass at every size (195.3 / 226.9 / 224.8 k against 193.4 / 225.1 / 218.6 k traj/s at 256 / 512 / 1 024), and the LM pass
-    // too, if barely (97.7 / 102.0 k against 96.6 / 101.3 k at 512 / 1 024).  So: Gauss-Newton and LM plans always, Dogleg plans
-    // (no fusion there) up to 256 trajectories.  GPMP2MI_LIN_SPLIT=1 / 2 / 4 forces a form.
-    const char* e = getenv("GPMP2MI_LIN_SPLIT");
-    const bool four = B <= 256 || s->opt_type != GPMP2MI_OPT_DOGLEG;
-    P.lin_split = (robot->h.kind == GPMP2MI_ROBOT_ARM && robot->h.nr_spheres >= 2) ? (four ? 4 : 2) : 1;
-    if (e && (e[0] == '1' || e[0] == '2' || e[0] == '4')) P.lin_split = e[0] - '0';
-    // (the four-wavefront form keeps the <= 24 states of a chunk in LDS: two or more sub-steps per interval)
-    if (P.lin_split == 4 && (robot->h.kind != GPMP2MI_ROBOT_ARM || s->obs_check_inter < 2)) P.lin_split = 2;
-    // fused finish of the Gauss-Newton fast path (k_linearize_arm); GPMP2MI_FUSED_FINISH=0: k_finish_step as before
-    const char* ff = getenv("GPMP2MI_FUSED_FINISH");
-    P.fuse_finish = (P.lin_split == 4 && P.split_back && !wide && !(ff && ff[0] == '0')) ? 1 : 0;
-    if (P.fuse_finish) P.spart_groups = P.Ppad / 64;   // the trial-step shares then come per chunk of k_linearize_arm
-  }
   P.eps = s->epsilon;
   P.obs_w = 1.0 / (s->cost_sigma * s->cost_sigma);
   // planner/BatchTrajOptimizer-inl.h:30-31
@@ -1204,16 +1232,16 @@ int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, cons
   G2_TRY(plan_alloc(p.get(), &pb.init, tsz));
   G2_TRY(plan_alloc(p.get(), &pb.result, tsz));
   G2_TRY(plan_alloc(p.get(), &pb.delta, tsz));
-  const size_t tq = wide ? 4 : 1;  // wide blocks: 2 x 2 tiles, 32-wide vectors
-  G2_TRY(plan_alloc(p.get(), &pb.gvec, (size_t)B * (P.N + 1) * (wide ? 32 : 16)));
+  const size_t tq = F.wide ? 4 : 1;  // wide blocks: 2 x 2 tiles, 32-wide vectors
+  G2_TRY(plan_alloc(p.get(), &pb.gvec, (size_t)B * (P.N + 1) * (F.wide ? 32 : 16)));
   G2_TRY(plan_alloc(p.get(), &pb.htiles, P.opt_type == GPMP2MI_OPT_DOGLEG ? (size_t)B * (P.N + 1) * 512 * tq : 1));
   G2_TRY(plan_alloc(p.get(), &pb.hgpart, (size_t)B * P.Npad));
   G2_TRY(plan_alloc(p.get(), &pb.scal, (size_t)B * SC_COUNT));
   G2_TRY(plan_alloc(p.get(), &pb.which, B));
   G2_TRY(plan_alloc(p.get(), &pb.stepped, B));
   G2_TRY(plan_alloc(p.get(), &pb.spart, (size_t)B * std::max((P.N + 4) / 4, P.Ppad / 64) * 3));
-  G2_TRY(plan_alloc(p.get(), &pb.xg, (size_t)B * (P.N + 1) * (wide ? 32 : 16)));
-  if (dense_path) {   // dense normal equations + the factors of the dense cyclic reduction
+  G2_TRY(plan_alloc(p.get(), &pb.xg, (size_t)B * (P.N + 1) * (F.wide ? 32 : 16)));
+  if (F.dense) {   // dense normal equations + the factors of the dense cyclic reduction
     G2_TRY(plan_alloc(p.get(), &pb.wHd, (size_t)B * (P.N + 1) * P.n * P.n));
     G2_TRY(plan_alloc(p.get(), &pb.wHo, (size_t)B * P.N * P.n * P.n));
     G2_TRY(plan_alloc(p.get(), &pb.wg, (size_t)B * (P.N + 1) * P.n));
@@ -1255,9 +1283,6 @@ int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, cons
   G2_TRY(plan_alloc(p.get(), &pb.notspd, B));
   G2_TRY(plan_alloc(p.get(), &pb.epart, (size_t)B * P.Npad));
   {
-    const char* e = getenv("GPMP2MI_GENERIC_GN");
-    p->generic_gn = e && e[0] == '1';
-    p->wide_dense = dense_path;   // GPMP2MI_WIDE_DENSE=1 (read above) or dof > 11
     const int cap = std::max(P.fixed_iters, P.max_iter);   // plan_update may run any iterations <= max_iter
     // passes: GN one per iteration (+1); LM up to ~5 lambda retries per iterate; Dogleg up to ~16 halvings
     const int mult = P.opt_type == GPMP2MI_OPT_LM ? 6 : P.opt_type == GPMP2MI_OPT_DOGLEG ? 18 : 1;
@@ -1338,7 +1363,7 @@ int gpmp2mi_plan_optimize(gpmp2mi_plan* p, void* stream) {
   G2_CHECK(p, GPMP2MI_ERR_INVALID, "null plan");
   G2_CHECK(p->problem_set, GPMP2MI_ERR_INVALID, "call gpmp2mi_plan_set_problem first");
   hipStream_t st = (hipStream_t)stream;
-  return plan_run(p, st, p->pb.init);   // cur = init is part of the reset kernel
+  return plan_run(p, st, p->pb.init, false);   // cur = init is part of the reset kernel
 }
 
 // Active-trajectory count of a finished pass.  The closing kernel of every pass publishes it to a pinned,
@@ -1390,38 +1415,33 @@ static int wait_pass_count(gpmp2mi_plan* p, int pass, hipStream_t st, int* count
   return spin_wait_flag(p->h_flags + pass, true, st, wait_timeout_seconds(), count);
 }
 
-// the optimizer driver: `cur` holds the starting values
-static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start) {
+// the optimizer driver: `cur` holds the starting values; `update`: gpmp2mi_plan_update's fixed Gauss-Newton steps
+static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start, bool update) {
   const PlanParams& P = p->hp;
+  const PlanForms& F = p->forms;
   PlanBuffers& pb = p->pb;
   p->timer.reset();
   for (int k = 0; k < p->n_active_len; k++) p->h_flags[k] = -1;  // the previous run has drained (stream sync below)
   G2_TRY(launch_plan_reset(P, pb, start, st));
   const int iter_cap = (P.fixed_iters > 0 ? P.fixed_iters : P.max_iter);
-  if (P.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && !p->generic_gn && !P.wide) {
+  if (P.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && F.gn_fast(update)) {
     // ---- Gauss-Newton fast path: 3 launches per pass, step control fused into the solve kernel.
-    // Software-pipelined driver: pass k+1 is enqueued before the host looks at the active count of
-    // pass k, so the GPU never waits for the host.  When pass k turns out to have finished every
-    // trajectory, the already enqueued pass k+1 is a no-op (all workgroups exit on active[b] == 0).
+    // Software-pipelined driver: the linearization of pass k+1 is enqueued before the host looks at the active count of
+    // pass k, which it learns while the GPU still has the finish kernel of pass k and that linearization (~23 us) to run,
+    // so the GPU never waits for the host.  When pass k finished every trajectory, the enqueued linearization is a no-op
+    // (all workgroups exit on active[b] == 0).
     const int max_pass = iter_cap + 1;
-    // How far the host runs ahead.  "pass" (rounds 1-2): pass k+1 is enqueued whole before the count of pass k-1 is
-    // looked at, so one idle pass (four empty kernels, ~18 us) follows the last active one.  "lin": only the
-    // linearization of pass k+1 is enqueued ahead; its other three kernels follow once the count of pass k is in, which
-    // the host learns while the GPU still has the finish kernel of pass k and that linearization (~23 us) to run -- the
-    // idle tail shrinks to one empty kernel.
-    const char* ahead_env = getenv("GPMP2MI_GN_LOOKAHEAD");
-    const bool ahead_lin = !(ahead_env && ahead_env[0] == 'p');
-    // Fused finish (P.fuse_finish): there is no k_finish_step; the linearization of pass k applies the step of pass k - 1
+    // Fused finish (F.fuse_finish): there is no k_finish_step; the linearization of pass k applies the step of pass k - 1
     // itself, reading the states of pass k - 1 from one of the plan's two state buffers and writing those of pass k to
     // the other -- cur / last swap roles every pass, the step kernel picks them by the parity of its pass number.
-    const bool fuse = P.fuse_finish != 0;
-    auto states_of = [&](int pass) -> double* { return (fuse && (pass & 1)) ? pb.last : pb.cur; };
+    auto states_of = [&](int pass) -> double* { return (F.fuse_finish && (pass & 1)) ? pb.last : pb.cur; };
     auto enqueue_lin = [&](int pass) -> int {
       p->timer.begin("linearize", st);
-      if (fuse && pass > 0) return plan_linearize(p, states_of(pass - 1), 0, pb.active, st, states_of(pass), pass);
+      if (F.fuse_finish && pass > 0) return plan_linearize(p, states_of(pass - 1), 0, pb.active, st, states_of(pass), pass);
       return plan_linearize(p, pb.cur, 0, pb.active, st);
     };
-    auto enqueue_rest = [&](int pass) -> int {
+    G2_TRY(enqueue_lin(0));
+    for (int pass = 0; pass < max_pass; pass++) {
       if (P.fixed_iters > 0 && pass == P.fixed_iters) {
         // closing pass of a fixed-iteration run: nothing is solved any more, only the error of the final values
         p->timer.begin("final_error", st);
@@ -1432,38 +1452,20 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start) {
       }
       p->timer.begin("gn_step_cr", st);
       G2_TRY(launch_gn_step_cr(P, pb, pass, st));
-      if (P.split_back && !fuse) {
+      if (F.split_back && !F.fuse_finish) {
         p->timer.begin("finish_step", st);
         G2_TRY(launch_finish_step(P, pb, pass, st));
       }
-      return GPMP2MI_OK;
-    };
-    if (ahead_lin) {
-      G2_TRY(enqueue_lin(0));
-      for (int pass = 0; pass < max_pass; pass++) {
-        G2_TRY(enqueue_rest(pass));
-        if (pass + 1 == max_pass) break;
-        G2_TRY(enqueue_lin(pass + 1));   // ahead of the count
-        p->timer.close(st);
-        int cnt = 0;
-        G2_TRY(wait_pass_count(p, pass, st, &cnt));
-        if (cnt == 0) break;
-      }
+      if (pass + 1 == max_pass) break;
+      G2_TRY(enqueue_lin(pass + 1));   // ahead of the count
       p->timer.close(st);
-    } else {
-      for (int pass = 0; pass < max_pass; pass++) {
-        G2_TRY(enqueue_lin(pass));
-        G2_TRY(enqueue_rest(pass));
-        p->timer.close(st);
-        if (pass >= 1) {
-          int cnt = 0;
-          G2_TRY(wait_pass_count(p, pass - 1, st, &cnt));
-          if (cnt == 0) break;
-        }
-      }
+      int cnt = 0;
+      G2_TRY(wait_pass_count(p, pass, st, &cnt));
+      if (cnt == 0) break;
     }
+    p->timer.close(st);
   } else {
-    // ---- generic trial-step path (LM, Dogleg; GN when forced): per pass
+    // ---- generic trial-step path (LM, Dogleg; GN on wide plans or when forced): per pass
     //   assemble (+ g^T H g) -> solve + trial point -> linearize(trial) into the spare buffer -> decide
     // LM may retry an iterate with a larger lambda, Dogleg with a smaller radius, hence the cap.
     const int max_pass = p->n_active_len - 1;
@@ -1473,13 +1475,13 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start) {
     G2_TRY(launch_decide(P, pb, 0, true, st));
     p->timer.close(st);
     for (int pass = 1; pass < max_pass; pass++) {
-      if (P.wide && p->wide_dense) {
-        // dof 12..18, or A-B for 8..11: dense normal equations + cyclic reduction over dense blocks
+      if (F.dense) {
+        // dof 12..18, or forced for 8..11: dense normal equations + cyclic reduction over dense blocks
         p->timer.begin("export_dense", st);
         G2_TRY(launch_export_normal_eq(P, pb, pb.cur, 0, pb.wHd, pb.wHo, pb.wg, st, pb.active));
         p->timer.begin("solve_dense", st);
         G2_TRY(launch_solve_dense(P, pb, st));
-      } else if (P.wide) {
+      } else if (F.wide) {
         // blocks wider than one tile (8 <= dof <= 11): the same cyclic reduction on 2x2 tiles
         p->timer.begin("assemble_wide", st);
         G2_TRY(launch_assemble_wide(P, pb, pb.cur, 0, pb.active, st));
@@ -1493,7 +1495,7 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start) {
         }
         p->timer.begin("solve_step_wide", st);
         G2_TRY(launch_solve_step_wide(P, pb, st));
-        if (P.split_back && P.opt_type != GPMP2MI_OPT_DOGLEG) {   // LM / GN: levels 4, 2, 1, step and trial point chip-wide
+        if (F.finish_trial(P.opt_type)) {   // levels 4, 2, 1, step and trial point chip-wide
           p->timer.begin("finish_trial_wide", st);
           G2_TRY(launch_finish_trial_wide(P, pb, st));
         }
@@ -1506,13 +1508,13 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start) {
         }
         p->timer.begin("solve_step", st);
         G2_TRY(launch_solve_step(P, pb, st));
-        if (P.split_back && P.opt_type != GPMP2MI_OPT_DOGLEG && !P.fuse_finish) {   // LM / GN: levels 2, 1, step and trial point chip-wide
+        if (F.finish_trial(P.opt_type)) {   // levels 2, 1, step and trial point chip-wide
           p->timer.begin("finish_trial", st);
           G2_TRY(launch_finish_trial(P, pb, st));
         }
       }
       p->timer.begin("linearize", st);
-      if (!P.wide && P.split_back && P.opt_type != GPMP2MI_OPT_DOGLEG && P.fuse_finish) {
+      if (F.trial_lin_steps(P.opt_type)) {
         // fused finish: the linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
         G2_TRY(plan_linearize(p, pb.cur, 1, pb.active, st, pb.trial, 1, true));
       } else {
@@ -1536,11 +1538,11 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start) {
   p->optimized = true;
   return GPMP2MI_OK;
 }
-static int plan_run(gpmp2mi_plan* p, hipStream_t st, const double* start) {
+static int plan_run(gpmp2mi_plan* p, hipStream_t st, const double* start, bool update) {
   G2_CHECK(!p->poisoned, GPMP2MI_ERR_TIMEOUT,
            "this plan timed out earlier and may still have a hung kernel in its stream: destroy it and create a new one");
   p->mark_dirty(st);
-  const int rc = plan_run_impl(p, st, start);
+  const int rc = plan_run_impl(p, st, start, update);
   if (rc == GPMP2MI_ERR_TIMEOUT) {
     // The stream may hold a kernel that never finishes: waiting for it here (or in gpmp2mi_plan_destroy) would hang
     // the caller after all.  The plan is poisoned instead: no further runs, no wait and no recycling at destroy.
@@ -1703,10 +1705,7 @@ int gpmp2mi_plan_update(gpmp2mi_plan* p, int iterations, void* stream) {
     p->hp = saved;
     return rc0;
   }
-  const bool gg = p->generic_gn;
-  p->generic_gn = false;
-  const int rc = plan_run(p, st, from);
-  p->generic_gn = gg;
+  const int rc = plan_run(p, st, from, true);
   p->hp = saved;
   G2_TRY(launch_set_mode(p->pb, p->hp.opt_type, p->hp.fixed_iters, st));
   G2_HIP(hipStreamSynchronize(st));

@@ -1,5 +1,6 @@
 // dense_kernels.hip -- solve step for robots whose blocks do not fit the tile kernels (12 <= dof <= 18, the PR2
-// model; also 8 <= dof <= 11 with GPMP2MI_WIDE_DENSE=1 as an independent implementation of the 2x2-tile path).
+// model; also 8 <= dof <= 11 when a plan is created with the forced form wide_dense (gpmp2mi_debug.h), as an independent
+// implementation of the 2x2-tile path).
 //
 // Same role as k_solve_step (cr_kernels.hip) on the trial-step path: solve the current linearization,
 // form the trial point and the step-control scalars of GN / LM / Dogleg.  The system arrives as dense

@@ -619,11 +619,12 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
 }
 
 // dst / pass: fused finish of the Gauss-Newton fast path (k_linearize_arm; only with hp.fuse_finish): apply the step of
-// pass - 1 to the states in `traj` and write the new states to `dst`; dst = nullptr: linearize `traj` as it is
+// pass - 1 to the states in `traj` and write the new states to `dst`; dst = nullptr: linearize `traj` as it is.
+// hp.lin_split names the form that runs: 2 and 4 only ever on fixed-base arms (api.hip choose_forms)
 int launch_linearize(const RobotDev& h, const RobotDev* robot, const SdfDev& sdf, const PlanParams& hp,
                      const PlanBuffers& pb, const double* traj, int bufsel, const int* active,
                      hipStream_t st, double* dst, int pass, bool trial) {
-  if (dst != nullptr && !(hp.fuse_finish && hp.lin_split == 4 && h.kind == GPMP2MI_ROBOT_ARM)) {
+  if (dst != nullptr && !(hp.fuse_finish && hp.lin_split == 4)) {
     set_error("fused finish asked of a plan that was not set up for it");
     return GPMP2MI_ERR_INVALID;
   }
@@ -635,14 +636,14 @@ int launch_linearize(const RobotDev& h, const RobotDev* robot, const SdfDev& sdf
   // workgroup (NSPLIT = 2, see the kernel).  A variant that kept 4-8 SDF cells in flight per lane was no faster
   // (DESIGN.md section 4).
   const dim3 grid(hp.B * (hp.Ppad / 64));
-  if (hp.lin_split == 4 && h.kind == GPMP2MI_ROBOT_ARM) {
+  if (hp.lin_split == 4) {
     const dim3 block(256);
     if (sdf.dim == 3) {
       G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize_arm<AD_, 3, 4><<<grid, block, 0, st>>>(robot, sdf, pb.params, pb, traj, bufsel, active, dst, pass, trial ? 1 : 0)));
     } else {
       G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize_arm<AD_, 2, 4><<<grid, block, 0, st>>>(robot, sdf, pb.params, pb, traj, bufsel, active, dst, pass, trial ? 1 : 0)));
     }
-  } else if (hp.lin_split == 2 && h.kind == GPMP2MI_ROBOT_ARM) {
+  } else if (hp.lin_split == 2) {
     const dim3 block(128);
     if (sdf.dim == 3) {
       G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize<GPMP2MI_ROBOT_ARM, AD_, 0, 3, 2><<<grid, block, 0, st>>>(robot, sdf, pb.params, pb, traj, bufsel, active)));

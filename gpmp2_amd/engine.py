@@ -267,41 +267,47 @@ class Engine:
         return cost
 
     # ---------------------------------------------------------------- plans
-    def plan(self, robot, sdf, setting, B):
-        return Plan(self, robot, sdf, setting, B)
+    def plan(self, robot, sdf, setting, B, forms=None):
+        return Plan(self, robot, sdf, setting, B, forms)
 
-    # graph-level helpers with the oracle's call shape
-    def _plan_for(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj):
+    # graph-level helpers with the oracle's call shape; forms: see Plan
+    def _plan_for(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj, forms=None):
         D = setting.dof
         sc = f64(start_conf).reshape(-1, D)
-        pl = Plan(self, robot, sdf, setting, sc.shape[0])
+        pl = Plan(self, robot, sdf, setting, sc.shape[0], forms)
         t = f64(traj).reshape(sc.shape[0], setting.total_step + 1, 2 * D)
         pl.set_problem(start_conf, start_vel, end_conf, end_vel, t)
         return pl, t
 
-    def graph_error(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj):
-        pl, t = self._plan_for(robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj)
+    def graph_error(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj, forms=None):
+        pl, t = self._plan_for(robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj, forms)
         return pl.graph_error(t)
 
-    def linearize(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj):
-        pl, t = self._plan_for(robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj)
+    def linearize(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj, forms=None):
+        pl, t = self._plan_for(robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj, forms)
         return pl.linearize(t)
 
-    def batch_optimize(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, init):
-        pl, t = self._plan_for(robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, init)
+    def batch_optimize(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, init, forms=None):
+        pl, t = self._plan_for(robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, init, forms)
         pl.optimize()
         return pl.result()
 
 
 class Plan:
-    """gpmp2mi_plan: B trajectory problems resident on the GPU."""
+    """gpmp2mi_plan: B trajectory problems resident on the GPU.  forms (tests, probes): a dict of the kernel forms to force
+    on the plan, e.g. {"lin_split": 2} (gpmp2mi_debug_forms, include/gpmp2mi_debug.h); None: the plan's own choice."""
 
-    def __init__(self, eng: Engine, robot, sdf, setting, B: int):
+    def __init__(self, eng: Engine, robot, sdf, setting, B: int, forms=None):
         self.eng, self.robot, self.sdf, self.setting, self.B = eng, robot, sdf, setting, int(B)
         s, o, keep = _capi.make_settings(setting)
         self._keep = (s, o, keep)
         out = C.c_void_p()
-        eng._ck(eng.lib.gpmp2mi_plan_create(robot.ptr, sdf.ptr, C.byref(s), C.byref(o), self.B, C.byref(out)))
+        if forms is None:
+            eng._ck(eng.lib.gpmp2mi_plan_create(robot.ptr, sdf.ptr, C.byref(s), C.byref(o), self.B, C.byref(out)))
+        else:
+            f = _capi.make_debug_forms(forms)
+            eng._ck(eng.lib.gpmp2mi_debug_plan_create(robot.ptr, sdf.ptr, C.byref(s), C.byref(o), self.B, C.byref(f),
+                                                      C.byref(out)))
         self.h = _Handle(out, eng.lib.gpmp2mi_plan_destroy)
         self.D, self.N = setting.dof, setting.total_step
 

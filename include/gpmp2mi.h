@@ -422,32 +422,7 @@ int gpmp2mi_version(void);
  * stream): names[i] / ms[i] / launches[i] for i < *n.  Used by bench.py for the roofline line. */
 int gpmp2mi_plan_enable_timing(gpmp2mi_plan* p, int enable);
 int gpmp2mi_plan_get_timing(gpmp2mi_plan* p, int* n, const char** names, double* ms, int* launches);
-/* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
-int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);
-/* Diagnostic: scalars of trajectory b's last LM / Dogleg trial step, out17 = {g.delta, |delta|^2, g.g, g^T H g,
- * g.dx_n, |dx_n|^2, model decrease q, |step|, zero-step flag, -, ..., [16] = current lambda / trust radius}. */
-int gpmp2mi_plan_debug_scalars(gpmp2mi_plan* p, int b, double* out17);
-/* Test hook, host only (no GPU needed): the wall-clock-bounded spin the pass driver uses on its device-mapped
- * pass flags, run on a caller-owned flag: returns GPMP2MI_OK with *value = *flag once *flag >= 0, or
- * GPMP2MI_ERR_TIMEOUT (gpmp2mi_last_error set) after timeout_ms.  The driver's own limit is 5 s
- * (GPMP2MI_WAIT_TIMEOUT_MS overrides). */
-int gpmp2mi_debug_wait_flag(const int* flag, int timeout_ms, int* value);
-/* Test hook (works without a GPU: all zeros then): arena chunks / pass-flag buffers owned by live plans, the pooled
- * ones, and the plans leaked because they were poisoned (GPMP2MI_ERR_TIMEOUT).  Any pointer may be NULL. */
-int gpmp2mi_debug_resource_counts(long* live_chunks, long* pooled_chunks, long* live_flagbufs, long* pooled_flagbufs,
-                                  long* leaked_plans);
-/* Test hooks: a one-thread kernel that occupies `stream` until gpmp2mi_debug_stall_release(token) -- or, whatever
- * happens, until max_ms (<= 10000) of device wall clock have passed -- so that the pass driver's timeout path can be
- * driven on a real stream.  release() sets the flag, waits for that stream and frees the token. */
-int gpmp2mi_debug_stall_begin(void* stream, int max_ms, void** token);
-int gpmp2mi_debug_stream_create(void** stream);   /* a non-blocking stream of the HIP runtime the library uses */
-int gpmp2mi_debug_stream_destroy(void* stream);
-int gpmp2mi_debug_stall_release(void* token);
-/* Diagnostic: lane semantics of the wave-level moves the solver relies on (tests/test_gpu_plan.py). */
-int gpmp2mi_debug_crosslane(const double* in64, double* out512);
-/* Diagnostic: raw device-to-host copy of a solver hand-over buffer of the plan (0: diagonal tiles [B][N+1][256],
- * 1: factor tiles [B][N+1][3][256], 2: pending Schur tiles [B][groups][256], 3: level-4 couplings [B][groups][256]). */
-int gpmp2mi_plan_debug_read(gpmp2mi_plan* p, int which, double* out, long count);
+/* Diagnostic and test entry points (forced kernel forms, failure injection, solver read-outs): gpmp2mi_debug.h */
 
 #ifdef __cplusplus
 }

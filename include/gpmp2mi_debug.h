@@ -1,0 +1,63 @@
+/*
+ * gpmp2mi_debug.h -- diagnostic and test entry points of the library behind include/gpmp2mi.h.
+ *
+ * Nothing here is needed to plan.  These calls exist for the test suite and the probes under scripts/:
+ * forcing one of the kernel forms a plan could take, failure injection, and read-outs of solver state.
+ * The library reads no environment variable to choose a form; it reads only GPMP2MI_WAIT_TIMEOUT_MS
+ * (include/gpmp2mi.h).
+ */
+#ifndef GPMP2MI_DEBUG_H
+#define GPMP2MI_DEBUG_H
+
+#include "gpmp2mi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Forms a plan would otherwise choose for itself (api.hip choose_forms).  The forms agree to rounding, not always bit for
+ * bit.  A forced form the plan cannot take is refused with GPMP2MI_ERR_UNSUPPORTED. */
+typedef struct gpmp2mi_debug_forms {   /* all zero = the plan's own choice */
+  int lin_split;        /* 1, 2, 4: force the fixed-base-arm linearization form (2 and 4: fixed-base arms only;
+                           4: obs_check_inter >= 2) */
+  int no_fused_finish;  /* 1: k_finish_step / k_finish_trial instead of the fused finish */
+  int generic_gn;       /* 1: Gauss-Newton through the trial-step driver (gpmp2mi_plan_update keeps the fast path) */
+  int wide_dense;       /* 1: dof 8..11 through the dense block solver */
+  int fail_alloc_at;    /* k > 0: the k-th device allocation of this create fails (GPMP2MI_ERR_ALLOC) */
+} gpmp2mi_debug_forms;
+/* gpmp2mi_plan_create with forced forms (forms = NULL: the same call) */
+int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
+                              const gpmp2mi_settings* setting, const gpmp2mi_graph_opts* opts /*NULL ok*/,
+                              int B, const gpmp2mi_debug_forms* forms /*NULL ok*/, gpmp2mi_plan** out);
+
+/* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
+int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);
+/* Diagnostic: scalars of trajectory b's last LM / Dogleg trial step, out17 = {g.delta, |delta|^2, g.g, g^T H g,
+ * g.dx_n, |dx_n|^2, model decrease q, |step|, zero-step flag, -, ..., [16] = current lambda / trust radius}. */
+int gpmp2mi_plan_debug_scalars(gpmp2mi_plan* p, int b, double* out17);
+/* Test hook, host only (no GPU needed): the wall-clock-bounded spin the pass driver uses on its device-mapped
+ * pass flags, run on a caller-owned flag: returns GPMP2MI_OK with *value = *flag once *flag >= 0, or
+ * GPMP2MI_ERR_TIMEOUT (gpmp2mi_last_error set) after timeout_ms.  The driver's own limit is 5 s
+ * (GPMP2MI_WAIT_TIMEOUT_MS overrides). */
+int gpmp2mi_debug_wait_flag(const int* flag, int timeout_ms, int* value);
+/* Test hook (works without a GPU: all zeros then): arena chunks / pass-flag buffers owned by live plans, the pooled
+ * ones, and the plans leaked because they were poisoned (GPMP2MI_ERR_TIMEOUT).  Any pointer may be NULL. */
+int gpmp2mi_debug_resource_counts(long* live_chunks, long* pooled_chunks, long* live_flagbufs, long* pooled_flagbufs,
+                                  long* leaked_plans);
+/* Test hooks: a one-thread kernel that occupies `stream` until gpmp2mi_debug_stall_release(token) -- or, whatever
+ * happens, until max_ms (<= 10000) of device wall clock have passed -- so that the pass driver's timeout path can be
+ * driven on a real stream.  release() sets the flag, waits for that stream and frees the token. */
+int gpmp2mi_debug_stall_begin(void* stream, int max_ms, void** token);
+int gpmp2mi_debug_stream_create(void** stream);   /* a non-blocking stream of the HIP runtime the library uses */
+int gpmp2mi_debug_stream_destroy(void* stream);
+int gpmp2mi_debug_stall_release(void* token);
+/* Diagnostic: lane semantics of the wave-level moves the solver relies on (tests/test_gpu_plan.py). */
+int gpmp2mi_debug_crosslane(const double* in64, double* out512);
+/* Diagnostic: raw device-to-host copy of a solver hand-over buffer of the plan (0: diagonal tiles [B][N+1][256],
+ * 1: factor tiles [B][N+1][3][256], 2: pending Schur tiles [B][groups][256], 3: level-4 couplings [B][groups][256]). */
+int gpmp2mi_plan_debug_read(gpmp2mi_plan* p, int which, double* out, long count);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GPMP2MI_DEBUG_H */

@@ -1,7 +1,8 @@
 """Measures, per sweep case, what tests/test_gpu_parity_at_size.py asserts: GPU-vs-oracle trajectory difference per
 trajectory and -- where it exceeds the 1e-6 contract -- the oracle's own sensitivity to a 2-ulp perturbation of its
 initial values (tests/parity_bound.py).
-usage: python scripts/parity_sensitivity.py [cases] [only]     (GPMP2MI_LIB / GPMP2MI_WIDE_DENSE select A/B builds)"""
+usage: python scripts/parity_sensitivity.py [--dense] [cases] [only]
+(GPMP2MI_LIB selects another build; --dense sends dof 8..11 through the dense block solver)"""
 import os
 import sys
 
@@ -13,15 +14,17 @@ from oracle import Oracle
 from parity_bound import CONTRACT, oracle_self_sensitivity, per_traj_diff, solve_both
 from sweep_cases import robot_sweep_cases
 
-cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
-only = int(sys.argv[2]) if len(sys.argv) > 2 else None
+dense = "--dense" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--dense"]
+cases = int(argv[0]) if len(argv) > 0 else 50
+only = int(argv[1]) if len(argv) > 1 else None
 eng, orc = engine.Engine(), Oracle()
-tag = os.environ.get("GPMP2MI_LIB", "HEAD") + (" dense" if os.environ.get("GPMP2MI_WIDE_DENSE") == "1" else "")
+tag = os.environ.get("GPMP2MI_LIB", "HEAD") + (" dense" if dense else "")
 n_over = 0
 for case, name, opt, p in robot_sweep_cases(cases):
     if only is not None and case != only:
         continue
-    res, ref, handles = solve_both(eng, orc, p)
+    res, ref, handles = solve_both(eng, orc, p, forms={"wide_dense": 1} if dense and p.setting.dof >= 8 else None)
     same = list(res["iters"]) == list(ref["iters"]) and list(res["status"]) == list(ref["status"])
     d = per_traj_diff(res, ref)
     rel = np.abs(res["final_error"] / ref["final_error"] - 1.0)

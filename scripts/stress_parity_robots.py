@@ -1,5 +1,6 @@
 """Randomised whole-plan parity sweep over robot kinds (Lie path, two-arm / lift robots, wide blocks) against the
-CPU oracle.  usage: python scripts/stress_parity_robots.py [cases]"""
+CPU oracle.  usage: python scripts/stress_parity_robots.py [--dense] [cases] [only]
+(--dense sends the dof 8..11 models through the dense block solver)"""
 import sys
 
 import numpy as np
@@ -10,8 +11,10 @@ from gpmp2_amd import engine, problems
 from gpmp2_amd.settings import TrajOptimizerSetting
 from oracle import Oracle
 
-cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-only = int(sys.argv[2]) if len(sys.argv) > 2 else None   # run just this case (e.g. under GPMP2MI_WIDE_DENSE=1)
+dense = "--dense" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--dense"]
+cases = int(argv[0]) if len(argv) > 0 else 40
+only = int(argv[1]) if len(argv) > 1 else None   # run just this case (e.g. with --dense)
 eng, orc = engine.Engine(), Oracle()
 rng = np.random.default_rng(777)
 wam = g.generateArm("WAMArm")
@@ -75,7 +78,7 @@ for case in range(cases):
         continue
     r, s = eng.robot(model), eng.sdf(origin, cell, data)
     ro, so = orc.robot(model), orc.sdf(origin, cell, data)
-    res = eng.batch_optimize(r, s, st, *args, init)
+    res = eng.batch_optimize(r, s, st, *args, init, forms={"wide_dense": 1} if dense and D >= 8 else None)
     ref = orc.batch_optimize(ro, so, st, *args, init)
     same = list(res["iters"]) == list(ref["iters"]) and list(res["status"]) == list(ref["status"])
     dtraj = float(np.abs(res["traj"] - ref["traj"]).max())

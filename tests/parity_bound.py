@@ -22,11 +22,11 @@ def _args(p):
     return p.start_conf, p.start_vel, p.end_conf, p.end_vel
 
 
-def solve_both(engine, oracle, p, nthreads=None):
+def solve_both(engine, oracle, p, nthreads=None, forms=None):
     r, s = engine.robot(p.model), engine.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
     ro, so = oracle.robot(p.model), oracle.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
     nthreads = nthreads or min(os.cpu_count() or 1, 64)
-    res = engine.batch_optimize(r, s, p.setting, *_args(p), p.init)
+    res = engine.batch_optimize(r, s, p.setting, *_args(p), p.init, forms=forms)
     ref = oracle.batch_optimize(ro, so, p.setting, *_args(p), p.init, nthreads=nthreads)
     return res, ref, (ro, so)
 

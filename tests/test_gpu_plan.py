@@ -246,14 +246,13 @@ def test_arm3_planner_config2_dogleg_with_limits(engine, oracle):
     _compare_solves(res, ref, p.setting.max_iter)
 
 
-def test_generic_path_reproduces_fused_gauss_newton(engine, small_wam, monkeypatch):
+def test_generic_path_reproduces_fused_gauss_newton(engine, small_wam):
     """The trial-step machinery (assemble / solve_step / linearize / decide) run with GaussNewton must
     give exactly what the fused fast path gives."""
     p = small_wam
     r, s = engine.robot(p.model), engine.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
     a = engine.batch_optimize(r, s, p.setting, *_args(p), p.init)
-    monkeypatch.setenv("GPMP2MI_GENERIC_GN", "1")
-    b = engine.batch_optimize(r, s, p.setting, *_args(p), p.init)
+    b = engine.batch_optimize(r, s, p.setting, *_args(p), p.init, forms={"generic_gn": 1})
     assert list(a["iters"]) == list(b["iters"]) and list(a["status"]) == list(b["status"])
     np.testing.assert_allclose(a["traj"], b["traj"], atol=1e-9)
     np.testing.assert_allclose(a["final_error"], b["final_error"], rtol=1e-10)
@@ -632,8 +631,8 @@ def test_every_block_width_of_the_one_tile_path(engine, oracle, D, opt):
 
 
 @pytest.mark.parametrize("case", ["wam3d", "planar3", "planar5"])
-def test_every_linearization_form_of_fixed_base_arms(engine, oracle, monkeypatch, case):
-    """Fixed-base arms have three forms of the linearization kernel: one wavefront per 64 points (GPMP2MI_LIN_SPLIT=1), two
+def test_every_linearization_form_of_fixed_base_arms(engine, oracle, case):
+    """Fixed-base arms have three forms of the linearization kernel: one wavefront per 64 points (forms lin_split=1), two
     wavefronts that both walk the chain (2; the default above 256 trajectories) and four that share one walk through LDS
     (4: k_linearize_arm, the default up to 256).  All three against the oracle's normal equations, and against each other."""
     import gpmp2_amd as g
@@ -665,8 +664,7 @@ def test_every_linearization_form_of_fixed_base_arms(engine, oracle, monkeypatch
     assert np.abs(ref[2]).max() > 0 and (np.abs(ref[0]).reshape(p.B, -1).max(axis=1) > 0).all()
     got = {}
     for form in ("1", "2", "4"):
-        monkeypatch.setenv("GPMP2MI_LIN_SPLIT", form)
-        got[form] = engine.linearize(r, s, p.setting, *_args(p), traj)
+        got[form] = engine.linearize(r, s, p.setting, *_args(p), traj, forms={"lin_split": int(form)})
         for x, y in zip(got[form][:3], ref[:3]):
             np.testing.assert_allclose(x, y, atol=1e-9 * np.abs(y).max(), err_msg=f"form {form}")
         np.testing.assert_allclose(got[form][3], ref[3], rtol=1e-9, err_msg=f"form {form}")
@@ -675,28 +673,10 @@ def test_every_linearization_form_of_fixed_base_arms(engine, oracle, monkeypatch
             np.testing.assert_allclose(x, y, atol=1e-12 * np.abs(y).max())
 
 
-def test_both_run_ahead_modes_of_the_gauss_newton_driver(engine, small_wam, monkeypatch):
-    """The host enqueues either the whole next pass or only its linearization before it looks at a pass count
-    (GPMP2MI_GN_LOOKAHEAD=pass / lin, api.hip: plan_run_impl): same kernels in the same order on the same data, so the
-    results are bit-identical; fixed-iteration runs (closing error pass) included."""
-    from copy import deepcopy
-    p = small_wam
-    r, s = engine.robot(p.model), engine.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
-    for fixed in (0, 2):
-        st = deepcopy(p.setting)
-        st.fixed_iterations = fixed
-        res = {}
-        for mode in ("pass", "lin"):
-            monkeypatch.setenv("GPMP2MI_GN_LOOKAHEAD", mode)
-            res[mode] = engine.batch_optimize(r, s, st, *_args(p), p.init)
-        for k in ("traj", "iters", "status", "final_error"):
-            np.testing.assert_array_equal(res["pass"][k], res["lin"][k])
-
-
 @pytest.mark.parametrize("N,inter,fixed", [(100, 5, 0), (37, 2, 0), (64, 3, 3), (23, 4, 0), (16, 2, 2)])
-def test_fused_finish_is_the_finish_kernel(engine, oracle, monkeypatch, N, inter, fixed):
+def test_fused_finish_is_the_finish_kernel(engine, oracle, N, inter, fixed):
     """Gauss-Newton fast path of fixed-base arms: levels 4, 2, 1 of the back-substitution and the retract run either in
-    k_finish_step or at the head of the next pass's k_linearize_arm (GPMP2MI_FUSED_FINISH=0 / default; the two state
+    k_finish_step or at the head of the next pass's k_linearize_arm (forms no_fused_finish=1 / default; the two state
     buffers then swap roles every pass).  Same tiles, same arithmetic: the results are bit-identical -- trajectories,
     iteration counts, status (including the rolled-back ones, which return the buffer the last step started from) --
     and they meet the oracle.  Sizes: the headline's, N not a multiple of 8, the smallest sub-step count the fused form
@@ -708,8 +688,7 @@ def test_fused_finish_is_the_finish_kernel(engine, oracle, monkeypatch, N, inter
     r, s = engine.robot(p.model), engine.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
     res = {}
     for mode in ("0", "1"):
-        monkeypatch.setenv("GPMP2MI_FUSED_FINISH", mode)
-        res[mode] = engine.batch_optimize(r, s, st, *_args(p), p.init)
+        res[mode] = engine.batch_optimize(r, s, st, *_args(p), p.init, forms={"no_fused_finish": int(mode == "0")})
     for k in ("traj", "iters", "status", "final_error", "error_trace"):
         np.testing.assert_array_equal(res["0"][k], res["1"][k], err_msg=k)
     ro, so = oracle.robot(p.model), oracle.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
@@ -719,17 +698,16 @@ def test_fused_finish_is_the_finish_kernel(engine, oracle, monkeypatch, N, inter
         np.testing.assert_allclose(res["1"]["traj"], ref["traj"], atol=1e-6)
 
 
-def test_fused_finish_of_the_trial_step_path(engine, oracle, monkeypatch):
+def test_fused_finish_of_the_trial_step_path(engine, oracle):
     """LM on a fixed-base arm: the trial point cur (+) delta and the step-control shares g.delta, |delta|^2, |g|^2 come either
     from k_finish_trial (per group of 8 blocks) or from the head of the trial linearization (per chunk of 64 evaluation
-    points; GPMP2MI_FUSED_FINISH=0 / default).  The shares are summed in another grouping, so the two forms agree to
+    points; forms no_fused_finish=1 / default).  The shares are summed in another grouping, so the two forms agree to
     rounding, not bit for bit; both meet the oracle."""
     p = problems.wam_restarts(B=6, total_step=37, obs_check_inter=3, opt="LM", sdf="40")
     r, s = engine.robot(p.model), engine.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
     res = {}
     for mode in ("0", "1"):
-        monkeypatch.setenv("GPMP2MI_FUSED_FINISH", mode)
-        res[mode] = engine.batch_optimize(r, s, p.setting, *_args(p), p.init)
+        res[mode] = engine.batch_optimize(r, s, p.setting, *_args(p), p.init, forms={"no_fused_finish": int(mode == "0")})
     assert list(res["0"]["iters"]) == list(res["1"]["iters"]) and list(res["0"]["status"]) == list(res["1"]["status"])
     np.testing.assert_allclose(res["0"]["traj"], res["1"]["traj"], atol=1e-9)
     ro, so = oracle.robot(p.model), oracle.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)

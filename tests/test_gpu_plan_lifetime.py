@@ -1,12 +1,13 @@
 """Lifetime of a gpmp2mi_plan (ownership notes SURVEY.md 8(b); gpmp2/planner/ISAM2TrajOptimizer.h:68-74 owns copies of
 everything it plans with, BatchTrajOptimize* builds and drops its graph per call):
 
-  * a gpmp2mi_plan_create that fails half-way (out of memory, here injected with GPMP2MI_FAIL_ALLOC_AT) or on an
-    invalid description returns every arena chunk and the pass-flag buffer;
+  * a gpmp2mi_plan_create that fails half-way (out of memory, here injected with the forced form fail_alloc_at), on
+    an invalid description or on a forced form the plan cannot take returns every arena chunk and the pass-flag buffer;
   * gpmp2mi_plan_destroy waits for the plan's own streams only: a one-shot gpmp2mi_batch_optimize on one stream is
     not held up by work another stream still has in flight;
   * a pass that does not finish within GPMP2MI_WAIT_TIMEOUT_MS returns GPMP2MI_ERR_TIMEOUT instead of hanging the
     caller, also in the calls that follow and in the destroy (the plan is poisoned, its memory leaked on purpose)."""
+import copy
 import ctypes as C
 import os
 import subprocess
@@ -39,7 +40,7 @@ def _stream(engine):
     return st
 
 
-def test_failed_create_returns_every_chunk_and_flag_buffer(engine, monkeypatch):
+def test_failed_or_refused_create_returns_every_chunk_and_flag_buffer(engine):
     p = problems.wam_restarts(B=4, total_step=20, obs_check_inter=3, sdf="40")
     r, s = engine.robot(p.model), engine.sdf(p.sdf_origin, p.sdf_cell, p.sdf_data)
     pl = engine.plan(r, s, p.setting, p.B)      # a plan that works: counts its allocations, fills the pools on close
@@ -51,9 +52,8 @@ def test_failed_create_returns_every_chunk_and_flag_buffer(engine, monkeypatch):
     p.setting.add_workspace_prior(0, 6, np.eye(4), 1e-2, 1, 5)
     failed = 0
     for k in (1, 2, 3, 5, 8, 13, 21, 34, 44, 46, 48, 50, 52, 90):
-        monkeypatch.setenv("GPMP2MI_FAIL_ALLOC_AT", str(k))
         try:
-            q = engine.plan(r, s, p.setting, p.B)
+            q = engine.plan(r, s, p.setting, p.B, forms={"fail_alloc_at": k})
         except Gpmp2miError as e:
             assert e.code == 5 and "injected" in str(e)
             failed += 1
@@ -62,10 +62,19 @@ def test_failed_create_returns_every_chunk_and_flag_buffer(engine, monkeypatch):
         now = _counts(engine)
         assert now["live_chunks"] == base["live_chunks"] and now["live_flagbufs"] == base["live_flagbufs"], (k, now, base)
     assert failed >= 10
-    monkeypatch.delenv("GPMP2MI_FAIL_ALLOC_AT")
+    pooled = _counts(engine)["pooled_chunks"]
+    # a forced form the plan cannot take is refused before anything is allocated: the four-wavefront linearization with
+    # one sub-step per interval, the dense block solver on a 7-dof arm (no wide blocks)
+    one_sub = copy.deepcopy(p.setting)
+    one_sub.set_obs_check_inter(1)
+    for st, forms in ((one_sub, {"lin_split": 4}), (p.setting, {"wide_dense": 1})):
+        with pytest.raises(Gpmp2miError) as ei:
+            engine.plan(r, s, st, p.B, forms=forms)
+        assert ei.value.code == 4, forms
+        now = _counts(engine)
+        assert now["live_chunks"] == base["live_chunks"] and now["pooled_chunks"] == pooled, forms
     # an invalid description is rejected before anything is allocated
     p.setting.add_workspace_prior(0, 99, np.eye(4), 1e-2, 1, 5)          # link out of range
-    pooled = _counts(engine)["pooled_chunks"]
     with pytest.raises(Gpmp2miError) as ei:
         engine.plan(r, s, p.setting, p.B)
     assert ei.value.code == 1

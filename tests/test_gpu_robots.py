@@ -258,8 +258,8 @@ def test_wide_long_trajectories(engine, oracle, name, N):
         assert rep["over"].size <= 1
 
 
-def test_wide_dense_fallback_agrees(engine, oracle, monkeypatch):
-    """GPMP2MI_WIDE_DENSE=1: the independent dense block-Cholesky implementation of the 8..11-dof solve"""
+def test_wide_dense_fallback_agrees(engine, oracle):
+    """forms wide_dense=1: the independent dense block-Cholesky implementation of the 8..11-dof solve"""
     model = _wide_models()["mobile WAM (dof 10)"]
     p = _tree_problem(model, N=10, inter=2, opt="LM")
     r, ro = engine.robot(p.model), oracle.robot(p.model)
@@ -267,8 +267,7 @@ def test_wide_dense_fallback_agrees(engine, oracle, monkeypatch):
     args = (p.start_conf, p.start_vel, p.end_conf, p.end_vel)
     ref = oracle.batch_optimize(ro, so, p.setting, *args, p.init)
     tiles = engine.batch_optimize(r, s, p.setting, *args, p.init)
-    monkeypatch.setenv("GPMP2MI_WIDE_DENSE", "1")
-    dense = engine.batch_optimize(r, s, p.setting, *args, p.init)
+    dense = engine.batch_optimize(r, s, p.setting, *args, p.init, forms={"wide_dense": 1})
     for res in (tiles, dense):
         assert list(res["iters"]) == list(ref["iters"]) and list(res["status"]) == list(ref["status"])
         np.testing.assert_allclose(res["traj"], ref["traj"], atol=1e-6)

@@ -1,5 +1,5 @@
 """CPU-side check (no GPU needed): the product library loads and exports every symbol that
-include/gpmp2mi.h declares; without a GPU its compute entry points fail loudly instead of
+include/gpmp2mi.h and include/gpmp2mi_debug.h declare; without a GPU its compute entry points fail loudly instead of
 falling back to anything."""
 import ctypes
 import os
@@ -13,7 +13,7 @@ LIB = os.path.join(ROOT, "gpmp2_amd", "csrc", "libgpmp2mi.so")
 
 
 def _declared_symbols():
-    text = open(os.path.join(ROOT, "include", "gpmp2mi.h")).read()
+    text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("gpmp2mi.h", "gpmp2mi_debug.h"))
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(gpmp2mi_[a-z0-9_]+)\s*\(", text)))
 
@@ -24,7 +24,7 @@ def test_header_symbols_are_exported():
     names = _declared_symbols()
     assert len(names) >= 30
     missing = [n for n in names if not hasattr(lib, n)]
-    assert not missing, f"declared in include/gpmp2mi.h but not exported: {missing}"
+    assert not missing, f"declared in include/gpmp2mi.h / gpmp2mi_debug.h but not exported: {missing}"
 
 
 def test_no_silent_fallback_without_gpu():
