@@ -14,6 +14,7 @@
 //                  gpmp2::optimize control flow (planner/BatchTrajOptimizer.cpp:273-307) and the
 //                  retract.
 #include "assembler.h"
+#include "dispatch.h"
 #include "plan_device.h"
 
 namespace g2 {
@@ -274,20 +275,11 @@ int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* t
   const dim3 grid(hp.B * ((hp.N + ASM_WAVES) / ASM_WAVES)), block(64 * ASM_WAVES);
   const size_t slotd = (size_t)(hp.I + 1) * hp.RECS + hp.GPS + 24 * hp.I;
   const size_t shmem = ((ASM_WAVES + 1) * slotd + (slotd >= TILE_DBL ? 4 : 5) * TILE_DBL) * sizeof(double);
-  switch (hp.D) {
-#define G2_ASM_CASE(DD) \
-  case DD:                                                                                              \
-    if (hp.lie) k_assemble<DD, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active); \
-    else k_assemble<DD, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active);       \
-    break;
-    G2_ASM_CASE(1) G2_ASM_CASE(2) G2_ASM_CASE(3) G2_ASM_CASE(4) G2_ASM_CASE(5) G2_ASM_CASE(6) G2_ASM_CASE(7)
-#undef G2_ASM_CASE
-    default:
-      set_error("block solver is instantiated for dof <= 7");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (hp.lie) k_assemble<D, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active);
+    else k_assemble<D, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active);
+  });
 }
 
 // =============================================================================== GN step (CR)
@@ -657,44 +649,33 @@ __global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_step(const PlanParam
 
 int launch_finish_step(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st) {
   const dim3 grid(hp.B * ((hp.N + FIN_BLOCKS) / FIN_BLOCKS)), block(64 * FIN_BLOCKS);
-  switch (hp.D) {
-#define G2_FIN_CASE(DD) \
-  case DD: k_finish_step<DD><<<grid, block, 0, st>>>(pb.params, pb, pass); break;
-    G2_FIN_CASE(1) G2_FIN_CASE(2) G2_FIN_CASE(3) G2_FIN_CASE(4) G2_FIN_CASE(5) G2_FIN_CASE(6) G2_FIN_CASE(7)
-#undef G2_FIN_CASE
-    default:
-      set_error("block solver is instantiated for dof <= 7");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
+    k_finish_step<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb, pass);
+  });
 }
 
-// Chip-wide tail of an LM / GN trial step (split form of k_solve_step): as k_finish_step, but the step goes to
-// `delta`, the trial point cur (+) delta to `trial` (cur stays), and every workgroup leaves its share of g.delta,
-// |delta|^2, |g|^2 in spart for the step control (k_decide sums them in group order).
-template <int D>
-__global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_trial(const PlanParams* __restrict__ pp, PlanBuffers pb) {
+// Group tail of k_finish_trial / k_finish_trial_wide, once the workgroup (FIN_BLOCKS wavefronts, blocks
+// FIN_BLOCKS q ..) has solved its blocks: wavefront wv writes the step x of its block i = FIN_BLOCKS q + wv (x: LDS,
+// in the layout of gvec rows of stride X) to `delta` and the trial point cur (+) x to `trial` (cur stays), and the
+// workgroup leaves its share of g.delta, |delta|^2, |g|^2 in spart for the step control (k_decide sums them in group
+// order).
+template <int D, int X>
+__device__ __forceinline__ void finish_trial_group(const PlanParams& P, const PlanBuffers& pb, int b, int q,
+                                                   const double* x) {
   constexpr int n = 2 * D;
-  const PlanParams& P = *pp;
-  const int N = P.N;
-  const int groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
-  const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
-  if (!pb.active[b] || pb.stepped[b] != 1) return;
-  __shared__ double xl_[FIN_BLOCKS + 1][16];
   __shared__ double psum[FIN_BLOCKS][3];
-  const FinishGroup<D> fg(pb, N, b, q, xl_);
-  fg.solve_all(xl_);
-  const int lane = fg.lane, i = fg.i, wv = fg.wv;
+  const int N = P.N, groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int i = FIN_BLOCKS * q + wv;
   double gd = 0.0, dd = 0.0, gg = 0.0;
-  if (fg.live && lane < n) {
+  if (i <= N && lane < n) {
     const size_t k = ((size_t)b * (N + 1) + i) * n + lane;
     const double* zs = pb.cur + ((size_t)b * (N + 1) + i) * n;
-    const double x = xl_[wv][lane], gk = pb.gvec[((size_t)b * (N + 1) + i) * 16 + lane];
-    pb.delta[k] = x;
-    pb.trial[k] = (lane < D) ? retract_coord(P.lie != 0, lane, zs, xl_[wv]) : zs[lane] + x;
-    gd = gk * x;
-    dd = x * x;
+    const double xk = x[lane], gk = pb.gvec[((size_t)b * (N + 1) + i) * X + lane];
+    pb.delta[k] = xk;
+    pb.trial[k] = (lane < D) ? retract_coord(P.lie != 0, lane, zs, x) : zs[lane] + xk;
+    gd = gk * xk;
+    dd = xk * xk;
     gg = gk * gk;
   }
   gd = wave_sum(gd);
@@ -714,19 +695,26 @@ __global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_trial(const PlanPara
   }
 }
 
+// Chip-wide tail of an LM / GN trial step (split form of k_solve_step): as k_finish_step, but the step goes to
+// `delta` and the trial point to `trial` (finish_trial_group).
+template <int D>
+__global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_trial(const PlanParams* __restrict__ pp, PlanBuffers pb) {
+  const PlanParams& P = *pp;
+  const int N = P.N;
+  const int groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
+  const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
+  if (!pb.active[b] || pb.stepped[b] != 1) return;
+  __shared__ double xl_[FIN_BLOCKS + 1][16];
+  const FinishGroup<D> fg(pb, N, b, q, xl_);
+  fg.solve_all(xl_);
+  finish_trial_group<D, 16>(P, pb, b, q, xl_[fg.wv]);
+}
+
 int launch_finish_trial(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
   const dim3 grid(hp.B * ((hp.N + FIN_BLOCKS) / FIN_BLOCKS)), block(64 * FIN_BLOCKS);
-  switch (hp.D) {
-#define G2_FINT_CASE(DD) \
-  case DD: k_finish_trial<DD><<<grid, block, 0, st>>>(pb.params, pb); break;
-    G2_FINT_CASE(1) G2_FINT_CASE(2) G2_FINT_CASE(3) G2_FINT_CASE(4) G2_FINT_CASE(5) G2_FINT_CASE(6) G2_FINT_CASE(7)
-#undef G2_FINT_CASE
-    default:
-      set_error("block solver is instantiated for dof <= 7");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
+    k_finish_trial<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb);
+  });
 }
 
 int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st) {
@@ -736,57 +724,58 @@ int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hip
     set_error("total_step too large for the LDS-resident solution buffer");
     return GPMP2MI_ERR_UNSUPPORTED;
   }
-  switch (hp.D) {
-#define G2_CR_CASE(DD) \
-  case DD: k_gn_step_cr<DD><<<grid, block, shmem, st>>>(pb.params, pb, pass); break;
-    G2_CR_CASE(1) G2_CR_CASE(2) G2_CR_CASE(3) G2_CR_CASE(4) G2_CR_CASE(5) G2_CR_CASE(6) G2_CR_CASE(7)
-#undef G2_CR_CASE
-    default:
-      set_error("block solver is instantiated for dof <= 7");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
+    k_gn_step_cr<decltype(d)::value><<<grid, block, shmem, st>>>(pb.params, pb, pass);
+  });
 }
 
+#include "wide_cr.h"
 
 // =============================================================================== trial steps (LM / Dogleg)
-// block-wide deterministic sum; every thread returns the total
-__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int k = 0; k < CR_WAVES; k++) t += red[k];
-  return t;
-}
+// The two tile forms of the per-trajectory solve, for the trial-step kernel they share: wavefronts per workgroup,
+// stride X of a block's solution in LDS and of its gradient in gvec, forward and backward elimination.
+template <int D_>
+struct CrForm {   // one 16 x 16 tile per block (dof <= 7)
+  static constexpr int D = D_, n = 2 * D, WAVES = CR_WAVES, X = 16;
+  static __device__ __forceinline__ bool forward(const PlanParams& P, const PlanBuffers& pb, int b, int tid) {
+    return cr_forward<n>(pb, b, P.N, tid);
+  }
+  static __device__ __forceinline__ void backward(const PlanBuffers& pb, int b, int N, int tid, double* xs, int hmin = 1) {
+    cr_backward<n>(pb, b, N, tid, xs, hmin);
+  }
+};
+template <int D_>
+struct WcrForm {  // 2 x 2 tiles per block (8 <= dof <= 11, wide_cr.h); levels below P.wide_h0 ran in k_cr_level_wide
+  static constexpr int D = D_, n = 2 * D, WAVES = WCR_WAVES, X = WX;
+  static __device__ __forceinline__ bool forward(const PlanParams& P, const PlanBuffers& pb, int b, int tid) {
+    return wcr_forward<n>(pb, b, P.N, tid, P.wide_h0);
+  }
+  static __device__ __forceinline__ void backward(const PlanBuffers& pb, int b, int N, int tid, double* xs, int hmin = 1) {
+    wcr_backward<n>(pb, b, N, tid, xs, hmin);
+  }
+};
 
 // Solve the current linearization of every active trajectory (cyclic reduction, factors from
-// k_assemble) and form the trial point, without any accept / reject decision:
+// k_assemble / k_assemble_wide) and form the trial point, without any accept / reject decision:
 //   LM     : delta = -(H + lambda I)^-1 g,  trial = cur + delta; scalars g.delta, |delta|^2
 //            (LevenbergMarquardtOptimizer::tryLambda up to the retract)
 //   Dogleg : dx_n = -H^-1 g, dx_u = -(g.g / g^T H g) g, dogleg point for the trust radius,
 //            trial = cur + dx_d, model decrease q(dx_d)  (DoglegOptimizerImpl::ComputeDoglegPoint /
 //            ComputeBlend); phase 1 (radius halved after a rejected step) re-blends without solving
 //   GN     : as LM with lambda = 0
-template <int D>
-__global__ __launch_bounds__(64 * CR_WAVES) void k_solve_step(const PlanParams* __restrict__ pp, PlanBuffers pb) {
-  constexpr int n = 2 * D;
+// F: the block form (CrForm, WcrForm)
+template <class F>
+__global__ __launch_bounds__(64 * F::WAVES) void k_solve_step(const PlanParams* __restrict__ pp, PlanBuffers pb) {
+  constexpr int X = F::X;
   const PlanParams& P = *pp;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (!pb.active[b]) return;
   const int N = P.N;
-  const size_t tsz = (size_t)(N + 1) * n;
-  const double* cur = pb.cur + b * tsz;
-  double* trial = pb.trial + b * tsz;
-  double* delta = pb.delta + b * tsz;
   double* sc = pb.scal + (size_t)b * SC_COUNT;
-  const double* gv = pb.gvec + (size_t)b * (N + 1) * 16;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* xs = smem;
-  double* red = smem + (size_t)(N + 1) * 16;
-  int* flags = reinterpret_cast<int*>(red + CR_WAVES);
+  double* red = smem + (size_t)(N + 1) * X;
+  int* flags = reinterpret_cast<int*>(red + F::WAVES);
   const bool dogleg = P.opt_type == GPMP2MI_OPT_DOGLEG;
   const bool resolve = !(dogleg && pb.phase[b] != 0);
   if (tid == 0) {
@@ -795,7 +784,7 @@ __global__ __launch_bounds__(64 * CR_WAVES) void k_solve_step(const PlanParams* 
   }
   __syncthreads();
   if (resolve) {
-    const bool ok = cr_forward<n>(pb, b, N, tid);
+    const bool ok = F::forward(P, pb, b, tid);
     if ((!ok && (tid & 63) == 0) || (tid == 0 && pb.notspd[b])) flags[1] = 1;
     __syncthreads();
     if (flags[1]) {
@@ -804,115 +793,47 @@ __global__ __launch_bounds__(64 * CR_WAVES) void k_solve_step(const PlanParams* 
     }
     if (P.split_back && !dogleg) {
       // LM / GN: as on the Gauss-Newton fast path only the blocks that are multiples of 8 are back-substituted
-      // here; levels 4, 2, 1, the step, the trial point and the step-control sums follow chip-wide in k_finish_trial
-      cr_backward<n>(pb, b, N, tid, xs, FIN_BLOCKS);
-      double* xg = pb.xg + (size_t)b * (N + 1) * 16;
-      for (int k = tid; k < (N / FIN_BLOCKS + 1) * 16; k += blockDim.x) {
-        const size_t o = (size_t)(k >> 4) * FIN_BLOCKS * 16 + (k & 15);
+      // here; levels 4, 2, 1, the step, the trial point and the step-control sums follow chip-wide in
+      // k_finish_trial (k_finish_trial_wide)
+      F::backward(pb, b, N, tid, xs, FIN_BLOCKS);
+      double* xg = pb.xg + (size_t)b * (N + 1) * X;
+      for (int k = tid; k < (N / FIN_BLOCKS + 1) * X; k += blockDim.x) {
+        const size_t o = (size_t)(k / X) * FIN_BLOCKS * X + (k % X);
         xg[o] = xs[o];
       }
       if (tid == 0) pb.stepped[b] = 1;
       return;
     }
-    cr_backward<n>(pb, b, N, tid, xs);
-    double gd = 0.0, dd = 0.0, gg = 0.0;
-    for (size_t k = tid; k < tsz; k += blockDim.x) {
-      const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-      const double x = xs[i * 16 + rho], gk = gv[i * 16 + rho];
-      delta[k] = x;
-      gd = fma(gk, x, gd);
-      dd = fma(x, x, dd);
-      gg = fma(gk, gk, gg);
-    }
-    gd = block_sum(gd, red, tid);
-    dd = block_sum(dd, red, tid);
-    gg = block_sum(gg, red, tid);
-    if (tid == 0) {
-      sc[SC_GD] = gd;
-      sc[SC_DD] = dd;
-      sc[SC_GG] = gg;
-      sc[SC_GN] = gd;
-      sc[SC_NN] = dd;
-    }
-    if (dogleg) {
+    F::backward(pb, b, N, tid, xs);
+    if (dogleg) {   // g^T H g from the block shares of k_ghg / k_ghg_wide
       double acc = 0.0;
       for (int i = tid; i <= N; i += blockDim.x) acc += pb.hgpart[(size_t)b * P.Npad + i];
-      acc = block_sum(acc, red, tid);
+      acc = block_sum<F::WAVES>(acc, red, tid);
       if (tid == 0) sc[SC_GHG] = acc;
     }
-    __syncthreads();
   }
-  if (!dogleg) {
-    for (size_t k = tid; k < tsz; k += blockDim.x) {
-      const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-      const double* zs = cur + (size_t)i * n;
-      const double* dz = xs + i * 16;
-      trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
-    }
-    return;
-  }
-  // ---- Powell dogleg point for trust radius pb.lambda[b]
-  const double Delta = pb.lambda[b];
-  const double gg = sc[SC_GG], gHg = sc[SC_GHG], gn = sc[SC_GN], nn = sc[SC_NN];
-  const double step = -gg / gHg;          // dx_u = step * g   (optimizeGradientSearch)
-  const double uu = step * step * gg, un = step * gn;
-  const double DeltaSq = Delta * Delta;
-  double cu, cn, q;                        // dx_d = cu * g + cn * dx_n
-  if (DeltaSq < uu) {
-    const double k = sqrt(DeltaSq / uu);
-    cu = k * step;
-    cn = 0.0;
-    q = cu * gg + 0.5 * cu * cu * gHg;
-  } else if (DeltaSq < nn) {
-    const double a = uu - 2. * un + nn, bq = 2. * (un - uu), cq = uu - Delta * Delta;
-    const double sq = sqrt(bq * bq - 4 * a * cq);
-    const double tau1 = (-bq + sq) / (2. * a), tau2 = (-bq - sq) / (2. * a);
-    const double tau = (0.0 <= tau1 && tau1 <= 1.0) ? tau1 : tau2;
-    cu = (1. - tau) * step;
-    cn = tau;
-    // g^T x + 0.5 x^T H x with H dx_n = -g
-    q = cu * gg + cn * gn + 0.5 * (cu * cu * gHg - 2.0 * cu * cn * gg - cn * cn * gn);
-  } else {
-    cu = 0.0;
-    cn = 1.0;
-    q = 0.5 * gn;
-  }
-  double xn = 0.0;
-  __syncthreads();
-  for (size_t k = tid; k < tsz; k += blockDim.x) {
-    const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-    const double x = cu * gv[i * 16 + rho] + cn * delta[k];
-    xs[i * 16 + rho] = x;
-    xn = fma(x, x, xn);
-  }
-  __syncthreads();
-  for (size_t k = tid; k < tsz; k += blockDim.x) {
-    const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-    const double* zs = cur + (size_t)i * n;
-    const double* dz = xs + i * 16;
-    trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
-  }
-  xn = block_sum(xn, red, tid);
-  if (tid == 0) {
-    sc[SC_Q] = q;
-    sc[SC_XNORM] = sqrt(xn);
-  }
+  trial_step_tail<F::WAVES, X>(P, pb, b, F::n, F::D, resolve, xs, xs, pb.gvec + (size_t)b * (N + 1) * X, red, tid,
+                               blockDim.x);
 }
 
 int launch_solve_step(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
   const dim3 grid(hp.B), block(64 * CR_WAVES);
   const size_t shmem = ((size_t)(hp.N + 1) * 16 + CR_WAVES + 2) * sizeof(double);
-  switch (hp.D) {
-#define G2_SS_CASE(DD) \
-  case DD: k_solve_step<DD><<<grid, block, shmem, st>>>(pb.params, pb); break;
-    G2_SS_CASE(1) G2_SS_CASE(2) G2_SS_CASE(3) G2_SS_CASE(4) G2_SS_CASE(5) G2_SS_CASE(6) G2_SS_CASE(7)
-#undef G2_SS_CASE
-    default:
-      set_error("block solver is instantiated for dof <= 7");
-      return GPMP2MI_ERR_UNSUPPORTED;
+  return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
+    k_solve_step<CrForm<decltype(d)::value>><<<grid, block, shmem, st>>>(pb.params, pb);
+  });
+}
+
+int launch_solve_step_wide(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
+  const dim3 grid(hp.B), block(64 * WCR_WAVES);
+  const size_t shmem = ((size_t)(hp.N + 1) * WX + WCR_WAVES + 2) * sizeof(double);
+  if (shmem > 150 * 1024) {
+    set_error("total_step too large for the LDS-resident solution buffer");
+    return GPMP2MI_ERR_UNSUPPORTED;
   }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(WIDE_DOFS, hp.D, [&](auto d) {
+    k_solve_step<WcrForm<decltype(d)::value>><<<grid, block, shmem, st>>>(pb.params, pb);
+  });
 }
 
 // g^T H g, block by block: share_i = g_i^T D_i g_i + 2 g_i^T H_{i,i+1} g_{i+1} from the tiles saved by
@@ -943,17 +864,7 @@ __global__ __launch_bounds__(64) void k_ghg(const PlanParams* __restrict__ pp, P
 
 int launch_ghg(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
   const dim3 grid(hp.B * (hp.N + 1)), block(64);
-  switch (hp.D) {
-#define G2_GHG_CASE(DD) \
-  case DD: k_ghg<DD><<<grid, block, 0, st>>>(pb.params, pb); break;
-    G2_GHG_CASE(1) G2_GHG_CASE(2) G2_GHG_CASE(3) G2_GHG_CASE(4) G2_GHG_CASE(5) G2_GHG_CASE(6) G2_GHG_CASE(7)
-#undef G2_GHG_CASE
-    default:
-      set_error("block solver is instantiated for dof <= 7");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) { k_ghg<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb); });
 }
 
 // diagnostic: exercises the cross-lane helpers so tests can pin their lane semantics on hardware
@@ -974,7 +885,5 @@ int launch_debug_crosslane(const double* in, double* out, hipStream_t st) {
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
 }
-
-#include "wide_cr.h"
 
 }  // namespace g2

@@ -6,28 +6,19 @@
 // form the trial point and the step-control scalars of GN / LM / Dogleg.  The system arrives as dense
 // blocks from k_export_normal_eq: D_i in wHd, block (i+1, i) in wHo, gradient in wg.  The solve is the same
 // cyclic reduction as the tile kernels with one launch per level (k_dense_cr_level forward, k_dense_cr_back
-// backward) and a per-trajectory tail (k_dense_tail).
+// backward) and a per-trajectory tail (k_dense_tail: the trial_step_tail of plan_device.h that k_solve_step ends in).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "device_math.h"
 #include "plan.h"
+#include "plan_device.h"
 #include "tiles.h"
 
 namespace g2 {
 
 constexpr int DENSE_THREADS = 256;
 constexpr int DENSE_WAVES = DENSE_THREADS / 64;
-
-__device__ __forceinline__ double dense_block_sum(double v, double* red, int tid) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int k = 0; k < DENSE_WAVES; k++) t += red[k];
-  return t;
-}
 
 // =============================================================================== dense blocks, cyclic reduction
 // The same tree as the tile kernels (cr_kernels.hip), for blocks of any width n <= 36, with the blocks in LDS and the
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(DENSE_THREADS) void k_dense_ghg(const PlanParams* _
     const int i = (int)(e / (n * n)), r = (int)((e / n) % n), c = (int)(e % n);
     acc = fma(2.0 * gv[(size_t)(i + 1) * n + r] * Ho[e], gv[(size_t)i * n + c], acc);
   }
-  acc = dense_block_sum(acc, red, tid);
+  acc = block_sum<DENSE_WAVES>(acc, red, tid);
   if (tid == 0) pb.scal[(size_t)b * SC_COUNT + SC_GHG] = acc;
 }
 
@@ -319,100 +310,20 @@ __global__ __launch_bounds__(64) void k_dense_cr_back(const PlanParams* __restri
   if (lane < n) x[(size_t)j * n + lane] = xn[lane];
 }
 
-// step, step-control sums and the trial point from the solution the back-substitution levels left in wx
+// step, step-control sums and the trial point (trial_step_tail) from the solution the back-substitution levels left
+// in wx; g^T H g came from k_dense_ghg
 __global__ __launch_bounds__(DENSE_THREADS) void k_dense_tail(const PlanParams* __restrict__ pp, PlanBuffers pb) {
   const PlanParams& P = *pp;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (!pb.active[b]) return;
-  const int N = P.N, n = P.n, D = P.D;
-  const size_t tsz = (size_t)(N + 1) * n;
-  const double* cur = pb.cur + b * tsz;
-  double* trial = pb.trial + b * tsz;
-  double* delta = pb.delta + b * tsz;
-  double* sc = pb.scal + (size_t)b * SC_COUNT;
-  const double* gv = pb.wg + (size_t)b * tsz;
-  const double* xg = pb.wx + (size_t)b * tsz;
+  const size_t tsz = (size_t)(P.N + 1) * P.n;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* xs = smem;                       // [(N+1)][n]
   double* red = xs + tsz;                  // [DENSE_WAVES]
-  const bool dogleg = P.opt_type == GPMP2MI_OPT_DOGLEG;
-  const bool resolve = !(dogleg && pb.phase[b] != 0);
-  if (resolve) {
-    if (pb.notspd[b]) return;              // bad pivot somewhere in the tree: k_decide consumes and clears the flag
-    double gd = 0.0, dd = 0.0, gg = 0.0;
-    for (size_t k = tid; k < tsz; k += DENSE_THREADS) {
-      const double x = xg[k], gk = gv[k];
-      xs[k] = x;
-      delta[k] = x;
-      gd = fma(gk, x, gd);
-      dd = fma(x, x, dd);
-      gg = fma(gk, gk, gg);
-    }
-    gd = dense_block_sum(gd, red, tid);
-    dd = dense_block_sum(dd, red, tid);
-    gg = dense_block_sum(gg, red, tid);
-    if (tid == 0) {
-      sc[SC_GD] = gd;
-      sc[SC_DD] = dd;
-      sc[SC_GG] = gg;
-      sc[SC_GN] = gd;
-      sc[SC_NN] = dd;
-    }
-    __syncthreads();
-  }
-  if (!dogleg) {
-    for (size_t k = tid; k < tsz; k += DENSE_THREADS) {
-      const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-      const double* zs = cur + (size_t)i * n;
-      const double* dz = xs + (size_t)i * n;
-      trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
-    }
-    return;
-  }
-  // ---- Powell dogleg point for trust radius pb.lambda[b]  (same blend as k_solve_step)
-  const double Delta = pb.lambda[b];
-  const double gg = sc[SC_GG], gHg = sc[SC_GHG], gn = sc[SC_GN], nn = sc[SC_NN];
-  const double step = -gg / gHg;  // dx_u = step * g   (optimizeGradientSearch)
-  const double uu = step * step * gg, un = step * gn;
-  const double DeltaSq = Delta * Delta;
-  double cu, cn, q;  // dx_d = cu * g + cn * dx_n
-  if (DeltaSq < uu) {
-    const double k = sqrt(DeltaSq / uu);
-    cu = k * step;
-    cn = 0.0;
-    q = cu * gg + 0.5 * cu * cu * gHg;
-  } else if (DeltaSq < nn) {
-    const double a = uu - 2. * un + nn, bq = 2. * (un - uu), cq = uu - Delta * Delta;
-    const double sq = sqrt(bq * bq - 4 * a * cq);
-    const double tau1 = (-bq + sq) / (2. * a), tau2 = (-bq - sq) / (2. * a);
-    const double tau = (0.0 <= tau1 && tau1 <= 1.0) ? tau1 : tau2;
-    cu = (1. - tau) * step;
-    cn = tau;
-    q = cu * gg + cn * gn + 0.5 * (cu * cu * gHg - 2.0 * cu * cn * gg - cn * cn * gn);
-  } else {
-    cu = 0.0;
-    cn = 1.0;
-    q = 0.5 * gn;
-  }
-  double xn = 0.0;
-  __syncthreads();
-  for (size_t k = tid; k < tsz; k += DENSE_THREADS) {
-    const double x = cu * gv[k] + cn * delta[k];
-    xs[k] = x;
-    xn = fma(x, x, xn);
-  }
-  __syncthreads();
-  for (size_t k = tid; k < tsz; k += DENSE_THREADS) {
-    const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-    const double* zs = cur + (size_t)i * n;
-    const double* dz = xs + (size_t)i * n;
-    trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
-  }
-  xn = dense_block_sum(xn, red, tid);
-  if (tid == 0) {
-    sc[SC_Q] = q;
-    sc[SC_XNORM] = sqrt(xn);
-  }
+  const bool resolve = !(P.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0);
+  if (resolve && pb.notspd[b]) return;     // bad pivot somewhere in the tree: k_decide consumes and clears the flag
+  trial_step_tail<DENSE_WAVES, 0>(P, pb, b, P.n, P.D, resolve, pb.wx + b * tsz, xs, pb.wg + b * tsz, red, tid,
+                                  DENSE_THREADS);
 }
 
 // cyclic-reduction form of the dense solve: g^T H g (Dogleg), forward levels, backward levels, tail

@@ -1,8 +1,33 @@
-// dispatch.h -- runtime (kind, arm_dof) -> compile-time template instantiation.
+// dispatch.h -- runtime (kind, arm_dof) or block-solver dof -> compile-time template instantiation.
 // Every kernel that unrolls over the kinematic chain is instantiated for this table only;
 // anything else returns GPMP2MI_ERR_UNSUPPORTED.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
+
+namespace g2 {
+
+// dofs a block-solver kernel is instantiated for, and the error of any other dof
+template <int... Ds>
+struct DofList {
+  const char* unsupported;
+};
+constexpr DofList<1, 2, 3, 4, 5, 6, 7> TILE_DOFS{"block solver is instantiated for dof <= 7"};  // one 16 x 16 tile
+constexpr DofList<8, 9, 10, 11> WIDE_DOFS{"wide blocks are instantiated for 8 <= dof <= 11"};  // 2 x 2 tiles (wide_cr.h)
+
+// launch(std::integral_constant<int, D>) for the runtime dof D, then the launch check
+template <int... Ds, class Launch>
+int launch_for_dof(DofList<Ds...> dofs, int D, Launch&& launch) {
+  if (!((D == Ds && (launch(std::integral_constant<int, Ds>{}), true)) || ...)) {
+    set_error(dofs.unsupported);
+    return GPMP2MI_ERR_UNSUPPORTED;
+  }
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+}  // namespace g2
 
 #define G2_CASE2_(K, A, A2, kind, ad, ad2, STMT)                  \
   if (!done_ && (kind) == (K) && (ad) == (A) && (ad2) == (A2)) {  \

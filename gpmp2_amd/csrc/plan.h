@@ -20,9 +20,9 @@ struct PlanParams {
   int end_conf_prior_off;              // 1: no PriorFactor on x_N (a goal / workspace factor stands in)
   int wide;                            // 2 dof > 15: blocks wider than one tile (2x2-tile kernels of wide_cr.h, or the dense path of dense_kernels.hip)
   int split_back;                      // GN: back-substitution levels 1, 2 and the retract run in k_finish_step
-  int spart_groups;                    // shares per trajectory in pb.spart: workgroups of k_finish_trial(_wide), or the chunks of
+  int spart_groups;                    // shares per trajectory in pb.spart: workgroups of k_finish_trial(_wide) (finish_trial_group), or the chunks of
                                        // k_linearize_arm when it applies the trial step itself (fuse_finish)
-  int wide_h0;                         // wide blocks: first forward level k_solve_step_wide runs itself (levels below: k_cr_level_wide)
+  int wide_h0;                         // wide blocks: first forward level k_solve_step<WcrForm> runs itself (levels below: k_cr_level_wide)
   int fuse_finish;                     // GN fast path: levels 4, 2, 1 of the back-substitution and the retract run at the head of the
                                        // NEXT pass's k_linearize_arm (no k_finish_step); the state buffers cur / last swap roles every pass
   double eps, obs_w, delta_t;          // obs_w = 1 / cost_sigma^2

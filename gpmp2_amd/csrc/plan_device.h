@@ -107,6 +107,126 @@ __device__ __forceinline__ bool check_convergence(double rel, double abs_, doubl
 }
 
 
+// block-wide deterministic sum over the WAVES wavefronts of a workgroup (a wave sum, then the per-wave partials in
+// wave order); every thread returns the total.  red: WAVES doubles of LDS.
+template <int WAVES>
+__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int k = 0; k < WAVES; k++) t += red[k];
+  return t;
+}
+
+// =============================================================================== trial-step tail
+// Powell dogleg point for trust radius Delta (DoglegOptimizerImpl::ComputeDoglegPoint / ComputeBlend):
+// dx_d = cu * g + cn * dx_n with model decrease q(dx_d), from g.g, g^T H g, g.dx_n and |dx_n|^2
+__device__ __forceinline__ void dogleg_blend(double gg, double gHg, double gn, double nn, double Delta, double& cu,
+                                             double& cn, double& q) {
+  const double step = -gg / gHg;          // dx_u = step * g   (optimizeGradientSearch)
+  const double uu = step * step * gg, un = step * gn;
+  const double DeltaSq = Delta * Delta;
+  if (DeltaSq < uu) {
+    const double k = sqrt(DeltaSq / uu);
+    cu = k * step;
+    cn = 0.0;
+    q = cu * gg + 0.5 * cu * cu * gHg;
+  } else if (DeltaSq < nn) {
+    const double a = uu - 2. * un + nn, bq = 2. * (un - uu), cq = uu - Delta * Delta;
+    const double sq = sqrt(bq * bq - 4 * a * cq);
+    const double tau1 = (-bq + sq) / (2. * a), tau2 = (-bq - sq) / (2. * a);
+    const double tau = (0.0 <= tau1 && tau1 <= 1.0) ? tau1 : tau2;
+    cu = (1. - tau) * step;
+    cn = tau;
+    // g^T x + 0.5 x^T H x with H dx_n = -g
+    q = cu * gg + cn * gn + 0.5 * (cu * cu * gHg - 2.0 * cu * cn * gg - cn * cn * gn);
+  } else {
+    cu = 0.0;
+    cn = 1.0;
+    q = 0.5 * gn;
+  }
+}
+
+// The end of a trial step, shared by the block solvers (k_solve_step of both tile forms, k_dense_tail); all nthr
+// threads (WAVES wavefronts) of the trajectory's workgroup call it.  The solution x of the linearization is read from
+// xsrc and the gradient from gv, block i at offset i * X (X = 0: packed at stride n, and x is staged into xs on the
+// way).  xs (LDS) holds the step the trial point is retracted along; red: WAVES doubles of LDS.
+//   resolve (all but a Dogleg retry): delta = x and the step-control sums SC_GD, SC_DD, SC_GG, SC_GN, SC_NN (GN, NN:
+//            of the Newton step)
+//   LM / GN: trial = cur (+) x                           (LevenbergMarquardtOptimizer::tryLambda up to the retract)
+//   Dogleg : xs = dogleg point of g and delta for the trust radius pb.lambda[b] (SC_GHG must be set),
+//            trial = cur (+) xs, SC_Q, SC_XNORM
+template <int WAVES, int X>
+__device__ __forceinline__ void trial_step_tail(const PlanParams& P, const PlanBuffers& pb, int b, int n, int D,
+                                                bool resolve, const double* xsrc, double* xs, const double* gv,
+                                                double* red, int tid, int nthr) {
+  const size_t tsz = (size_t)(P.N + 1) * n;
+  const double* cur = pb.cur + b * tsz;
+  double* trial = pb.trial + b * tsz;
+  double* delta = pb.delta + b * tsz;
+  double* sc = pb.scal + (size_t)b * SC_COUNT;
+  const int xstride = X ? X : n;
+  auto off = [&](size_t k) -> size_t {   // entry k = i n + rho of the trajectory in xsrc / xs / gv
+    if constexpr (X == 0) {
+      return k;
+    } else {
+      const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
+      return i * X + rho;
+    }
+  };
+  if (resolve) {
+    double gd = 0.0, dd = 0.0, gg = 0.0;
+    for (size_t k = tid; k < tsz; k += nthr) {
+      const size_t o = off(k);
+      const double x = xsrc[o], gk = gv[o];
+      if constexpr (X == 0) xs[o] = x;
+      delta[k] = x;
+      gd = fma(gk, x, gd);
+      dd = fma(x, x, dd);
+      gg = fma(gk, gk, gg);
+    }
+    gd = block_sum<WAVES>(gd, red, tid);
+    dd = block_sum<WAVES>(dd, red, tid);
+    gg = block_sum<WAVES>(gg, red, tid);
+    if (tid == 0) {
+      sc[SC_GD] = gd;
+      sc[SC_DD] = dd;
+      sc[SC_GG] = gg;
+      sc[SC_GN] = gd;
+      sc[SC_NN] = dd;
+    }
+    __syncthreads();
+  }
+  const bool dogleg = P.opt_type == GPMP2MI_OPT_DOGLEG;
+  double q = 0.0, xn = 0.0;
+  if (dogleg) {
+    double cu, cn;
+    dogleg_blend(sc[SC_GG], sc[SC_GHG], sc[SC_GN], sc[SC_NN], pb.lambda[b], cu, cn, q);
+    __syncthreads();
+    for (size_t k = tid; k < tsz; k += nthr) {
+      const size_t o = off(k);
+      const double x = cu * gv[o] + cn * delta[k];
+      xs[o] = x;
+      xn = fma(x, x, xn);
+    }
+    __syncthreads();
+  }
+  for (size_t k = tid; k < tsz; k += nthr) {
+    const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
+    const double* zs = cur + (size_t)i * n;
+    const double* dz = xs + i * xstride;
+    trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
+  }
+  if (!dogleg) return;
+  xn = block_sum<WAVES>(xn, red, tid);
+  if (tid == 0) {
+    sc[SC_Q] = q;
+    sc[SC_XNORM] = sqrt(xn);
+  }
+}
+
 // Called by one thread of every workgroup of the kernel that closes a pass, after its own work: the last
 // workgroup to arrive publishes the pass's active count to the host-mapped flag array, so the host
 // driver learns it without a copy command or an event in the stream.

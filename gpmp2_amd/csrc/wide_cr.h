@@ -1,13 +1,14 @@
 // wide_cr.h -- cyclic reduction with blocks wider than one tile (8 <= dof <= 11, n = 2 dof <= 22).
 //
-// Included at the end of cr_kernels.hip (inside namespace g2).  A block is a 32 x 32 matrix held as
+// Included by cr_kernels.hip (inside namespace g2) after the one-tile kernels.  A block is a 32 x 32 matrix held as
 // 2 x 2 MFMA-layout tiles (WTile); element (row, col) lives in tile (row >> 4, col >> 4).  The right-hand
 // side rides in column 31.  Everything mirrors the one-tile kernels: k_assemble_wide forms the block of
 // one support state (four Assembler passes with tile offsets; the interpolated factors of Pose2 robots as
 // E^T G E congruences on the matrix cores) and eliminates the odd blocks (level 1); k_cr_level_wide runs forward
-// levels 2 and 4 chip-wide; k_solve_step_wide runs the levels above, the back-substitution down to the multiples
-// of 8 and (Dogleg) the whole trial-step tail; k_finish_trial_wide finishes the back-substitution, the step and the
-// trial point chip-wide for GN / LM (GN runs through the trial-step driver).
+// levels 2 and 4 chip-wide; k_solve_step (cr_kernels.hip, form WcrForm: wcr_forward / wcr_backward) runs the levels
+// above, the back-substitution down to the multiples of 8 and (Dogleg) the whole trial-step tail; k_finish_trial_wide
+// finishes the back-substitution, the step and the trial point chip-wide for GN / LM (GN runs through the trial-step
+// driver).
 #pragma once
 
 struct WTile {
@@ -458,20 +459,11 @@ int launch_assemble_wide(const PlanParams& hp, const PlanBuffers& pb, const doub
                          const int* active, hipStream_t st) {
   const dim3 grid(hp.B * (hp.N + 1)), block(64);
   const size_t shmem = 2 * (size_t)((hp.I + 1) * hp.RECS + hp.GPS + 24 * hp.I) * sizeof(double);
-  switch (hp.D) {
-#define G2_ASMW_CASE(DD) \
-  case DD:                                                                                      \
-    if (hp.lie) k_assemble_wide<DD, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, active); \
-    else k_assemble_wide<DD, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, active);       \
-    break;
-    G2_ASMW_CASE(8) G2_ASMW_CASE(9) G2_ASMW_CASE(10) G2_ASMW_CASE(11)
-#undef G2_ASMW_CASE
-    default:
-      set_error("wide blocks are instantiated for 8 <= dof <= 11");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(WIDE_DOFS, hp.D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (hp.lie) k_assemble_wide<D, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, active);
+    else k_assemble_wide<D, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, active);
+  });
 }
 
 // g^T H g share of block i from the blocks saved by k_assemble_wide (Dogleg)
@@ -507,20 +499,12 @@ __global__ __launch_bounds__(64) void k_ghg_wide(const PlanParams* __restrict__ 
 
 int launch_ghg_wide(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
   const dim3 grid(hp.B * (hp.N + 1)), block(64);
-  switch (hp.D) {
-#define G2_GHGW_CASE(DD) \
-  case DD: k_ghg_wide<DD><<<grid, block, 0, st>>>(pb.params, pb); break;
-    G2_GHGW_CASE(8) G2_GHGW_CASE(9) G2_GHGW_CASE(10) G2_GHGW_CASE(11)
-#undef G2_GHGW_CASE
-    default:
-      set_error("wide blocks are instantiated for 8 <= dof <= 11");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(WIDE_DOFS, hp.D, [&](auto d) {
+    k_ghg_wide<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb);
+  });
 }
 
-// =============================================================================== solve step (wide)
+// =============================================================================== cyclic reduction (wide)
 constexpr int WCR_WAVES = 8;  // 16 tiles of state per elimination: 2 wavefronts per SIMD keep 256 VGPRs each
 
 // One task of forward level h: idx < countE eliminates the idx-th odd multiple of h (E task), the others bring the
@@ -583,7 +567,7 @@ __device__ __forceinline__ bool wcr_forward(const PlanBuffers& pb, int b, int N,
 }
 
 // One forward level (never the final one) spread over the chip: one wavefront per task.  The first levels of a
-// 100-state trajectory are 51 and 26 tasks -- 7 and 4 rounds of the 8 wavefronts of k_solve_step_wide.
+// 100-state trajectory are 51 and 26 tasks -- 7 and 4 rounds of the 8 wavefronts of k_solve_step<WcrForm>.
 template <int D>
 __global__ __launch_bounds__(64, 2) void k_cr_level_wide(const PlanParams* __restrict__ pp, PlanBuffers pb, int h) {
   constexpr int n = 2 * D;
@@ -600,17 +584,9 @@ __global__ __launch_bounds__(64, 2) void k_cr_level_wide(const PlanParams* __res
 int launch_cr_level_wide(const PlanParams& hp, const PlanBuffers& pb, int h, hipStream_t st) {
   const int countE = ((hp.N / h) + 1) / 2, countU = (hp.N / (2 * h)) + 1;
   const dim3 grid(hp.B * (countE + countU)), block(64);
-  switch (hp.D) {
-#define G2_CRLW_CASE(DD) \
-  case DD: k_cr_level_wide<DD><<<grid, block, 0, st>>>(pb.params, pb, h); break;
-    G2_CRLW_CASE(8) G2_CRLW_CASE(9) G2_CRLW_CASE(10) G2_CRLW_CASE(11)
-#undef G2_CRLW_CASE
-    default:
-      set_error("wide blocks are instantiated for 8 <= dof <= 11");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_for_dof(WIDE_DOFS, hp.D, [&](auto d) {
+    k_cr_level_wide<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb, h);
+  });
 }
 
 template <int n>
@@ -643,162 +619,21 @@ __device__ __forceinline__ void wcr_backward(const PlanBuffers& pb, int b, int N
   }
 }
 
-__device__ __forceinline__ double wblock_sum(double v, double* red, int tid) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int k = 0; k < WCR_WAVES; k++) t += red[k];
-  return t;
-}
-
-// k_solve_step for wide blocks: same contract (delta, trial point, step-control scalars)
+// Chip-wide tail of an LM / GN trial step for wide blocks: one workgroup of FIN_BLOCKS (8) wavefronts per (trajectory,
+// blocks 8q .. 8q+7).  Block 8q+4 is back-substituted from x_{8q}, x_{8q+8} (level 4), then 8q+2 / 8q+6 (level 2), then
+// the odd blocks (level 1); then the step and the trial point as in k_finish_trial (finish_trial_group).
 template <int D>
-__global__ __launch_bounds__(64 * WCR_WAVES) void k_solve_step_wide(const PlanParams* __restrict__ pp, PlanBuffers pb) {
-  constexpr int n = 2 * D;
-  const PlanParams& P = *pp;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (!pb.active[b]) return;
-  const int N = P.N;
-  const size_t tsz = (size_t)(N + 1) * n;
-  const double* cur = pb.cur + b * tsz;
-  double* trial = pb.trial + b * tsz;
-  double* delta = pb.delta + b * tsz;
-  double* sc = pb.scal + (size_t)b * SC_COUNT;
-  const double* gv = pb.gvec + (size_t)b * (N + 1) * WX;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* xs = smem;
-  double* red = smem + (size_t)(N + 1) * WX;
-  int* flags = reinterpret_cast<int*>(red + WCR_WAVES);
-  const bool dogleg = P.opt_type == GPMP2MI_OPT_DOGLEG;
-  const bool resolve = !(dogleg && pb.phase[b] != 0);
-  if (tid == 0) {
-    flags[1] = 0;
-    pb.stepped[b] = 0;   // set again once the factorisation has succeeded (split form)
-  }
-  __syncthreads();
-  if (resolve) {
-    const bool ok = wcr_forward<n>(pb, b, N, tid, P.wide_h0);
-    if ((!ok && (tid & 63) == 0) || (tid == 0 && pb.notspd[b])) flags[1] = 1;
-    __syncthreads();
-    if (flags[1]) {
-      if (tid == 0) pb.notspd[b] = 1;  // k_decide consumes and clears it
-      return;
-    }
-    if (P.split_back && !dogleg) {
-      // LM / GN: only the blocks that are multiples of 8 are back-substituted here; levels 4, 2, 1, the step, the
-      // trial point and the step-control sums follow chip-wide in k_finish_trial_wide
-      wcr_backward<n>(pb, b, N, tid, xs, 8);
-      double* xg = pb.xg + (size_t)b * (N + 1) * WX;
-      for (int k = tid; k < (N / 8 + 1) * WX; k += blockDim.x) {
-        const size_t o = (size_t)(k / WX) * 8 * WX + (k % WX);
-        xg[o] = xs[o];
-      }
-      if (tid == 0) pb.stepped[b] = 1;
-      return;
-    }
-    wcr_backward<n>(pb, b, N, tid, xs);
-    double gd = 0.0, dd = 0.0, gg = 0.0;
-    for (size_t k = tid; k < tsz; k += blockDim.x) {
-      const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-      const double x = xs[i * WX + rho], gk = gv[i * WX + rho];
-      delta[k] = x;
-      gd = fma(gk, x, gd);
-      dd = fma(x, x, dd);
-      gg = fma(gk, gk, gg);
-    }
-    gd = wblock_sum(gd, red, tid);
-    dd = wblock_sum(dd, red, tid);
-    gg = wblock_sum(gg, red, tid);
-    if (tid == 0) {
-      sc[SC_GD] = gd;
-      sc[SC_DD] = dd;
-      sc[SC_GG] = gg;
-      sc[SC_GN] = gd;
-      sc[SC_NN] = dd;
-    }
-    if (dogleg) {
-      double acc = 0.0;
-      for (int i = tid; i <= N; i += blockDim.x) acc += pb.hgpart[(size_t)b * P.Npad + i];
-      acc = wblock_sum(acc, red, tid);
-      if (tid == 0) sc[SC_GHG] = acc;
-    }
-    __syncthreads();
-  }
-  if (!dogleg) {
-    for (size_t k = tid; k < tsz; k += blockDim.x) {
-      const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-      const double* zs = cur + (size_t)i * n;
-      const double* dz = xs + i * WX;
-      trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
-    }
-    return;
-  }
-  // ---- Powell dogleg point for trust radius pb.lambda[b]  (same blend as k_solve_step)
-  const double Delta = pb.lambda[b];
-  const double gg = sc[SC_GG], gHg = sc[SC_GHG], gn = sc[SC_GN], nn = sc[SC_NN];
-  const double step = -gg / gHg;
-  const double uu = step * step * gg, un = step * gn;
-  const double DeltaSq = Delta * Delta;
-  double cu, cn, q;
-  if (DeltaSq < uu) {
-    const double k = sqrt(DeltaSq / uu);
-    cu = k * step;
-    cn = 0.0;
-    q = cu * gg + 0.5 * cu * cu * gHg;
-  } else if (DeltaSq < nn) {
-    const double a = uu - 2. * un + nn, bq = 2. * (un - uu), cq = uu - Delta * Delta;
-    const double sq = sqrt(bq * bq - 4 * a * cq);
-    const double tau1 = (-bq + sq) / (2. * a), tau2 = (-bq - sq) / (2. * a);
-    const double tau = (0.0 <= tau1 && tau1 <= 1.0) ? tau1 : tau2;
-    cu = (1. - tau) * step;
-    cn = tau;
-    q = cu * gg + cn * gn + 0.5 * (cu * cu * gHg - 2.0 * cu * cn * gg - cn * cn * gn);
-  } else {
-    cu = 0.0;
-    cn = 1.0;
-    q = 0.5 * gn;
-  }
-  double xn = 0.0;
-  __syncthreads();
-  for (size_t k = tid; k < tsz; k += blockDim.x) {
-    const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-    const double x = cu * gv[i * WX + rho] + cn * delta[k];
-    xs[i * WX + rho] = x;
-    xn = fma(x, x, xn);
-  }
-  __syncthreads();
-  for (size_t k = tid; k < tsz; k += blockDim.x) {
-    const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
-    const double* zs = cur + (size_t)i * n;
-    const double* dz = xs + i * WX;
-    trial[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
-  }
-  xn = wblock_sum(xn, red, tid);
-  if (tid == 0) {
-    sc[SC_Q] = q;
-    sc[SC_XNORM] = sqrt(xn);
-  }
-}
-
-// Chip-wide tail of an LM / GN trial step for wide blocks: one workgroup of 8 wavefronts per (trajectory, blocks
-// 8q .. 8q+7).  Block 8q+4 is back-substituted from x_{8q}, x_{8q+8} (level 4), then 8q+2 / 8q+6 (level 2), then the odd
-// blocks (level 1); every wavefront then writes the step and the trial point cur (+) delta of its own state and the
-// workgroup leaves its share of g.delta, |delta|^2, |g|^2 in spart (k_decide sums them in group order).
-template <int D>
-__global__ __launch_bounds__(512) void k_finish_trial_wide(const PlanParams* __restrict__ pp, PlanBuffers pb) {
+__global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_trial_wide(const PlanParams* __restrict__ pp, PlanBuffers pb) {
   constexpr int n = 2 * D;
   const PlanParams& P = *pp;
   const int N = P.N;
-  const int groups = (N + 8) / 8;
+  const int groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
   const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
   if (!pb.active[b] || pb.stepped[b] != 1) return;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int i = 8 * q + wv;
+  const int i = FIN_BLOCKS * q + wv;
   const bool live = i <= N;
-  __shared__ double xl_[9][WX];
-  __shared__ double psum[8][3];
+  __shared__ double xl_[FIN_BLOCKS + 1][WX];
   const double* xg = pb.xg + (size_t)b * (N + 1) * WX;
   const double* f = pb.fac + ((size_t)b * (N + 1) + i) * 3 * WTILE_DBL;
   const bool has_block = live && wv != 0;
@@ -808,16 +643,17 @@ __global__ __launch_bounds__(512) void k_finish_trial_wide(const PlanParams* __r
     Wr = wtile_load_rows<n>(f + WTILE_DBL, lane);
     V = wtile_load_rows<n>(f + 2 * WTILE_DBL, lane);
   }
-  if (wv == 0 && lane < WX) xl_[0][lane] = xg[(size_t)(8 * q) * WX + lane];
-  if (wv == 1 && lane < WX) xl_[8][lane] = (8 * q + 8 <= N) ? xg[(size_t)(8 * q + 8) * WX + lane] : 0.0;
+  if (wv == 0 && lane < WX) xl_[0][lane] = xg[(size_t)(FIN_BLOCKS * q) * WX + lane];
+  if (wv == 1 && lane < WX)
+    xl_[FIN_BLOCKS][lane] = (FIN_BLOCKS * q + FIN_BLOCKS <= N) ? xg[(size_t)(FIN_BLOCKS * q + FIN_BLOCKS) * WX + lane] : 0.0;
   __syncthreads();
   auto solve = [&](int h) {
     const int jl = i - h, jr = i + h;
     double xl[2], xr[2], x[2];
 #pragma unroll
     for (int tc = 0; tc < 2; tc++) {
-      xl[tc] = (jl >= 0) ? xl_[jl - 8 * q][16 * tc + c] : 0.0;
-      xr[tc] = (jr <= N) ? xl_[jr - 8 * q][16 * tc + c] : 0.0;
+      xl[tc] = (jl >= 0) ? xl_[jl - FIN_BLOCKS * q][16 * tc + c] : 0.0;
+      xr[tc] = (jr <= N) ? xl_[jr - FIN_BLOCKS * q][16 * tc + c] : 0.0;
     }
     wcr_backsolve<n>(Wl, Wr, V, xl, xr, lane, x);
     if (g == 0) {
@@ -831,65 +667,12 @@ __global__ __launch_bounds__(512) void k_finish_trial_wide(const PlanParams* __r
   __syncthreads();
   if ((wv & 1) && live) solve(1);
   __syncthreads();
-  double gd = 0.0, dd = 0.0, gg = 0.0;
-  if (live && lane < n) {
-    const size_t k = ((size_t)b * (N + 1) + i) * n + lane;
-    const double* zs = pb.cur + ((size_t)b * (N + 1) + i) * n;
-    const double x = xl_[wv][lane], gk = pb.gvec[((size_t)b * (N + 1) + i) * WX + lane];
-    pb.delta[k] = x;
-    pb.trial[k] = (lane < D) ? retract_coord(P.lie != 0, lane, zs, xl_[wv]) : zs[lane] + x;
-    gd = gk * x;
-    dd = x * x;
-    gg = gk * gk;
-  }
-  gd = wave_sum(gd);
-  dd = wave_sum(dd);
-  gg = wave_sum(gg);
-  if (lane == 0) {
-    psum[wv][0] = gd;
-    psum[wv][1] = dd;
-    psum[wv][2] = gg;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int t = threadIdx.x;
-    double a = 0.0;
-    for (int w = 0; w < 8; w++) a += psum[w][t];
-    pb.spart[((size_t)b * groups + q) * 3 + t] = a;
-  }
+  finish_trial_group<D, WX>(P, pb, b, q, xl_[wv]);
 }
 
 int launch_finish_trial_wide(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
-  const dim3 grid(hp.B * ((hp.N + 8) / 8)), block(512);
-  switch (hp.D) {
-#define G2_FTW_CASE(DD) \
-  case DD: k_finish_trial_wide<DD><<<grid, block, 0, st>>>(pb.params, pb); break;
-    G2_FTW_CASE(8) G2_FTW_CASE(9) G2_FTW_CASE(10) G2_FTW_CASE(11)
-#undef G2_FTW_CASE
-    default:
-      set_error("wide blocks are instantiated for 8 <= dof <= 11");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
-}
-
-int launch_solve_step_wide(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
-  const dim3 grid(hp.B), block(64 * WCR_WAVES);
-  const size_t shmem = ((size_t)(hp.N + 1) * WX + WCR_WAVES + 2) * sizeof(double);
-  if (shmem > 150 * 1024) {
-    set_error("total_step too large for the LDS-resident solution buffer");
-    return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  switch (hp.D) {
-#define G2_SSW_CASE(DD) \
-  case DD: k_solve_step_wide<DD><<<grid, block, shmem, st>>>(pb.params, pb); break;
-    G2_SSW_CASE(8) G2_SSW_CASE(9) G2_SSW_CASE(10) G2_SSW_CASE(11)
-#undef G2_SSW_CASE
-    default:
-      set_error("wide blocks are instantiated for 8 <= dof <= 11");
-      return GPMP2MI_ERR_UNSUPPORTED;
-  }
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  const dim3 grid(hp.B * ((hp.N + FIN_BLOCKS) / FIN_BLOCKS)), block(64 * FIN_BLOCKS);
+  return launch_for_dof(WIDE_DOFS, hp.D, [&](auto d) {
+    k_finish_trial_wide<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb);
+  });
 }
