@@ -81,6 +81,23 @@ def make_debug_forms(forms):
     return DebugForms(**{k: int(v) for k, v in forms.items()})
 
 
+class QueueStats(C.Structure):
+    """gpmp2mi_queue_stats (include/gpmp2mi.h)."""
+    _fields_ = [("passes", C.c_int), ("slot_passes", C.c_long), ("busy_slot_passes", C.c_long)]
+
+
+def declare_queue(lib):
+    """argtypes of the queue entry points (gpmp2mi_plan_optimize_queue*, gpmp2mi_plan_queue_stats)."""
+    vp, i, d = C.c_void_p, C.c_int, c_double_p
+    ip = c_int_p
+    lib.gpmp2mi_plan_optimize_queue.argtypes = [vp, i, d, d, d, d, d, d, ip, d, ip, d]
+    lib.gpmp2mi_plan_optimize_queue.restype = i
+    lib.gpmp2mi_plan_optimize_queue_dev.argtypes = [vp, i] + [vp] * 11
+    lib.gpmp2mi_plan_optimize_queue_dev.restype = i
+    lib.gpmp2mi_plan_queue_stats.argtypes = [vp, C.POINTER(QueueStats)]
+    lib.gpmp2mi_plan_queue_stats.restype = i
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

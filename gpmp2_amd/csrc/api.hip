@@ -360,6 +360,7 @@ struct gpmp2mi_plan {
   KernelTimer timer;
   int n_active_len = 0;
   std::vector<int> h_xp_n;   // host mirror of the extra-prior counts
+  std::vector<char> goal_removed;   // 1 after gpmp2mi_plan_remove_goal until gpmp2mi_plan_change_goal (queue runs refuse it)
   PlanExtras ex;             // extra factors carried as data (host copy of the specs + device workspace)
   bool has_extras = false;
   bool problem_set = false;
@@ -372,6 +373,13 @@ struct gpmp2mi_plan {
   // plan refuses further work, and its memory is neither waited for nor recycled (a hung kernel would hang the wait,
   // a late one would write into recycled memory): it is deliberately leaked.
   bool poisoned = false;
+  // queue runs (plan_queue_impl): device workspace of the per-slot words and the pass-indexed scratch of the step
+  // kernels, grown on demand; host-mapped per-pass counts; the statistics of the last run
+  void* qws = nullptr;
+  size_t qws_bytes = 0;
+  FlagBuf qflags;
+  gpmp2mi_queue_stats qstats{};
+  bool queue_ran = false;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -405,6 +413,11 @@ struct gpmp2mi_plan {
     if (flagbuf.host) {
       g_live_flagbufs.fetch_sub(1);
       flags_release(flagbuf);
+    }
+    if (qws) (void)hipFree(qws);
+    if (qflags.host) {
+      g_live_flagbufs.fetch_sub(1);
+      flags_release(qflags);
     }
   }
 };
@@ -1261,6 +1274,7 @@ int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf
     std::vector<int> ones(B, 1);
     G2_HIP(hipMemcpy(pb.goal_on, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
     p->h_xp_n.assign(B, 0);
+    p->goal_removed.assign(B, 0);
   }
   G2_TRY(plan_alloc(p.get(), &pb.rec, (size_t)B * P.RECS * P.Ppad));
   G2_TRY(plan_alloc(p.get(), &pb.rec2, (size_t)B * P.RECS * P.Ppad));
@@ -1415,6 +1429,96 @@ static int wait_pass_count(gpmp2mi_plan* p, int pass, hipStream_t st, int* count
   return spin_wait_flag(p->h_flags + pass, true, st, wait_timeout_seconds(), count);
 }
 
+// ---- the pass bodies shared by the plain driver (plan_run_impl) and the queue driver (plan_queue_impl); `pb` is the
+// plan's buffers, or a copy whose pass-indexed arrays point elsewhere (queue runs)
+// Gauss-Newton fast path, one pass: assemble (the closing pass of a fixed-iteration round only sums the error), the
+// step kernel (step control + solve), and k_finish_step on the split path without the fused finish.  `states`: the
+// states of the pass.
+static int enqueue_gn_pass(gpmp2mi_plan* p, const PlanBuffers& pb, int pass, double* states, hipStream_t st) {
+  const PlanParams& P = p->hp;
+  const PlanForms& F = p->forms;
+  if (P.fixed_iters > 0 && pass % (P.fixed_iters + 1) == P.fixed_iters) {
+    // closing pass of a fixed-iteration run: nothing is solved any more, only the error of the final values
+    p->timer.begin("final_error", st);
+    G2_TRY(launch_error_parts(P, pb, states, 0, pb.active, st));
+  } else {
+    p->timer.begin("assemble", st);
+    G2_TRY(launch_assemble(P, pb, states, 0, pb.active, st));
+  }
+  p->timer.begin("gn_step_cr", st);
+  G2_TRY(launch_gn_step_cr(P, pb, pass, st));
+  if (F.split_back && !F.fuse_finish) {
+    p->timer.begin("finish_step", st);
+    G2_TRY(launch_finish_step(P, pb, pass, st));
+  }
+  return GPMP2MI_OK;
+}
+
+// trial-step path, one pass up to the decision: assemble (+ g^T H g) -> solve + trial point -> linearize(trial) into
+// the spare buffer
+static int enqueue_trial_pass(gpmp2mi_plan* p, const PlanBuffers& pb, hipStream_t st) {
+  const PlanParams& P = p->hp;
+  const PlanForms& F = p->forms;
+  if (F.dense) {
+    // dof 12..18, or forced for 8..11: dense normal equations + cyclic reduction over dense blocks
+    p->timer.begin("export_dense", st);
+    G2_TRY(launch_export_normal_eq(P, pb, pb.cur, 0, pb.wHd, pb.wHo, pb.wg, st, pb.active));
+    p->timer.begin("solve_dense", st);
+    G2_TRY(launch_solve_dense(P, pb, st));
+  } else if (F.wide) {
+    // blocks wider than one tile (8 <= dof <= 11): the same cyclic reduction on 2x2 tiles
+    p->timer.begin("assemble_wide", st);
+    G2_TRY(launch_assemble_wide(P, pb, pb.cur, 0, pb.active, st));
+    if (P.opt_type == GPMP2MI_OPT_DOGLEG) {
+      p->timer.begin("ghg_wide", st);
+      G2_TRY(launch_ghg_wide(P, pb, st));
+    }
+    for (int h = 2; h < P.wide_h0; h *= 2) {
+      p->timer.begin(h == 2 ? "cr_level2_wide" : "cr_level4_wide", st);
+      G2_TRY(launch_cr_level_wide(P, pb, h, st));
+    }
+    p->timer.begin("solve_step_wide", st);
+    G2_TRY(launch_solve_step_wide(P, pb, st));
+    if (F.finish_trial(P.opt_type)) {   // levels 4, 2, 1, step and trial point chip-wide
+      p->timer.begin("finish_trial_wide", st);
+      G2_TRY(launch_finish_trial_wide(P, pb, st));
+    }
+  } else {
+    p->timer.begin("assemble", st);
+    G2_TRY(launch_assemble(P, pb, pb.cur, 0, pb.active, st));
+    if (P.opt_type == GPMP2MI_OPT_DOGLEG) {
+      p->timer.begin("ghg", st);
+      G2_TRY(launch_ghg(P, pb, st));
+    }
+    p->timer.begin("solve_step", st);
+    G2_TRY(launch_solve_step(P, pb, st));
+    if (F.finish_trial(P.opt_type)) {   // levels 2, 1, step and trial point chip-wide
+      p->timer.begin("finish_trial", st);
+      G2_TRY(launch_finish_trial(P, pb, st));
+    }
+  }
+  p->timer.begin("linearize", st);
+  if (F.trial_lin_steps(P.opt_type)) {
+    // fused finish: the linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
+    return plan_linearize(p, pb.cur, 1, pb.active, st, pb.trial, 1, true);
+  }
+  return plan_linearize(p, pb.trial, 1, pb.active, st);
+}
+
+// Fused finish (F.fuse_finish): there is no k_finish_step; the linearization of pass k applies the step of pass k - 1
+// itself, reading the states of pass k - 1 from one of the plan's two state buffers and writing those of pass k to
+// the other -- cur / last swap roles every pass, the step kernel picks them by the parity of its pass number.
+static double* states_of(const gpmp2mi_plan* p, int pass) {
+  return (p->forms.fuse_finish && (pass & 1)) ? p->pb.last : p->pb.cur;
+}
+// the linearization that opens Gauss-Newton pass `pass` (fast path)
+static int enqueue_gn_lin(gpmp2mi_plan* p, int pass, hipStream_t st) {
+  p->timer.begin("linearize", st);
+  if (p->forms.fuse_finish && pass > 0)
+    return plan_linearize(p, states_of(p, pass - 1), 0, p->pb.active, st, states_of(p, pass), pass);
+  return plan_linearize(p, p->pb.cur, 0, p->pb.active, st);
+}
+
 // the optimizer driver: `cur` holds the starting values; `update`: gpmp2mi_plan_update's fixed Gauss-Newton steps
 static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start, bool update) {
   const PlanParams& P = p->hp;
@@ -1431,33 +1535,11 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start, b
     // so the GPU never waits for the host.  When pass k finished every trajectory, the enqueued linearization is a no-op
     // (all workgroups exit on active[b] == 0).
     const int max_pass = iter_cap + 1;
-    // Fused finish (F.fuse_finish): there is no k_finish_step; the linearization of pass k applies the step of pass k - 1
-    // itself, reading the states of pass k - 1 from one of the plan's two state buffers and writing those of pass k to
-    // the other -- cur / last swap roles every pass, the step kernel picks them by the parity of its pass number.
-    auto states_of = [&](int pass) -> double* { return (F.fuse_finish && (pass & 1)) ? pb.last : pb.cur; };
-    auto enqueue_lin = [&](int pass) -> int {
-      p->timer.begin("linearize", st);
-      if (F.fuse_finish && pass > 0) return plan_linearize(p, states_of(pass - 1), 0, pb.active, st, states_of(pass), pass);
-      return plan_linearize(p, pb.cur, 0, pb.active, st);
-    };
-    G2_TRY(enqueue_lin(0));
+    G2_TRY(enqueue_gn_lin(p, 0, st));
     for (int pass = 0; pass < max_pass; pass++) {
-      if (P.fixed_iters > 0 && pass == P.fixed_iters) {
-        // closing pass of a fixed-iteration run: nothing is solved any more, only the error of the final values
-        p->timer.begin("final_error", st);
-        G2_TRY(launch_error_parts(P, pb, states_of(pass), 0, pb.active, st));
-      } else {
-        p->timer.begin("assemble", st);
-        G2_TRY(launch_assemble(P, pb, states_of(pass), 0, pb.active, st));
-      }
-      p->timer.begin("gn_step_cr", st);
-      G2_TRY(launch_gn_step_cr(P, pb, pass, st));
-      if (F.split_back && !F.fuse_finish) {
-        p->timer.begin("finish_step", st);
-        G2_TRY(launch_finish_step(P, pb, pass, st));
-      }
+      G2_TRY(enqueue_gn_pass(p, pb, pass, states_of(p, pass), st));
       if (pass + 1 == max_pass) break;
-      G2_TRY(enqueue_lin(pass + 1));   // ahead of the count
+      G2_TRY(enqueue_gn_lin(p, pass + 1, st));   // ahead of the count
       p->timer.close(st);
       int cnt = 0;
       G2_TRY(wait_pass_count(p, pass, st, &cnt));
@@ -1475,51 +1557,7 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start, b
     G2_TRY(launch_decide(P, pb, 0, true, st));
     p->timer.close(st);
     for (int pass = 1; pass < max_pass; pass++) {
-      if (F.dense) {
-        // dof 12..18, or forced for 8..11: dense normal equations + cyclic reduction over dense blocks
-        p->timer.begin("export_dense", st);
-        G2_TRY(launch_export_normal_eq(P, pb, pb.cur, 0, pb.wHd, pb.wHo, pb.wg, st, pb.active));
-        p->timer.begin("solve_dense", st);
-        G2_TRY(launch_solve_dense(P, pb, st));
-      } else if (F.wide) {
-        // blocks wider than one tile (8 <= dof <= 11): the same cyclic reduction on 2x2 tiles
-        p->timer.begin("assemble_wide", st);
-        G2_TRY(launch_assemble_wide(P, pb, pb.cur, 0, pb.active, st));
-        if (P.opt_type == GPMP2MI_OPT_DOGLEG) {
-          p->timer.begin("ghg_wide", st);
-          G2_TRY(launch_ghg_wide(P, pb, st));
-        }
-        for (int h = 2; h < P.wide_h0; h *= 2) {
-          p->timer.begin(h == 2 ? "cr_level2_wide" : "cr_level4_wide", st);
-          G2_TRY(launch_cr_level_wide(P, pb, h, st));
-        }
-        p->timer.begin("solve_step_wide", st);
-        G2_TRY(launch_solve_step_wide(P, pb, st));
-        if (F.finish_trial(P.opt_type)) {   // levels 4, 2, 1, step and trial point chip-wide
-          p->timer.begin("finish_trial_wide", st);
-          G2_TRY(launch_finish_trial_wide(P, pb, st));
-        }
-      } else {
-        p->timer.begin("assemble", st);
-        G2_TRY(launch_assemble(P, pb, pb.cur, 0, pb.active, st));
-        if (P.opt_type == GPMP2MI_OPT_DOGLEG) {
-          p->timer.begin("ghg", st);
-          G2_TRY(launch_ghg(P, pb, st));
-        }
-        p->timer.begin("solve_step", st);
-        G2_TRY(launch_solve_step(P, pb, st));
-        if (F.finish_trial(P.opt_type)) {   // levels 2, 1, step and trial point chip-wide
-          p->timer.begin("finish_trial", st);
-          G2_TRY(launch_finish_trial(P, pb, st));
-        }
-      }
-      p->timer.begin("linearize", st);
-      if (F.trial_lin_steps(P.opt_type)) {
-        // fused finish: the linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
-        G2_TRY(plan_linearize(p, pb.cur, 1, pb.active, st, pb.trial, 1, true));
-      } else {
-        G2_TRY(plan_linearize(p, pb.trial, 1, pb.active, st));
-      }
+      G2_TRY(enqueue_trial_pass(p, pb, st));
       p->timer.begin("decide", st);
       G2_TRY(launch_decide(P, pb, pass, false, st));
       p->timer.close(st);
@@ -1555,6 +1593,199 @@ static int plan_run(gpmp2mi_plan* p, hipStream_t st, const double* start, bool u
   return rc;
 }
 
+// ---- queue runs (gpmp2mi_plan_optimize_queue): M problems through the B slots.  The passes are those of
+// plan_run_impl, on a copy of the plan's buffers whose pass-indexed arrays are sized for the run; after the kernel that
+// closes a pass, k_queue_scan and k_queue_refill harvest the finished slots and load the next problems, and the host
+// follows the count k_queue_scan publishes (active slots + problems not loaded yet) instead of the step kernels'.
+static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* passes_out) {
+  const PlanParams& P = p->hp;
+  const PlanForms& F = p->forms;
+  const int B = P.B;
+  const bool gn = P.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && F.gn_fast(false);
+  const int iter_cap = (P.fixed_iters > 0 ? P.fixed_iters : P.max_iter);
+  // passes one problem may take: the fast path ends every trajectory by pass iter_cap; the trial-step path gives each
+  // problem the plain run's budget of n_active_len - 2 iterative passes (its first one shares a pass with the initial
+  // evaluation), then finishes it as k_finalize_unfinished does
+  q.budget = gn ? 0 : p->n_active_len - 2;
+  const long per = gn ? iter_cap + 1 : q.budget;
+  // while problems wait, every slot is busy, so that phase takes at most M per / B passes; the last problems then
+  // take at most `per` more (fixed-iteration rounds: ceil(M / B) (iter_cap + 1))
+  const long cap_l = ((long)q.M * per + B - 1) / B + per + 2;
+  G2_CHECK(cap_l <= (1L << 26), GPMP2MI_ERR_UNSUPPORTED, "too many problems for one queue run");
+  const int cap = (int)cap_l;
+
+  // workspace: busy counter, job / next / act / fresh / qpass [B], head, then the step kernels' n_active / done /
+  // host_flags [cap] (device memory: the host reads k_queue_scan's counts instead)
+  const size_t ints = 5 * (size_t)B + 1 + 3 * (size_t)cap;
+  const size_t bytes = sizeof(long long) + ints * sizeof(int);
+  if (bytes > p->qws_bytes) {
+    if (p->qws) G2_HIP(hipFree(p->qws));
+    p->qws = nullptr;
+    p->qws_bytes = 0;
+    const hipError_t e = hipMalloc(&p->qws, bytes);
+    if (e != hipSuccess) {
+      p->qws = nullptr;
+      set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
+      return GPMP2MI_ERR_ALLOC;
+    }
+    p->qws_bytes = bytes;
+  }
+  if (p->qflags.cap < cap) {
+    if (p->qflags.host) {
+      g_live_flagbufs.fetch_sub(1);
+      flags_release(p->qflags);
+      p->qflags = FlagBuf{};
+    }
+    G2_TRY(flags_acquire(cap, &p->qflags));
+    g_live_flagbufs.fetch_add(1);
+  }
+  q.busy = (long long*)p->qws;
+  int* w = (int*)(q.busy + 1);
+  q.job = w;
+  q.next = w + B;
+  q.act = w + 2 * B;
+  q.fresh = w + 3 * B;
+  q.qpass = w + 4 * B;
+  q.head = w + 5 * B;
+  PlanBuffers qb = p->pb;
+  qb.n_active = q.head + 1;
+  qb.done = qb.n_active + cap;
+  qb.host_flags = qb.done + cap;
+  q.flags = p->qflags.dev;
+  for (int k = 0; k < cap; k++) p->qflags.host[k] = -1;   // the previous run has drained
+  G2_HIP(hipMemsetAsync(qb.n_active, 0, 3 * (size_t)cap * sizeof(int), st));
+
+  const PlanBuffers& pb = p->pb;
+  p->timer.reset();
+  G2_TRY(launch_queue_reset(P, qb, q, st));
+  G2_TRY(launch_queue_refill(P, qb, q, pb.cur, st));   // slots 0 .. min(M, B) - 1 take problems 0 ..
+  auto refill = [&](int pass, bool load, double* states) -> int {
+    p->timer.begin("queue_scan", st);
+    G2_TRY(launch_queue_scan(P, qb, q, pass, load, st));
+    p->timer.begin("queue_refill", st);
+    return launch_queue_refill(P, qb, q, states, st);
+  };
+  auto wait = [&](int pass, int* cnt) { return spin_wait_flag(p->qflags.host + pass, true, st, wait_timeout_seconds(), cnt); };
+  int passes = 0;
+  if (gn) {
+    // Gauss-Newton fast path: a fresh slot's first evaluation is the step kernel's iters == 0 branch.  A new problem's
+    // initial values go where the next pass's linearization reads the states (states_of(pass)).  Fixed-iteration plans
+    // load only at the boundary that closes a round, where the host runs k_error_parts for every slot.
+    G2_TRY(enqueue_gn_lin(p, 0, st));
+    for (int pass = 0;; pass++) {
+      G2_CHECK(pass < cap, GPMP2MI_ERR_HIP, "queue run exceeded its pass bound");
+      G2_TRY(enqueue_gn_pass(p, qb, pass, states_of(p, pass), st));
+      const bool load = P.fixed_iters == 0 || pass % (P.fixed_iters + 1) == P.fixed_iters;
+      G2_TRY(refill(pass, load, states_of(p, pass)));
+      G2_TRY(enqueue_gn_lin(p, pass + 1, st));   // ahead of the count
+      p->timer.close(st);
+      passes = pass + 1;
+      int cnt = 0;
+      G2_TRY(wait(pass, &cnt));
+      if (cnt == 0) break;
+    }
+  } else {
+    // trial-step path: the slots loaded at the last boundary (fresh) get the plain run's pass 0 -- linearization at
+    // the initial values and the decide-init -- at the head of the pass, then join its trial step
+    for (int pass = 0;; pass++) {
+      G2_CHECK(pass < cap, GPMP2MI_ERR_HIP, "queue run exceeded its pass bound");
+      p->timer.begin("linearize_fresh", st);
+      G2_TRY(plan_linearize(p, pb.cur, 0, q.fresh, st));
+      p->timer.begin("decide_fresh", st);
+      G2_TRY(launch_queue_first(P, qb, q, pass, st));
+      G2_TRY(enqueue_trial_pass(p, qb, st));
+      p->timer.begin("decide", st);
+      G2_TRY(launch_decide(P, qb, pass, false, st));
+      G2_TRY(refill(pass, true, pb.cur));
+      p->timer.close(st);
+      passes = pass + 1;
+      if (pass >= 1) {
+        int cnt = 0;
+        G2_TRY(wait(pass - 1, &cnt));
+        if (cnt == 0) {
+          passes = pass;   // this pass found nothing to do
+          break;
+        }
+      }
+    }
+  }
+  G2_HIP(hipStreamSynchronize(st));
+  if (p->timer.enabled) p->timer.collect();
+  *passes_out = passes;
+  return GPMP2MI_OK;
+}
+
+static int plan_optimize_queue(gpmp2mi_plan* p, int M, const double* sc, const double* sv, const double* ec,
+                               const double* ev, const double* init, double* traj, int* iters, double* ferr,
+                               int* status, double* trace, bool host, hipStream_t st) {
+  G2_CHECK(p, GPMP2MI_ERR_INVALID, "null plan");
+  G2_CHECK(M >= 1, GPMP2MI_ERR_INVALID, "queue: M must be >= 1");
+  G2_CHECK(sc && sv && ec && ev && init, GPMP2MI_ERR_INVALID, "queue: null input");
+  G2_CHECK(!p->poisoned, GPMP2MI_ERR_TIMEOUT,
+           "this plan timed out earlier and may still have a hung kernel in its stream: destroy it and create a new one");
+  const PlanParams& P = p->hp;
+  for (int b = 0; b < P.B; b++) {
+    G2_CHECK(p->h_xp_n[b] == 0, GPMP2MI_ERR_INVALID,
+             "queue: slot " + std::to_string(b) + " carries state priors (fix_state / add_state_estimate): clear them with "
+             "gpmp2mi_plan_clear_state_priors first");
+    G2_CHECK(!p->goal_removed[b], GPMP2MI_ERR_INVALID,
+             "queue: the goal of slot " + std::to_string(b) + " was removed (remove_goal): restore it with "
+             "gpmp2mi_plan_change_goal first");
+  }
+  const size_t md = (size_t)M * P.D, mt = (size_t)M * (P.N + 1) * P.n, mtr = (size_t)M * (P.max_iter + 1);
+  QueueRun q{};
+  q.M = M;
+  // host variant: the M problems are staged once, the results come back once
+  DevBuf<double> dsc, dsv, dec, dev, dinit, dtraj, dferr, dtrace;
+  DevBuf<int> diters, dstatus;
+  if (host) {
+    G2_TRY(dsc.upload(sc, md));
+    G2_TRY(dsv.upload(sv, md));
+    G2_TRY(dec.upload(ec, md));
+    G2_TRY(dev.upload(ev, md));
+    G2_TRY(dinit.upload(init, mt));
+    if (traj) G2_TRY(dtraj.alloc(mt));
+    if (iters) G2_TRY(diters.alloc(M));
+    if (ferr) G2_TRY(dferr.alloc(M));
+    if (status) G2_TRY(dstatus.alloc(M));
+    if (trace) G2_TRY(dtrace.alloc(mtr));
+    q.start_conf = dsc.p; q.start_vel = dsv.p; q.end_conf = dec.p; q.end_vel = dev.p; q.init = dinit.p;
+    q.traj = dtraj.p; q.iters = diters.p; q.final_err = dferr.p; q.status = dstatus.p; q.trace = dtrace.p;
+  } else {
+    q.start_conf = sc; q.start_vel = sv; q.end_conf = ec; q.end_vel = ev; q.init = init;
+    q.traj = traj; q.iters = iters; q.final_err = ferr; q.status = status; q.trace = trace;
+  }
+  // the resident problem is overwritten slot by slot
+  p->problem_set = false;
+  p->optimized = false;
+  p->queue_ran = false;
+  p->mark_dirty(st);
+  int passes = 0;
+  const int rc = plan_queue_impl(p, st, q, &passes);
+  if (rc == GPMP2MI_ERR_TIMEOUT) {
+    // as plan_run: the plan is poisoned, and the staging buffers a hung kernel may still write are leaked with it
+    p->poisoned = true;
+    for (DevBuf<double>* d : {&dsc, &dsv, &dec, &dev, &dinit, &dtraj, &dferr, &dtrace}) d->p = nullptr;
+    diters.p = dstatus.p = nullptr;
+    return rc;
+  }
+  if (rc != GPMP2MI_OK) (void)hipStreamSynchronize(st);
+  p->mark_clean(st);   // plan_queue_impl ends with a stream synchronisation as well
+  if (rc != GPMP2MI_OK) return rc;
+  p->qstats.passes = passes;
+  p->qstats.slot_passes = (long)P.B * passes;
+  G2_HIP(hipMemcpy(&p->qstats.busy_slot_passes, p->qws, sizeof(long long), hipMemcpyDeviceToHost));
+  p->queue_ran = true;
+  if (host) {
+    G2_TRY(dtraj.download(traj));
+    G2_TRY(diters.download(iters));
+    G2_TRY(dferr.download(ferr));
+    G2_TRY(dstatus.download(status));
+    G2_TRY(dtrace.download(trace));
+  }
+  return GPMP2MI_OK;
+}
+
 static int plan_get_result(gpmp2mi_plan* p, double* traj, int* iters, double* ferr, int* status,
                            double* trace, hipMemcpyKind kind, hipStream_t st) {
   G2_CHECK(p, GPMP2MI_ERR_INVALID, "null plan");
@@ -1581,6 +1812,25 @@ int gpmp2mi_plan_get_result_dev(gpmp2mi_plan* p, double* traj, int* iters, doubl
   return plan_get_result(p, traj, iters, ferr, status, nullptr, hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 const double* gpmp2mi_plan_traj_dev(const gpmp2mi_plan* p) { return p ? p->pb.result : nullptr; }
+
+int gpmp2mi_plan_optimize_queue(gpmp2mi_plan* p, int M, const double* start_conf, const double* start_vel,
+                                const double* end_conf, const double* end_vel, const double* init, double* traj,
+                                int* iters, double* final_error, int* status, double* error_trace) {
+  return plan_optimize_queue(p, M, start_conf, start_vel, end_conf, end_vel, init, traj, iters, final_error, status,
+                             error_trace, true, nullptr);
+}
+int gpmp2mi_plan_optimize_queue_dev(gpmp2mi_plan* p, int M, const double* start_conf, const double* start_vel,
+                                    const double* end_conf, const double* end_vel, const double* init, double* traj,
+                                    int* iters, double* final_error, int* status, double* error_trace, void* stream) {
+  return plan_optimize_queue(p, M, start_conf, start_vel, end_conf, end_vel, init, traj, iters, final_error, status,
+                             error_trace, false, (hipStream_t)stream);
+}
+int gpmp2mi_plan_queue_stats(const gpmp2mi_plan* p, gpmp2mi_queue_stats* out) {
+  G2_CHECK(p && out, GPMP2MI_ERR_INVALID, "null argument");
+  G2_CHECK(p->queue_ran, GPMP2MI_ERR_INVALID, "no queue run on this plan yet");
+  *out = p->qstats;
+  return GPMP2MI_OK;
+}
 
 int gpmp2mi_plan_graph_error(gpmp2mi_plan* p, const double* traj, double* err) {
   G2_CHECK(p && traj && err, GPMP2MI_ERR_INVALID, "null argument");
@@ -1672,6 +1922,7 @@ int gpmp2mi_plan_change_goal(gpmp2mi_plan* p, int b, const double* goal_conf, co
   G2_HIP(hipMemcpy(p->pb.end_conf + (size_t)b * D, goal_conf, D * sizeof(double), hipMemcpyHostToDevice));
   G2_HIP(hipMemcpy(p->pb.end_vel + (size_t)b * D, goal_vel, D * sizeof(double), hipMemcpyHostToDevice));
   G2_HIP(hipMemcpy(p->pb.goal_on + b, &one, sizeof(int), hipMemcpyHostToDevice));
+  p->goal_removed[b] = 0;
   return GPMP2MI_OK;
 }
 
@@ -1679,6 +1930,7 @@ int gpmp2mi_plan_remove_goal(gpmp2mi_plan* p, int b) {
   G2_CHECK(p && b >= 0 && b < p->hp.B, GPMP2MI_ERR_INVALID, "bad argument");
   const int zero = 0;
   G2_HIP(hipMemcpy(p->pb.goal_on + b, &zero, sizeof(int), hipMemcpyHostToDevice));
+  p->goal_removed[b] = 1;
   return GPMP2MI_OK;
 }
 

@@ -480,7 +480,8 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
     int decision = 0;  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
     double* tr = pb.trace + (size_t)b * (P.max_iter + 1);
     if (it <= P.max_iter) tr[it] = new_err;
-    if (pass == 0) {
+    // first evaluation of the slot's problem: pass 0 of a plain run; a queue run loads problems at later passes
+    if (it == 0) {
       pb.prev_err[b] = new_err;
       if (P.fixed_iters > 0) decision = 0;
       else if (new_err <= P.err_tol) { decision = 1; pb.status[b] = GPMP2MI_TRAJ_ALREADY_OPTIMAL; }

@@ -133,6 +133,33 @@ struct PlanBuffers {
   unsigned long long* stamps;  // [B][64] s_memtime stamps (diagnostic builds only)
 };
 
+// A queue run (gpmp2mi_plan_optimize_queue): M problems through the plan's B slots.  At each pass boundary
+// k_queue_scan ranks the slots whose problem finished, in slot order, and hands them the next problems;
+// k_queue_refill writes the finished problems' results to their output rows and loads the new ones.  Inputs and
+// outputs are rows of problem j; the per-slot words live in a workspace of the plan.
+struct QueueRun {
+  int M;
+  int budget;                // trial-step path: iterative passes a problem may take (plain run: n_active_len - 2); 0: none
+  const double* start_conf;  // [M][D]
+  const double* start_vel;
+  const double* end_conf;
+  const double* end_vel;
+  const double* init;        // [M][N+1][2D]
+  double* traj;              // [M][N+1][2D]  outputs; any may be null
+  int* iters;                // [M]
+  double* final_err;         // [M]
+  int* status;               // [M]
+  double* trace;             // [M][max_iter+1]
+  int* job;                  // [B] problem the slot holds, -1: none
+  int* next;                 // [B] problem the scan hands the slot at this boundary, -1: none
+  int* act;                  // [B] 1: the problem finished, harvest it; 2: its pass budget is spent (k_finalize_unfinished)
+  int* fresh;                // [B] 1: loaded at the last boundary, its first evaluation is still to come
+  int* qpass;                // [B] iterative passes of the slot's problem so far (budget)
+  int* head;                 // [1] next problem to load
+  long long* busy;           // [1] sum over passes of the slots that held a problem
+  int* flags;                // [passes] host-mapped: after each pass's scan, the active slots + problems not loaded yet
+};
+
 // scalars of a trial step (PlanBuffers::scal)
 enum { SC_GD = 0, SC_DD, SC_GG, SC_GHG, SC_GN, SC_NN, SC_Q, SC_XNORM, SC_ZERO_STEP, SC_COUNT = 16 };
 
@@ -159,6 +186,11 @@ int launch_solve_step(const PlanParams& hp, const PlanBuffers& pb, hipStream_t s
 int launch_ghg(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st);
 int launch_decide(const PlanParams& hp, const PlanBuffers& pb, int pass, bool init, hipStream_t st);
 int launch_finalize_unfinished(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st);
+// queue runs (plan_kernels.hip)
+int launch_queue_reset(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, hipStream_t st);
+int launch_queue_first(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, int pass, hipStream_t st);
+int launch_queue_scan(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, int pass, bool load, hipStream_t st);
+int launch_queue_refill(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, double* states, hipStream_t st);
 int launch_debug_crosslane(const double* in, double* out, hipStream_t st);
 int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st);
 int launch_finish_step(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st);

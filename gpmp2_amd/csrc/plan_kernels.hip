@@ -768,6 +768,19 @@ int launch_set_mode(const PlanBuffers& pb, int opt_type, int fixed_iters, hipStr
   return GPMP2MI_OK;
 }
 
+// the per-trajectory scalars of a fresh run (k_plan_reset; k_queue_refill when it loads a slot)
+__device__ __forceinline__ void reset_slot(const PlanParams& P, const PlanBuffers& pb, size_t b) {
+  pb.iters[b] = 0;
+  pb.status[b] = GPMP2MI_TRAJ_MAX_ITER;
+  pb.active[b] = 1;
+  pb.phase[b] = 0;
+  pb.which[b] = 0;
+  pb.stepped[b] = 0;
+  pb.notspd[b] = 0;
+  pb.cur_err[b] = pb.prev_err[b] = pb.last_err[b] = pb.final_err[b] = 0.0;
+  pb.lambda[b] = (P.opt_type == GPMP2MI_OPT_DOGLEG) ? P.dl_delta0 : P.lm_lambda0;
+}
+
 // reset the optimizer state before a run and load the starting values: cur = start (no separate copy command in
 // the stream); grid-stride over the flat index ranges so that no thread writes a long serial run
 __global__ __launch_bounds__(256) void k_plan_reset(const PlanParams* __restrict__ pp, PlanBuffers pb,
@@ -782,17 +795,7 @@ __global__ __launch_bounds__(256) void k_plan_reset(const PlanParams* __restrict
   for (size_t k = tid; k < (size_t)P.max_pass; k += nth) pb.n_active[k] = pb.done[k] = 0;
   for (size_t k = tid; k < B * SC_COUNT; k += nth) pb.scal[k] = 0.0;
   for (size_t k = tid; k < B * (size_t)(P.max_iter + 1); k += nth) pb.trace[k] = __longlong_as_double(0x7ff8000000000000LL);
-  for (size_t b = tid; b < B; b += nth) {
-    pb.iters[b] = 0;
-    pb.status[b] = GPMP2MI_TRAJ_MAX_ITER;
-    pb.active[b] = 1;
-    pb.phase[b] = 0;
-    pb.which[b] = 0;
-    pb.stepped[b] = 0;
-    pb.notspd[b] = 0;
-    pb.cur_err[b] = pb.prev_err[b] = pb.last_err[b] = pb.final_err[b] = 0.0;
-    pb.lambda[b] = (P.opt_type == GPMP2MI_OPT_DOGLEG) ? P.dl_delta0 : P.lm_lambda0;
-  }
+  for (size_t b = tid; b < B; b += nth) reset_slot(P, pb, b);
 }
 
 int launch_plan_reset(const PlanParams& hp, const PlanBuffers& pb, const double* start, hipStream_t st) {
@@ -1038,6 +1041,167 @@ __global__ __launch_bounds__(256) void k_finalize_unfinished(const PlanParams* _
 }
 int launch_finalize_unfinished(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
   k_finalize_unfinished<<<dim3(hp.B), dim3(256), 0, st>>>(pb.params, pb);
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+// =============================================================================== queue runs
+// Before the first pass: no slot holds a problem, slot b < M is handed problem b (k_queue_refill loads it).
+__global__ __launch_bounds__(256) void k_queue_reset(const PlanParams* __restrict__ pp, PlanBuffers pb, QueueRun q) {
+  const int B = pp->B;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    q.job[b] = -1;
+    q.act[b] = 0;
+    q.next[b] = b < q.M ? b : -1;
+    q.fresh[b] = 0;
+    q.qpass[b] = 0;
+    pb.active[b] = 0;
+  }
+  if (threadIdx.x == 0) {
+    *q.head = min(q.M, B);
+    *q.busy = 0;
+  }
+}
+int launch_queue_reset(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, hipStream_t st) {
+  k_queue_reset<<<dim3(1), dim3(256), 0, st>>>(pb.params, pb, q);
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+// Trial-step path: the decide-init of a plain run's pass 0 (error of the initial values, early exits) for the slots
+// loaded at the last boundary, after their own first linearization.
+__global__ __launch_bounds__(256) void k_queue_first(const PlanParams* __restrict__ pp, PlanBuffers pb,
+                                                     const int* __restrict__ fresh, int pass) {
+  if (!fresh[blockIdx.x]) return;
+  decide_body(*pp, pb, pass, 1);
+}
+int launch_queue_first(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, int pass, hipStream_t st) {
+  k_queue_first<<<dim3(hp.B), dim3(256), 0, st>>>(pb.params, pb, q.fresh, pass);
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+// After the kernel that closes a pass: which slots finished (act), and which problem each slot takes next.  The slots
+// that finished (and those without a problem) take the next problems in ascending slot order: rank = exclusive scan
+// of that predicate over the slots.  `load` = 0 holds the new problems back (fixed-iteration plans refill only at the
+// boundary that closes a round, so that the slots stay in lockstep).  Publishes the active slots after the refill plus
+// the problems not loaded yet; zero ends the run.  One workgroup; thread t owns the slots [t per, (t + 1) per).
+__global__ __launch_bounds__(256) void k_queue_scan(const PlanParams* __restrict__ pp, PlanBuffers pb, QueueRun q, int pass,
+                                                    int load) {
+  constexpr int NT = 256;
+  const int B = pp->B, tid = threadIdx.x;
+  const int per = (B + NT - 1) / NT, b0 = min(B, tid * per), b1 = min(B, b0 + per);
+  const int head = *q.head;
+  int elig = 0, still = 0, busy = 0;
+  for (int b = b0; b < b1; b++) {
+    const int j = q.job[b];
+    int a = 0;
+    if (j >= 0) {
+      busy++;
+      if (!pb.active[b]) {
+        a = 1;
+      } else if (q.budget > 0) {
+        const int qp = q.qpass[b] + 1;
+        q.qpass[b] = qp;
+        if (qp >= q.budget) a = 2;
+      }
+      if (!a) still++;
+    }
+    q.act[b] = a;
+    if (a || j < 0) elig++;
+  }
+  __shared__ int scan[NT];
+  __shared__ int sums[2];
+  if (tid == 0) sums[0] = sums[1] = 0;
+  scan[tid] = elig;
+  __syncthreads();
+  if (still) atomicAdd(&sums[0], still);
+  if (busy) atomicAdd(&sums[1], busy);
+  for (int d = 1; d < NT; d *= 2) {   // inclusive scan (Hillis-Steele)
+    const int v = (tid >= d) ? scan[tid - d] : 0;
+    __syncthreads();
+    scan[tid] += v;
+    __syncthreads();
+  }
+  int r = scan[tid] - elig;
+  for (int b = b0; b < b1; b++) {
+    int nj = -1;
+    if (q.act[b] || q.job[b] < 0) {
+      if (load && head + r < q.M) nj = head + r;
+      r++;
+    }
+    q.next[b] = nj;
+  }
+  if (tid == 0) {
+    const int loaded = load ? min(scan[NT - 1], q.M - head) : 0;
+    *q.head = head + loaded;
+    *q.busy += sums[1];
+    __hip_atomic_store(q.flags + pass, sums[0] + loaded + (q.M - head - loaded), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+int launch_queue_scan(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, int pass, bool load, hipStream_t st) {
+  k_queue_scan<<<dim3(1), dim3(256), 0, st>>>(pb.params, pb, q, pass, load ? 1 : 0);
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+// One workgroup per slot, after k_queue_scan.  A finished problem's result, iterations, status, final error and trace
+// row go to its output rows (act 2: the pass budget ran out, and the values are what k_finalize_unfinished would
+// leave).  A slot handed a new problem loads its start / end rows and its initial values into `states`, the buffer the
+// next pass's first kernel reads (pb.cur; on the fused Gauss-Newton path the states of the pass just closed, which
+// k_linearize_arm copies forward for a slot that did not step), and takes the per-trajectory state of a fresh run.
+__global__ __launch_bounds__(256) void k_queue_refill(const PlanParams* __restrict__ pp, PlanBuffers pb, QueueRun q,
+                                                      double* __restrict__ states) {
+  const PlanParams& P = *pp;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int a = q.act[b], nj = q.next[b];
+  if (!a && nj < 0) {
+    if (tid == 0) q.fresh[b] = 0;
+    return;
+  }
+  const int D = P.D, T = P.max_iter + 1;
+  const size_t tsz = (size_t)(P.N + 1) * P.n;
+  if (a) {
+    const size_t j = q.job[b];
+    const double* src = (a == 2 ? pb.cur : pb.result) + b * tsz;
+    if (q.traj)
+      for (size_t k = tid; k < tsz; k += blockDim.x) q.traj[j * tsz + k] = src[k];
+    if (q.trace)
+      for (int k = tid; k < T; k += blockDim.x) q.trace[j * T + k] = pb.trace[(size_t)b * T + k];
+    if (tid == 0) {
+      if (q.iters) q.iters[j] = pb.iters[b];
+      if (q.status) q.status[j] = (a == 2) ? GPMP2MI_TRAJ_MAX_ITER : pb.status[b];
+      if (q.final_err) q.final_err[j] = (a == 2) ? pb.cur_err[b] : pb.final_err[b];
+      pb.active[b] = 0;
+    }
+    __syncthreads();   // the slot's rows are read before the next problem overwrites them
+  }
+  if (nj < 0) {
+    if (tid == 0) {
+      q.job[b] = -1;
+      q.fresh[b] = 0;
+    }
+    return;
+  }
+  const size_t jn = nj;
+  if (tid < D) {
+    pb.start_conf[(size_t)b * D + tid] = q.start_conf[jn * D + tid];
+    pb.start_vel[(size_t)b * D + tid] = q.start_vel[jn * D + tid];
+    pb.end_conf[(size_t)b * D + tid] = q.end_conf[jn * D + tid];
+    pb.end_vel[(size_t)b * D + tid] = q.end_vel[jn * D + tid];
+  }
+  for (size_t k = tid; k < tsz; k += blockDim.x) states[b * tsz + k] = q.init[jn * tsz + k];
+  for (int k = tid; k < SC_COUNT; k += blockDim.x) pb.scal[(size_t)b * SC_COUNT + k] = 0.0;
+  for (int k = tid; k < T; k += blockDim.x) pb.trace[(size_t)b * T + k] = __longlong_as_double(0x7ff8000000000000LL);
+  if (tid == 0) {
+    reset_slot(P, pb, b);
+    q.job[b] = nj;
+    q.fresh[b] = 1;
+    q.qpass[b] = 0;
+  }
+}
+int launch_queue_refill(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, double* states, hipStream_t st) {
+  k_queue_refill<<<dim3(hp.B), dim3(256), 0, st>>>(pb.params, pb, q, states);
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
 }

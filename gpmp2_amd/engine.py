@@ -39,7 +39,27 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     for name in ("gpmp2mi_robot_destroy", "gpmp2mi_sdf_destroy", "gpmp2mi_plan_destroy"):
         getattr(lib, name).argtypes = [C.c_void_p]
         getattr(lib, name).restype = None
+    _capi.declare_queue(lib)
     return lib
+
+
+def queue_inputs(D, N, start_conf, start_vel, end_conf, end_vel, init):
+    """The M problems of a queue run as contiguous float64 arrays ([M][D] x 4, [M][N+1][2D]); ValueError unless every
+    input has the same number M >= 1 of rows and the plan's row shape."""
+    rows = [f64(x) for x in (start_conf, start_vel, end_conf, end_vel)]
+    t = f64(init)
+    rows = [x.reshape(1, D) if x.shape == (D,) else x for x in rows]
+    if t.shape == (N + 1, 2 * D):
+        t = t.reshape(1, N + 1, 2 * D)
+    for name, x in zip(("start_conf", "start_vel", "end_conf", "end_vel"), rows):
+        if x.ndim != 2 or x.shape[1] != D:
+            raise ValueError(f"{name}: expected [M][{D}], got {list(x.shape)}")
+    if t.ndim != 3 or t.shape[1:] != (N + 1, 2 * D):
+        raise ValueError(f"init: expected [M][{N + 1}][{2 * D}], got {list(t.shape)}")
+    M = t.shape[0]
+    if M < 1 or any(x.shape[0] != M for x in rows):
+        raise ValueError(f"queue inputs disagree on the number of problems: {[x.shape[0] for x in rows] + [M]}")
+    return M, rows, t
 
 
 class _Handle:
@@ -292,6 +312,18 @@ class Engine:
         pl.optimize()
         return pl.result()
 
+    def queue_optimize(self, robot, sdf, setting, slots, start_conf, start_vel, end_conf, end_vel, init, forms=None):
+        """M problems ([M][D] x 4, [M][N+1][2D]) through one plan of `slots` trajectories (Plan.optimize_queue): the
+        result() dict with M rows, plus the run's queue_stats() under "stats"."""
+        queue_inputs(setting.dof, setting.total_step, start_conf, start_vel, end_conf, end_vel, init)
+        pl = Plan(self, robot, sdf, setting, slots, forms)
+        try:
+            res = pl.optimize_queue(start_conf, start_vel, end_conf, end_vel, init)
+            res["stats"] = pl.queue_stats()
+        finally:
+            pl.close()
+        return res
+
 
 class Plan:
     """gpmp2mi_plan: B trajectory problems resident on the GPU.  forms (tests, probes): a dict of the kernel forms to force
@@ -342,6 +374,54 @@ class Plan:
         iters, status, ferr = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B)
         self.eng._ck(self.eng.lib.gpmp2mi_plan_get_result(self.h.ptr, None, iptr(iters), dptr(ferr), iptr(status), None))
         return iters, status, ferr
+
+    # ---- a queue of problems through the plan's B slots (gpmp2mi_plan_optimize_queue, include/gpmp2mi.h)
+    def optimize_queue(self, start_conf, start_vel, end_conf, end_vel, init):
+        """M problems ([M][D] x 4, [M][N+1][2D], host arrays): the result() dict with M rows, row j = problem j."""
+        M, (sc, sv, ec, ev), t = queue_inputs(self.D, self.N, start_conf, start_vel, end_conf, end_vel, init)
+        D, N = self.D, self.N
+        traj = np.zeros((M, N + 1, 2 * D))
+        iters, status = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        ferr, trace = np.zeros(M), np.zeros((M, self.setting.max_iter + 1))
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_optimize_queue(self.h.ptr, M, dptr(sc), dptr(sv), dptr(ec), dptr(ev),
+                                                              dptr(t), dptr(traj), iptr(iters), dptr(ferr), iptr(status),
+                                                              dptr(trace)))
+        return dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+
+    def optimize_queue_dev(self, M, start_conf, start_vel, end_conf, end_vel, init, traj=None, iters=None,
+                           final_error=None, status=None, error_trace=None, stream=None):
+        """The same on device buffers: torch tensors (checked for device, dtype, contiguity and shape) or raw device
+        pointers (ints); outputs may be None.  stream: a hipStream_t as int (e.g. torch.cuda.Stream.cuda_stream)."""
+        D, N, T = self.D, self.N, self.setting.max_iter + 1
+        M = int(M)
+        if M < 1:
+            raise ValueError("M must be >= 1")
+        shapes = [(M, D)] * 4 + [(M, N + 1, 2 * D), (M, N + 1, 2 * D), (M,), (M,), (M,), (M, T)]
+        names = ["start_conf", "start_vel", "end_conf", "end_vel", "init", "traj", "iters", "final_error", "status",
+                 "error_trace"]
+        ints = {"iters", "status"}
+        args = []
+        for name, shape, x in zip(names, shapes, (start_conf, start_vel, end_conf, end_vel, init, traj, iters,
+                                                  final_error, status, error_trace)):
+            if x is None:
+                if len(args) < 5:
+                    raise ValueError(f"{name} is required")
+                args.append(None)
+                continue
+            if hasattr(x, "data_ptr"):
+                want = "torch.int32" if name in ints else "torch.float64"
+                if str(x.dtype) != want or not x.is_contiguous() or tuple(x.shape) != shape or x.device.type != "cuda":
+                    raise ValueError(f"{name}: expected a contiguous {want} cuda tensor of shape {list(shape)}, got "
+                                     f"{x.dtype} {list(x.shape)} on {x.device}")
+                x = x.data_ptr()
+            args.append(C.c_void_p(int(x)))
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_optimize_queue_dev(self.h.ptr, M, *args, C.c_void_p(stream or 0)))
+
+    def queue_stats(self):
+        """of the last queue run: passes, slot_passes (B * passes), busy_slot_passes (slots that held a problem)."""
+        st = _capi.QueueStats()
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_queue_stats(self.h.ptr, C.byref(st)))
+        return dict(passes=st.passes, slot_passes=st.slot_passes, busy_slot_passes=st.busy_slot_passes)
 
     def traj_dev_ptr(self):
         return int(self.eng.lib.gpmp2mi_plan_traj_dev(self.h.ptr))

@@ -269,6 +269,51 @@ int gpmp2mi_plan_get_result_dev(gpmp2mi_plan* p, double* traj, int* iters, doubl
 /* device pointer to the resident [B][N+1][2D] result (valid until the plan is destroyed) */
 const double* gpmp2mi_plan_traj_dev(const gpmp2mi_plan* p);
 
+/* ---- a queue of problems through one plan -----------------------------------------------------
+ * M >= 1 independent problems of this plan's graph (BatchTrajOptimize* called M times with the plan's
+ * robot, SDF, setting and graph_opts) through its B slots.  When a slot's problem finishes, the device
+ * writes out its result and loads the next problem into the slot at the pass boundary; the host only
+ * follows the per-pass counts, as in gpmp2mi_plan_optimize.
+ * Inputs: start_conf, start_vel, end_conf, end_vel [M][D]; init [M][N+1][2D].
+ * Outputs, row j = problem j whichever slot it ran in; any may be NULL: traj [M][N+1][2D], iters [M],
+ * final_error [M], status [M], error_trace [M][max_iter+1].
+ * Contract:
+ *  - Results.  For problem j the queue returns the iters, status, final_error and error_trace that
+ *    set_problem + optimize would return for j on the same plan, and a value-identical trajectory (+0 and
+ *    -0 compare equal): the forms are chosen once per plan and no kernel mixes trajectories.
+ *  - Coverage: every plan gpmp2mi_plan_optimize accepts (GN, LM, Dogleg, fixed_iterations, all robot
+ *    kinds, narrow / wide / dense blocks, plan-level extra factors).
+ *  - Slot assignment is deterministic: at each pass boundary the slots whose problem finished take the next
+ *    problems in ascending slot order (a rank from a scan over the slots, no atomic pop).  Fixed-iteration
+ *    Gauss-Newton plans load new problems only at the boundaries that close a round of fixed_iterations + 1
+ *    passes, so that the slots stay in lockstep.
+ *  - Errors: GPMP2MI_ERR_INVALID for M < 1 or a NULL input, and for a slot that carries replanning state:
+ *    state priors (gpmp2mi_plan_fix_state / add_state_estimate; clear them with
+ *    gpmp2mi_plan_clear_state_priors) or a removed goal (gpmp2mi_plan_remove_goal; undo it with
+ *    gpmp2mi_plan_change_goal).  A goal set by change_goal alone is fine: every problem brings its own
+ *    end conf / vel.  A poisoned plan returns GPMP2MI_ERR_TIMEOUT, and a pass that times out poisons the plan
+ *    as in gpmp2mi_plan_optimize.
+ *  - Afterwards the plan holds no problem: gpmp2mi_plan_get_result returns GPMP2MI_ERR_INVALID until the
+ *    next set_problem + optimize.
+ * Host pointers: the M problems are staged on the device once and the results copied back once; the call
+ * runs on the default stream and returns when it is done. */
+int gpmp2mi_plan_optimize_queue(gpmp2mi_plan* p, int M, const double* start_conf, const double* start_vel,
+                                const double* end_conf, const double* end_vel, const double* init,
+                                double* traj, int* iters, double* final_error, int* status, double* error_trace);
+/* the same on device pointers, all work on `stream` (hipStream_t); returns once the stream has drained */
+int gpmp2mi_plan_optimize_queue_dev(gpmp2mi_plan* p, int M, const double* start_conf, const double* start_vel,
+                                    const double* end_conf, const double* end_vel, const double* init,
+                                    double* traj, int* iters, double* final_error, int* status,
+                                    double* error_trace, void* stream);
+/* of the last queue run on this plan: passes, B * passes, and the sum over passes of the slots that held a
+ * problem (GPMP2MI_ERR_INVALID before the first queue run) */
+typedef struct gpmp2mi_queue_stats {
+  int passes;
+  long slot_passes;
+  long busy_slot_passes;
+} gpmp2mi_queue_stats;
+int gpmp2mi_plan_queue_stats(const gpmp2mi_plan* p, gpmp2mi_queue_stats* out);
+
 /* ---- incremental replanning ---------------------------------------
  * The role of gpmp2::ISAM2TrajOptimizer{2DArm,3DArm,Pose2MobileArm...}
  * (planner/ISAM2TrajOptimizer.h:57-171, planner/ISAM2TrajOptimizer-inl.h:16-195; usage
