@@ -98,6 +98,33 @@ def declare_queue(lib):
     lib.gpmp2mi_plan_queue_stats.restype = i
 
 
+MAX_SHARDS = 16
+
+
+def declare_multi(lib):
+    """argtypes of the multi-device plan entry points (gpmp2mi_multi_plan_*, include/gpmp2mi.h) and their debug hooks."""
+    vp, i, d, ip = C.c_void_p, C.c_int, c_double_p, c_int_p
+    lp = C.POINTER(C.c_long)
+    decl = {
+        "gpmp2mi_multi_plan_create": [vp, vp, vp, vp, i, i, ip, vp],
+        "gpmp2mi_debug_multi_plan_create": [vp, vp, vp, vp, i, i, ip, vp, i, vp],
+        "gpmp2mi_multi_plan_shards": [vp, ip, ip, ip],
+        "gpmp2mi_multi_plan_set_problem": [vp, d, d, d, d, d],
+        "gpmp2mi_multi_plan_optimize": [vp],
+        "gpmp2mi_multi_plan_get_result": [vp, d, ip, d, ip, d],
+        "gpmp2mi_multi_plan_get_result_dev": [vp, i, vp, vp, vp, vp, vp],
+        "gpmp2mi_multi_plan_optimize_queue": [vp, i, d, d, d, d, d, d, ip, d, ip, d],
+        "gpmp2mi_multi_plan_queue_stats": [vp, i, C.POINTER(QueueStats)],
+        "gpmp2mi_debug_replica_counts": [lp, lp],
+        "gpmp2mi_debug_current_device": [i, ip],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_multi_plan_destroy.argtypes = [vp]
+    lib.gpmp2mi_multi_plan_destroy.restype = None
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

@@ -40,6 +40,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_void_p]
         getattr(lib, name).restype = None
     _capi.declare_queue(lib)
+    _capi.declare_multi(lib)
     return lib
 
 
@@ -60,6 +61,18 @@ def queue_inputs(D, N, start_conf, start_vel, end_conf, end_vel, init):
     if M < 1 or any(x.shape[0] != M for x in rows):
         raise ValueError(f"queue inputs disagree on the number of problems: {[x.shape[0] for x in rows] + [M]}")
     return M, rows, t
+
+
+def multi_plan_args(B, devices):
+    """(B, devices as a list of ints); ValueError for an empty list, more than MAX_SHARDS devices or B < len(devices)."""
+    devices = [int(x) for x in devices]
+    if not devices:
+        raise ValueError("devices must name at least one device")
+    if len(devices) > _capi.MAX_SHARDS:
+        raise ValueError(f"at most {_capi.MAX_SHARDS} shards, got {len(devices)}")
+    if int(B) < len(devices):
+        raise ValueError(f"B = {int(B)} is smaller than the number of shards ({len(devices)})")
+    return int(B), devices
 
 
 class _Handle:
@@ -290,6 +303,16 @@ class Engine:
     def plan(self, robot, sdf, setting, B, forms=None):
         return Plan(self, robot, sdf, setting, B, forms)
 
+    def multi_plan(self, robot, sdf, setting, B, devices, forms=None, replicate_all=False):
+        """B trajectories sharded over `devices` (one plan per entry, repeats allowed): MultiPlan."""
+        return MultiPlan(self, robot, sdf, setting, B, devices, forms, replicate_all)
+
+    def replica_counts(self):
+        """(robot, field) copies owned by live multi plans (gpmp2mi_debug_replica_counts)."""
+        r, s = C.c_long(), C.c_long()
+        self._ck(self.lib.gpmp2mi_debug_replica_counts(C.byref(r), C.byref(s)))
+        return r.value, s.value
+
     # graph-level helpers with the oracle's call shape; forms: see Plan
     def _plan_for(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, traj, forms=None):
         D = setting.dof
@@ -480,3 +503,93 @@ class Plan:
         launches = (C.c_int * 16)()
         self.eng._ck(self.eng.lib.gpmp2mi_plan_get_timing(self.h.ptr, C.byref(n), names, ms, launches))
         return {names[i].decode(): dict(ms=ms[i], launches=launches[i]) for i in range(min(n.value, 16))}
+
+
+class MultiPlan:
+    """gpmp2mi_multi_plan: B trajectory problems sharded over several devices of this process, one plan and one stream
+    per entry of `devices` (include/gpmp2mi.h).  Rows are in batch order everywhere; forms / replicate_all (tests): see
+    gpmp2mi_debug_multi_plan_create in include/gpmp2mi_debug.h."""
+
+    def __init__(self, eng: Engine, robot, sdf, setting, B, devices, forms=None, replicate_all=False):
+        B, devices = multi_plan_args(B, devices)
+        self.eng, self.robot, self.sdf, self.setting, self.B = eng, robot, sdf, setting, B
+        self.D, self.N, self.T = setting.dof, setting.total_step, setting.max_iter + 1
+        s, o, keep = _capi.make_settings(setting)
+        self._keep = (s, o, keep)
+        devs = np.asarray(devices, dtype=np.int32)
+        out = C.c_void_p()
+        if forms is None and not replicate_all:
+            eng._ck(eng.lib.gpmp2mi_multi_plan_create(robot.ptr, sdf.ptr, C.byref(s), C.byref(o), B, len(devices),
+                                                      iptr(devs), C.byref(out)))
+        else:
+            f = _capi.make_debug_forms(forms or {})
+            eng._ck(eng.lib.gpmp2mi_debug_multi_plan_create(robot.ptr, sdf.ptr, C.byref(s), C.byref(o), B, len(devices),
+                                                            iptr(devs), C.byref(f), int(bool(replicate_all)),
+                                                            C.byref(out)))
+        self.h = _Handle(out, eng.lib.gpmp2mi_multi_plan_destroy)
+
+    def close(self):
+        self.h.close()
+
+    def shards(self):
+        """(devices, row_begin): shard k holds rows row_begin[k] .. row_begin[k + 1] - 1."""
+        n = C.c_int()
+        devs, rb = np.zeros(_capi.MAX_SHARDS, dtype=np.int32), np.zeros(_capi.MAX_SHARDS + 1, dtype=np.int32)
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_shards(self.h.ptr, C.byref(n), iptr(devs), iptr(rb)))
+        return [int(x) for x in devs[:n.value]], [int(x) for x in rb[:n.value + 1]]
+
+    def set_problem(self, start_conf, start_vel, end_conf, end_vel, init):
+        B, (sc, sv, ec, ev), t = queue_inputs(self.D, self.N, start_conf, start_vel, end_conf, end_vel, init)
+        if B != self.B:
+            raise ValueError(f"expected {self.B} rows, got {B}")
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_set_problem(self.h.ptr, dptr(sc), dptr(sv), dptr(ec), dptr(ev),
+                                                                 dptr(t)))
+
+    def optimize(self):
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_optimize(self.h.ptr))
+
+    def result(self):
+        B, D, N = self.B, self.D, self.N
+        traj = np.zeros((B, N + 1, 2 * D))
+        iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        ferr, trace = np.zeros(B), np.zeros((B, self.T))
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_get_result(self.h.ptr, dptr(traj), iptr(iters), dptr(ferr),
+                                                                iptr(status), dptr(trace)))
+        return dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+
+    def result_dev(self, device, traj=None, iters=None, final_error=None, status=None, stream=None):
+        """Gather onto `device` (no host synchronisation): torch tensors there (checked for device, dtype, contiguity and
+        shape) or raw device pointers (ints); any may be None.  stream: a hipStream_t on `device` as int."""
+        B, D, N = self.B, self.D, self.N
+        shapes = [(B, N + 1, 2 * D), (B,), (B,), (B,)]
+        names, ints = ["traj", "iters", "final_error", "status"], {"iters", "status"}
+        args = []
+        for name, shape, x in zip(names, shapes, (traj, iters, final_error, status)):
+            if x is not None and hasattr(x, "data_ptr"):
+                want = "torch.int32" if name in ints else "torch.float64"
+                if (str(x.dtype) != want or not x.is_contiguous() or tuple(x.shape) != shape or x.device.type != "cuda"
+                        or x.device.index != int(device)):
+                    raise ValueError(f"{name}: expected a contiguous {want} tensor of shape {list(shape)} on cuda:{device},"
+                                     f" got {x.dtype} {list(x.shape)} on {x.device}")
+                x = x.data_ptr()
+            args.append(None if x is None else C.c_void_p(int(x)))
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_get_result_dev(self.h.ptr, int(device), *args,
+                                                                    C.c_void_p(stream or 0)))
+
+    def optimize_queue(self, start_conf, start_vel, end_conf, end_vel, init):
+        """M problems (host arrays), split over the shards: the result() dict with M rows, row j = problem j."""
+        M, (sc, sv, ec, ev), t = queue_inputs(self.D, self.N, start_conf, start_vel, end_conf, end_vel, init)
+        D, N = self.D, self.N
+        traj = np.zeros((M, N + 1, 2 * D))
+        iters, status = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        ferr, trace = np.zeros(M), np.zeros((M, self.T))
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_optimize_queue(self.h.ptr, M, dptr(sc), dptr(sv), dptr(ec), dptr(ev),
+                                                                    dptr(t), dptr(traj), iptr(iters), dptr(ferr),
+                                                                    iptr(status), dptr(trace)))
+        return dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+
+    def queue_stats(self, shard):
+        """of the last queue run, shard `shard`: passes, slot_passes, busy_slot_passes (zeros if it had no problems)."""
+        st = _capi.QueueStats()
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_queue_stats(self.h.ptr, int(shard), C.byref(st)))
+        return dict(passes=st.passes, slot_passes=st.slot_passes, busy_slot_passes=st.busy_slot_passes)

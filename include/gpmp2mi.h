@@ -314,6 +314,60 @@ typedef struct gpmp2mi_queue_stats {
 } gpmp2mi_queue_stats;
 int gpmp2mi_plan_queue_stats(const gpmp2mi_plan* p, gpmp2mi_queue_stats* out);
 
+/* ---- one batch sharded across several GPUs of this process ------------------------------------
+ * A multi plan owns one ordinary gpmp2mi_plan per shard, each on its own device and its own non-blocking stream, with
+ * B's rows split into contiguous shards.  The robot and the field are used on the device they
+ * were created on; every other device in `devices` gets one copy of each, owned by the multi plan (the field copy is
+ * a device-to-device copy of the voxels, re-packed there: bit-identical cells).  As with gpmp2mi_plan_create the
+ * caller keeps the robot and the field alive until the multi plan is destroyed.
+ * Contract:
+ *  - Rows.  Shard k holds batch rows [row_begin[k], row_begin[k+1]); the first B % nshards shards get one row more
+ *    (gpmp2_amd/sharding.py shard_range).  The M problems of a queue run are split by the same rule; a shard without
+ *    problems sits out, so M < nshards is fine.
+ *  - Devices may repeat ({0, 0}): every shard still has its own plan and stream.
+ *  - Results.  For every row, iters, status, final_error and error_trace are identical to those of a single-device
+ *    gpmp2mi_plan of that shard's size solving the same rows, and traj is value-identical (+0 and -0 compare equal).
+ *    The same holds against one plan of size B whenever both choose the same kernel forms: every Gauss-Newton and LM
+ *    plan.  Dogleg plans of B > 256 split into shards of <= 256 rows are the exception (the four-wavefront
+ *    linearization is taken up to 256 rows only), and agree with the one plan within the parity contract.
+ *  - Errors.  GPMP2MI_ERR_INVALID for a NULL argument, nshards outside 1..GPMP2MI_MAX_SHARDS, B < nshards, a device id
+ *    outside 0..gpmp2mi_device_count()-1 (checked after the other arguments, once a device is known to be usable),
+ *    results requested before optimize, and a NULL queue input.  A failing shard sets gpmp2mi_last_error to
+ *    "shard k (device d): <message>", the first failing shard in shard order when several fail.  A shard that times out
+ *    poisons its plan as gpmp2mi_plan_optimize does; the multi plan then returns GPMP2MI_ERR_TIMEOUT from every later
+ *    call, and gpmp2mi_multi_plan_destroy leaks what the poisoned shards may still use (their plans, streams, staging
+ *    and the copies on their devices) and frees the rest.
+ *  - The caller's current device is the same on return as on entry.
+ *  - Concurrency: shard 0 runs on the calling thread, shards 1.. on one host thread each, which spins on its plan's pass
+ *    counts like gpmp2mi_plan_optimize.  Each call returns when every shard is done, except get_result_dev. */
+#define GPMP2MI_MAX_SHARDS 16   /* one spinning host thread per shard */
+typedef struct gpmp2mi_multi_plan gpmp2mi_multi_plan;
+int gpmp2mi_multi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const gpmp2mi_settings* setting,
+                              const gpmp2mi_graph_opts* opts /*NULL ok*/, int B, int nshards, const int* devices,
+                              gpmp2mi_multi_plan** out);
+void gpmp2mi_multi_plan_destroy(gpmp2mi_multi_plan* m);   /* NULL: no-op */
+/* nshards, devices [nshards] and row_begin [nshards + 1] (row_begin[nshards] = B); devices / row_begin may be NULL */
+int gpmp2mi_multi_plan_shards(const gpmp2mi_multi_plan* m, int* nshards, int* devices, int* row_begin);
+/* host pointers, B rows as gpmp2mi_plan_set_problem */
+int gpmp2mi_multi_plan_set_problem(gpmp2mi_multi_plan* m, const double* start_conf, const double* start_vel,
+                                   const double* end_conf, const double* end_vel, const double* init);
+/* every shard concurrently; returns when all are done */
+int gpmp2mi_multi_plan_optimize(gpmp2mi_multi_plan* m);
+/* host pointers in batch order, as gpmp2mi_plan_get_result; any may be NULL */
+int gpmp2mi_multi_plan_get_result(gpmp2mi_multi_plan* m, double* traj, int* iters, double* final_error, int* status,
+                                  double* error_trace);
+/* Gather onto `device`: the outputs are device pointers there (any may be NULL).  Each shard copies its rows on its own
+ * stream (a peer copy from another device), after `stream` (hipStream_t on `device`, NULL = its default stream) has
+ * reached this call; `stream` then waits for every shard's copies.  Returns without a host synchronisation. */
+int gpmp2mi_multi_plan_get_result_dev(gpmp2mi_multi_plan* m, int device, double* traj, int* iters, double* final_error,
+                                      int* status, void* stream);
+/* M problems, host pointers as gpmp2mi_plan_optimize_queue; shard k runs its contiguous share through its plan's queue */
+int gpmp2mi_multi_plan_optimize_queue(gpmp2mi_multi_plan* m, int M, const double* start_conf, const double* start_vel,
+                                      const double* end_conf, const double* end_vel, const double* init, double* traj,
+                                      int* iters, double* final_error, int* status, double* error_trace);
+/* of the last queue run, shard `shard` (all zero for a shard that had no problems); GPMP2MI_ERR_INVALID before one */
+int gpmp2mi_multi_plan_queue_stats(const gpmp2mi_multi_plan* m, int shard, gpmp2mi_queue_stats* out);
+
 /* ---- incremental replanning ---------------------------------------
  * The role of gpmp2::ISAM2TrajOptimizer{2DArm,3DArm,Pose2MobileArm...}
  * (planner/ISAM2TrajOptimizer.h:57-171, planner/ISAM2TrajOptimizer-inl.h:16-195; usage

@@ -29,6 +29,17 @@ typedef struct gpmp2mi_debug_forms {   /* all zero = the plan's own choice */
 int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
                               const gpmp2mi_settings* setting, const gpmp2mi_graph_opts* opts /*NULL ok*/,
                               int B, const gpmp2mi_debug_forms* forms /*NULL ok*/, gpmp2mi_plan** out);
+/* gpmp2mi_multi_plan_create with `forms` forced on every shard's plan; replicate_all = 1 copies the robot and the field
+ * to every device in `devices`, the handles' own device included (so that the copy path runs on one GPU) */
+int gpmp2mi_debug_multi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
+                                    const gpmp2mi_settings* setting, const gpmp2mi_graph_opts* opts /*NULL ok*/, int B,
+                                    int nshards, const int* devices, const gpmp2mi_debug_forms* forms /*NULL ok*/,
+                                    int replicate_all, gpmp2mi_multi_plan** out);
+/* Test hook (works without a GPU): robot / field copies owned by live multi plans.  Any pointer may be NULL. */
+int gpmp2mi_debug_replica_counts(long* robots, long* sdfs);
+/* Test hook: makes set_to (>= 0) the calling thread's current device of the HIP runtime the library uses, then returns
+ * that thread's current device in *current (multi-plan calls must leave it as they found it). */
+int gpmp2mi_debug_current_device(int set_to, int* current);
 
 /* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
 int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);

@@ -19,10 +19,12 @@
 // Errors: the C ABI's status codes are rethrown as std::runtime_error, matching the reference's use of
 // exceptions.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstddef>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gpmp2mi.h"
@@ -634,6 +636,84 @@ class ISAM2TrajOptimizer {
 /// gpmp2/planner/ISAM2TrajOptimizer.h:143-156
 typedef internal::ISAM2TrajOptimizer<ArmModel, PlanarSDF> ISAM2TrajOptimizer2DArm;
 typedef internal::ISAM2TrajOptimizer<ArmModel, SignedDistanceField> ISAM2TrajOptimizer3DArm;
+
+/// B independent BatchTrajOptimize problems of one robot, field and setting, sharded over several GPUs of this process
+/// (gpmp2mi_multi_plan, include/gpmp2mi.h): shard k of `devices` holds a contiguous share of the rows, repeats allowed.
+/// The robot model and the field must outlive the planner.  Not in the reference (one problem per call there).
+class MultiDeviceBatchPlanner {
+ public:
+  template <class ROBOT, class SDF>
+  MultiDeviceBatchPlanner(const ROBOT& robot, const SDF& sdf, const TrajOptimizerSetting& setting, std::size_t B,
+                          const std::vector<int>& devices)
+      : dof_(robot.dof()), setting_(setting), B_(B) {
+    if (devices.empty()) throw std::runtime_error("[MultiDeviceBatchPlanner] devices must name at least one device");
+    const gpmp2mi_settings s = setting_.c_struct();
+    check(gpmp2mi_multi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, static_cast<int>(B),
+                                    static_cast<int>(devices.size()), devices.data(), &plan_),
+          "gpmp2mi_multi_plan_create");
+  }
+  ~MultiDeviceBatchPlanner() {
+    if (plan_) gpmp2mi_multi_plan_destroy(plan_);
+  }
+  MultiDeviceBatchPlanner(const MultiDeviceBatchPlanner&) = delete;
+  MultiDeviceBatchPlanner& operator=(const MultiDeviceBatchPlanner&) = delete;
+
+  /// B problems, one entry per problem; returns the optimized trajectories in the same order
+  std::vector<Trajectory> optimize(const std::vector<Vector>& start_conf, const std::vector<Vector>& start_vel,
+                                   const std::vector<Vector>& end_conf, const std::vector<Vector>& end_vel,
+                                   const std::vector<Trajectory>& init_values) {
+    const std::size_t D = dof_, T = (setting_.total_step + 1) * 2 * D;
+    Vector sc(B_ * D), sv(B_ * D), ec(B_ * D), ev(B_ * D), init(B_ * T);
+    auto rows = [&](const std::vector<Vector>& in, Vector& out, const char* name) {
+      if (in.size() != B_) throw std::runtime_error(std::string("[MultiDeviceBatchPlanner] ") + name + ": expected B entries");
+      for (std::size_t b = 0; b < B_; b++) {
+        if (in[b].size() != D) throw std::runtime_error(std::string("[MultiDeviceBatchPlanner] ") + name + " dim does not fit dof");
+        std::copy(in[b].begin(), in[b].end(), out.begin() + b * D);
+      }
+    };
+    rows(start_conf, sc, "start_conf");
+    rows(start_vel, sv, "start_vel");
+    rows(end_conf, ec, "end_conf");
+    rows(end_vel, ev, "end_vel");
+    if (init_values.size() != B_) throw std::runtime_error("[MultiDeviceBatchPlanner] init_values: expected B entries");
+    for (std::size_t b = 0; b < B_; b++) {
+      if (init_values[b].dof != D || init_values[b].total_step != setting_.total_step)
+        throw std::runtime_error("[MultiDeviceBatchPlanner] init_values do not match dof / total_step");
+      std::copy(init_values[b].data.begin(), init_values[b].data.end(), init.begin() + b * T);
+    }
+    check(gpmp2mi_multi_plan_set_problem(plan_, sc.data(), sv.data(), ec.data(), ev.data(), init.data()),
+          "gpmp2mi_multi_plan_set_problem");
+    check(gpmp2mi_multi_plan_optimize(plan_), "gpmp2mi_multi_plan_optimize");
+    Vector traj(B_ * T);
+    iters_.assign(B_, 0);
+    status_.assign(B_, 0);
+    check(gpmp2mi_multi_plan_get_result(plan_, traj.data(), iters_.data(), nullptr, status_.data(), nullptr),
+          "gpmp2mi_multi_plan_get_result");
+    std::vector<Trajectory> out(B_, Trajectory(D, setting_.total_step));
+    for (std::size_t b = 0; b < B_; b++) std::copy(traj.begin() + b * T, traj.begin() + (b + 1) * T, out[b].data.begin());
+    return out;
+  }
+  /// of the last optimize, per problem: GTSAM iterations() and GPMP2MI_TRAJ_* status
+  const std::vector<int>& iterations() const { return iters_; }
+  const std::vector<int>& status() const { return status_; }
+  /// shard k holds problems row_begin()[k] .. row_begin()[k + 1] - 1 on devices()[k]
+  std::vector<int> devices() const { return shards().first; }
+  std::vector<int> row_begin() const { return shards().second; }
+
+ private:
+  std::pair<std::vector<int>, std::vector<int>> shards() const {
+    int n = 0;
+    check(gpmp2mi_multi_plan_shards(plan_, &n, nullptr, nullptr), "gpmp2mi_multi_plan_shards");
+    std::vector<int> dev(n), rb(n + 1);
+    check(gpmp2mi_multi_plan_shards(plan_, &n, dev.data(), rb.data()), "gpmp2mi_multi_plan_shards");
+    return {dev, rb};
+  }
+  std::size_t dof_;
+  TrajOptimizerSetting setting_;
+  std::size_t B_;
+  gpmp2mi_multi_plan* plan_ = nullptr;
+  std::vector<int> iters_, status_;
+};
 
 #ifdef GPMP2MI_HAVE_GTSAM
 /// gtsam::Values (keys Symbol('x', i) / Symbol('v', i), gpmp2/planner/BatchTrajOptimizer.h:39-41) <-> Trajectory
