@@ -1,0 +1,287 @@
+// host.h -- what the units of the host driver (host/*.hip: the C ABI of include/gpmp2mi.h) share: the handle structs, the
+// plan, and the guards the entry points repeat.  The driver deliberately has no CPU path: every call launches kernels.
+#pragma once
+#include <algorithm>
+#include <atomic>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../common.h"
+#include "../../../include/gpmp2mi_debug.h"
+#include "../launch.h"
+#include "../plan.h"
+
+namespace g2 {
+// The thread_local last-error string is private to handles.hip: set_error (common.h) writes it, this reads it.
+const std::string& last_error();
+
+// hipMalloc with the library's error plumbing; `no_device`: the code for hipErrorNoDevice (DevBuf: the calls that may be
+// the first to touch the runtime)
+inline int dev_malloc(void** p, size_t bytes, int no_device = GPMP2MI_ERR_ALLOC) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) return GPMP2MI_OK;
+  *p = nullptr;
+  set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
+  return (e == hipErrorNoDevice) ? no_device : GPMP2MI_ERR_ALLOC;
+}
+
+// RAII device buffer used by the host-pointer convenience entry points: upload() an input, alloc() scratch, out() room
+// for an output that fetch() copies back to the caller's array (a null array is left alone)
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  T* host = nullptr;
+  size_t n = 0;
+  int alloc(size_t count) {
+    n = count;
+    return count ? dev_malloc((void**)&p, count * sizeof(T), GPMP2MI_ERR_NO_DEVICE) : GPMP2MI_OK;
+  }
+  int upload(const T* h, size_t count) {
+    G2_TRY(alloc(count));
+    if (count) G2_HIP(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
+    return GPMP2MI_OK;
+  }
+  int out(T* h, size_t count) {
+    host = h;
+    return alloc(count);
+  }
+  int fetch() const {
+    if (n && host) G2_HIP(hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost));
+    return GPMP2MI_OK;
+  }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+// the closing step of a host-array call on the null stream: wait for the kernels, then copy the outputs back
+template <class... Bufs>
+int fetch_all(const Bufs&... bufs) {
+  G2_HIP(hipStreamSynchronize(nullptr));
+  int rc = GPMP2MI_OK;
+  ((rc = rc != GPMP2MI_OK ? rc : bufs.fetch()), ...);
+  return rc;
+}
+
+// handles.hip
+int ensure_device();
+void gp_winv(double dt, double W[4]);
+GpCoef gp_coef(double dt, double tau);
+bool invert_small(int n, const double* A, double* Ainv);
+// copies of robot / field handles on other devices (multi_plan.hip) alive now: gpmp2mi_debug_replica_counts
+extern std::atomic<long> g_robot_replicas, g_sdf_replicas;
+
+}  // namespace g2
+
+struct gpmp2mi_robot {
+  g2::RobotDev h;
+  g2::RobotDev* d = nullptr;
+  int device = -1;        // the device `d` lives on (current device at creation)
+  bool replica = false;   // a multi plan's copy (robot_replica)
+  ~gpmp2mi_robot() {
+    if (d) (void)hipFree(d);
+    if (replica) g2::g_robot_replicas.fetch_sub(1);
+  }
+};
+struct gpmp2mi_sdf {
+  g2::SdfDev h;
+  double* plain = nullptr;
+  double* cells = nullptr;
+  int device = -1;        // the device `plain` / `cells` live on (current device at sdf_alloc)
+  bool replica = false;   // a multi plan's copy (sdf_replica)
+  ~gpmp2mi_sdf() {   // also runs when a create function fails half-way (unique_ptr)
+    if (plain) (void)hipFree(plain);
+    if (cells) (void)hipFree(cells);
+    if (replica) g2::g_sdf_replicas.fetch_sub(1);
+  }
+};
+
+namespace g2 {
+// geometry + device storage of a field handle; the caller fills s->plain ([nz][ny][nx]) and packs (handles.hip)
+int sdf_alloc(int dim, const double origin[3], double cell, int nx, int ny, int nz, std::unique_ptr<gpmp2mi_sdf>& s);
+
+struct KernelTimer {
+  // One HIP event per kernel boundary on the launch stream: begin(name) is recorded right before kernel `name`,
+  // close() after the last kernel of a pass; a kernel's time is the distance to the next mark.
+  bool enabled = false;
+  struct Rec {
+    const char* name;  // nullptr = closing mark
+    hipEvent_t ev;
+  };
+  std::vector<Rec> recs;
+  std::vector<std::string> names;
+  std::vector<double> ms;
+  std::vector<int> launches;
+  std::vector<const char*> cnames;
+  std::vector<hipEvent_t> pool;
+  size_t pool_used = 0;
+  hipEvent_t get() {
+    if (pool_used == pool.size()) {
+      hipEvent_t e;
+      // timing only: no system-scope fence when the event fires (the default flushes caches between the
+      // two kernels it separates)
+      (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
+      pool.push_back(e);
+    }
+    return pool[pool_used++];
+  }
+  void begin(const char* name, hipStream_t st) {
+    if (!enabled) return;
+    Rec r{name, get()};
+    (void)hipEventRecord(r.ev, st);
+    recs.push_back(r);
+  }
+  void close(hipStream_t st) { begin(nullptr, st); }
+  void reset() {
+    recs.clear();
+    pool_used = 0;
+    names.clear();
+    ms.clear();
+    launches.clear();
+  }
+  void collect();   // plan_run.hip
+  ~KernelTimer() {
+    for (auto e : pool) (void)hipEventDestroy(e);
+  }
+};
+
+// a pinned, device-mapped int array from the pool of flags_acquire / flags_release
+struct FlagBuf {
+  int* host = nullptr;
+  int* dev = nullptr;
+  int cap = 0;
+  int device = -1;   // pooled buffers are reused on the device they were mapped / allocated for only
+};
+// plan_create.hip; the pools, their mutex and the live counters are private to that unit
+int flags_acquire(int need, FlagBuf* out);
+void flags_release(const FlagBuf& f);   // a buffer that was never acquired (host == nullptr) is left alone
+
+// The kernel forms of a plan, chosen once at creation (choose_forms).  The int fields go to PlanParams (plan.h), where
+// the kernels read them; `dense` and `generic_gn` are host-only choices of the drivers in plan_run_impl.
+struct PlanForms {
+  int wide = 0, split_back = 0, wide_h0 = 2, lin_split = 1, fuse_finish = 0, spart_groups = 0;
+  bool dense = false;        // dense normal equations + cyclic reduction over dense blocks: dof 12..18, or forced for 8..11
+  bool generic_gn = false;   // forced: the plan's Gauss-Newton optimize runs through the trial-step driver
+  // Gauss-Newton takes the fast driver (3 launches per pass) on every plan that is not wide; a forced generic GN sends
+  // only the plan's own optimize through the trial-step driver, not plan_update
+  bool gn_fast(bool update) const { return !wide && (update || !generic_gn); }
+  // trial-step driver, LM / GN (Dogleg's step kernel does the whole back-substitution): k_finish_trial(_wide) finishes
+  // the step, or the trial linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
+  bool finish_trial(int opt) const { return split_back && opt != GPMP2MI_OPT_DOGLEG && !fuse_finish; }
+  bool trial_lin_steps(int opt) const { return fuse_finish && opt != GPMP2MI_OPT_DOGLEG; }
+};
+}  // namespace g2
+
+struct gpmp2mi_plan {
+  const gpmp2mi_robot* robot = nullptr;
+  const gpmp2mi_sdf* sdf = nullptr;
+  g2::PlanParams hp;
+  g2::PlanForms forms;         // the kernel forms chosen at creation (choose_forms); hp carries the device-visible ones
+  g2::PlanBuffers pb;
+  std::vector<void*> allocs;   // arena chunks (plan_alloc)
+  std::vector<size_t> alloc_bytes;
+  char* arena_cur = nullptr;   // bump pointer into the newest chunk
+  size_t arena_left = 0;
+  int alloc_calls = 0;         // plan_alloc calls so far
+  int fail_alloc_at = 0;       // gpmp2mi_debug_forms::fail_alloc_at: the k-th plan_alloc call fails (0: none)
+  int device = -1;             // the device the plan was created on: its chunks / flags go back to that device's pools
+  g2::FlagBuf flagbuf;
+  int* h_flags = nullptr;    // pinned + device-mapped [n_active_len]: per-pass active count, -1 = not yet known
+  g2::KernelTimer timer;
+  int n_active_len = 0;
+  std::vector<int> h_xp_n;   // host mirror of the extra-prior counts
+  std::vector<char> goal_removed;   // 1 after gpmp2mi_plan_remove_goal until gpmp2mi_plan_change_goal (queue runs refuse it)
+  g2::PlanExtras ex;         // extra factors carried as data (host copy of the specs + device workspace)
+  bool has_extras = false;
+  bool problem_set = false;
+  bool optimized = false;
+  // Streams that may still carry work of this plan (asynchronous copies / kernels enqueued without a closing
+  // synchronisation).  gpmp2mi_plan_destroy waits for exactly these, never for the whole device.
+  std::vector<hipStream_t> dirty_streams;
+  bool null_stream_dirty = false;
+  // A pass that did not finish within GPMP2MI_WAIT_TIMEOUT_MS: the stream may hold a hung kernel of this plan.  The
+  // plan refuses further work, and its memory is neither waited for nor recycled (a hung kernel would hang the wait,
+  // a late one would write into recycled memory): it is deliberately leaked.
+  bool poisoned = false;
+  // queue runs (plan_queue_impl): device workspace of the per-slot words and the pass-indexed scratch of the step
+  // kernels, grown on demand; host-mapped per-pass counts; the statistics of the last run
+  void* qws = nullptr;
+  size_t qws_bytes = 0;
+  g2::FlagBuf qflags;
+  gpmp2mi_queue_stats qstats{};
+  bool queue_ran = false;
+  size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
+  void mark_dirty(hipStream_t st) {
+    if (!st) { null_stream_dirty = true; return; }
+    if (std::find(dirty_streams.begin(), dirty_streams.end(), st) == dirty_streams.end()) dirty_streams.push_back(st);
+  }
+  void mark_clean(hipStream_t st) {
+    if (!st) { null_stream_dirty = false; return; }
+    dirty_streams.erase(std::remove(dirty_streams.begin(), dirty_streams.end(), st), dirty_streams.end());
+  }
+  // closes a group of copies enqueued on `st`: host-side ones are waited for, device-side ones leave the stream dirty
+  int close_copies(hipMemcpyKind kind, hipStream_t st) {
+    mark_dirty(st);
+    if (kind == hipMemcpyDeviceToDevice) return GPMP2MI_OK;
+    G2_HIP(hipStreamSynchronize(st));
+    mark_clean(st);
+    return GPMP2MI_OK;
+  }
+  // wait for whatever this plan still has in flight (a no-op after the usual optimize -> get_result sequence)
+  void drain() {
+    if (poisoned) return;
+    for (hipStream_t st : dirty_streams) (void)hipStreamSynchronize(st);
+    dirty_streams.clear();
+    if (null_stream_dirty) (void)hipStreamSynchronize(nullptr);
+    null_stream_dirty = false;
+  }
+  ~gpmp2mi_plan();   // plan_create.hip, next to the pools it returns the plan's memory to
+};
+
+// The liveness guards: a plan (a multi plan) whose pass timed out refuses further work.  They stand in the entry points
+// after the null-argument checks.
+#define G2_PLAN_LIVE(p)                         \
+  G2_CHECK(!(p)->poisoned, GPMP2MI_ERR_TIMEOUT, \
+           "this plan timed out earlier and may still have a hung kernel in its stream: destroy it and create a new one")
+#define G2_MULTI_LIVE(m)                                                                                            \
+  do {                                                                                                              \
+    G2_CHECK(m, GPMP2MI_ERR_INVALID, "null multi plan");                                                            \
+    G2_CHECK(!(m)->poisoned, GPMP2MI_ERR_TIMEOUT,                                                                   \
+             "a shard of this multi plan timed out earlier and may still have a hung kernel: destroy it and create a new one"); \
+  } while (0)
+
+namespace g2 {
+// restores the calling thread's current device on scope exit (multi-plan calls switch devices shard by shard)
+struct DeviceGuard {
+  int dev = -1;
+  DeviceGuard() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
+  ~DeviceGuard() { if (dev >= 0) (void)hipSetDevice(dev); }
+};
+
+// Device staging of M problems of a queue run given in host arrays `io`: one slab, the ten arrays of a QueueRun carved
+// out of it (doubles first, ints after; an output the caller does not ask for gets no room).  upload / download copy rows
+// [j, j + M) of the caller's arrays on a stream; the caller synchronises.
+struct QueueStage {
+  QueueStage() = default;
+  QueueStage(const QueueStage&) = delete;   // owns `base`
+  void* base = nullptr;
+  QueueRun q{};   // M and the ten array pointers
+  size_t D = 0, tr = 0, T = 0;
+  int alloc(int M, const QueueRun& io, int D_, size_t trow, int T_);
+  int upload(const QueueRun& io, size_t j, hipStream_t st) const;
+  int download(const QueueRun& io, size_t j, hipStream_t st) const;
+  void leak() { base = nullptr; }   // a hung kernel may still write the slab: it goes with the poisoned plan
+  void release() {                  // hipFree waits for the whole device
+    if (base) (void)hipFree(base);
+    base = nullptr;
+  }
+  ~QueueStage() { release(); }
+};
+
+// plan_run.hip
+int plan_set_problem(gpmp2mi_plan* p, const double* sc, const double* sv, const double* ec, const double* ev,
+                     const double* init, hipMemcpyKind kind, hipStream_t st);
+int plan_get_result(gpmp2mi_plan* p, double* traj, int* iters, double* ferr, int* status, double* trace,
+                    hipMemcpyKind kind, hipStream_t st);
+// `io`: M and the ten arrays of the queue run; `host`: they are host arrays, staged here
+int plan_optimize_queue(gpmp2mi_plan* p, QueueRun io, bool host, hipStream_t st);
+int spin_wait_flag(const volatile int* flag, bool st_valid, hipStream_t st, double timeout_s, int* count);
+}  // namespace g2

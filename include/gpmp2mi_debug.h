@@ -15,8 +15,8 @@
 extern "C" {
 #endif
 
-/* Forms a plan would otherwise choose for itself (api.hip choose_forms).  The forms agree to rounding, not always bit for
- * bit.  A forced form the plan cannot take is refused with GPMP2MI_ERR_UNSUPPORTED. */
+/* Forms a plan would otherwise choose for itself (host/plan_create.hip choose_forms).  The forms agree to rounding, not
+ * always bit for bit.  A forced form the plan cannot take is refused with GPMP2MI_ERR_UNSUPPORTED. */
 typedef struct gpmp2mi_debug_forms {   /* all zero = the plan's own choice */
   int lin_split;        /* 1, 2, 4: force the fixed-base-arm linearization form (2 and 4: fixed-base arms only;
                            4: obs_check_inter >= 2) */

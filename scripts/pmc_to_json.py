@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def kernel_sources_digest(root=ROOT):
-    """sha1 over the device sources (gpmp2_amd/csrc/*.hip and *.h, api.hip -- the host driver -- left out): what a stored
-    traffic profile is valid for.  bench.py computes the same digest of the tree it runs from."""
+    """sha1 over the device sources (the *.hip and *.h directly in gpmp2_amd/csrc; the host driver, csrc/host, is left
+    out): what a stored traffic profile is valid for.  bench.py computes the same digest of the tree it runs from."""
     h = hashlib.sha1()
     src = os.path.join(root, "gpmp2_amd", "csrc")
     for f in sorted(os.listdir(src)):
