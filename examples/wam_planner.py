@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's matlab/WAMPlannerExample.m with gpmp2_amd: 7-DOF WAM arm in the desk scene, signed distance
-field built on the GPU, batch trajectory optimisation, dense up-sampling, collision cost, then one replanning
-step (matlab/WAMReplannerExample.m:102-126).  Runs on an MI355X; there is no CPU path."""
+field built on the GPU, batch trajectory optimisation, dense up-sampling, collision cost, dense collision check and best-of-restarts
+selection on the device, then one replanning step (matlab/WAMReplannerExample.m:102-126).  Runs on an MI355X; there is no CPU path."""
 import os
 import sys
 import time
@@ -10,6 +10,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import gpmp2_amd as g
+from gpmp2_amd import engine
 
 # ---- scene: occupancy grid -> signed distance field (both on the device)
 dataset = g.generate3Ddataset("WAMDeskDataset")
@@ -47,6 +48,31 @@ print(f"BatchTrajOptimize3DArm: {1e3 * (time.perf_counter() - t0):.1f} ms, "
       f"collision cost {g.CollisionCost3DArm(arm, sdf, result, opt_setting):.4f}")
 dense = g.interpolateArmTraj(result, opt_setting.Qc, total_time_sec / total_time_step, 9)
 print(f"up-sampled to {len(dense) // 2} states; x_50 = {np.round(dense[('x', 50)], 3)}")
+
+# ---- what gets executed: the up-sampled states, checked on the device (the support states alone can look clean)
+print(f"dense collision cost {g.DenseCollisionCost3DArm(arm, sdf, result, opt_setting, 9):.4f}, minimum clearance "
+      "%.4f m at checked state %d, sphere %d" % g.MinClearance3DArm(arm, sdf, result, opt_setting, 9))
+
+# ---- restarts: 16 perturbed initial trajectories in one plan, then pick the one to execute on the device
+eng, B = engine.Engine(), 16
+straight = g.initArmTrajStraightLine(start_conf, end_conf, total_time_step)
+inits = np.repeat(straight[None], B, axis=0)
+bump = np.sin(np.pi * np.arange(total_time_step + 1) / total_time_step)
+for b in range(1, B):
+    inits[b, :, :7] += bump[:, None] * np.random.default_rng(1234 + b).normal(0.0, 0.5, size=7)[None, :]
+robot = eng.robot(arm)
+plan = eng.plan(robot, sdf.handle(), opt_setting, B)
+plan.set_problem(*[np.repeat(v[None], B, axis=0) for v in (start_conf, zero, end_conf, zero)], inits)
+plan.optimize()
+scores, pick = plan.score(9), plan.select(9, required_clearance=0.0, require_in_range=True)
+hidden = int(((scores["support_cost"] == 0) & (scores["dense_cost"] > 0)).sum())
+print(f"{B} restarts: {pick['n_eligible']} collision-free when up-sampled, {hidden} clean at the support states only; "
+      f"best = restart {pick['best']}")
+if pick["best"] >= 0:
+    b = pick["best"]
+    print(f"  support cost {scores['support_cost'][b]:.4f}, dense cost {scores['dense_cost'][b]:.4f}, clearance "
+          f"{scores['min_clearance'][b]:.4f} m; {pick['dense_best'].shape[0]} states ready to execute")
+plan.close()
 
 # ---- replanning: execute to state 5, the goal moves (WAMReplannerExample.m:102-126)
 isam = g.ISAM2TrajOptimizer3DArm(arm, sdf, opt_setting)

@@ -27,6 +27,13 @@ from .planner import (BatchTrajOptimize2DArm, BatchTrajOptimize3DArm, BatchTrajO
                       ISAM2TrajOptimizer3DArm, ISAM2TrajOptimizerPose2MobileArm, ISAM2TrajOptimizerPose2MobileArm2D,
                       PlanarSDF, SDFQueryOutOfRange, SignedDistanceField, readSDFvolfile, signedDistanceField2D,
                       signedDistanceField3D)
+from .planner import (DenseCollisionCost2DArm, DenseCollisionCost3DArm, DenseCollisionCostPose2Mobile2Arms,  # noqa: F401
+                      DenseCollisionCostPose2MobileArm, DenseCollisionCostPose2MobileArm2D,
+                      DenseCollisionCostPose2MobileBase, DenseCollisionCostPose2MobileBase2D,
+                      DenseCollisionCostPose2MobileVetLin2Arms, DenseCollisionCostPose2MobileVetLinArm, MinClearance2DArm,
+                      MinClearance3DArm, MinClearancePose2Mobile2Arms, MinClearancePose2MobileArm,
+                      MinClearancePose2MobileArm2D, MinClearancePose2MobileBase, MinClearancePose2MobileBase2D,
+                      MinClearancePose2MobileVetLin2Arms, MinClearancePose2MobileVetLinArm)
 from .settings import TrajOptimizerSetting  # noqa: F401
 from .trajutils import (initArmTrajStraightLine, initPose2TrajStraightLine, initPose2VectorTrajStraightLine,  # noqa: F401
                         interpolateArmTraj, interpolatePose2MobileArmTraj, interpolatePose2Traj, traj_from_values,

@@ -125,6 +125,27 @@ def declare_multi(lib):
     lib.gpmp2mi_multi_plan_destroy.restype = None
 
 
+def declare_score(lib):
+    """argtypes of the scoring entry points (include/gpmp2mi.h "scoring").  The host-pointer forms take typed pointers;
+    the `_dev` forms take device addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_score_traj": [vp, vp, f, i, i, i, d, d, d, d, ip, ip],
+        "gpmp2mi_score_traj_dev": [vp, vp, f, i, i, i] + [vp] * 7,
+        "gpmp2mi_select_best": [i, d, ip, d, ip, f, i, ip, ip],
+        "gpmp2mi_select_best_dev": [i, vp, vp, vp, vp, f, i, vp, vp, vp],
+        "gpmp2mi_plan_score": [vp, i, d, d, d, ip, ip],
+        "gpmp2mi_plan_score_dev": [vp, i] + [vp] * 6,
+        "gpmp2mi_plan_select": [vp, i, f, i, ip, ip, d, d],
+        "gpmp2mi_plan_select_dev": [vp, i, f, i] + [vp] * 5,
+        "gpmp2mi_multi_plan_score": [vp, i, d, d, d, ip, ip],
+        "gpmp2mi_multi_plan_select": [vp, i, f, i, ip, ip, d, d],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

@@ -365,25 +365,6 @@ __global__ void k_gp_interp_lie(GpCoef gc, int M, const double* __restrict__ c1,
   }
 }
 
-// Lambda / Psi scalars of one sub-step (gpmp2/gp/GPutils.h:44-59 with Qc factored out); device twin of
-// the host gp_coef in api.hip so that a densify launch needs no coefficient upload
-__device__ __forceinline__ GpCoef gp_coef_dev(double dt, double tau) {
-  const double a0 = tau * tau * tau / 3.0, a1 = 0.5 * tau * tau, r = dt - tau;
-  const double w0 = 12.0 / (dt * dt * dt), w1 = -6.0 / (dt * dt), w3 = 4.0 / dt;
-  // T = A(tau) Phi(dt - tau)^T ;  Psi = T Q^-1(dt)
-  const double t0 = a0 + a1 * r, t1 = a1, t2 = a1 + tau * r, t3 = tau;
-  GpCoef c;
-  c.p11 = t0 * w0 + t1 * w1;
-  c.p12 = t0 * w1 + t1 * w3;
-  c.p21 = t2 * w0 + t3 * w1;
-  c.p22 = t2 * w1 + t3 * w3;
-  c.l11 = 1.0 - c.p11;
-  c.l12 = tau - (c.p11 * dt + c.p12);
-  c.l21 = -c.p21;
-  c.l22 = 1.0 - (c.p21 * dt + c.p22);
-  return c;
-}
-
 // interpolateArmTraj / interpolatePose2MobileArmTraj  gpmp2/planner/TrajUtils.cpp:162-236
 // one thread per output state: support state i copies, the inter_step states after it interpolate
 // between i and i + 1 at tau = j * delta_t / (inter_step + 1).  traj [B][N+1][2D] -> out [B][Mo][2D]

@@ -104,6 +104,37 @@ int gpmp2mi_debug_stall_release(void* token) {
   return GPMP2MI_OK;
 }
 
+// test hooks: device buffers for the tests of the `_dev` entry points, from this library's HIP runtime
+int gpmp2mi_debug_device_alloc(size_t bytes, int fill_byte, void** out) {
+  G2_CHECK(out && bytes > 0, GPMP2MI_ERR_INVALID, "bad argument");
+  *out = nullptr;
+  G2_TRY(ensure_device());
+  void* p = nullptr;
+  G2_TRY(dev_malloc(&p, bytes));
+  const hipError_t e = hipMemset(p, fill_byte, bytes);
+  if (e != hipSuccess) (void)hipFree(p);
+  G2_HIP(e);
+  G2_HIP(hipStreamSynchronize(nullptr));
+  *out = p;
+  return GPMP2MI_OK;
+}
+int gpmp2mi_debug_device_read(void* dst_host, const void* src_dev, size_t bytes) {
+  G2_CHECK(dst_host && src_dev && bytes > 0, GPMP2MI_ERR_INVALID, "bad argument");
+  G2_TRY(ensure_device());
+  G2_HIP(hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
+  return GPMP2MI_OK;
+}
+int gpmp2mi_debug_device_write(void* dst_dev, const void* src_host, size_t bytes) {
+  G2_CHECK(dst_dev && src_host && bytes > 0, GPMP2MI_ERR_INVALID, "bad argument");
+  G2_TRY(ensure_device());
+  G2_HIP(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));
+  return GPMP2MI_OK;
+}
+int gpmp2mi_debug_device_free(void* p) {
+  if (p) G2_HIP(hipFree(p));
+  return GPMP2MI_OK;
+}
+
 int gpmp2mi_debug_current_device(int set_to, int* current) {
   G2_CHECK(current, GPMP2MI_ERR_INVALID, "null argument");
   G2_TRY(ensure_device());

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -76,8 +77,15 @@ struct gpmp2mi_robot {
   g2::RobotDev* d = nullptr;
   int device = -1;        // the device `d` lives on (current device at creation)
   bool replica = false;   // a multi plan's copy (robot_replica)
+  // records of gpmp2mi_score_traj(_dev) calls on this handle (score.hip), on `device`, grown on demand and kept.
+  // score_mu guards the pointer against host threads that share the handle; the records themselves belong to one
+  // call at a time, so such calls must be in stream order (include/gpmp2mi.h "scoring", Memory).
+  mutable std::mutex score_mu;
+  mutable void* score_ws = nullptr;
+  mutable size_t score_ws_bytes = 0;
   ~gpmp2mi_robot() {
     if (d) (void)hipFree(d);
+    if (score_ws) (void)hipFree(score_ws);
     if (replica) g2::g_robot_replicas.fetch_sub(1);
   }
 };
@@ -208,6 +216,10 @@ struct gpmp2mi_plan {
   g2::FlagBuf qflags;
   gpmp2mi_queue_stats qstats{};
   bool queue_ran = false;
+  // scoring (score.hip): the records of k_score and the staging of the host-pointer forms, taken at the first score
+  // call for an inter_step and kept (grown when a later call needs more)
+  void* score_ws = nullptr;
+  size_t score_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -284,4 +296,24 @@ int plan_get_result(gpmp2mi_plan* p, double* traj, int* iters, double* ferr, int
 // `io`: M and the ten arrays of the queue run; `host`: they are host arrays, staged here
 int plan_optimize_queue(gpmp2mi_plan* p, QueueRun io, bool host, hipStream_t st);
 int spin_wait_flag(const volatile int* flag, bool st_valid, hipStream_t st, double timeout_s, int* count);
+
+// score.hip: the per-row outputs of a score call and the selection of a select call (any pointer may be null)
+struct ScoreOut {
+  double *support = nullptr, *dense = nullptr, *clearance = nullptr;
+  int *worst = nullptr, *oor = nullptr;
+};
+struct ScoreSel {
+  double required_clearance = 0.0;
+  int require_in_range = 0;
+  int *best = nullptr, *n_eligible = nullptr;
+  double *traj_best = nullptr, *dense_best = nullptr;
+  double* best_error = nullptr;   // host forms only: final_error of the chosen row (the multi plan's pick needs it)
+};
+// Scores the plan's resident result on `st`; sel != null: applies the rule and copies the chosen row as well.
+// host: the outputs are host arrays (staged in the plan's scoring workspace, copied back, `st` synchronised);
+// otherwise device pointers, and the call returns without a host synchronisation.
+int plan_score(gpmp2mi_plan* p, int inter, const ScoreOut& out, const ScoreSel* sel, bool host, hipStream_t st);
+// B comparisons on the host: the rule of gpmp2mi_select_best
+void select_rule_host(int B, const double* ferr, const int* status, const double* clearance, const int* oor,
+                      double required_clearance, int require_in_range, int* best, int* n_eligible);
 }  // namespace g2

@@ -377,4 +377,67 @@ int gpmp2mi_multi_plan_queue_stats(const gpmp2mi_multi_plan* m, int shard, gpmp2
   return GPMP2MI_OK;
 }
 
+// Scoring (score.hip): every shard scores its rows on its own device and stream, the outputs land in batch order.
+int gpmp2mi_multi_plan_score(gpmp2mi_multi_plan* m, int inter_step, double* support_cost, double* dense_cost,
+                             double* min_clearance, int* worst, int* out_of_range) {
+  G2_MULTI_LIVE(m);
+  G2_CHECK(m->optimized, GPMP2MI_ERR_INVALID, "multi plan has not been optimized");
+  G2_CHECK(inter_step >= 0, GPMP2MI_ERR_INVALID, "inter_step must be >= 0");
+  DeviceGuard guard;
+  const std::vector<char> all(m->shards.size(), 1);
+  return run_shards(m, all, [&](int k) {
+    const MultiShard& sh = m->shards[k];
+    const size_t r = sh.row0;
+    ScoreOut o;
+    o.support = support_cost ? support_cost + r : nullptr;
+    o.dense = dense_cost ? dense_cost + r : nullptr;
+    o.clearance = min_clearance ? min_clearance + r : nullptr;
+    o.worst = worst ? worst + 2 * r : nullptr;
+    o.oor = out_of_range ? out_of_range + r : nullptr;
+    return plan_score(sh.plan, inter_step, o, nullptr, true, sh.stream);
+  });
+}
+
+// Every shard selects among its rows; the pick over the shards' candidates is the same rule on the host: the smallest
+// final_error, the lowest shard (= the lowest row) on ties.
+int gpmp2mi_multi_plan_select(gpmp2mi_multi_plan* m, int inter_step, double required_clearance, int require_in_range,
+                              int* best, int* n_eligible, double* traj_best, double* dense_best) {
+  G2_MULTI_LIVE(m);
+  G2_CHECK(m->optimized, GPMP2MI_ERR_INVALID, "multi plan has not been optimized");
+  G2_CHECK(inter_step >= 0, GPMP2MI_ERR_INVALID, "inter_step must be >= 0");
+  DeviceGuard guard;
+  const int n = (int)m->shards.size();
+  const size_t Md = (size_t)m->N * (inter_step + 1) + 1;
+  std::vector<int> cand(n, -1), cnt(n, 0);
+  std::vector<double> fe(n, 0.0);
+  std::vector<std::vector<double>> tb(n), db(n);
+  const std::vector<char> all(n, 1);
+  G2_TRY(run_shards(m, all, [&](int k) -> int {
+    const MultiShard& sh = m->shards[k];
+    if (traj_best) tb[k].resize(m->trow());
+    if (dense_best) db[k].resize(Md * 2 * m->D);
+    ScoreSel sel;
+    sel.required_clearance = required_clearance;
+    sel.require_in_range = require_in_range;
+    sel.best = &cand[k];
+    sel.n_eligible = &cnt[k];
+    sel.traj_best = traj_best ? tb[k].data() : nullptr;
+    sel.dense_best = dense_best ? db[k].data() : nullptr;
+    sel.best_error = &fe[k];
+    return plan_score(sh.plan, inter_step, ScoreOut{}, &sel, true, sh.stream);
+  }));
+  int win = -1, total = 0;
+  for (int k = 0; k < n; k++) {
+    total += cnt[k];
+    if (cand[k] >= 0 && (win < 0 || fe[k] < fe[win])) win = k;
+  }
+  if (best) *best = win < 0 ? -1 : m->shards[win].row0 + cand[win];
+  if (n_eligible) *n_eligible = total;
+  if (win >= 0) {
+    if (traj_best) std::copy(tb[win].begin(), tb[win].end(), traj_best);
+    if (dense_best) std::copy(db[win].begin(), db[win].end(), dense_best);
+  }
+  return GPMP2MI_OK;
+}
+
 }  // extern "C"

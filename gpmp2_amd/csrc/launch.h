@@ -42,4 +42,34 @@ int launch_gp_interp_lie(int D, const GpCoef& gc, int M, const double* c1, const
 int launch_joint_limit(int D, const double* down, const double* up, const double* th, int M,
                        const double* x, double* err, double* Hd, hipStream_t st);
 
+// score_kernels.hip
+constexpr int SCORE_TILE = 64;   // checked states per workgroup of k_score: fixes the summation order
+// what one workgroup of k_score leaves for k_score_finish; k = s = INT_MAX: no pair of the tile was in range
+struct ScoreRec {
+  double support, dense, clearance;
+  int k, s, oor, pad;
+};
+// arguments of k_score_finish; every output may be null
+struct ScoreFinish {
+  int B, N, D, lie, inter, Md, nblk;
+  double dt;
+  const ScoreRec* recs;              // [B][nblk], or null: selection over in_clearance / in_oor
+  const double* in_clearance;
+  const int* in_oor;
+  double *support, *dense, *clearance;
+  int *worst, *oor;
+  int select, require_in_range;      // select: one workgroup applies the rule over the B rows
+  double required_clearance;
+  const double* ferr;
+  const int* status;
+  int *best, *n_eligible;
+  double* best_err;                  // final_error of the chosen row (left alone when none is)
+  const double* traj;                // [B][N+1][2D]: the rows traj_best / dense_best are taken from
+  double *traj_best, *dense_best;
+};
+int score_blocks(int Md);   // records per row
+int launch_score(const RobotDev& h, const RobotDev* R, const SdfDev& s, double dt, int inter, int B, int N,
+                 const double* traj, ScoreRec* recs, hipStream_t st);
+int launch_score_finish(const ScoreFinish& a, hipStream_t st);
+
 }  // namespace g2

@@ -1,0 +1,268 @@
+// score_kernels.hip -- the score-and-select stage behind gpmp2mi_score_traj / gpmp2mi_plan_score / gpmp2mi_plan_select
+// (include/gpmp2mi.h "scoring"): which of these trajectories is executed, and is it collision-free between its
+// support states as well?
+//
+//   k_score         one lane per checked state of a trajectory: GP up-sampling (the arithmetic of k_interpolate_traj,
+//                   factor_kernels.hip) -> value-only walk of the kinematic chain -> field lookup per sphere -> hinge
+//                   sum, minimum clearance with its (state, sphere) and the out-of-range count; the up-sampled states
+//                   never reach memory.  A workgroup covers SCORE_TILE consecutive states; its `nsub` wavefronts share
+//                   the spheres of those states (s % nsub).  Wavefront butterfly -> LDS -> ONE record per workgroup.
+//   k_score_finish  reduces the records of every row in index order to the five per-row outputs, applies the
+//                   selection rule when asked and copies the chosen row and its up-sampled form.
+//
+// Determinism: the tile and nsub depend on (N, inter_step, S) only, every sum is taken in a fixed order (lane
+// butterfly, wavefronts in index order, records in index order) and no floating-point atomic is used, so a row's
+// results do not depend on the batch, its position in it or the device.
+#include <climits>
+
+#include "device_math.h"
+#include "dispatch.h"
+#include "launch.h"
+
+namespace g2 {
+
+// (clearance, state, sphere) compared lexicographically: the minimum and where it occurs travel together, exact ties
+// go to the lowest state, then the lowest sphere.  "none" is (+inf, INT_MAX, INT_MAX).
+struct ScoreKey {
+  double c;
+  int k, s;
+};
+__device__ __forceinline__ bool key_less(const ScoreKey& a, const ScoreKey& b) {
+  return a.c < b.c || (a.c == b.c && (a.k < b.k || (a.k == b.k && a.s < b.s)));
+}
+
+template <int KIND, int AD, int AD2, int SDIM>
+__global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, SdfDev sdf, double dt, int inter, int N,
+                                               int Md, int nblk, const double* __restrict__ traj,
+                                               ScoreRec* __restrict__ recs) {
+  using K = Kin<KIND, AD, AD2>;
+  constexpr int D = K::DOF;
+  __shared__ RobotDev R;
+  __shared__ double w_sup[4], w_den[4], w_clr[4];
+  __shared__ int w_k[4], w_s[4], w_oor[4];
+  stage_robot(&R, Rg);
+  const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6, nsub = blockDim.x >> 6;
+  const int m = blk * SCORE_TILE + lane;   // checked state of this lane
+  double dense = 0.0;
+  int oor = 0;
+  ScoreKey best{HUGE_VAL, INT_MAX, INT_MAX};
+  bool support = false;
+  if (m < Md) {
+    const int seg = m / (inter + 1), j = m % (inter + 1);
+    support = j == 0;
+    const double* s0 = traj + ((size_t)b * (N + 1) + seg) * 2 * D;
+    double q[D];
+    if (j == 0) {
+#pragma unroll
+      for (int k = 0; k < D; k++) q[k] = s0[k];
+    } else {
+      const double* s1 = s0 + 2 * D;
+      const GpCoef gc = gp_coef_dev(dt, (double)j * (dt / (double)(inter + 1)));
+      if constexpr (K::MOBILE) {
+        // GaussianProcessInterpolatorPose2Vector: the Pose2 part through lie_interpolate, the rest as it does
+        double x0[3], w0[3], x1[3], w1[3], qp[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { x0[k] = s0[k]; w0[k] = s0[D + k]; x1[k] = s1[k]; w1[k] = s1[D + k]; }
+        lie_interpolate<3>(gc, x0, w0, x1, w1, qp, nullptr);
+#pragma unroll
+        for (int k = 0; k < 3; k++) q[k] = qp[k];
+#pragma unroll
+        for (int k = 3; k < D; k++) q[k] = s0[k] + (gc.l12 * s0[D + k] + gc.p11 * (s1[k] - s0[k]) + gc.p12 * s1[D + k]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < D; k++) q[k] = gc.l11 * s0[k] + gc.l12 * s0[D + k] + gc.p11 * s1[k] + gc.p12 * s1[D + k];
+      }
+    }
+    typename K::Axes A;   // filled by the walk, never read here: the Jacobian work is dead code
+    K::walk(R, q, A, [&](int s, const double (&p)[3], auto) {
+      // negated conjunction: a NaN centre fails every comparison and counts as out of range
+      bool in = p[0] >= sdf.ox && p[0] <= sdf.hix && p[1] >= sdf.oy && p[1] <= sdf.hiy;
+      if (SDIM == 3) in = in && p[2] >= sdf.oz && p[2] <= sdf.hiz;
+      if (!in) {
+        oor++;
+        return;
+      }
+      double d, gx, gy, gz;
+      if (SDIM == 3) (void)sdf3_lookup(sdf, p[0], p[1], p[2], d, gx, gy, gz);
+      else (void)sdf2_lookup(sdf, p[0], p[1], d, gx, gy);
+      const double r = R.sph_r[s];
+      dense += d > r ? 0.0 : r - d;
+      const ScoreKey key{d - r, m, R.sph_orig[s]};
+      if (key_less(key, best)) best = key;
+    }, sub, nsub);
+  }
+  double sup = support ? dense : 0.0;
+  // wavefront: butterfly (both partners add the same two numbers, so all 64 lanes end with the same bits)
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    sup += __shfl_xor(sup, off);
+    dense += __shfl_xor(dense, off);
+    oor += __shfl_xor(oor, off);
+    const ScoreKey o{__shfl_xor(best.c, off), __shfl_xor(best.k, off), __shfl_xor(best.s, off)};
+    if (key_less(o, best)) best = o;
+  }
+  if (lane == 0) {
+    w_sup[sub] = sup; w_den[sub] = dense; w_clr[sub] = best.c;
+    w_k[sub] = best.k; w_s[sub] = best.s; w_oor[sub] = oor;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    ScoreRec r{w_sup[0], w_den[0], w_clr[0], w_k[0], w_s[0], w_oor[0], 0};
+    for (int w = 1; w < nsub; w++) {   // wavefronts in index order
+      r.support += w_sup[w];
+      r.dense += w_den[w];
+      r.oor += w_oor[w];
+      const ScoreKey a{w_clr[w], w_k[w], w_s[w]}, c{r.clearance, r.k, r.s};
+      if (key_less(a, c)) { r.clearance = a.c; r.k = a.k; r.s = a.s; }
+    }
+    recs[blockIdx.x] = r;
+  }
+}
+
+// One output state of interpolateArmTraj / interpolatePose2MobileArmTraj, coordinate k: the expressions of
+// k_interpolate_traj (factor_kernels.hip) element by element.  s0 / s1: the support states around it.
+__device__ __forceinline__ void score_dense_coord(bool lie, double dt, int inter, int D, int j, int k, const double* s0,
+                                                  double* o) {
+  if (j == 0) {
+    o[k] = s0[k];
+    o[D + k] = s0[D + k];
+    return;
+  }
+  const double* s1 = s0 + 2 * D;
+  const GpCoef gc = gp_coef_dev(dt, (double)j * (dt / (double)(inter + 1)));
+  if (lie) {
+    double r, qk;
+    if (k < 3) {
+      double x0[3], w0[3], x1[3], w1[3], qp[3], lg[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) { x0[i] = s0[i]; w0[i] = s0[D + i]; x1[i] = s1[i]; w1[i] = s1[D + i]; }
+      lie_interpolate<3>(gc, x0, w0, x1, w1, qp, nullptr);
+      pose2_logmap(pose2_between(P2{x0[0], x0[1], x0[2]}, P2{x1[0], x1[1], x1[2]}), lg);
+      qk = k == 0 ? qp[0] : k == 1 ? qp[1] : qp[2];
+      r = k == 0 ? lg[0] : k == 1 ? lg[1] : lg[2];
+    } else {
+      qk = s0[k] + (gc.l12 * s0[D + k] + gc.p11 * (s1[k] - s0[k]) + gc.p12 * s1[D + k]);
+      r = s1[k] - s0[k];
+    }
+    o[k] = qk;
+    o[D + k] = gc.l22 * s0[D + k] + gc.p21 * r + gc.p22 * s1[D + k];
+  } else {
+    o[k] = gc.l11 * s0[k] + gc.l12 * s0[D + k] + gc.p11 * s1[k] + gc.p12 * s1[D + k];
+    o[D + k] = gc.l21 * s0[k] + gc.l22 * s0[D + k] + gc.p21 * s1[k] + gc.p22 * s1[D + k];
+  }
+}
+
+// Second stage.  Rows are taken by thread (row = thread id + multiple of the thread count): a row's records are summed
+// in index order.  With a.select the grid is one workgroup: every thread keeps the best (final_error, row) of its rows,
+// the workgroup reduces them through LDS, then all its threads copy the chosen row.  a.recs == nullptr: selection over
+// given scores (gpmp2mi_select_best_dev).
+__global__ __launch_bounds__(256) void k_score_finish(ScoreFinish a) {
+  __shared__ double s_err[256];
+  __shared__ int s_row[256], s_cnt[256];
+  double my_err = HUGE_VAL;
+  int my_row = INT_MAX, my_cnt = 0;
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
+    double clr;
+    int oor;
+    if (a.recs) {
+      const ScoreRec* r = a.recs + (size_t)b * a.nblk;
+      ScoreRec t = r[0];
+      for (int i = 1; i < a.nblk; i++) {   // records in index order
+        t.support += r[i].support;
+        t.dense += r[i].dense;
+        t.oor += r[i].oor;
+        const ScoreKey x{r[i].clearance, r[i].k, r[i].s}, c{t.clearance, t.k, t.s};
+        if (key_less(x, c)) { t.clearance = x.c; t.k = x.k; t.s = x.s; }
+      }
+      const bool none = t.k == INT_MAX;
+      if (a.support) a.support[b] = t.support;
+      if (a.dense) a.dense[b] = t.dense;
+      if (a.clearance) a.clearance[b] = t.clearance;
+      if (a.worst) {
+        a.worst[2 * b] = none ? -1 : t.k;
+        a.worst[2 * b + 1] = none ? -1 : t.s;
+      }
+      if (a.oor) a.oor[b] = t.oor;
+      clr = t.clearance;
+      oor = t.oor;
+    } else {
+      clr = a.in_clearance[b];
+      oor = a.in_oor ? a.in_oor[b] : 0;
+    }
+    if (!a.select) continue;
+    const double fe = a.ferr[b];
+    const bool ok = (!a.status || a.status[b] != GPMP2MI_TRAJ_NOT_SPD) && isfinite(fe) && clr >= a.required_clearance &&
+                    (!a.require_in_range || oor == 0);
+    if (!ok) continue;
+    my_cnt++;
+    if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row
+      my_err = fe;
+      my_row = b;
+    }
+  }
+  if (!a.select) return;
+  s_err[threadIdx.x] = my_err;
+  s_row[threadIdx.x] = my_row;
+  s_cnt[threadIdx.x] = my_cnt;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      const int o = threadIdx.x + h;
+      if (s_err[o] < s_err[threadIdx.x] || (s_err[o] == s_err[threadIdx.x] && s_row[o] < s_row[threadIdx.x])) {
+        s_err[threadIdx.x] = s_err[o];
+        s_row[threadIdx.x] = s_row[o];
+      }
+      s_cnt[threadIdx.x] += s_cnt[o];
+    }
+    __syncthreads();
+  }
+  const int best = s_row[0] == INT_MAX ? -1 : s_row[0];
+  if (threadIdx.x == 0) {
+    if (a.best) *a.best = best;
+    if (a.n_eligible) *a.n_eligible = s_cnt[0];
+  }
+  if (best < 0) return;   // the trajectory outputs are left untouched
+  if (threadIdx.x == 0 && a.best_err) *a.best_err = s_err[0];
+  const size_t trow = (size_t)(a.N + 1) * 2 * a.D;
+  const double* row = a.traj + (size_t)best * trow;
+  if (a.traj_best)
+    for (size_t i = threadIdx.x; i < trow; i += blockDim.x) a.traj_best[i] = row[i];
+  if (a.dense_best)
+    for (int e = threadIdx.x; e < a.Md * a.D; e += blockDim.x) {
+      const int m = e / a.D, k = e % a.D;
+      const int seg = m / (a.inter + 1), j = m % (a.inter + 1);
+      score_dense_coord(a.lie != 0, a.dt, a.inter, a.D, j, k, row + (size_t)seg * 2 * a.D, a.dense_best + (size_t)m * 2 * a.D);
+    }
+}
+
+int score_blocks(int Md) { return (Md + SCORE_TILE - 1) / SCORE_TILE; }
+
+int launch_score(const RobotDev& h, const RobotDev* R, const SdfDev& s, double dt, int inter, int B, int N,
+                 const double* traj, ScoreRec* recs, hipStream_t st) {
+  const long long Md = (long long)N * (inter + 1) + 1;
+  const long long nblk = (Md + SCORE_TILE - 1) / SCORE_TILE;
+  if (Md >= (1ll << 31) / GPMP2MI_MAX_DOF || nblk * B >= (1ll << 31)) {
+    set_error("too many checked states for one launch");
+    return GPMP2MI_ERR_INVALID;
+  }
+  // wavefronts that share the spheres of a tile: a function of the sphere count alone
+  const int nsub = h.nr_spheres >= 8 ? 4 : 1;
+  const dim3 grid((unsigned)(nblk * B)), block(64 * nsub);
+  if (s.dim == 3) {
+    G2_DISPATCH_ROBOT_H(h, (k_score<KIND_, AD_, AD2_, 3><<<grid, block, 0, st>>>(R, s, dt, inter, N, (int)Md, (int)nblk, traj, recs)));
+  } else {
+    G2_DISPATCH_ROBOT_H(h, (k_score<KIND_, AD_, AD2_, 2><<<grid, block, 0, st>>>(R, s, dt, inter, N, (int)Md, (int)nblk, traj, recs)));
+  }
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+int launch_score_finish(const ScoreFinish& a, hipStream_t st) {
+  const int grid = a.select ? 1 : (a.B + 255) / 256;
+  k_score_finish<<<dim3(grid), dim3(256), 0, st>>>(a);
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+}  // namespace g2

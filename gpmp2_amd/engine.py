@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from . import _capi
+from . import _capi, scoring
 from ._capi import dptr, f64, iptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,6 +41,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         getattr(lib, name).restype = None
     _capi.declare_queue(lib)
     _capi.declare_multi(lib)
+    _capi.declare_score(lib)
     return lib
 
 
@@ -61,6 +62,32 @@ def queue_inputs(D, N, start_conf, start_vel, end_conf, end_vel, init):
     if M < 1 or any(x.shape[0] != M for x in rows):
         raise ValueError(f"queue inputs disagree on the number of problems: {[x.shape[0] for x in rows] + [M]}")
     return M, rows, t
+
+
+def _dev_arg(name, x, shape, integer=False):
+    """A device output of a `_dev` call as c_void_p: None, a raw device pointer (int), or a torch tensor checked for
+    device, dtype, contiguity and shape."""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        want = "torch.int32" if integer else "torch.float64"
+        if str(x.dtype) != want or not x.is_contiguous() or tuple(x.shape) != tuple(shape) or x.device.type != "cuda":
+            raise ValueError(f"{name}: expected a contiguous {want} cuda tensor of shape {list(shape)}, got "
+                             f"{x.dtype} {list(x.shape)} on {x.device}")
+        x = x.data_ptr()
+    return C.c_void_p(int(x))
+
+
+def _score_args(inter_step):
+    inter_step = int(inter_step)
+    if inter_step < 0:
+        raise ValueError("inter_step must be >= 0")
+    return inter_step
+
+
+def _score_ptrs(o):
+    return (dptr(o["support_cost"]), dptr(o["dense_cost"]), dptr(o["min_clearance"]), iptr(o["worst"]),
+            iptr(o["out_of_range"]))
 
 
 def multi_plan_args(B, devices):
@@ -299,6 +326,30 @@ class Engine:
         self._ck(self.lib.gpmp2mi_collision_cost(robot.ptr, sdf.ptr, total_step, t.shape[0], dptr(t), dptr(cost)))
         return cost
 
+    # ---------------------------------------------------------------- scoring (include/gpmp2mi.h "scoring")
+    def score_traj(self, robot, sdf, delta_t, inter_step, traj, out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) -> dict(support_cost [B], dense_cost [B], min_clearance [B],
+        worst [B][2] = (checked state, sphere), out_of_range [B]) of the inter_step-up-sampled trajectories.
+        out: a dict of caller arrays to fill instead (checked).  ValueError for mis-shaped arrays."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        o = scoring.score_outputs(B, out)
+        self._ck(self.lib.gpmp2mi_score_traj(robot.ptr, sdf.ptr, float(delta_t), inter_step, B, N, dptr(t),
+                                             *_score_ptrs(o)))
+        return o
+
+    def select_best(self, final_error, status, min_clearance, out_of_range=None, required_clearance=0.0,
+                    require_in_range=False):
+        """(best, n_eligible) by the selection rule (scoring.select_rule states it); host arrays, no device needed."""
+        B, fe, st, clr, oor = scoring.select_inputs(final_error, status, min_clearance, out_of_range, require_in_range)
+        best, n = C.c_int(-1), C.c_int(0)
+        self._ck(self.lib.gpmp2mi_select_best(B, dptr(fe), iptr(st), dptr(clr), iptr(oor), float(required_clearance),
+                                              int(bool(require_in_range)), C.byref(best), C.byref(n)))
+        return best.value, n.value
+
     # ---------------------------------------------------------------- plans
     def plan(self, robot, sdf, setting, B, forms=None):
         return Plan(self, robot, sdf, setting, B, forms)
@@ -449,6 +500,49 @@ class Plan:
     def traj_dev_ptr(self):
         return int(self.eng.lib.gpmp2mi_plan_traj_dev(self.h.ptr))
 
+    # ---- scoring and selection of the resident result (include/gpmp2mi.h "scoring")
+    def score(self, inter_step, out=None):
+        """dict(support_cost, dense_cost, min_clearance, worst, out_of_range) of the plan's result, B rows."""
+        inter_step = _score_args(inter_step)
+        o = scoring.score_outputs(self.B, out)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_score(self.h.ptr, inter_step, *_score_ptrs(o)))
+        return o
+
+    def score_dev(self, inter_step, support_cost=None, dense_cost=None, min_clearance=None, worst=None,
+                  out_of_range=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        B = self.B
+        args = [_dev_arg("support_cost", support_cost, (B,)), _dev_arg("dense_cost", dense_cost, (B,)),
+                _dev_arg("min_clearance", min_clearance, (B,)), _dev_arg("worst", worst, (B, 2), True),
+                _dev_arg("out_of_range", out_of_range, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_score_dev(self.h.ptr, _score_args(inter_step), *args,
+                                                         C.c_void_p(stream or 0)))
+
+    def select(self, inter_step, required_clearance=0.0, require_in_range=False):
+        """Score, apply the rule to the plan's final_error / status, fetch the chosen row: dict(best, n_eligible,
+        traj_best [N+1][2D], dense_best [Md][2D]); best = -1: the two trajectories are None."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D))
+        best, n = C.c_int(-1), C.c_int(0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select(self.h.ptr, inter_step, float(required_clearance),
+                                                      int(bool(require_in_range)), C.byref(best), C.byref(n), dptr(tb),
+                                                      dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_dev(self, inter_step, required_clearance=0.0, require_in_range=False, best=None, n_eligible=None,
+                   traj_best=None, dense_best=None, stream=None):
+        """The same with device outputs: best / n_eligible int32 [1], traj_best [N+1][2D], dense_best [Md][2D] (torch
+        tensors or raw pointers, any may be None).  One enqueue on `stream`, no host synchronisation."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_dev(self.h.ptr, inter_step, float(required_clearance),
+                                                          int(bool(require_in_range)), *args, C.c_void_p(stream or 0)))
+
     def graph_error(self, traj):
         t = f64(traj).reshape(self.B, self.N + 1, 2 * self.D)
         err = np.zeros(self.B)
@@ -587,6 +681,25 @@ class MultiPlan:
                                                                     dptr(t), dptr(traj), iptr(iters), dptr(ferr),
                                                                     iptr(status), dptr(trace)))
         return dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+
+    def score(self, inter_step, out=None):
+        """Plan.score over all shards, rows in batch order."""
+        inter_step = _score_args(inter_step)
+        o = scoring.score_outputs(self.B, out)
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_score(self.h.ptr, inter_step, *_score_ptrs(o)))
+        return o
+
+    def select(self, inter_step, required_clearance=0.0, require_in_range=False):
+        """Plan.select over all shards: `best` is a batch row."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D))
+        best, n = C.c_int(-1), C.c_int(0)
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_select(self.h.ptr, inter_step, float(required_clearance),
+                                                            int(bool(require_in_range)), C.byref(best), C.byref(n),
+                                                            dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, traj_best=tb if hit else None, dense_best=db if hit else None)
 
     def queue_stats(self, shard):
         """of the last queue run, shard `shard`: passes, slot_passes, busy_slot_passes (zeros if it had no problems)."""

@@ -198,6 +198,37 @@ CollisionCostPose2MobileVetLinArm = _collision_cost
 CollisionCostPose2MobileVetLin2Arms = _collision_cost
 
 
+def _score_one(model, sdf, result, setting, inter_step):
+    traj, _ = _flat(result, setting)
+    delta_t = setting.total_time / setting.total_step
+    return _eng().score_traj(_robot_handle(model), sdf.handle(), delta_t, inter_step, traj[None])
+
+
+def _dense_collision_cost(model, sdf, result, setting, inter_step):
+    """CollisionCost* over the trajectory up-sampled with inter_step GP-interpolated states per interval: the states
+    interpolateArmTraj / interpolatePose2MobileArmTraj hand to the controller (inter_step = 0: CollisionCost* itself)"""
+    return float(_score_one(model, sdf, result, setting, inter_step)["dense_cost"][0])
+
+
+def _min_clearance(model, sdf, result, setting, inter_step):
+    """(clearance, checked state, sphere): the smallest signed distance minus radius over the up-sampled trajectory
+    and where it occurs; (+inf, -1, -1) when no sphere centre is inside the field"""
+    r = _score_one(model, sdf, result, setting, inter_step)
+    return float(r["min_clearance"][0]), int(r["worst"][0, 0]), int(r["worst"][0, 1])
+
+
+DenseCollisionCost2DArm = DenseCollisionCost3DArm = _dense_collision_cost
+DenseCollisionCostPose2MobileBase2D = DenseCollisionCostPose2MobileBase = _dense_collision_cost
+DenseCollisionCostPose2MobileArm2D = DenseCollisionCostPose2MobileArm = _dense_collision_cost
+DenseCollisionCostPose2Mobile2Arms = _dense_collision_cost
+DenseCollisionCostPose2MobileVetLinArm = DenseCollisionCostPose2MobileVetLin2Arms = _dense_collision_cost
+MinClearance2DArm = MinClearance3DArm = _min_clearance
+MinClearancePose2MobileBase2D = MinClearancePose2MobileBase = _min_clearance
+MinClearancePose2MobileArm2D = MinClearancePose2MobileArm = _min_clearance
+MinClearancePose2Mobile2Arms = _min_clearance
+MinClearancePose2MobileVetLinArm = MinClearancePose2MobileVetLin2Arms = _min_clearance
+
+
 class _ISAM2TrajOptimizer:
     """gpmp2::internal::ISAM2TrajOptimizer (gpmp2/planner/ISAM2TrajOptimizer.h:58-137).  Same call
     sequence; update() is one full relinearise + solve of the resident plan (gpmp2mi_plan_update)

@@ -237,7 +237,8 @@ void gpmp2mi_graph_opts_default(gpmp2mi_graph_opts* o);
  * (planner/BatchTrajOptimizer.h:43-73; graph rules planner/BatchTrajOptimizer-inl.h:21-84;
  * optimizer loop planner/BatchTrajOptimizer.cpp:212-308) for B independent problems sharing one
  * robot, one SDF and one setting.  The plan owns all device workspace; nothing is allocated in
- * the optimize call, so it can be enqueued repeatedly (receding horizon). */
+ * the optimize call, so it can be enqueued repeatedly (receding horizon).  (The scoring calls take their workspace
+ * at their first use for an inter_step and keep it: see "scoring" below.) */
 typedef struct gpmp2mi_plan gpmp2mi_plan;
 int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
                         const gpmp2mi_settings* setting, const gpmp2mi_graph_opts* opts /*NULL ok*/,
@@ -414,6 +415,85 @@ int gpmp2mi_batch_optimize(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
  * sum over all states of the unary obstacle error with epsilon = 0.  traj [B][N+1][2D] host. */
 int gpmp2mi_collision_cost(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, int total_step,
                            int B, const double* traj, double* cost);
+
+/* ---- scoring: dense collision check and selection, on the device ----------------------------------
+ * gpmp2::CollisionCost* looks at the support states only, and the reference's workflow then up-samples the
+ * trajectory for execution (interpolateArmTraj, matlab/WAMPlannerExample.m): between two support states the robot
+ * can be inside an obstacle that both of them clear.  These calls check the states that are executed and pick
+ * the trajectory to execute, without the trajectories leaving the device.
+ *
+ * Definitions, for one trajectory traj [N+1][2D], delta_t and inter_step = J >= 0:
+ *  - Checked states: gpmp2mi_interpolate_traj(inter_step = J, start 0, end N), Md = N*(J+1) + 1 states (linear GP for
+ *    vector-space robots, the Pose2 interpolator for the mobile kinds, following the robot's kind).  State k is a
+ *    support state iff k % (J+1) == 0; only the configuration half is used.  J = 0 checks the support states only.
+ *  - For checked state k and sphere s (ids in the order of the robot description): centre = sphereCenters(conf_k)[s],
+ *    field lookup as gpmp2mi_sdf_query (planar fields use x, y); in_range as there, and a non-finite centre is out of
+ *    range; clearance(k, s) = dist - radius_s where in range.
+ *  - support_cost [B]: sum over support states and spheres of (dist > radius ? 0 : radius - dist), 0 out of range:
+ *    the value of gpmp2mi_collision_cost.  dense_cost [B]: the same sum over all Md checked states.
+ *    min_clearance [B]: min of clearance(k, s) over the in-range pairs, +inf if there is none.  worst [B][2]: the
+ *    (k, s) attaining it, on exact ties the lowest k, then the lowest s; (-1, -1) if none.  out_of_range [B]: number
+ *    of (k, s) pairs out of range.  Any output may be NULL.
+ *  - Determinism: a row's results are a function of that row, the robot, the field, delta_t and J alone.  Sums are
+ *    taken in an order fixed by (N, J, S), not by B, the row's position, the entry point or the device, and without
+ *    floating-point atomics: a row scores bit-identically alone, in any batch, through a plan or a multi plan.
+ *  - Selection over B rows with required_clearance and require_in_range:
+ *      eligible(b) = status[b] != GPMP2MI_TRAJ_NOT_SPD && isfinite(final_error[b])
+ *                    && min_clearance[b] >= required_clearance && (!require_in_range || out_of_range[b] == 0)
+ *    best = the eligible row with the smallest final_error, the lowest row on ties, -1 if none; n_eligible = their
+ *    number.  status NULL = all fine; a NaN clearance is never eligible.
+ * Errors: GPMP2MI_ERR_INVALID (checked before any device work) for a NULL robot / sdf / traj / plan / final_error /
+ * min_clearance, inter_step < 0, B < 0, total_step < 1, delta_t <= 0; B == 0 is fine and does nothing.
+ * Memory: the `_dev` forms enqueue two kernels on `stream` and return without a host synchronisation.  They need a
+ * workspace of one 40-byte record per 64 checked states of every row: a plan takes it (with the staging of its
+ * host-pointer forms) at the first score / select call for an inter_step and keeps it -- the one exception to
+ * "nothing is allocated after gpmp2mi_plan_create"; gpmp2mi_score_traj_dev keeps it with the robot handle.  A later
+ * call that needs no more room neither allocates nor synchronises; one that needs more waits for the device while
+ * the block is replaced.  Calls that share a robot handle (gpmp2mi_score_traj*) or a plan therefore belong on one
+ * stream, or in stream order. */
+
+/* caller buffers, e.g. the traj output of gpmp2mi_plan_optimize_queue(_dev); traj [B][total_step+1][2D].
+ * The record workspace of these two calls lives with the robot handle, on the device the handle was created on: that
+ * device must be current (GPMP2MI_ERR_INVALID otherwise).  Host threads may share the handle, but its records serve one
+ * call at a time: calls on one robot handle must follow each other in stream order (one stream, or events between
+ * streams).  To score concurrently on several streams use one robot handle per stream, or gpmp2mi_plan_score on one
+ * plan per stream. */
+int gpmp2mi_score_traj(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, double delta_t, int inter_step, int B,
+                       int total_step, const double* traj, double* support_cost, double* dense_cost,
+                       double* min_clearance, int* worst, int* out_of_range);
+int gpmp2mi_score_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, double delta_t, int inter_step, int B,
+                           int total_step, const double* traj, double* support_cost, double* dense_cost,
+                           double* min_clearance, int* worst, int* out_of_range, void* stream);
+/* The selection rule.  Host pointers: B comparisons on the host, no device needed (out_of_range may be NULL unless
+ * require_in_range).  _dev: one kernel; best / n_eligible are device ints. */
+int gpmp2mi_select_best(int B, const double* final_error, const int* status, const double* min_clearance,
+                        const int* out_of_range, double required_clearance, int require_in_range, int* best,
+                        int* n_eligible);
+int gpmp2mi_select_best_dev(int B, const double* final_error, const int* status, const double* min_clearance,
+                            const int* out_of_range, double required_clearance, int require_in_range, int* best,
+                            int* n_eligible, void* stream);
+/* The plan's resident result (delta_t from its setting).  GPMP2MI_ERR_INVALID before the first optimize / update and
+ * after a queue run (the plan then holds no problem, as gpmp2mi_plan_get_result); GPMP2MI_ERR_TIMEOUT for a poisoned
+ * plan, before anything is enqueued. */
+int gpmp2mi_plan_score(gpmp2mi_plan* p, int inter_step, double* support_cost, double* dense_cost,
+                       double* min_clearance, int* worst, int* out_of_range);
+int gpmp2mi_plan_score_dev(gpmp2mi_plan* p, int inter_step, double* support_cost, double* dense_cost,
+                           double* min_clearance, int* worst, int* out_of_range, void* stream);
+/* Score, apply the rule to the plan's final_error / status and copy the chosen row in one enqueue:
+ * traj_best [N+1][2D] and its up-sampled form dense_best [Md][2D]: what gpmp2mi_interpolate_traj gives for that row,
+ * bit for bit for vector-space robots; for Pose2 robots the same arithmetic evaluated once per coordinate, equal to
+ * rounding (tested at 1e-12).  With best == -1 both are left untouched.  Any output may be NULL. */
+int gpmp2mi_plan_select(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range, int* best,
+                        int* n_eligible, double* traj_best, double* dense_best);
+int gpmp2mi_plan_select_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range, int* best,
+                            int* n_eligible, double* traj_best, double* dense_best, void* stream);
+/* Multi plans, host pointers in batch order: every shard scores its rows concurrently on its own device and stream as
+ * in gpmp2mi_multi_plan_optimize; the pick over the shards' candidates is the same rule on the host, so the answer is
+ * that of one plan of size B.  Errors and the caller's current device as the other multi-plan calls. */
+int gpmp2mi_multi_plan_score(gpmp2mi_multi_plan* m, int inter_step, double* support_cost, double* dense_cost,
+                             double* min_clearance, int* worst, int* out_of_range);
+int gpmp2mi_multi_plan_select(gpmp2mi_multi_plan* m, int inter_step, double required_clearance, int require_in_range,
+                              int* best, int* n_eligible, double* traj_best, double* dense_best);
 
 /* ---- factor-level entry points (the GTSAM plug-in contract: evaluateError(x..., H...)) -----
  * All batched over M independent evaluations, host pointers, Jacobian outputs may be NULL. */

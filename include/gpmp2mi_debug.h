@@ -62,6 +62,14 @@ int gpmp2mi_debug_stall_begin(void* stream, int max_ms, void** token);
 int gpmp2mi_debug_stream_create(void** stream);   /* a non-blocking stream of the HIP runtime the library uses */
 int gpmp2mi_debug_stream_destroy(void* stream);
 int gpmp2mi_debug_stall_release(void* token);
+/* Test hooks: device memory from the HIP runtime the library uses, for the tests of the `_dev` entry points (a test
+ * process must not pull in a second runtime to own a buffer).  alloc fills with `fill_byte`; read / write are blocking
+ * copies on the default stream, which does not wait for the non-blocking streams of gpmp2mi_debug_stream_create; free
+ * waits for the device. */
+int gpmp2mi_debug_device_alloc(size_t bytes, int fill_byte, void** out);
+int gpmp2mi_debug_device_read(void* dst_host, const void* src_dev, size_t bytes);
+int gpmp2mi_debug_device_write(void* dst_dev, const void* src_host, size_t bytes);
+int gpmp2mi_debug_device_free(void* p);
 /* Diagnostic: lane semantics of the wave-level moves the solver relies on (tests/test_gpu_plan.py). */
 int gpmp2mi_debug_crosslane(const double* in64, double* out512);
 /* Diagnostic: raw device-to-host copy of a solver hand-over buffer of the plan (0: diagonal tiles [B][N+1][256],

@@ -514,6 +514,53 @@ inline double CollisionCost2DArm(const ArmModel& arm, const PlanarSDF& sdf, cons
   return c;
 }
 
+/// What the executed trajectory looks like to the obstacles (include/gpmp2mi.h "scoring"): the collision cost of the
+/// support states (= CollisionCost*), the same sum over the trajectory up-sampled with inter_step states per interval
+/// (the states interpolateArmTraj hands to the controller), the smallest signed clearance with the checked state and
+/// sphere where it occurs ((-1, -1) and +inf when no sphere centre is inside the field) and the number of
+/// (state, sphere) pairs outside the field.
+struct TrajectoryScore {
+  double support_cost = 0.0, dense_cost = 0.0, min_clearance = 0.0;
+  int worst_state = -1, worst_sphere = -1, out_of_range = 0;
+};
+/// ROBOT: any of the robot models; SDF: SignedDistanceField or PlanarSDF.  delta_t = total_time / total_step.
+template <class ROBOT, class SDF>
+inline TrajectoryScore ScoreTrajectory(const ROBOT& robot, const SDF& sdf, const Trajectory& result,
+                                       const TrajOptimizerSetting& setting, std::size_t inter_step) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[ScoreTrajectory] result does not match dof / total_step");
+  TrajectoryScore sc;
+  int worst[2] = {-1, -1};
+  check(gpmp2mi_score_traj(robot.handle(), sdf.handle(), setting.total_time / static_cast<double>(setting.total_step),
+                           static_cast<int>(inter_step), 1, static_cast<int>(result.total_step), result.data.data(),
+                           &sc.support_cost, &sc.dense_cost, &sc.min_clearance, worst, &sc.out_of_range),
+        "gpmp2mi_score_traj");
+  sc.worst_state = worst[0];
+  sc.worst_sphere = worst[1];
+  return sc;
+}
+/// Best of several results (restarts): the index of the eligible one with the smallest final_error, the lowest index
+/// on ties, -1 if none is eligible.  Eligible: status != GPMP2MI_TRAJ_NOT_SPD (status may be empty: all fine), finite
+/// final_error, min_clearance >= required_clearance and, with require_in_range, no pair outside the field.  Host code.
+inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int>& status,
+                                const std::vector<TrajectoryScore>& scores, double required_clearance = 0.0,
+                                bool require_in_range = false, std::size_t* n_eligible = nullptr) {
+  if (scores.size() != final_error.size() || (!status.empty() && status.size() != final_error.size()))
+    throw std::runtime_error("[SelectBestTrajectory] final_error, status and scores differ in length");
+  Vector clearance(scores.size());
+  std::vector<int> oor(scores.size());
+  for (std::size_t b = 0; b < scores.size(); b++) {
+    clearance[b] = scores[b].min_clearance;
+    oor[b] = scores[b].out_of_range;
+  }
+  int best = -1, n = 0;
+  check(gpmp2mi_select_best(static_cast<int>(scores.size()), final_error.data(), status.empty() ? nullptr : status.data(),
+                            clearance.data(), oor.data(), required_clearance, require_in_range ? 1 : 0, &best, &n),
+        "gpmp2mi_select_best");
+  if (n_eligible) *n_eligible = static_cast<std::size_t>(n);
+  return best;
+}
+
 namespace internal {
 inline Trajectory interpolateTraj(const Trajectory& opt_values, const Vector& Qc, double delta_t, std::size_t inter_step,
                                   std::size_t start_index, std::size_t end_index, bool lie) {
