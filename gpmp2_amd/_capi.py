@@ -70,7 +70,7 @@ class GraphOpts(C.Structure):
 class DebugForms(C.Structure):
     """gpmp2mi_debug_forms (include/gpmp2mi_debug.h): kernel forms forced on a plan; all zero = the plan's own choice."""
     _fields_ = [("lin_split", C.c_int), ("no_fused_finish", C.c_int), ("generic_gn", C.c_int), ("wide_dense", C.c_int),
-                ("fail_alloc_at", C.c_int)]
+                ("fail_alloc_at", C.c_int), ("no_early_stop", C.c_int)]
 
 
 def make_debug_forms(forms):

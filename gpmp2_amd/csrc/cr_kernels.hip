@@ -127,7 +127,7 @@ template <int D, bool LIE>
 __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assemble(const PlanParams* __restrict__ pp, PlanBuffers pb,
                                                               const double* __restrict__ traj, int bufsel,
                                                               double* __restrict__ tiles,
-                                                              const int* __restrict__ active) {
+                                                              const int* __restrict__ active, int early_stop) {
   constexpr int n = 2 * D;
   using Asm = Assembler<D, LIE>;
   const PlanParams& P = *pp;
@@ -135,6 +135,13 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   const int groups = (N + ASM_WAVES) / ASM_WAVES;  // ceil((N + 1) / 4)
   const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
   if (active && !active[b]) return;
+  // Early stop (Gauss-Newton fast driver): the graph error at these states is already known -- k_linearize_arm left its
+  // shares -- so the step control of k_gn_step_cr is evaluated here, on the same inputs: a trajectory that stops in this
+  // pass (converged, rolled back, out of iterations) builds and eliminates nothing and leaves the hand-over tiles alone.
+  if (early_stop) {
+    int status;
+    if (gn_decide(P, pb.iters[b], pb.prev_err[b], error_from_shares(P, pb, b), status) != 0) return;
+  }
   // Dogleg retries (phase 1: same linearization, smaller trust region) need no new factorisation
   if (P.opt_type == GPMP2MI_OPT_DOGLEG && active && pb.phase[b] != 0) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
@@ -166,12 +173,14 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
                                   odd || P.opt_type == GPMP2MI_OPT_DOGLEG);
   G2_ASTAMP(2);
   if (live) {
-    err_acc = wave_sum(err_acc);
-    if (lane == 0) pb.epart[(size_t)b * P.Npad + i] = 0.5 * err_acc;
-    // gradient g_i (the rhs column holds -g_i), kept for the step-control scalars of LM / Dogleg
-    if (c == RHSCOL) {
+    if (!early_stop) {   // (early stop: the error comes from pb.cshare, and only the trial-step kernels read gvec)
+      err_acc = wave_sum(err_acc);
+      if (lane == 0) pb.epart[(size_t)b * P.Npad + i] = 0.5 * err_acc;
+      // gradient g_i (the rhs column holds -g_i), kept for the step-control scalars of LM / Dogleg
+      if (c == RHSCOL) {
 #pragma unroll
-      for (int k = 0; k < 4; k++) pb.gvec[((size_t)b * (N + 1) + i) * 16 + g + 4 * k] = -S.r[k];
+        for (int k = 0; k < 4; k++) pb.gvec[((size_t)b * (N + 1) + i) * 16 + g + 4 * k] = -S.r[k];
+      }
     }
     if (P.opt_type == GPMP2MI_OPT_DOGLEG) {  // un-eliminated blocks for g^T H g (k_ghg)
       double* ht = pb.htiles + ((size_t)b * (N + 1) + i) * 2 * TILE_DBL;
@@ -271,14 +280,15 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
 }
 
 int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel,
-                    const int* active, hipStream_t st) {
+                    const int* active, hipStream_t st, bool early_stop) {
+  const int es = early_stop ? 1 : 0;
   const dim3 grid(hp.B * ((hp.N + ASM_WAVES) / ASM_WAVES)), block(64 * ASM_WAVES);
   const size_t slotd = (size_t)(hp.I + 1) * hp.RECS + hp.GPS + 24 * hp.I;
   const size_t shmem = ((ASM_WAVES + 1) * slotd + (slotd >= TILE_DBL ? 4 : 5) * TILE_DBL) * sizeof(double);
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    if (hp.lie) k_assemble<D, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active);
-    else k_assemble<D, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active);
+    if (hp.lie) k_assemble<D, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else k_assemble<D, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
   });
 }
 
@@ -441,7 +451,7 @@ __device__ __forceinline__ void cr_backward(const PlanBuffers& pb, int b, int N,
 }
 
 template <int D>
-__device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuffers& pb, int pass) {
+__device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuffers& pb, int pass, int early_stop) {
   constexpr int n = 2 * D;
   const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
   if (!pb.active[b]) return;
@@ -463,54 +473,49 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
   // what the step control below needs from HBM is requested before the error sum, not after its barrier
   const int it = pb.iters[b];
   const double prev = pb.prev_err[b];
-  // ---- graph error at `cur`: fixed-order sum of the per-block partials written by k_assemble,
-  // then the gpmp2::optimize control flow
-  if (w == 0) {
-    double acc = 0.0;
-    for (int i = lane; i <= N; i += 64) acc += pb.epart[(size_t)b * P.Npad + i];
-    acc = wave_sum(acc);
-    if (lane == 0) {
-      red[0] = acc;
-      flags[1] = 0;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const double new_err = red[0];
-    int decision = 0;  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
-    double* tr = pb.trace + (size_t)b * (P.max_iter + 1);
-    if (it <= P.max_iter) tr[it] = new_err;
-    // first evaluation of the slot's problem: pass 0 of a plain run; a queue run loads problems at later passes
-    if (it == 0) {
-      pb.prev_err[b] = new_err;
-      if (P.fixed_iters > 0) decision = 0;
-      else if (new_err <= P.err_tol) { decision = 1; pb.status[b] = GPMP2MI_TRAJ_ALREADY_OPTIMAL; }
-      else if (P.max_iter <= 0) { decision = 1; pb.status[b] = GPMP2MI_TRAJ_MAX_ITER; }
-    } else if (P.fixed_iters > 0) {
-      if (it >= P.fixed_iters) { decision = 1; pb.status[b] = GPMP2MI_TRAJ_MAX_ITER; }
-    } else {
-      const bool conv = check_convergence(P.rel_thresh, P.abs_tol, P.err_tol, prev, new_err);
-      if (it < P.max_iter && !conv) {
-        pb.prev_err[b] = new_err;
-      } else if (new_err > prev && P.no_increase) {
-        decision = 2;
-        pb.status[b] = GPMP2MI_TRAJ_ROLLED_BACK;
-        pb.final_err[b] = prev;
-      } else {
-        decision = 1;
-        pb.status[b] = conv ? GPMP2MI_TRAJ_CONVERGED : GPMP2MI_TRAJ_MAX_ITER;
+  // ---- graph error at `cur`, then the gpmp2::optimize control flow (gn_decide): every thread evaluates it on the same
+  // values, thread 0 records the outcome.
+  // Early stop: the error is the fixed-order sum of the per-chunk shares of k_linearize_arm -- uniform loads, no
+  // cross-lane step and no barrier; k_assemble took the same decision from the same words and built nothing for a
+  // trajectory that stops.  Otherwise: the per-block partials of k_assemble (or the sum k_error_parts left in block 0).
+  double new_err;
+  if (early_stop) {
+    new_err = error_from_shares(P, pb, b);
+    if (tid == 0) flags[1] = 0;   // (set only behind the barriers of cr_forward)
+  } else {
+    if (w == 0) {
+      double acc = 0.0;
+      for (int i = lane; i <= N; i += 64) acc += pb.epart[(size_t)b * P.Npad + i];
+      acc = wave_sum(acc);
+      if (lane == 0) {
+        red[0] = acc;
+        flags[1] = 0;
       }
     }
-    if (decision == 1) pb.final_err[b] = new_err;
-    pb.cur_err[b] = new_err;
-    flags[0] = decision;
+    __syncthreads();
+    new_err = red[0];
   }
-  __syncthreads();
-  const int decision = flags[0];
+  int status;
+  const int decision = gn_decide(P, it, prev, new_err, status);  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
+  if (tid == 0) {
+    if (it <= P.max_iter) pb.trace[(size_t)b * (P.max_iter + 1) + it] = new_err;
+    pb.cur_err[b] = new_err;
+    if (decision != 0) {
+      pb.status[b] = status;
+      pb.final_err[b] = (decision == 2) ? prev : new_err;
+    }
+  }
+  // prev_err and active are inputs of this very decision: they are written only behind a barrier that every wavefront
+  // reaches after it has read them
+  const bool keep_err = it == 0 || (decision == 0 && P.fixed_iters == 0);   // currentError = the error just found
   if (decision != 0) {
     const double* src = (decision == 2) ? last : cur;
     for (size_t k = tid; k < tsz; k += blockDim.x) result[k] = src[k];
-    if (tid == 0) pb.active[b] = 0;
+    __syncthreads();
+    if (tid == 0) {
+      if (keep_err) pb.prev_err[b] = new_err;
+      pb.active[b] = 0;
+    }
     return;
   }
 
@@ -519,6 +524,7 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
   G2_STAMP(2);
   if ((!ok && lane == 0) || (tid == 0 && pb.notspd[b])) flags[1] = 1;
   __syncthreads();
+  if (tid == 0 && keep_err) pb.prev_err[b] = new_err;
   if (flags[1]) {
     if (tid == 0) pb.notspd[b] = 0;
     for (size_t k = tid; k < tsz; k += blockDim.x) result[k] = cur[k];
@@ -569,8 +575,8 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
 }
 template <int D>
 __global__ __launch_bounds__(64 * CR_WAVES) void k_gn_step_cr(const PlanParams* __restrict__ pp,
-                                                               PlanBuffers pb, int pass) {
-  gn_step_body<D>(*pp, pb, pass);
+                                                               PlanBuffers pb, int pass, int early_stop) {
+  gn_step_body<D>(*pp, pb, pass, early_stop);
   if (threadIdx.x == 0) publish_pass_count(pb, pass);
 }
 
@@ -718,7 +724,7 @@ int launch_finish_trial(const PlanParams& hp, const PlanBuffers& pb, hipStream_t
   });
 }
 
-int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st) {
+int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st, bool early_stop) {
   const dim3 grid(hp.B), block(64 * CR_WAVES);
   const size_t shmem = ((size_t)(hp.N + 1) * 16 + CR_WAVES + 2) * sizeof(double);
   if (shmem > 150 * 1024) {
@@ -726,7 +732,7 @@ int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hip
     return GPMP2MI_ERR_UNSUPPORTED;
   }
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
-    k_gn_step_cr<decltype(d)::value><<<grid, block, shmem, st>>>(pb.params, pb, pass);
+    k_gn_step_cr<decltype(d)::value><<<grid, block, shmem, st>>>(pb.params, pb, pass, early_stop ? 1 : 0);
   });
 }
 

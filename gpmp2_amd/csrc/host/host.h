@@ -168,9 +168,15 @@ struct PlanForms {
   int wide = 0, split_back = 0, wide_h0 = 2, lin_split = 1, fuse_finish = 0, spart_groups = 0;
   bool dense = false;        // dense normal equations + cyclic reduction over dense blocks: dof 12..18, or forced for 8..11
   bool generic_gn = false;   // forced: the plan's Gauss-Newton optimize runs through the trial-step driver
+  bool no_early_stop = false;   // forced: the Gauss-Newton fast driver keeps the step control behind k_assemble
   // Gauss-Newton takes the fast driver (3 launches per pass) on every plan that is not wide; a forced generic GN sends
   // only the plan's own optimize through the trial-step driver, not plan_update
   bool gn_fast(bool update) const { return !wide && (update || !generic_gn); }
+  // Gauss-Newton fast driver: the step control reads the per-chunk error shares of k_linearize_arm, in k_assemble (which
+  // then builds nothing for a trajectory that stops) and in k_gn_step_cr alike.  A property of the run, not of the
+  // parameter block: gpmp2mi_plan_update sends LM / Dogleg plans through that driver too, and a plan's extra factors
+  // (`extras`) add their errors to the records behind the linearization, where the shares do not see them.
+  bool early_stop(bool extras) const { return lin_split == 4 && !extras && !no_early_stop; }
   // trial-step driver, LM / GN (Dogleg's step kernel does the whole back-substitution): k_finish_trial(_wide) finishes
   // the step, or the trial linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
   bool finish_trial(int opt) const { return split_back && opt != GPMP2MI_OPT_DOGLEG && !fuse_finish; }

@@ -155,6 +155,7 @@ static int choose_forms(const RobotDev& h, const gpmp2mi_settings& s, int B, con
   F.fuse_finish = F.lin_split == 4 && F.split_back && !F.wide && !f.no_fused_finish;
   F.spart_groups = F.fuse_finish ? (1 + N * (I + 1) + 63) / 64 : (N + 8) / 8;
   F.generic_gn = f.generic_gn != 0;
+  F.no_early_stop = f.no_early_stop != 0;
   *out = F;
   return GPMP2MI_OK;
 }
@@ -346,6 +347,7 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
   G2_TRY(plan_alloc(p, &pb.trace, (size_t)B * (P.max_iter + 1)));
   for (int** q : {&pb.iters, &pb.status, &pb.active, &pb.phase, &pb.notspd}) G2_TRY(plan_alloc(p, q, B));
   G2_TRY(plan_alloc(p, &pb.epart, (size_t)B * P.Npad));
+  G2_TRY(plan_alloc(p, &pb.cshare, (size_t)B * (P.Ppad / 64) * 3));
   if (ex.n_ws > 0) {
     G2_TRY(plan_alloc(p, &ex.des, hx.des.size()));
     G2_TRY(plan_alloc(p, &ex.poses, M * h.nr_links * 16));

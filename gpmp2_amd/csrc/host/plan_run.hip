@@ -85,22 +85,25 @@ static int wait_pass_count(const int* flags, int pass, hipStream_t st, int* coun
 
 // ---- the pass bodies shared by the plain driver (plan_run_impl) and the queue driver (plan_queue_impl); `pb` is the
 // plan's buffers, or a copy whose pass-indexed arrays point elsewhere (queue runs)
-// Gauss-Newton fast path, one pass: assemble (the closing pass of a fixed-iteration round only sums the error), the
-// step kernel (step control + solve), and k_finish_step on the split path without the fused finish.  `states`: the
-// states of the pass.
+// Gauss-Newton fast path, one pass: assemble, the step kernel (step control + solve), and k_finish_step on the split
+// path without the fused finish.  `states`: the states of the pass.  The closing pass of a fixed-iteration round solves
+// nothing: it only needs the error of the final values, which the linearization's shares already hold (early stop:
+// nothing is launched in front of the step kernel) or k_error_parts sums.
 static int enqueue_gn_pass(gpmp2mi_plan* p, const PlanBuffers& pb, int pass, double* states, hipStream_t st) {
   const PlanParams& P = p->hp;
   const PlanForms& F = p->forms;
+  const bool early = F.early_stop(p->has_extras);
   if (P.fixed_iters > 0 && pass % (P.fixed_iters + 1) == P.fixed_iters) {
-    // closing pass of a fixed-iteration run: nothing is solved any more, only the error of the final values
-    p->timer.begin("final_error", st);
-    G2_TRY(launch_error_parts(P, pb, states, 0, pb.active, st));
+    if (!early) {
+      p->timer.begin("final_error", st);
+      G2_TRY(launch_error_parts(P, pb, states, 0, pb.active, st));
+    }
   } else {
     p->timer.begin("assemble", st);
-    G2_TRY(launch_assemble(P, pb, states, 0, pb.active, st));
+    G2_TRY(launch_assemble(P, pb, states, 0, pb.active, st, early));
   }
   p->timer.begin("gn_step_cr", st);
-  G2_TRY(launch_gn_step_cr(P, pb, pass, st));
+  G2_TRY(launch_gn_step_cr(P, pb, pass, st, early));
   if (F.split_back && !F.fuse_finish) {
     p->timer.begin("finish_step", st);
     G2_TRY(launch_finish_step(P, pb, pass, st));
@@ -320,7 +323,7 @@ static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* pas
   if (gn) {
     // Gauss-Newton fast path: a fresh slot's first evaluation is the step kernel's iters == 0 branch.  A new problem's
     // initial values go where the next pass's linearization reads the states (states_of(pass)).  Fixed-iteration plans
-    // load only at the boundary that closes a round, where the host runs k_error_parts for every slot.
+    // load only at the boundary that closes a round.
     G2_TRY(enqueue_gn_lin(p, 0, st));
     for (int pass = 0;; pass++) {
       G2_CHECK(pass < cap, GPMP2MI_ERR_HIP, "queue run exceeded its pass bound");

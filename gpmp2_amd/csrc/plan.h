@@ -126,7 +126,10 @@ struct PlanBuffers {
   int* active;             // 1 while the trajectory is still iterating
   int* phase;              // optimizer-specific sub-state
   int* notspd;             // [B] set when a level-1 pivot (k_assemble) was not positive
-  double* epart;           // [B][Npad] per-block share of the graph error (k_assemble)
+  double* epart;           // [B][Npad] per-block share of the graph error (k_assemble, or k_error_parts: the whole sum in block
+                           // 0); not written when the step control reads cshare instead (early stop)
+  double* cshare;          // [B][Ppad/64][3] per-chunk share of the graph error at `cur`: obstacle, GP prior, priors / limits
+                           // (k_linearize_arm, buffer 0 only; summed by error_from_shares)
   int* n_active;           // [max_pass] trajectories that iterated in each pass
   int* done;               // [max_pass] workgroups of the pass-closing kernel that have finished
   int* host_flags;         // [max_pass] pinned, device-mapped: n_active[pass] once the pass is complete, else -1
@@ -180,8 +183,10 @@ int launch_set_mode(const PlanBuffers& pb, int opt_type, int fixed_iters, hipStr
 int launch_error_parts(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel, const int* active,
                        hipStream_t st);
 int launch_plan_reset(const PlanParams& hp, const PlanBuffers& pb, const double* start, hipStream_t st);
+// early_stop (Gauss-Newton fast driver, shares in pb.cshare): the step control runs at the head of k_assemble and of
+// k_gn_step_cr; a trajectory that stops builds nothing
 int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel,
-                    const int* active, hipStream_t st);
+                    const int* active, hipStream_t st, bool early_stop = false);
 int launch_solve_step(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st);
 int launch_ghg(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st);
 int launch_decide(const PlanParams& hp, const PlanBuffers& pb, int pass, bool init, hipStream_t st);
@@ -192,7 +197,7 @@ int launch_queue_first(const PlanParams& hp, const PlanBuffers& pb, const QueueR
 int launch_queue_scan(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, int pass, bool load, hipStream_t st);
 int launch_queue_refill(const PlanParams& hp, const PlanBuffers& pb, const QueueRun& q, double* states, hipStream_t st);
 int launch_debug_crosslane(const double* in, double* out, hipStream_t st);
-int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st);
+int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st, bool early_stop = false);
 int launch_finish_step(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st);
 int launch_finish_trial(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st);
 int launch_solve_dense(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st);

@@ -11,59 +11,72 @@ namespace g2 {
 // prior + limit + vehicle-dynamics error of one trajectory (0.5 * whitened squared residuals),
 // wave-reduced.  PriorFactor (planner/BatchTrajOptimizer-inl.h:41-48), JointLimitFactorVector,
 // VelocityLimitFactorVector (:50-59), VehicleDynamicsFactor (dynamics/VehicleDynamics.h:19-27).
+// One entry of that sum: `acc` plus the terms of coordinate rho of state i (start / goal prior, replanner state priors,
+// position / velocity limit, vehicle dynamics).  zs: the state's 2D values; nxp = pb.xp_n[b].  Every caller that sums
+// these terms goes through here: misc_error_partial below and the per-chunk shares of k_linearize_arm.
+// MAYBE_LIE = false: the caller knows the robot has no Pose2 base (fixed-base arms), and the chart code is left out.
+template <bool MAYBE_LIE = true>
+__device__ __forceinline__ double misc_entry_add(double acc, const PlanParams& P, const PlanBuffers& pb, int b, int nxp,
+                                                 int i, int rho, const double* __restrict__ zs) {
+  const int D = P.D, n = P.n, N = P.N;
+  const bool lie = MAYBE_LIE && P.lie;
+  const int a = rho >= D, k = rho - a * D;
+  const double z = zs[rho];
+  if (i == 0 || (i == N && pb.goal_on[b] && (a || !P.end_conf_prior_off))) {
+    const double* tg = (i == 0) ? (a ? pb.start_vel : pb.start_conf) : (a ? pb.end_vel : pb.end_conf);
+    tg += (size_t)b * D;
+    double d = z - tg[k];
+    if (lie && !a && k < 3) {  // -Local(x, prior) of PriorFactor<Pose2Vector>
+      const P2 bt = pose2_between(P2{zs[0], zs[1], zs[2]}, P2{tg[0], tg[1], tg[2]});
+      d = -(k == 0 ? bt.x : k == 1 ? bt.y : bt.th);
+    }
+    acc += (a ? P.vel_prior_w : P.conf_prior_w) * d * d;
+  }
+  for (int e = 0; e < nxp; e++) {  // replanner state priors: r^T W r, row k's share
+    const size_t xe = (size_t)b * XP_MAX + e;
+    if (pb.xp_state[xe] != i || (a && !pb.xp_has_vel[xe])) continue;
+    const double* Wm = pb.xp_info + (xe * 2 + a) * D * D + (size_t)k * D;
+    const double* tg = pb.xp_target + xe * n + a * D;
+    double wr = 0.0, rk = 0.0;
+    for (int cc = 0; cc < D; cc++) {
+      double rc = zs[a * D + cc] - tg[cc];
+      if (lie && !a && cc < 3) {
+        const P2 bt = pose2_between(P2{zs[0], zs[1], zs[2]}, P2{tg[0], tg[1], tg[2]});
+        rc = -(cc == 0 ? bt.x : cc == 1 ? bt.y : bt.th);
+      }
+      wr = fma(Wm[cc], rc, wr);
+      if (cc == k) rk = rc;
+    }
+    acc += wr * rk;
+  }
+  double H;
+  if (!a && P.flag_pos_limit && !(lie && k < 3)) {
+    const double e = hinge_limit(z, P.pos_lo[k], P.pos_hi[k], P.pos_th[k], H);
+    acc += P.pos_w[k] * e * e;
+  }
+  if (a && P.flag_vel_limit) {
+    const double e = hinge_limit(z, -P.vel_lim[k], P.vel_lim[k], P.vel_th[k], H);
+    acc += P.vel_w[k] * e * e;
+  }
+  if (a && k == 1 && P.vdyn_w > 0.0) acc += P.vdyn_w * z * z;
+  return acc;
+}
+// without limit / dynamics factors and replanner priors only the first and the last state carry terms
+__device__ __forceinline__ bool misc_every_state(const PlanParams& P, int nxp) {
+  return P.flag_pos_limit || P.flag_vel_limit || P.vdyn_w > 0.0 || nxp > 0;
+}
 // this thread's share when `nthr` threads split the entries (not yet reduced)
 __device__ __forceinline__ double misc_error_partial(const PlanParams& P, const PlanBuffers& pb, int b,
                                                      const double* __restrict__ tr, int tid, int nthr) {
-  const int D = P.D, n = P.n, N = P.N;
+  const int n = P.n, N = P.N;
   double acc = 0.0;
-  // without limit / dynamics factors and replanner priors only the first and the last state carry terms
   const int nxp = pb.xp_n[b];
-  const bool every_state = P.flag_pos_limit || P.flag_vel_limit || P.vdyn_w > 0.0 || nxp > 0;
+  const bool every_state = misc_every_state(P, nxp);
   const int count = every_state ? (N + 1) * n : (N > 0 ? 2 * n : n);
   for (int q = tid; q < count; q += nthr) {
     const int idx = (every_state || q < n) ? q : N * n + (q - n);
     const int i = idx / n, rho = idx - i * n;
-    const int a = rho >= D, k = rho - a * D;
-    const double z = tr[idx];
-    if (i == 0 || (i == N && pb.goal_on[b] && (a || !P.end_conf_prior_off))) {
-      const double* tg = (i == 0) ? (a ? pb.start_vel : pb.start_conf) : (a ? pb.end_vel : pb.end_conf);
-      tg += (size_t)b * D;
-      double d = z - tg[k];
-      if (P.lie && !a && k < 3) {  // -Local(x, prior) of PriorFactor<Pose2Vector>
-        const double* zs = tr + (size_t)i * n;
-        const P2 bt = pose2_between(P2{zs[0], zs[1], zs[2]}, P2{tg[0], tg[1], tg[2]});
-        d = -(k == 0 ? bt.x : k == 1 ? bt.y : bt.th);
-      }
-      acc += (a ? P.vel_prior_w : P.conf_prior_w) * d * d;
-    }
-    for (int e = 0; e < nxp; e++) {  // replanner state priors: r^T W r, row k's share
-      const size_t xe = (size_t)b * XP_MAX + e;
-      if (pb.xp_state[xe] != i || (a && !pb.xp_has_vel[xe])) continue;
-      const double* Wm = pb.xp_info + (xe * 2 + a) * D * D + (size_t)k * D;
-      const double* tg = pb.xp_target + xe * n + a * D;
-      const double* zs = tr + (size_t)i * n;
-      double wr = 0.0, rk = 0.0;
-      for (int cc = 0; cc < D; cc++) {
-        double rc = zs[a * D + cc] - tg[cc];
-        if (P.lie && !a && cc < 3) {
-          const P2 bt = pose2_between(P2{zs[0], zs[1], zs[2]}, P2{tg[0], tg[1], tg[2]});
-          rc = -(cc == 0 ? bt.x : cc == 1 ? bt.y : bt.th);
-        }
-        wr = fma(Wm[cc], rc, wr);
-        if (cc == k) rk = rc;
-      }
-      acc += wr * rk;
-    }
-    double H;
-    if (!a && P.flag_pos_limit && !(P.lie && k < 3)) {
-      const double e = hinge_limit(z, P.pos_lo[k], P.pos_hi[k], P.pos_th[k], H);
-      acc += P.pos_w[k] * e * e;
-    }
-    if (a && P.flag_vel_limit) {
-      const double e = hinge_limit(z, -P.vel_lim[k], P.vel_lim[k], P.vel_th[k], H);
-      acc += P.vel_w[k] * e * e;
-    }
-    if (a && k == 1 && P.vdyn_w > 0.0) acc += P.vdyn_w * z * z;
+    acc = misc_entry_add(acc, P, pb, b, nxp, i, rho, tr + (size_t)i * n);
   }
   return acc;
 }
@@ -104,6 +117,37 @@ __device__ __forceinline__ bool check_convergence(double rel, double abs_, doubl
   const double abs_dec = cur - nw;
   const double rel_dec = abs_dec / cur;
   return (rel != 0.0 && rel_dec <= rel) || (abs_dec <= abs_);
+}
+
+// =============================================================================== Gauss-Newton step control
+// The do/while of gpmp2::optimize (planner/BatchTrajOptimizer.cpp:273-307) for one trajectory of the Gauss-Newton fast
+// path, as a pure function of the trajectory's iteration count `it`, the error `prev` the last comparison kept
+// (currentError) and the error `new_err` of the values just linearized: 0 iterate, 1 stop with these values, 2 stop
+// with the values before the last step (no-increase rollback).  `status` is set when the trajectory stops.  it == 0 is
+// the first evaluation of a problem (pass 0 of a plain run; a queue run loads problems at later passes).  k_assemble and
+// k_gn_step_cr both call it on the same inputs, which only earlier kernels wrote, so they agree by construction.
+__device__ __forceinline__ int gn_decide(const PlanParams& P, int it, double prev, double new_err, int& status) {
+  status = GPMP2MI_TRAJ_MAX_ITER;
+  if (it == 0) {
+    if (P.fixed_iters > 0) return 0;
+    if (new_err <= P.err_tol) { status = GPMP2MI_TRAJ_ALREADY_OPTIMAL; return 1; }
+    return P.max_iter <= 0 ? 1 : 0;
+  }
+  if (P.fixed_iters > 0) return it >= P.fixed_iters ? 1 : 0;
+  const bool conv = check_convergence(P.rel_thresh, P.abs_tol, P.err_tol, prev, new_err);
+  if (it < P.max_iter && !conv) return 0;
+  if (new_err > prev && P.no_increase) { status = GPMP2MI_TRAJ_ROLLED_BACK; return 2; }
+  if (conv) status = GPMP2MI_TRAJ_CONVERGED;
+  return 1;
+}
+// Graph error of trajectory b from the per-chunk shares k_linearize_arm left (pb.cshare): chunks in ascending order,
+// obstacle + GP + misc of each, halved.  Uniform loads, every lane forms the same value: no cross-lane step, no barrier.
+__device__ __forceinline__ double error_from_shares(const PlanParams& P, const PlanBuffers& pb, int b) {
+  const int nchunk = P.Ppad / 64;
+  const double* __restrict__ cs = pb.cshare + (size_t)b * nchunk * 3;
+  double acc = 0.0;
+  for (int q = 0; q < nchunk; q++) acc += (cs[3 * q] + cs[3 * q + 1]) + cs[3 * q + 2];
+  return 0.5 * acc;
 }
 
 

@@ -309,6 +309,11 @@ __global__ __launch_bounds__(64 * NSPLIT, KIND == GPMP2MI_ROBOT_ARM ? 2 : 1) voi
 // reads from `traj` (the buffer of the previous pass, which nobody writes during this kernel), keeps the new states in
 // LDS for its own points and writes those whose unary point lies in its chunk to `dst`.  The two state buffers of a
 // plan (cur / last) swap roles from pass to pass, so `last` is simply the buffer the step started from.
+// Error shares (linearization at `cur`: bufsel == 0, not `trial`): the kernel holds every term of the graph error
+// 0.5 (sum of point errors + sum of GP energies + prior / limit terms), so each workgroup leaves its chunk's three sums in
+// pb.cshare -- obstacle (wavefront 0, the values it stores in the records), GP prior (last wavefront), and the prior /
+// limit / state-prior terms of the states it owns (wavefront 1, from the states in LDS, while wavefront 0 walks the chain).
+// The Gauss-Newton step control reads them (error_from_shares) instead of a sum over k_assemble's blocks.
 template <int AD, int SDIM, int NW>
 __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __restrict__ Rg, SdfDev sdf,
                                                                const PlanParams* __restrict__ pp, PlanBuffers pb,
@@ -357,6 +362,8 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
   auto state_of = [&](int pt) { return pt == 0 ? 0 : 1 + (pt - 1) / (I + 1); };
   const int s1 = state_of(p_hi), s0 = max(0, state_of(p_lo) - 1), ns = s1 - s0 + 1;   // ns <= ZNS: launch_linearize checks
   const bool apply = dst != nullptr && pb.stepped[b] == pass;
+  const bool shares = bufsel == 0 && !trial;
+  double* __restrict__ cshare = pb.cshare + ((size_t)b * nchunk + chunk) * 3;
   if (apply) {
     const double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;
     const double* xg = pb.xg + (size_t)b * (N + 1) * 16;
@@ -481,6 +488,19 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
         buf[FR * k + 6 + t][lane] = F.t[t];
       }
     });
+  } else if (wv == 1 && shares) {
+    // misc share: the entries of the states this chunk owns (the test that guards dst[k] = z above), from zn
+    const int nxp = pb.xp_n[b];
+    const bool every_state = misc_every_state(P, nxp);
+    double acc = 0.0;
+    for (int e = lane; e < ns * n; e += 64) {
+      const int t = e / n, rho = e - t * n, st = s0 + t;
+      const int pu = st * (I + 1);
+      if (pu < p_lo || pu > p_lo + 63 || !(every_state || st == 0 || st == N)) continue;
+      acc = misc_entry_add<false>(acc, P, pb, b, nxp, st, rho, &zn[t][0]);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) cshare[2] = acc;
   }
   __syncthreads();
   G2_LSTAMP(2);
@@ -581,10 +601,15 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
 #pragma unroll
     for (int k = 0; k < (RECL + 1) / 2; k++)
       if (store_ok) rb[k] = double2{rv[2 * k], rv[2 * k + 1]};
+    if (shares) {   // obstacle share: the point errors as stored
+      const double es = wave_sum(store_ok ? rv[NG + D] : 0.0);
+      if (lane == 0) cshare[0] = es;
+    }
   }
   G2_LSTAMP(14);
   // GP prior of the interval ending at state i: GaussianProcessPriorLinear (gp/GaussianProcessPriorLinear.h:57-83),
   // r = Phi z_{i-1} - z_i, u = Q^-1 r (Q^-1 = B(dt) (x) Qc^-1), energy r^T u -- as in k_linearize above
+  double en = 0.0;
   if (unary && i > 0 && store_ok && wv == NW - 1) {
     double rx[D], rv[D], sx[D], sv[D];
     double* gb = gpu + ((size_t)b * P.Npad + i) * P.GPS;
@@ -604,7 +629,6 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
       sx[k] = ax;
       sv[k] = av;
     }
-    double en = 0.0;
 #pragma unroll
     for (int k = 0; k < D; k++) {
       const double ux = P.Winv[0] * sx[k] + P.Winv[1] * sv[k];
@@ -614,6 +638,10 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
       en += rx[k] * ux + rv[k] * uv;
     }
     gb[n] = en;
+  }
+  if (wv == NW - 1 && shares) {   // GP share: the energies as stored
+    const double gs = wave_sum(en);
+    if (lane == 0) cshare[1] = gs;
   }
   G2_LSTAMP(15);
 }
@@ -732,7 +760,9 @@ int launch_error_reduce(const PlanParams& hp, const PlanBuffers& pb, const doubl
 // The closing pass of a run with a fixed number of iterations only evaluates the error of the final values (every
 // trajectory stops in the step kernel before it factorises anything): instead of k_assemble, which would build and
 // eliminate all blocks for nothing, this kernel leaves the graph error of each active trajectory where the step kernel
-// looks for it -- the whole sum in the share of block 0, zeros in the others.
+// looks for it -- the whole sum in the share of block 0, zeros in the others.  Only plans whose step control reads
+// pb.epart launch it: with the early stop (per-chunk shares of k_linearize_arm in pb.cshare) the closing pass runs
+// nothing between the linearization and the step kernel.
 __global__ __launch_bounds__(256) void k_error_parts(const PlanParams* __restrict__ pp, PlanBuffers pb,
                                                       const double* __restrict__ traj, int bufsel,
                                                       const int* __restrict__ active) {

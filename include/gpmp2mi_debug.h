@@ -24,6 +24,8 @@ typedef struct gpmp2mi_debug_forms {   /* all zero = the plan's own choice */
   int generic_gn;       /* 1: Gauss-Newton through the trial-step driver (gpmp2mi_plan_update keeps the fast path) */
   int wide_dense;       /* 1: dof 8..11 through the dense block solver */
   int fail_alloc_at;    /* k > 0: the k-th device allocation of this create fails (GPMP2MI_ERR_ALLOC) */
+  int no_early_stop;    /* 1: the Gauss-Newton fast driver sums the error behind k_assemble and decides in the step
+                           kernel alone, instead of deciding from the linearization's error shares before the build */
 } gpmp2mi_debug_forms;
 /* gpmp2mi_plan_create with forced forms (forms = NULL: the same call) */
 int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
