@@ -1,5 +1,6 @@
-"""GPU parity, graph level: linearization (block-tridiagonal normal equations), the batched
-block-tridiagonal Cholesky, and the whole Gauss-Newton solve against the CPU oracle.
+"""GPU parity, graph level: linearization (block-tridiagonal normal equations), the sequential chain solver of the
+stand-alone entry point gpmp2mi_block_tridiag_solve, and the whole Gauss-Newton solve against the CPU oracle.  (The
+cyclic reductions that plans solve with are held to their backward error in tests/test_gpu_step_backward_error.py.)
 
 Stated tolerances (BASELINE.md parity gate): normal-equation entries and gradients relative 1e-9
 of the block's largest entry; per-iteration graph error relative 1e-9; final trajectory absolute
@@ -66,6 +67,12 @@ def test_linearize_point_robot_skip_first(engine, oracle):
 
 @pytest.mark.parametrize("n,nblk", [(14, 101), (4, 11), (6, 51), (1, 7), (15, 3), (10, 1)])
 def test_block_tridiag_solve(engine, oracle, n, nblk):
+    """gpmp2mi_block_tridiag_solve: the sequential chain solver (chain_solve<n> of tiles.h, n <= 15) behind that
+    stand-alone entry point.  No plan uses that kernel: the plans' cyclic reductions (one tile, 2x2 tiles, dense
+    blocks) are covered by tests/test_gpu_step_backward_error.py.  Checked forward against a dense solve, scaled by
+    the condition number, and backward: eta of tests/backward_error.py (right-hand side b = -g) at a few units of
+    roundoff whatever the condition number -- 1e-14, the bound the CPU oracle's own steps are held to."""
+    from backward_error import eta_rows
     rng = np.random.default_rng(n * 100 + nblk)
     B = 3
     # SPD block-tridiagonal from a random banded Jacobian
@@ -92,6 +99,9 @@ def test_block_tridiag_solve(engine, oracle, n, nblk):
         xd = np.linalg.solve(H, rhs[b].reshape(-1))
         cond = np.linalg.cond(H)
         np.testing.assert_allclose(x[b].reshape(-1), xd, atol=1e-13 * cond * np.abs(xd).max())
+    eta_gpu, eta_orc = eta_rows(Hd, Ho, -rhs, x), eta_rows(Hd, Ho, -rhs, xo)
+    print(f"n = {n}, {nblk} blocks: eta {eta_gpu.max():.2e} (oracle {eta_orc.max():.2e})")
+    assert eta_orc.max() <= 1e-14 and eta_gpu.max() <= 1e-14, (eta_gpu, eta_orc)
     np.testing.assert_allclose(x, xo, atol=1e-9 * np.abs(xo).max())
 
 

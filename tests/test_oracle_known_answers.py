@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import gpmp2_amd as g
+from backward_error import p2v_local as _p2v_local
 from helpers import arm_from_golden, num, numeric_jacobian, sdf_to_err, vec
 
 
@@ -260,17 +261,6 @@ def _p2v_retract(x, d):
     out = x + d
     out[0] = x[0] + c * d[0] - s * d[1]
     out[1] = x[1] + s * d[0] + c * d[1]
-    return out
-
-
-def _p2v_local(a, b):
-    """Pose2Vector localCoordinates(a -> b) in the same chart."""
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    c, s = math.cos(a[2]), math.sin(a[2])
-    dx, dy = b[0] - a[0], b[1] - a[1]
-    out = b - a
-    out[0], out[1] = c * dx + s * dy, -s * dx + c * dy
-    out[2] = math.atan2(math.sin(b[2] - a[2]), math.cos(b[2] - a[2]))
     return out
 
 
