@@ -14,6 +14,7 @@
 //                  gpmp2::optimize control flow (planner/BatchTrajOptimizer.cpp:273-307) and the
 //                  retract.
 #include "assembler.h"
+#include "cr_schedule.h"
 #include "dispatch.h"
 #include "plan_device.h"
 
@@ -140,10 +141,10 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   // pass (converged, rolled back, out of iterations) builds and eliminates nothing and leaves the hand-over tiles alone.
   if (early_stop) {
     int status;
-    if (gn_decide(P, pb.iters[b], pb.prev_err[b], error_from_shares(P, pb, b), status) != 0) return;
+    if (gn_decide(P.rules, pb.iters[b], pb.prev_err[b], error_from_shares(P, pb, b), status) != 0) return;
   }
   // Dogleg retries (phase 1: same linearization, smaller trust region) need no new factorisation
-  if (P.opt_type == GPMP2MI_OPT_DOGLEG && active && pb.phase[b] != 0) return;
+  if (active && dogleg_retry(P, pb, b)) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int i = ASM_WAVES * q + wv;
   const bool live = i <= N;             // the last group may be partly empty
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   const bool lvl2 = fuse2 && wv == 2 && live;
   Tile S, Cl, Cr;
   double err_acc = as.build_tiles(ic, slot0, slot1, traj + ((size_t)b * (N + 1) + ic) * n, S, Cl, Cr,
-                                  odd || P.opt_type == GPMP2MI_OPT_DOGLEG);
+                                  odd || P.rules.opt_type == GPMP2MI_OPT_DOGLEG);
   G2_ASTAMP(2);
   if (live) {
     if (!early_stop) {   // (early stop: the error comes from pb.cshare, and only the trial-step kernels read gvec)
@@ -182,12 +183,12 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
         for (int k = 0; k < 4; k++) pb.gvec[((size_t)b * (N + 1) + i) * 16 + g + 4 * k] = -S.r[k];
       }
     }
-    if (P.opt_type == GPMP2MI_OPT_DOGLEG) {  // un-eliminated blocks for g^T H g (k_ghg)
+    if (P.rules.opt_type == GPMP2MI_OPT_DOGLEG) {  // un-eliminated blocks for g^T H g (k_ghg)
       double* ht = pb.htiles + ((size_t)b * (N + 1) + i) * 2 * TILE_DBL;
       tile_store(ht, S, lane);
       tile_store(ht + TILE_DBL, Cr, lane);
     }
-    if (P.opt_type == GPMP2MI_OPT_LM) {  // LM damping: sqrt(lambda) I prior rows on every variable
+    if (P.rules.opt_type == GPMP2MI_OPT_LM) {  // LM damping: sqrt(lambda) I prior rows on every variable
       const double lam = pb.lambda[b];
 #pragma unroll
       for (int k = 0; k < 4; k++)
@@ -315,8 +316,7 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
   double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;  // per block: Wl, Wr, V
   bool ok = true;
   G2_STAMP_DECL;
-  int hfinal = 1;
-  while (hfinal <= N) hfinal <<= 1;
+  const int hfinal = cr_hfinal(N);
   // levels 1 and 2 were done by k_assemble (level 2 only when it is not the final one, N >= 2), including
   // their Schur complements on the surviving blocks (multiples of 4) and the level-4 couplings
   const int h0 = (N >= 2) ? 4 : 2;
@@ -325,13 +325,12 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
   // level-2 and level-4 neighbours in one go, so both levels take a single round.
   const bool defer4 = (h0 == 4) && (hfinal >= 8);
   for (int h = h0; h <= hfinal; h <<= 1) {
-    const bool final = (h == hfinal);
+    const CrLevel level = cr_level(N, h, !(defer4 && h == 4));
+    const bool final = level.final;
     const int hh = h >> 1;
-    const int countE = final ? 1 : ((N / h) + 1) / 2;
-    const int countU = (final || (defer4 && h == 4)) ? 0 : (N / (2 * h)) + 1;  // multiples of 2h in [0, N]
-    for (int idx = w; idx < countE + countU; idx += CR_WAVES) {
-      const bool elim = idx < countE;
-      const int j = elim ? (final ? 0 : h * (2 * idx + 1)) : 2 * h * (idx - countE);
+    for (int idx = w; idx < level.tasks(); idx += CR_WAVES) {
+      const bool elim = level.elim(idx);
+      const int j = level.block(idx);
       // every tile this task needs is requested before the first product: the level-1 / level-2 factors come from
       // the previous kernel (other XCDs' L2 -> Infinity Cache / HBM latency), and one latency is paid instead of
       // one per neighbour
@@ -409,16 +408,13 @@ __device__ __forceinline__ void cr_backward(const PlanBuffers& pb, int b, int N,
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, c = lane & 15, g = lane >> 4;
   const double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;
   G2_STAMP_DECL;
-  int hfinal = 1;
-  while (hfinal <= N) hfinal <<= 1;
+  const int hfinal = cr_hfinal(N);
   // the factor tiles of a wavefront's first task of a level do not depend on the level above: they are requested
   // BEFORE the barrier that publishes that level's solutions, so their latency hides behind it
-  auto block_of = [&](int h, int idx) { return (h == hfinal) ? 0 : h * (2 * idx + 1); };
-  auto count_of = [&](int h) { return (h == hfinal) ? 1 : ((N / h) + 1) / 2; };
   Tile pWl = tile_zero(), pWr = tile_zero(), pV = tile_zero();
   auto prefetch = [&](int h) {
-    if (h >= hmin && w < count_of(h)) {
-      const double* f = fac + (size_t)block_of(h, w) * 3 * TILE_DBL;
+    if (h >= hmin && w < cr_back_count(N, h)) {
+      const double* f = fac + (size_t)cr_back_block(N, h, w) * 3 * TILE_DBL;
       pWl = tile_load_rows<n>(f, lane);
       pWr = tile_load_rows<n>(f + TILE_DBL, lane);
       pV = load_v<n>(f + 2 * TILE_DBL, h, N, lane);
@@ -427,9 +423,9 @@ __device__ __forceinline__ void cr_backward(const PlanBuffers& pb, int b, int N,
   prefetch(hfinal);
   for (int h = hfinal; h >= hmin; h >>= 1) {
     const bool final = (h == hfinal);
-    const int count = count_of(h);
+    const int count = cr_back_count(N, h);
     for (int idx = w; idx < count; idx += CR_WAVES) {
-      const int j = block_of(h, idx);
+      const int j = cr_back_block(N, h, idx);
       Tile Wl = pWl, Wr = pWr, V = pV;
       if (idx != w) {
         const double* f = fac + (size_t)j * 3 * TILE_DBL;
@@ -496,9 +492,9 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
     new_err = red[0];
   }
   int status;
-  const int decision = gn_decide(P, it, prev, new_err, status);  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
+  const int decision = gn_decide(P.rules, it, prev, new_err, status);  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
   if (tid == 0) {
-    if (it <= P.max_iter) pb.trace[(size_t)b * (P.max_iter + 1) + it] = new_err;
+    if (it <= P.rules.max_iter) pb.trace[(size_t)b * (P.rules.max_iter + 1) + it] = new_err;
     pb.cur_err[b] = new_err;
     if (decision != 0) {
       pb.status[b] = status;
@@ -507,7 +503,7 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
   }
   // prev_err and active are inputs of this very decision: they are written only behind a barrier that every wavefront
   // reaches after it has read them
-  const bool keep_err = it == 0 || (decision == 0 && P.fixed_iters == 0);   // currentError = the error just found
+  const bool keep_err = it == 0 || (decision == 0 && P.rules.fixed_iters == 0);   // currentError = the error just found
   if (decision != 0) {
     const double* src = (decision == 2) ? last : cur;
     for (size_t k = tid; k < tsz; k += blockDim.x) result[k] = src[k];
@@ -783,8 +779,8 @@ __global__ __launch_bounds__(64 * F::WAVES) void k_solve_step(const PlanParams* 
   double* xs = smem;
   double* red = smem + (size_t)(N + 1) * X;
   int* flags = reinterpret_cast<int*>(red + F::WAVES);
-  const bool dogleg = P.opt_type == GPMP2MI_OPT_DOGLEG;
-  const bool resolve = !(dogleg && pb.phase[b] != 0);
+  const bool dogleg = P.rules.opt_type == GPMP2MI_OPT_DOGLEG;
+  const bool resolve = !dogleg_retry(P, pb, b);
   if (tid == 0) {
     flags[1] = 0;
     pb.stepped[b] = 0;   // set again once the factorisation has succeeded (split form)
@@ -851,7 +847,7 @@ __global__ __launch_bounds__(64) void k_ghg(const PlanParams* __restrict__ pp, P
   const PlanParams& P = *pp;
   const int N = P.N;
   const int b = blockIdx.x / (N + 1), i = blockIdx.x - b * (N + 1);
-  if (!pb.active[b] || pb.phase[b] != 0) return;
+  if (!pb.active[b] || dogleg_retry(P, pb, b)) return;
   const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
   const double* ht = pb.htiles + ((size_t)b * (N + 1) + i) * 2 * TILE_DBL;
   const Tile Dt = tile_load(ht, lane), Ht = tile_load(ht + TILE_DBL, lane);

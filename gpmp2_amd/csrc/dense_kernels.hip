@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "cr_schedule.h"
 #include "device_math.h"
 #include "plan.h"
 #include "plan_device.h"
@@ -27,16 +28,10 @@ constexpr int DENSE_WAVES = DENSE_THREADS / 64;
 // multiples are then eliminated (E task: [S | b | C_l | C_r] -> R, y = R^-T b, W_l = R^-T C_l, W_r = R^-T C_r), even
 // multiples store their updated block (U task).  Backward level h: x_j = R_j^-1 (y_j - W_l x_{j-h} - W_r x_{j+h}).
 // N = 50, n = 36 (PR2): 7 + 7 launches of <= 25 tasks per trajectory instead of 51 dependent blocks in one workgroup.
-__device__ __forceinline__ int dense_hfinal(int N) {
-  int h = 1;
-  while (h <= N) h <<= 1;
-  return h;
-}
-
 __global__ __launch_bounds__(DENSE_THREADS) void k_dense_ghg(const PlanParams* __restrict__ pp, PlanBuffers pb) {
   const PlanParams& P = *pp;
   const int b = blockIdx.x, tid = threadIdx.x;
-  if (!pb.active[b] || pb.phase[b] != 0) return;
+  if (!pb.active[b] || dogleg_retry(P, pb, b)) return;
   const int N = P.N, n = P.n;
   const double* Hd = pb.wHd + (size_t)b * (N + 1) * n * n;
   const double* Ho = pb.wHo + (size_t)b * N * n * n;
@@ -67,18 +62,15 @@ constexpr int LVG = G2_DENSE_GRID, LVS = (LVG == 32) ? 5 : (LVG == 16) ? 4 : 3; 
 constexpr int LVL_THREADS = LVG * LVG;
 constexpr int DENSE_NR = (36 + LVG - 1) / LVG, DENSE_NC = (3 * 36 + 1 + LVG - 1) / LVG;   // 3 x 7 (measured: a 32 x 32 grid
 // pays more for its 16-wavefront barriers than it gains, 448 vs 348 us per solve; one wavefront per block 550 us)
-__global__ __launch_bounds__(LVL_THREADS) void k_dense_cr_level(const PlanParams* __restrict__ pp, PlanBuffers pb, int h,
-                                                                 int final) {
+__global__ __launch_bounds__(LVL_THREADS) void k_dense_cr_level(const PlanParams* __restrict__ pp, PlanBuffers pb, CrLevel level) {
   const PlanParams& P = *pp;
   const int N = P.N, n = P.n, tid = threadIdx.x;
-  const int countE = final ? 1 : ((N / h) + 1) / 2;
-  const int countU = (final || h == 1) ? 0 : (N / (2 * h)) + 1;   // nothing to absorb at level 1
-  const int per = countE + countU;
+  const int h = level.h, per = level.tasks();   // (the launcher sized the grid from the same level)
   const int b = blockIdx.x / per, idx = blockIdx.x - b * per;
   if (!pb.active[b]) return;
-  if (P.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0) return;
-  const bool elim = idx < countE;
-  const int j = elim ? (final ? 0 : h * (2 * idx + 1)) : 2 * h * (idx - countE);
+  if (dogleg_retry(P, pb, b)) return;
+  const bool elim = level.elim(idx), final = level.final;
+  const int j = level.block(idx);
   const int hh = h >> 1, nn = n * n;
   const int AW = 3 * n + 1;  // [S (n) | b (1) | C_l (n) | C_r (n)]
   double* __restrict__ Hd = pb.wHd + (size_t)b * (N + 1) * nn;
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(LVL_THREADS) void k_dense_cr_level(const PlanParams
   const int ty = tid >> LVS, tx = tid & (LVG - 1);
   // a block is first touched at level 1 (odd) or 2 (even): LM damping and -g enter there
   const bool first = (h == 1) || (h == 2 && !(j & 1));
-  const double lam = (first && P.opt_type == GPMP2MI_OPT_LM) ? pb.lambda[b] : 0.0;
+  const double lam = (first && P.rules.opt_type == GPMP2MI_OPT_LM) ? pb.lambda[b] : 0.0;
   const bool want_l = elim && !final && j - h >= 0, want_r = elim && !final && j + h <= N;
   double reg[DENSE_NR][DENSE_NC];
 #pragma unroll
@@ -257,14 +249,15 @@ __global__ __launch_bounds__(LVL_THREADS) void k_dense_cr_level(const PlanParams
 }
 
 // one back-substitution level: one wavefront per block, R_j staged in LDS, lane r carries t_r
-__global__ __launch_bounds__(64) void k_dense_cr_back(const PlanParams* __restrict__ pp, PlanBuffers pb, int h, int final) {
+__global__ __launch_bounds__(64) void k_dense_cr_back(const PlanParams* __restrict__ pp, PlanBuffers pb, int h) {
   const PlanParams& P = *pp;
   const int N = P.N, n = P.n, lane = threadIdx.x;
-  const int count = final ? 1 : ((N / h) + 1) / 2;
+  const bool final = (h == cr_hfinal(N));
+  const int count = cr_back_count(N, h);
   const int b = blockIdx.x / count, idx = blockIdx.x - b * count;
   if (!pb.active[b] || pb.notspd[b]) return;
-  if (P.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0) return;
-  const int j = final ? 0 : h * (2 * idx + 1), nn = n * n;
+  if (dogleg_retry(P, pb, b)) return;
+  const int j = cr_back_block(N, h, idx), nn = n * n;
   const double* R = pb.wHd + ((size_t)b * (N + 1) + j) * nn;
   const double* Wl = pb.wWl + ((size_t)b * (N + 1) + j) * nn;
   const double* Wr = pb.wWr + ((size_t)b * (N + 1) + j) * nn;
@@ -320,7 +313,7 @@ __global__ __launch_bounds__(DENSE_THREADS) void k_dense_tail(const PlanParams* 
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* xs = smem;                       // [(N+1)][n]
   double* red = xs + tsz;                  // [DENSE_WAVES]
-  const bool resolve = !(P.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0);
+  const bool resolve = !dogleg_retry(P, pb, b);
   if (resolve && pb.notspd[b]) return;     // bad pivot somewhere in the tree: k_decide consumes and clears the flag
   trial_step_tail<DENSE_WAVES, 0>(P, pb, b, P.n, P.D, resolve, pb.wx + b * tsz, xs, pb.wg + b * tsz, red, tid,
                                   DENSE_THREADS);
@@ -340,18 +333,14 @@ int launch_solve_dense(const PlanParams& hp, const PlanBuffers& pb, hipStream_t 
     set_error("block / trajectory too large for the LDS-resident dense solve");
     return GPMP2MI_ERR_UNSUPPORTED;
   }
-  int hfinal = 1;
-  while (hfinal <= N) hfinal <<= 1;
-  if (hp.opt_type == GPMP2MI_OPT_DOGLEG) k_dense_ghg<<<dim3(hp.B), dim3(DENSE_THREADS), 0, st>>>(pb.params, pb);
+  const int hfinal = cr_hfinal(N);
+  if (hp.rules.opt_type == GPMP2MI_OPT_DOGLEG) k_dense_ghg<<<dim3(hp.B), dim3(DENSE_THREADS), 0, st>>>(pb.params, pb);
   for (int h = 1; h <= hfinal; h <<= 1) {
-    const int final = h == hfinal;
-    const int countE = final ? 1 : ((N / h) + 1) / 2, countU = (final || h == 1) ? 0 : (N / (2 * h)) + 1;
-    k_dense_cr_level<<<dim3(hp.B * (countE + countU)), dim3(LVL_THREADS), sh_level, st>>>(pb.params, pb, h, final);
+    const CrLevel level = cr_level(N, h, h != 1);   // nothing to absorb at level 1: no U tasks
+    k_dense_cr_level<<<dim3(hp.B * level.tasks()), dim3(LVL_THREADS), sh_level, st>>>(pb.params, pb, level);
   }
   for (int h = hfinal; h >= 1; h >>= 1) {
-    const int final = h == hfinal;
-    const int count = final ? 1 : ((N / h) + 1) / 2;
-    k_dense_cr_back<<<dim3(hp.B * count), dim3(64), sh_back, st>>>(pb.params, pb, h, final);
+    k_dense_cr_back<<<dim3(hp.B * cr_back_count(N, h)), dim3(64), sh_back, st>>>(pb.params, pb, h);
   }
   k_dense_tail<<<dim3(hp.B), dim3(DENSE_THREADS), sh_tail, st>>>(pb.params, pb);
   G2_HIP(hipGetLastError());

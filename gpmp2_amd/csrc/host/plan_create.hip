@@ -184,10 +184,10 @@ static int fill_params(const RobotDev& h, const gpmp2mi_settings* s, const gpmp2
   P.obs_skip_first = o.obs_skip_first_state;
   P.flag_pos_limit = s->flag_pos_limit;
   P.flag_vel_limit = s->flag_vel_limit;
-  P.opt_type = s->opt_type;
-  P.max_iter = s->max_iter;
-  P.no_increase = s->final_iter_no_increase;
-  P.fixed_iters = o.fixed_iterations;
+  P.rules.opt_type = s->opt_type;
+  P.rules.max_iter = s->max_iter;
+  P.rules.no_increase = s->final_iter_no_increase;
+  P.rules.fixed_iters = o.fixed_iterations;
   P.end_conf_prior_off = o.end_conf_prior_off ? 1 : 0;
   P.eps = s->epsilon;
   P.obs_w = 1.0 / (s->cost_sigma * s->cost_sigma);
@@ -197,15 +197,15 @@ static int fill_params(const RobotDev& h, const gpmp2mi_settings* s, const gpmp2
   P.conf_prior_w = 1.0 / (s->conf_prior_sigma * s->conf_prior_sigma);
   P.vel_prior_w = 1.0 / (s->vel_prior_sigma * s->vel_prior_sigma);
   P.vdyn_w = o.vehicle_dynamics_sigma > 0 ? 1.0 / (o.vehicle_dynamics_sigma * o.vehicle_dynamics_sigma) : 0.0;
-  P.rel_thresh = s->rel_thresh;
-  P.abs_tol = o.abs_error_tol;
-  P.err_tol = o.error_tol;
-  P.lm_lambda0 = o.lm_lambda_initial;
-  P.lm_factor = o.lm_lambda_factor;
-  P.lm_upper = o.lm_lambda_upper;
-  P.lm_lower = o.lm_lambda_lower;
-  P.lm_min_fidelity = o.lm_min_model_fidelity;
-  P.dl_delta0 = o.dogleg_delta_initial;
+  P.rules.rel_thresh = s->rel_thresh;
+  P.rules.abs_tol = o.abs_error_tol;
+  P.rules.err_tol = o.error_tol;
+  P.rules.lm_lambda0 = o.lm_lambda_initial;
+  P.rules.lm_factor = o.lm_lambda_factor;
+  P.rules.lm_upper = o.lm_lambda_upper;
+  P.rules.lm_lower = o.lm_lambda_lower;
+  P.rules.lm_min_fidelity = o.lm_min_model_fidelity;
+  P.rules.dl_delta0 = o.dogleg_delta_initial;
   for (int j = 0; j < P.I; j++) {
     P.coef[j] = gp_coef(P.delta_t, inter_dt * static_cast<double>(j + 1));
     const double lam[2] = {P.coef[j].l11, P.coef[j].l12}, psi[2] = {P.coef[j].p11, P.coef[j].p12};
@@ -252,8 +252,8 @@ static int fill_params(const RobotDev& h, const gpmp2mi_settings* s, const gpmp2
       }
   }
   // passes: GN one per iteration (+1); LM up to ~5 lambda retries per iterate; Dogleg up to ~16 halvings
-  const int cap = std::max(P.fixed_iters, P.max_iter);   // plan_update may run any iterations <= max_iter
-  P.max_pass = cap * (P.opt_type == GPMP2MI_OPT_LM ? 6 : P.opt_type == GPMP2MI_OPT_DOGLEG ? 18 : 1) + 3;
+  const int cap = std::max(P.rules.fixed_iters, P.rules.max_iter);   // plan_update may run any iterations <= max_iter
+  P.max_pass = cap * (P.rules.opt_type == GPMP2MI_OPT_LM ? 6 : P.rules.opt_type == GPMP2MI_OPT_DOGLEG ? 18 : 1) + 3;
   return GPMP2MI_OK;
 }
 
@@ -320,7 +320,7 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
   for (double** q : {&pb.cur, &pb.last, &pb.trial, &pb.init, &pb.result, &pb.delta}) G2_TRY(plan_alloc(p, q, tsz));
   const size_t tq = F.wide ? 4 : 1;  // wide blocks: 2 x 2 tiles, 32-wide vectors
   G2_TRY(plan_alloc(p, &pb.gvec, (size_t)B * (P.N + 1) * (F.wide ? 32 : 16)));
-  G2_TRY(plan_alloc(p, &pb.htiles, P.opt_type == GPMP2MI_OPT_DOGLEG ? (size_t)B * (P.N + 1) * 512 * tq : 1));
+  G2_TRY(plan_alloc(p, &pb.htiles, P.rules.opt_type == GPMP2MI_OPT_DOGLEG ? (size_t)B * (P.N + 1) * 512 * tq : 1));
   G2_TRY(plan_alloc(p, &pb.hgpart, (size_t)B * P.Npad));
   G2_TRY(plan_alloc(p, &pb.scal, (size_t)B * SC_COUNT));
   for (int** q : {&pb.which, &pb.stepped}) G2_TRY(plan_alloc(p, q, B));
@@ -344,7 +344,7 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
   G2_TRY(plan_alloc(p, &pb.fac, (size_t)B * (P.N + 1) * 768 * tq));
   for (double** q : {&pb.pend, &pb.coup}) G2_TRY(plan_alloc(p, q, (size_t)B * ((P.N + 4) / 4) * 256));
   for (double** q : {&pb.cur_err, &pb.prev_err, &pb.last_err, &pb.final_err, &pb.lambda}) G2_TRY(plan_alloc(p, q, B));
-  G2_TRY(plan_alloc(p, &pb.trace, (size_t)B * (P.max_iter + 1)));
+  G2_TRY(plan_alloc(p, &pb.trace, (size_t)B * (P.rules.max_iter + 1)));
   for (int** q : {&pb.iters, &pb.status, &pb.active, &pb.phase, &pb.notspd}) G2_TRY(plan_alloc(p, q, B));
   G2_TRY(plan_alloc(p, &pb.epart, (size_t)B * P.Npad));
   G2_TRY(plan_alloc(p, &pb.cshare, (size_t)B * (P.Ppad / 64) * 3));

@@ -93,7 +93,7 @@ static int enqueue_gn_pass(gpmp2mi_plan* p, const PlanBuffers& pb, int pass, dou
   const PlanParams& P = p->hp;
   const PlanForms& F = p->forms;
   const bool early = F.early_stop(p->has_extras);
-  if (P.fixed_iters > 0 && pass % (P.fixed_iters + 1) == P.fixed_iters) {
+  if (P.rules.fixed_iters > 0 && pass % (P.rules.fixed_iters + 1) == P.rules.fixed_iters) {
     if (!early) {
       p->timer.begin("final_error", st);
       G2_TRY(launch_error_parts(P, pb, states, 0, pb.active, st));
@@ -126,7 +126,7 @@ static int enqueue_trial_pass(gpmp2mi_plan* p, const PlanBuffers& pb, hipStream_
     // blocks wider than one tile (8 <= dof <= 11): the same cyclic reduction on 2x2 tiles
     p->timer.begin("assemble_wide", st);
     G2_TRY(launch_assemble_wide(P, pb, pb.cur, 0, pb.active, st));
-    if (P.opt_type == GPMP2MI_OPT_DOGLEG) {
+    if (P.rules.opt_type == GPMP2MI_OPT_DOGLEG) {
       p->timer.begin("ghg_wide", st);
       G2_TRY(launch_ghg_wide(P, pb, st));
     }
@@ -136,26 +136,26 @@ static int enqueue_trial_pass(gpmp2mi_plan* p, const PlanBuffers& pb, hipStream_
     }
     p->timer.begin("solve_step_wide", st);
     G2_TRY(launch_solve_step_wide(P, pb, st));
-    if (F.finish_trial(P.opt_type)) {   // levels 4, 2, 1, step and trial point chip-wide
+    if (F.finish_trial(P.rules.opt_type)) {   // levels 4, 2, 1, step and trial point chip-wide
       p->timer.begin("finish_trial_wide", st);
       G2_TRY(launch_finish_trial_wide(P, pb, st));
     }
   } else {
     p->timer.begin("assemble", st);
     G2_TRY(launch_assemble(P, pb, pb.cur, 0, pb.active, st));
-    if (P.opt_type == GPMP2MI_OPT_DOGLEG) {
+    if (P.rules.opt_type == GPMP2MI_OPT_DOGLEG) {
       p->timer.begin("ghg", st);
       G2_TRY(launch_ghg(P, pb, st));
     }
     p->timer.begin("solve_step", st);
     G2_TRY(launch_solve_step(P, pb, st));
-    if (F.finish_trial(P.opt_type)) {   // levels 2, 1, step and trial point chip-wide
+    if (F.finish_trial(P.rules.opt_type)) {   // levels 2, 1, step and trial point chip-wide
       p->timer.begin("finish_trial", st);
       G2_TRY(launch_finish_trial(P, pb, st));
     }
   }
   p->timer.begin("linearize", st);
-  if (F.trial_lin_steps(P.opt_type)) {
+  if (F.trial_lin_steps(P.rules.opt_type)) {
     // fused finish: the linearization forms the trial point cur (+) delta itself (k_linearize_arm, `trial`)
     return plan_linearize(p, pb.cur, 1, pb.active, st, pb.trial, 1, true);
   }
@@ -184,8 +184,8 @@ static int plan_run_impl(gpmp2mi_plan* p, hipStream_t st, const double* start, b
   p->timer.reset();
   for (int k = 0; k < p->n_active_len; k++) p->h_flags[k] = -1;  // the previous run has drained (stream sync below)
   G2_TRY(launch_plan_reset(P, pb, start, st));
-  const int iter_cap = (P.fixed_iters > 0 ? P.fixed_iters : P.max_iter);
-  if (P.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && F.gn_fast(update)) {
+  const int iter_cap = (P.rules.fixed_iters > 0 ? P.rules.fixed_iters : P.rules.max_iter);
+  if (P.rules.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && F.gn_fast(update)) {
     // ---- Gauss-Newton fast path: 3 launches per pass, step control fused into the solve kernel.
     // Software-pipelined driver: the linearization of pass k+1 is enqueued before the host looks at the active count of
     // pass k, which it learns while the GPU still has the finish kernel of pass k and that linearization (~23 us) to run,
@@ -264,8 +264,8 @@ static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* pas
   const PlanParams& P = p->hp;
   const PlanForms& F = p->forms;
   const int B = P.B;
-  const bool gn = P.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && F.gn_fast(false);
-  const int iter_cap = (P.fixed_iters > 0 ? P.fixed_iters : P.max_iter);
+  const bool gn = P.rules.opt_type == GPMP2MI_OPT_GAUSS_NEWTON && F.gn_fast(false);
+  const int iter_cap = (P.rules.fixed_iters > 0 ? P.rules.fixed_iters : P.rules.max_iter);
   // passes one problem may take: the fast path ends every trajectory by pass iter_cap; the trial-step path gives each
   // problem the plain run's budget of n_active_len - 2 iterative passes (its first one shares a pass with the initial
   // evaluation), then finishes it as k_finalize_unfinished does
@@ -328,7 +328,7 @@ static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* pas
     for (int pass = 0;; pass++) {
       G2_CHECK(pass < cap, GPMP2MI_ERR_HIP, "queue run exceeded its pass bound");
       G2_TRY(enqueue_gn_pass(p, qb, pass, states_of(p, pass), st));
-      const bool load = P.fixed_iters == 0 || pass % (P.fixed_iters + 1) == P.fixed_iters;
+      const bool load = P.rules.fixed_iters == 0 || pass % (P.rules.fixed_iters + 1) == P.rules.fixed_iters;
       G2_TRY(refill(pass, load, states_of(p, pass)));
       G2_TRY(enqueue_gn_lin(p, pass + 1, st));   // ahead of the count
       p->timer.close(st);
@@ -461,7 +461,7 @@ int g2::plan_optimize_queue(gpmp2mi_plan* p, QueueRun io, bool host, hipStream_t
   QueueStage stage;
   if (host) {
     // host variant: the M problems are staged once, the results come back once
-    G2_TRY(stage.alloc(io.M, io, P.D, (size_t)(P.N + 1) * P.n, P.max_iter + 1));
+    G2_TRY(stage.alloc(io.M, io, P.D, (size_t)(P.N + 1) * P.n, P.rules.max_iter + 1));
     G2_TRY(stage.upload(io, 0, st));   // if it fails half-way, ~QueueStage's hipFree waits for the copies in flight
   }
   const QueueRun q = host ? stage.q : io;
@@ -493,7 +493,7 @@ int g2::plan_get_result(gpmp2mi_plan* p, double* traj, int* iters, double* ferr,
   if (ferr) G2_HIP(hipMemcpyAsync(ferr, p->pb.final_err, B * sizeof(double), kind, st));
   if (status) G2_HIP(hipMemcpyAsync(status, p->pb.status, B * sizeof(int), kind, st));
   if (trace)
-    G2_HIP(hipMemcpyAsync(trace, p->pb.trace, (size_t)B * (p->hp.max_iter + 1) * sizeof(double), kind, st));
+    G2_HIP(hipMemcpyAsync(trace, p->pb.trace, (size_t)B * (p->hp.rules.max_iter + 1) * sizeof(double), kind, st));
   return p->close_copies(kind, st);
 }
 
@@ -645,22 +645,22 @@ int gpmp2mi_plan_clear_state_priors(gpmp2mi_plan* p, int b) {
 int gpmp2mi_plan_update(gpmp2mi_plan* p, int iterations, void* stream) {
   G2_CHECK(p && iterations > 0, GPMP2MI_ERR_INVALID, "bad argument");
   G2_CHECK(p->problem_set, GPMP2MI_ERR_INVALID, "call gpmp2mi_plan_set_problem first");
-  G2_CHECK(iterations <= p->hp.max_iter, GPMP2MI_ERR_INVALID, "iterations exceeds max_iter");
+  G2_CHECK(iterations <= p->hp.rules.max_iter, GPMP2MI_ERR_INVALID, "iterations exceeds max_iter");
   G2_CHECK(iterations + 3 <= p->n_active_len, GPMP2MI_ERR_INVALID, "iterations exceeds the plan's pass budget");
   hipStream_t st = (hipStream_t)stream;
   // warm start: the previous estimate becomes the initial values of this run
   const double* from = p->optimized ? p->pb.result : p->pb.init;
   // temporarily switch the resident parameters to `iterations` fixed Gauss-Newton steps
   PlanParams saved = p->hp;
-  p->hp.opt_type = GPMP2MI_OPT_GAUSS_NEWTON;
-  p->hp.fixed_iters = iterations;
-  if (const int rc0 = launch_set_mode(p->pb, p->hp.opt_type, p->hp.fixed_iters, st)) {
+  p->hp.rules.opt_type = GPMP2MI_OPT_GAUSS_NEWTON;
+  p->hp.rules.fixed_iters = iterations;
+  if (const int rc0 = launch_set_mode(p->pb, p->hp.rules.opt_type, p->hp.rules.fixed_iters, st)) {
     p->hp = saved;
     return rc0;
   }
   const int rc = plan_run(p, st, from, true);
   p->hp = saved;
-  G2_TRY(launch_set_mode(p->pb, p->hp.opt_type, p->hp.fixed_iters, st));
+  G2_TRY(launch_set_mode(p->pb, p->hp.rules.opt_type, p->hp.rules.fixed_iters, st));
   G2_HIP(hipStreamSynchronize(st));
   return rc;
 }

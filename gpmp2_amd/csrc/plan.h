@@ -2,6 +2,7 @@
 // launchers of the fused hot-path kernels in plan_kernels.hip.
 #pragma once
 #include "common.h"
+#include "step_control.h"
 
 namespace g2 {
 
@@ -14,8 +15,7 @@ struct PlanParams {
   int B, N, I, P, Ppad, D, n, NG, REC, Npad, GPREC;
   int RECS, GPS;                       // record strides in HBM and LDS: REC / GPREC rounded up to even (16-B pieces)
   int max_pass;
-  int obs_skip_first, flag_pos_limit, flag_vel_limit, opt_type, max_iter, no_increase, fixed_iters,
-      lie;
+  int obs_skip_first, flag_pos_limit, flag_vel_limit, lie;
   int lin_split;                       // 2: k_linearize splits the spheres of a point over 2 wavefronts (fixed-base arms)
   int end_conf_prior_off;              // 1: no PriorFactor on x_N (a goal / workspace factor stands in)
   int wide;                            // 2 dof > 15: blocks wider than one tile (2x2-tile kernels of wide_cr.h, or the dense path of dense_kernels.hip)
@@ -28,8 +28,7 @@ struct PlanParams {
   double eps, obs_w, delta_t;          // obs_w = 1 / cost_sigma^2
   double conf_prior_w, vel_prior_w;    // 1 / sigma^2
   double vdyn_w;                       // 1 / dynamics_sigma^2 or 0
-  double rel_thresh, abs_tol, err_tol;
-  double lm_lambda0, lm_factor, lm_upper, lm_lower, lm_min_fidelity, dl_delta0;
+  StepRules rules;                     // optimizer, iteration limits, thresholds (step_control.h)
   alignas(16) GpCoef coef[MAXI];
   // per sub-step, for the assembler (staged into LDS): [0..3] Psi_r Psi_c, [4..7] Lam_r Lam_c, [8..11] Lam_r Psi_c,
   // [12..15] Psi_r Lam_c at index ar * 2 + ac (a = 0 conf / 1 vel; Lam = (l11, l12), Psi = (p11, p12)); [16..19]
@@ -124,7 +123,8 @@ struct PlanBuffers {
   int* iters;
   int* status;
   int* active;             // 1 while the trajectory is still iterating
-  int* phase;              // optimizer-specific sub-state
+  int* phase;              // Dogleg: 1 while the trial point is a retry from the same linearization (dogleg_retry);
+                           // LM: its count of calls to iterate(), the index into `trace`
   int* notspd;             // [B] set when a level-1 pivot (k_assemble) was not positive
   double* epart;           // [B][Npad] per-block share of the graph error (k_assemble, or k_error_parts: the whole sum in block
                            // 0); not written when the step control reads cshare instead (early stop)

@@ -1,5 +1,5 @@
-// plan_device.h -- device helpers shared by the plan kernels: graph-error terms and the
-// gtsam::checkConvergence rule.
+// plan_device.h -- device helpers shared by the plan kernels: graph-error terms, the Dogleg retry test and the tail of
+// a trial step.  The step-control rules themselves are in step_control.h.
 #pragma once
 #include "device_math.h"
 #include "plan.h"
@@ -111,35 +111,12 @@ __device__ __forceinline__ double total_error_partial(const PlanParams& P, const
   return acc + misc_error_partial(P, pb, b, tr, tid, nthr);
 }
 
-__device__ __forceinline__ bool check_convergence(double rel, double abs_, double err_tol, double cur,
-                                                  double nw) {
-  if (nw <= err_tol) return true;
-  const double abs_dec = cur - nw;
-  const double rel_dec = abs_dec / cur;
-  return (rel != 0.0 && rel_dec <= rel) || (abs_dec <= abs_);
+// Dogleg only: the trial point in the making is a retry from the linearization already factorised (a smaller trust
+// radius after a rejected point), so everything up to the solve is skipped.  LM counts its calls in the same word.
+__device__ __forceinline__ bool dogleg_retry(const PlanParams& P, const PlanBuffers& pb, int b) {
+  return P.rules.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0;
 }
 
-// =============================================================================== Gauss-Newton step control
-// The do/while of gpmp2::optimize (planner/BatchTrajOptimizer.cpp:273-307) for one trajectory of the Gauss-Newton fast
-// path, as a pure function of the trajectory's iteration count `it`, the error `prev` the last comparison kept
-// (currentError) and the error `new_err` of the values just linearized: 0 iterate, 1 stop with these values, 2 stop
-// with the values before the last step (no-increase rollback).  `status` is set when the trajectory stops.  it == 0 is
-// the first evaluation of a problem (pass 0 of a plain run; a queue run loads problems at later passes).  k_assemble and
-// k_gn_step_cr both call it on the same inputs, which only earlier kernels wrote, so they agree by construction.
-__device__ __forceinline__ int gn_decide(const PlanParams& P, int it, double prev, double new_err, int& status) {
-  status = GPMP2MI_TRAJ_MAX_ITER;
-  if (it == 0) {
-    if (P.fixed_iters > 0) return 0;
-    if (new_err <= P.err_tol) { status = GPMP2MI_TRAJ_ALREADY_OPTIMAL; return 1; }
-    return P.max_iter <= 0 ? 1 : 0;
-  }
-  if (P.fixed_iters > 0) return it >= P.fixed_iters ? 1 : 0;
-  const bool conv = check_convergence(P.rel_thresh, P.abs_tol, P.err_tol, prev, new_err);
-  if (it < P.max_iter && !conv) return 0;
-  if (new_err > prev && P.no_increase) { status = GPMP2MI_TRAJ_ROLLED_BACK; return 2; }
-  if (conv) status = GPMP2MI_TRAJ_CONVERGED;
-  return 1;
-}
 // Graph error of trajectory b from the per-chunk shares k_linearize_arm left (pb.cshare): chunks in ascending order,
 // obstacle + GP + misc of each, halved.  Uniform loads, every lane forms the same value: no cross-lane step, no barrier.
 __device__ __forceinline__ double error_from_shares(const PlanParams& P, const PlanBuffers& pb, int b) {
@@ -165,34 +142,6 @@ __device__ __forceinline__ double block_sum(double v, double* red, int tid) {
 }
 
 // =============================================================================== trial-step tail
-// Powell dogleg point for trust radius Delta (DoglegOptimizerImpl::ComputeDoglegPoint / ComputeBlend):
-// dx_d = cu * g + cn * dx_n with model decrease q(dx_d), from g.g, g^T H g, g.dx_n and |dx_n|^2
-__device__ __forceinline__ void dogleg_blend(double gg, double gHg, double gn, double nn, double Delta, double& cu,
-                                             double& cn, double& q) {
-  const double step = -gg / gHg;          // dx_u = step * g   (optimizeGradientSearch)
-  const double uu = step * step * gg, un = step * gn;
-  const double DeltaSq = Delta * Delta;
-  if (DeltaSq < uu) {
-    const double k = sqrt(DeltaSq / uu);
-    cu = k * step;
-    cn = 0.0;
-    q = cu * gg + 0.5 * cu * cu * gHg;
-  } else if (DeltaSq < nn) {
-    const double a = uu - 2. * un + nn, bq = 2. * (un - uu), cq = uu - Delta * Delta;
-    const double sq = sqrt(bq * bq - 4 * a * cq);
-    const double tau1 = (-bq + sq) / (2. * a), tau2 = (-bq - sq) / (2. * a);
-    const double tau = (0.0 <= tau1 && tau1 <= 1.0) ? tau1 : tau2;
-    cu = (1. - tau) * step;
-    cn = tau;
-    // g^T x + 0.5 x^T H x with H dx_n = -g
-    q = cu * gg + cn * gn + 0.5 * (cu * cu * gHg - 2.0 * cu * cn * gg - cn * cn * gn);
-  } else {
-    cu = 0.0;
-    cn = 1.0;
-    q = 0.5 * gn;
-  }
-}
-
 // The end of a trial step, shared by the block solvers (k_solve_step of both tile forms, k_dense_tail); all nthr
 // threads (WAVES wavefronts) of the trajectory's workgroup call it.  The solution x of the linearization is read from
 // xsrc and the gradient from gv, block i at offset i * X (X = 0: packed at stride n, and x is staged into xs on the
@@ -243,7 +192,7 @@ __device__ __forceinline__ void trial_step_tail(const PlanParams& P, const PlanB
     }
     __syncthreads();
   }
-  const bool dogleg = P.opt_type == GPMP2MI_OPT_DOGLEG;
+  const bool dogleg = P.rules.opt_type == GPMP2MI_OPT_DOGLEG;
   double q = 0.0, xn = 0.0;
   if (dogleg) {
     double cu, cn;

@@ -789,8 +789,8 @@ int launch_error_parts(const PlanParams& hp, const PlanBuffers& pb, const double
 // gpmp2mi_plan_update switches the resident parameter block to `iterations` fixed Gauss-Newton steps and back: two
 // words, written in stream order by this kernel instead of re-uploading the block from pageable host memory twice
 __global__ void k_set_mode(PlanParams* pp, int opt_type, int fixed_iters) {
-  pp->opt_type = opt_type;
-  pp->fixed_iters = fixed_iters;
+  pp->rules.opt_type = opt_type;
+  pp->rules.fixed_iters = fixed_iters;
 }
 int launch_set_mode(const PlanBuffers& pb, int opt_type, int fixed_iters, hipStream_t st) {
   k_set_mode<<<dim3(1), dim3(1), 0, st>>>(pb.params, opt_type, fixed_iters);
@@ -808,7 +808,7 @@ __device__ __forceinline__ void reset_slot(const PlanParams& P, const PlanBuffer
   pb.stepped[b] = 0;
   pb.notspd[b] = 0;
   pb.cur_err[b] = pb.prev_err[b] = pb.last_err[b] = pb.final_err[b] = 0.0;
-  pb.lambda[b] = (P.opt_type == GPMP2MI_OPT_DOGLEG) ? P.dl_delta0 : P.lm_lambda0;
+  pb.lambda[b] = (P.rules.opt_type == GPMP2MI_OPT_DOGLEG) ? P.rules.dl_delta0 : P.rules.lm_lambda0;
 }
 
 // reset the optimizer state before a run and load the starting values: cur = start (no separate copy command in
@@ -824,7 +824,7 @@ __global__ __launch_bounds__(256) void k_plan_reset(const PlanParams* __restrict
   }
   for (size_t k = tid; k < (size_t)P.max_pass; k += nth) pb.n_active[k] = pb.done[k] = 0;
   for (size_t k = tid; k < B * SC_COUNT; k += nth) pb.scal[k] = 0.0;
-  for (size_t k = tid; k < B * (size_t)(P.max_iter + 1); k += nth) pb.trace[k] = __longlong_as_double(0x7ff8000000000000LL);
+  for (size_t k = tid; k < B * (size_t)(P.rules.max_iter + 1); k += nth) pb.trace[k] = __longlong_as_double(0x7ff8000000000000LL);
   for (size_t b = tid; b < B; b += nth) reset_slot(P, pb, b);
 }
 
@@ -844,7 +844,8 @@ int launch_plan_reset(const PlanParams& hp, const PlanBuffers& pb, const double*
 //   LevenbergMarquardtOptimizer::tryLambda  (model fidelity test, lambda *= / /= 10, give up at 1e5)
 //   DoglegOptimizerImpl::Iterate(ONE_STEP_PER_ITERATION)  (gain ratio rho, trust radius update)
 // followed by the do/while of gpmp2::optimize (checkConvergence, max_iter, no-increase rollback).
-// GTSAM semantics restated from upstream.
+// The rules themselves are the pure functions of step_control.h; the first lane loads the trajectory's scalars, calls
+// them and stores what changed.
 __device__ __forceinline__ void decide_body(const PlanParams& P, const PlanBuffers& pb, int pass, int init) {
   // 4 wavefronts: all of them sum the graph error of the point in question (fixed-order block reduction),
   // the first thread takes the decision, all four wavefronts then move the trajectories
@@ -860,7 +861,7 @@ __device__ __forceinline__ void decide_body(const PlanParams& P, const PlanBuffe
   double* trial = pb.trial + b * tsz;
   double* result = pb.result + b * tsz;
   double* sc = pb.scal + (size_t)b * SC_COUNT;
-  double* tr = pb.trace + (size_t)b * (P.max_iter + 1);
+  double* tr = pb.trace + (size_t)b * (P.rules.max_iter + 1);
   const int wh = pb.which[b];
   // action: 0 keep iterating, 1 finish with cur, 2 finish with last; accept: copy trial -> cur
   int action = 0, accept = 0;
@@ -891,15 +892,19 @@ __device__ __forceinline__ void decide_body(const PlanParams& P, const PlanBuffe
     if (lane == 0) {
       pb.cur_err[b] = pb.prev_err[b] = err;
       tr[0] = err;
-      if (P.fixed_iters == 0 && err <= P.err_tol) { action = 1; pb.status[b] = GPMP2MI_TRAJ_ALREADY_OPTIMAL; }
-      else if (P.fixed_iters == 0 && P.max_iter <= 0) { action = 1; pb.status[b] = GPMP2MI_TRAJ_MAX_ITER; }
-      if (action) pb.final_err[b] = err;
+      int status;
+      action = first_decide(P.rules, err, status);
+      if (action) {
+        pb.status[b] = status;
+        pb.final_err[b] = err;
+      }
     }
   } else if (w0) {
     const double new_err = err_sum;
+    const int opt = P.rules.opt_type;
     // LM / GN split form: g.delta, |delta|^2, |g|^2 arrive as per-group shares of k_finish_trial (fixed-order wave sums)
     double sp_gd = 0.0, sp_dd = 0.0, sp_gg = 0.0;
-    if (P.split_back && P.opt_type == GPMP2MI_OPT_LM && !failed) {
+    if (P.split_back && opt == GPMP2MI_OPT_LM && !failed) {
       const int groups = P.spart_groups;
       const double* sp = pb.spart + (size_t)b * groups * 3;
       for (int qq = lane; qq < groups; qq += 64) {
@@ -914,81 +919,49 @@ __device__ __forceinline__ void decide_body(const PlanParams& P, const PlanBuffe
     if (lane == 0) {
       pb.notspd[b] = 0;
       const double cur_err = pb.cur_err[b];
-      bool iterate_done = false;   // GTSAM iterate() returned
-      bool moved = false;          // ... with new values
-      double err_after = cur_err;
-      if (P.opt_type == GPMP2MI_OPT_GAUSS_NEWTON) {
-        if (failed) { action = 1; pb.status[b] = GPMP2MI_TRAJ_NOT_SPD; pb.final_err[b] = cur_err; }
-        else { iterate_done = moved = true; err_after = new_err; }
-      } else if (P.opt_type == GPMP2MI_OPT_LM) {
-        double lambda = pb.lambda[b];
-        bool step_ok = false, stop = false;
+      // one call to the optimizer's iterate() (step_control.h) ...
+      TrialOutcome o;
+      if (opt == GPMP2MI_OPT_GAUSS_NEWTON) {
+        o = gn_iterate(failed);
+      } else if (opt == GPMP2MI_OPT_LM) {
+        if (P.split_back && !failed) {   // per-group shares of k_finish_trial, summed by wavefront 0 above
+          sc[SC_GD] = sp_gd;
+          sc[SC_DD] = sp_dd;
+          sc[SC_GG] = sp_gg;
+        }
+        o = lm_try_lambda(P.rules, pb.lambda[b], cur_err, new_err, sc[SC_GD], sc[SC_DD], failed);
+        pb.lambda[b] = o.param;
+      } else {
+        o = dogleg_iterate(pb.lambda[b], cur_err, new_err, sc[SC_Q], sc[SC_XNORM], failed);
         if (!failed) {
-          const double old_lin = cur_err;
-          if (P.split_back) {   // per-group shares of k_finish_trial, summed by wavefront 0 above
-            sc[SC_GD] = sp_gd;
-            sc[SC_DD] = sp_dd;
-            sc[SC_GG] = sp_gg;
-          }
-          const double lin_change = -(0.5 * sc[SC_GD] - 0.5 * lambda * sc[SC_DD]);
-          if (lin_change >= 0) {
-            const double cost_change = cur_err - new_err;
-            if (lin_change > 2.220446049250313e-16 * old_lin) step_ok = (cost_change / lin_change) > P.lm_min_fidelity;
-            if (fabs(cost_change) < P.rel_thresh * cur_err) stop = true;
-          }
-        }
-        if (step_ok) {
-          iterate_done = moved = true;
-          err_after = new_err;
-          lambda = fmax(P.lm_lower, lambda / P.lm_factor);
-        } else if (!stop) {
-          lambda *= P.lm_factor;
-          if (lambda >= P.lm_upper) iterate_done = true;  // give up: state unchanged
-        } else {
-          iterate_done = true;                            // relative cost change tiny: state unchanged
-        }
-        pb.lambda[b] = lambda;
-      } else {  // Dogleg
-        if (failed) { action = 1; pb.status[b] = GPMP2MI_TRAJ_NOT_SPD; pb.final_err[b] = cur_err; }
-        else {
-          double Delta = pb.lambda[b];
-          const double f_error = cur_err, M_error = cur_err, new_M = M_error + sc[SC_Q];
-          const double rho = (fabs(f_error - new_err) < 1e-15 || fabs(M_error - new_M) < 1e-15)
-                                 ? 0.5 : (f_error - new_err) / (M_error - new_M);
-          if (rho >= 0.75) { Delta = fmax(Delta, 3.0 * sc[SC_XNORM]); iterate_done = moved = true; err_after = new_err; }
-          else if (rho >= 0.25) { iterate_done = moved = true; err_after = new_err; }
-          else if (rho >= 0.0) { if (Delta > 1e-5) Delta = 0.5 * Delta; iterate_done = moved = true; err_after = new_err; }
-          else if (Delta > 1e-5) { Delta *= 0.5; pb.phase[b] = 1; }           // retry, same linearization
-          else { iterate_done = true; err_after = cur_err; }                  // zero step
-          pb.lambda[b] = Delta;
-          if (iterate_done) pb.phase[b] = 0;
+          pb.lambda[b] = o.param;
+          pb.phase[b] = o.retry ? 1 : 0;
         }
       }
-      if (iterate_done) {
-        const bool counted = moved || P.opt_type == GPMP2MI_OPT_DOGLEG;  // LM give-up does not count
+      if (o.not_spd) {
+        action = 1;
+        pb.status[b] = GPMP2MI_TRAJ_NOT_SPD;
+        pb.final_err[b] = cur_err;
+      }
+      // ... and, once it has returned, the do/while of gpmp2::optimize
+      if (o.returned) {
+        const double err_after = o.moved ? new_err : cur_err;
+        const bool counted = o.moved || opt == GPMP2MI_OPT_DOGLEG;  // LM give-up does not count
         const int it = pb.iters[b] + (counted ? 1 : 0);
         pb.iters[b] = it;
-        if (moved) accept = 1;
+        if (o.moved) accept = 1;
         // trace = error after every call to iterate() (an LM call that gives up repeats the value);
         // LM keeps its call counter in `phase`, which only Dogleg uses otherwise
-        const int call = (P.opt_type == GPMP2MI_OPT_LM) ? ++pb.phase[b] : it;
-        if (call <= P.max_iter) tr[call] = err_after;
+        const int call = (opt == GPMP2MI_OPT_LM) ? ++pb.phase[b] : it;
+        if (call <= P.rules.max_iter) tr[call] = err_after;
         const double prev = pb.prev_err[b];
-        if (P.fixed_iters > 0) {
-          if (it >= P.fixed_iters || !counted) { action = 1; pb.status[b] = GPMP2MI_TRAJ_MAX_ITER; pb.final_err[b] = err_after; }
-        } else {
-          const bool conv = check_convergence(P.rel_thresh, P.abs_tol, P.err_tol, prev, err_after);
-          if (it < P.max_iter && !conv) {
-            pb.prev_err[b] = err_after;
-          } else if (err_after > prev && P.no_increase) {
-            action = 2;  // the values before this iterate
-            pb.status[b] = GPMP2MI_TRAJ_ROLLED_BACK;
-            pb.final_err[b] = prev;
-          } else {
-            action = 1;
-            pb.status[b] = conv ? GPMP2MI_TRAJ_CONVERGED : GPMP2MI_TRAJ_MAX_ITER;
-            pb.final_err[b] = err_after;
-          }
+        int status;
+        action = loop_decide(P.rules, it, counted, prev, err_after, status);
+        if (action) {
+          pb.status[b] = status;
+          pb.final_err[b] = (action == 2) ? prev : err_after;
+        } else if (P.rules.fixed_iters == 0) {
+          pb.prev_err[b] = err_after;   // currentError of the next comparison
         }
         pb.cur_err[b] = err_after;
       }
@@ -1189,7 +1162,7 @@ __global__ __launch_bounds__(256) void k_queue_refill(const PlanParams* __restri
     if (tid == 0) q.fresh[b] = 0;
     return;
   }
-  const int D = P.D, T = P.max_iter + 1;
+  const int D = P.D, T = P.rules.max_iter + 1;
   const size_t tsz = (size_t)(P.N + 1) * P.n;
   if (a) {
     const size_t j = q.job[b];
@@ -1248,7 +1221,7 @@ __global__ __launch_bounds__(64) void k_export_normal_eq(const PlanParams* __res
   const int N = P.N;
   const int b = blockIdx.x / (N + 1), i = blockIdx.x - b * (N + 1);
   // optimizer use (wide path): finished trajectories and Dogleg retries keep their last system
-  if (active && (!active[b] || (P.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0))) return;
+  if (active && (!active[b] || dogleg_retry(P, pb, b))) return;
   const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
   extern __shared__ __attribute__((aligned(16))) double asm_smem[];
   Asm as(P, pb, rec_of(pb, pb.which[b], bufsel), gpu_of(pb, pb.which[b], bufsel), b, lane);

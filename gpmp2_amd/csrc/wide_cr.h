@@ -402,7 +402,7 @@ __global__ __launch_bounds__(64, 2) void k_assemble_wide(const PlanParams* __res
   const int N = P.N;
   const int b = blockIdx.x / (N + 1), i = blockIdx.x - b * (N + 1);
   if (active && !active[b]) return;
-  if (P.opt_type == GPMP2MI_OPT_DOGLEG && active && pb.phase[b] != 0) return;
+  if (active && dogleg_retry(P, pb, b)) return;
   const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
   extern __shared__ __attribute__((aligned(16))) double asm_smem[];
   const double* rec = rec_of(pb, pb.which[b], bufsel);
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(64, 2) void k_assemble_wide(const PlanParams* __res
   as.stage2(i, slot0, slot1);
   __syncthreads();
   const bool odd = (i & 1) != 0;
-  const bool want_c = odd || P.opt_type == GPMP2MI_OPT_DOGLEG;
+  const bool want_c = odd || P.rules.opt_type == GPMP2MI_OPT_DOGLEG;
   const double* zi = traj + ((size_t)b * (N + 1) + i) * n;
   WTile S, Cl, Cr;
   static_for<0, 4>([&](auto qc) {  // forced unrolling: the four tiles must stay in registers
@@ -429,12 +429,12 @@ __global__ __launch_bounds__(64, 2) void k_assemble_wide(const PlanParams* __res
 #pragma unroll
       for (int k = 0; k < 4; k++) pb.gvec[((size_t)b * (N + 1) + i) * WX + 16 * ti + g + 4 * k] = -S.t[ti][1].r[k];
   }
-  if (P.opt_type == GPMP2MI_OPT_DOGLEG) {  // un-eliminated blocks for g^T H g
+  if (P.rules.opt_type == GPMP2MI_OPT_DOGLEG) {  // un-eliminated blocks for g^T H g
     double* ht = pb.htiles + ((size_t)b * (N + 1) + i) * 2 * WTILE_DBL;
     wtile_store(ht, S, lane);
     wtile_store(ht + WTILE_DBL, Cr, lane);
   }
-  if (P.opt_type == GPMP2MI_OPT_LM) {
+  if (P.rules.opt_type == GPMP2MI_OPT_LM) {
     const double lam = pb.lambda[b];
 #pragma unroll
     for (int ti = 0; ti < 2; ti++)
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(64) void k_ghg_wide(const PlanParams* __restrict__ 
   const PlanParams& P = *pp;
   const int N = P.N;
   const int b = blockIdx.x / (N + 1), i = blockIdx.x - b * (N + 1);
-  if (!pb.active[b] || pb.phase[b] != 0) return;
+  if (!pb.active[b] || dogleg_retry(P, pb, b)) return;
   const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
   const double* ht = pb.htiles + ((size_t)b * (N + 1) + i) * 2 * WTILE_DBL;
   const WTile Dt = wtile_load(ht, lane), Ht = wtile_load(ht + WTILE_DBL, lane);
@@ -507,16 +507,15 @@ int launch_ghg_wide(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st)
 // =============================================================================== cyclic reduction (wide)
 constexpr int WCR_WAVES = 8;  // 16 tiles of state per elimination: 2 wavefronts per SIMD keep 256 VGPRs each
 
-// One task of forward level h: idx < countE eliminates the idx-th odd multiple of h (E task), the others bring the
-// diagonal block of an even multiple up to date (U task).
+// One task of a forward level (cr_schedule.h): an E task eliminates an odd multiple of h, a U task brings the diagonal
+// block of an even multiple up to date.
 template <int n>
-__device__ __forceinline__ bool wcr_task(const PlanBuffers& pb, int b, int N, int h, int idx, int countE, bool final,
-                                         int lane) {
+__device__ __forceinline__ bool wcr_task(const PlanBuffers& pb, int b, int N, const CrLevel& level, int idx, int lane) {
   double* tiles = pb.tiles + (size_t)b * (N + 1) * WTILE_DBL;
   double* fac = pb.fac + (size_t)b * (N + 1) * 3 * WTILE_DBL;
-  const int hh = h >> 1;
-  const bool elim = idx < countE;
-  const int j = elim ? (final ? 0 : h * (2 * idx + 1)) : 2 * h * (idx - countE);
+  const int h = level.h, hh = h >> 1;
+  const bool elim = level.elim(idx), final = level.final;
+  const int j = level.block(idx);
   WTile S = wtile_load_rows<n>(tiles + (size_t)j * WTILE_DBL, lane);
   WTile Cl = wtile_zero(), Cr = wtile_zero();
   const int jm = j - hh, jp = j + hh;
@@ -554,13 +553,10 @@ template <int n>
 __device__ __forceinline__ bool wcr_forward(const PlanBuffers& pb, int b, int N, int tid, int h0) {
   const int w = tid >> 6, lane = tid & 63;
   bool ok = true;
-  int hfinal = 1;
-  while (hfinal <= N) hfinal <<= 1;
+  const int hfinal = cr_hfinal(N);
   for (int h = h0; h <= hfinal; h <<= 1) {
-    const bool final = (h == hfinal);
-    const int countE = final ? 1 : ((N / h) + 1) / 2;
-    const int countU = final ? 0 : (N / (2 * h)) + 1;
-    for (int idx = w; idx < countE + countU; idx += WCR_WAVES) ok = wcr_task<n>(pb, b, N, h, idx, countE, final, lane) && ok;
+    const CrLevel level = cr_level(N, h);
+    for (int idx = w; idx < level.tasks(); idx += WCR_WAVES) ok = wcr_task<n>(pb, b, N, level, idx, lane) && ok;
     __syncthreads();
   }
   return ok;
@@ -569,23 +565,23 @@ __device__ __forceinline__ bool wcr_forward(const PlanBuffers& pb, int b, int N,
 // One forward level (never the final one) spread over the chip: one wavefront per task.  The first levels of a
 // 100-state trajectory are 51 and 26 tasks -- 7 and 4 rounds of the 8 wavefronts of k_solve_step<WcrForm>.
 template <int D>
-__global__ __launch_bounds__(64, 2) void k_cr_level_wide(const PlanParams* __restrict__ pp, PlanBuffers pb, int h) {
+__global__ __launch_bounds__(64, 2) void k_cr_level_wide(const PlanParams* __restrict__ pp, PlanBuffers pb, CrLevel level) {
   constexpr int n = 2 * D;
   const PlanParams& P = *pp;
   const int N = P.N;
-  const int countE = ((N / h) + 1) / 2, countU = (N / (2 * h)) + 1, per = countE + countU;
+  const int per = level.tasks();   // (the launcher sized the grid from the same level)
   const int b = blockIdx.x / per, idx = blockIdx.x - b * per;
   if (!pb.active[b]) return;
-  if (P.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0) return;
-  const bool ok = wcr_task<n>(pb, b, N, h, idx, countE, false, threadIdx.x);
+  if (dogleg_retry(P, pb, b)) return;
+  const bool ok = wcr_task<n>(pb, b, N, level, idx, threadIdx.x);
   if (!ok && threadIdx.x == 0) pb.notspd[b] = 1;
 }
 
 int launch_cr_level_wide(const PlanParams& hp, const PlanBuffers& pb, int h, hipStream_t st) {
-  const int countE = ((hp.N / h) + 1) / 2, countU = (hp.N / (2 * h)) + 1;
-  const dim3 grid(hp.B * (countE + countU)), block(64);
+  const CrLevel level = cr_level(hp.N, h);
+  const dim3 grid(hp.B * level.tasks()), block(64);
   return launch_for_dof(WIDE_DOFS, hp.D, [&](auto d) {
-    k_cr_level_wide<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb, h);
+    k_cr_level_wide<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb, level);
   });
 }
 
@@ -593,13 +589,12 @@ template <int n>
 __device__ __forceinline__ void wcr_backward(const PlanBuffers& pb, int b, int N, int tid, double* xs, int hmin = 1) {
   const int w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
   const double* fac = pb.fac + (size_t)b * (N + 1) * 3 * WTILE_DBL;
-  int hfinal = 1;
-  while (hfinal <= N) hfinal <<= 1;
+  const int hfinal = cr_hfinal(N);
   for (int h = hfinal; h >= hmin; h >>= 1) {
     const bool final = (h == hfinal);
-    const int count = final ? 1 : ((N / h) + 1) / 2;
+    const int count = cr_back_count(N, h);
     for (int idx = w; idx < count; idx += WCR_WAVES) {
-      const int j = final ? 0 : h * (2 * idx + 1);
+      const int j = cr_back_block(N, h, idx);
       const double* f = fac + (size_t)j * 3 * WTILE_DBL;
       const WTile Wl = wtile_load_rows<n>(f, lane), Wr = wtile_load_rows<n>(f + WTILE_DBL, lane), V = wtile_load_rows<n>(f + 2 * WTILE_DBL, lane);
       const int jl = j - h, jr = j + h;

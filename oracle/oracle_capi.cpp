@@ -489,6 +489,11 @@ int orc_set_dogleg_probe(double* buf, int cap_rows) {
   return 0;
 }
 int orc_dogleg_probe_rows() { return dogleg_probe_rows(); }
+int orc_set_lm_probe(double* buf, int cap_rows) {
+  set_lm_probe(buf, cap_rows);
+  return 0;
+}
+int orc_lm_probe_rows() { return lm_probe_rows(); }
 
 int orc_collision_cost(const void* r, const void* s, int total_step, int B, const double* traj,
                        double* cost) {

@@ -1498,6 +1498,18 @@ static void iterate_gn(const Problem& P, State& st) {
   st.iterations++;
 }
 
+// test probe: when set, every tryLambda call appends {lambda, error, solved, g.dx, dx.dx, lin_change, new_err, step_ok,
+// stop} (lambda and error as the call found them; new_err = inf when the trial point was not evaluated).
+// Single-threaded use only (tests/, scripts/).
+static double* g_lm_probe = nullptr;
+static int g_lm_probe_cap = 0, g_lm_probe_n = 0;
+void set_lm_probe(double* buf, int cap_rows) {
+  g_lm_probe = buf;
+  g_lm_probe_cap = cap_rows;
+  g_lm_probe_n = 0;
+}
+int lm_probe_rows() { return g_lm_probe_n; }
+
 static void iterate_lm(const Problem& P, State& st) {
   // LevenbergMarquardtOptimizer::iterate -> tryLambda loop (fixed lambda factor, no diagonal damping)
   const Settings& s = P.set;
@@ -1508,12 +1520,12 @@ static void iterate_lm(const Problem& P, State& st) {
   std::vector<double> dx(st.values.size()), nv(st.values.size());
   for (;;) {
     bool step_ok = false, stop = false;
-    double new_err = std::numeric_limits<double>::infinity(), fidelity = 0;
+    double new_err = std::numeric_limits<double>::infinity(), fidelity = 0, lin_change = 0;
     const bool solved = ne.solve(st.lambda, dx.data());
     if (solved) {
       const double old_lin = st.error;           // linear.error(0) == nonlinear error (no robust)
       const double new_lin = st.error + ne.quad(dx.data());
-      const double lin_change = old_lin - new_lin;
+      lin_change = old_lin - new_lin;
       if (lin_change >= 0) {
         P.retract(st.values.data(), dx.data(), nv.data());
         new_err = P.error(nv.data());
@@ -1525,6 +1537,18 @@ static void iterate_lm(const Problem& P, State& st) {
         const double min_abs = s.rel_thresh * st.error;
         if (std::fabs(cost_change) < min_abs) stop = true;
       }
+    }
+    if (g_lm_probe && g_lm_probe_n < g_lm_probe_cap) {
+      double gd = 0, dd = 0;
+      for (size_t i = 0; solved && i < dx.size(); i++) {
+        gd += ne.g[i] * dx[i];
+        dd += dx[i] * dx[i];
+      }
+      double* row = g_lm_probe + (size_t)g_lm_probe_n * 9;
+      const double vals[9] = {st.lambda, st.error, solved ? 1.0 : 0.0, gd, dd, lin_change, new_err,
+                              step_ok ? 1.0 : 0.0, stop ? 1.0 : 0.0};
+      for (int k = 0; k < 9; k++) row[k] = vals[k];
+      g_lm_probe_n++;
     }
     if (step_ok) {
       st.values = nv;

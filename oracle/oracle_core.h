@@ -231,5 +231,8 @@ OptResult optimize(const Problem& P, const double* init, double* out);
 // test probe of the Dogleg trial points (see oracle_core.cpp); buf = nullptr switches it off
 void set_dogleg_probe(double* buf, int cap_rows);
 int dogleg_probe_rows();
+// the same for the tryLambda calls of Levenberg-Marquardt
+void set_lm_probe(double* buf, int cap_rows);
+int lm_probe_rows();
 
 }  // namespace orc

@@ -276,6 +276,23 @@ class Oracle:
 
         return _Probe()
 
+    def lm_probe(self, rows=512):
+        """context manager: records {lambda, error, solved, g.dx, dx.dx, lin_change, new_err, step_ok, stop} of every
+        tryLambda call of the LM solves run inside it (single-threaded solves only)"""
+        orc = self
+
+        class _Probe:
+            def __enter__(self_):
+                self_.buf = np.zeros((rows, 9))
+                orc.lib.orc_set_lm_probe(dptr(self_.buf), rows)
+                return self_
+
+            def __exit__(self_, *a):
+                self_.rows = self_.buf[: orc.lib.orc_lm_probe_rows()].copy()
+                orc.lib.orc_set_lm_probe(None, 0)
+
+        return _Probe()
+
     def batch_optimize_xp(self, robot, sdf, setting, start_conf, start_vel, end_conf, end_vel, init, priors, goal_on):
         """priors: per trajectory a list of dicts(state, conf, Wc, vel=None, Wv=None); goal_on: [B] ints."""
         s, o, keep = _capi.make_settings(setting)

@@ -1,29 +1,20 @@
-"""Host-side arithmetic of the cyclic-reduction launches (no GPU): the level / task decode that
-gpmp2_amd/csrc/wide_cr.h (k_cr_level_wide, wcr_forward / wcr_backward, k_finish_trial_wide) and dense_kernels.hip
-(k_dense_cr_level, k_dense_cr_back) share with their launchers, restated and checked for every trajectory length:
-each block is eliminated exactly once, after both neighbours it absorbs, and back-substituted after the blocks it
-reads."""
+"""The cyclic-reduction schedule (no GPU): the level / task decode of gpmp2_amd/csrc/cr_schedule.h, which cr_kernels.hip
+(cr_forward / cr_backward), wide_cr.h (k_cr_level_wide, wcr_forward / wcr_backward) and dense_kernels.hip
+(k_dense_cr_level, k_dense_cr_back) share with their launchers, built by the host compiler (control_shim) and checked
+for every trajectory length: each block is eliminated exactly once, after both neighbours it absorbs, and
+back-substituted after the blocks it reads."""
 import pytest
+
+import control_shim as shim
 
 
 def hfinal_of(N):
-    h = 1
-    while h <= N:
-        h <<= 1
-    return h
+    return shim.cr_hfinal(N)
 
 
 def forward_tasks(N, h, first_level):
     """(kind, block) of every task of forward level h; level `first_level` has no U tasks (nothing to absorb)"""
-    final = h == hfinal_of(N)
-    countE = 1 if final else ((N // h) + 1) // 2
-    countU = 0 if (final or h == first_level == 1) else (N // (2 * h)) + 1
-    out = []
-    for idx in range(countE + countU):
-        elim = idx < countE
-        j = (0 if final else h * (2 * idx + 1)) if elim else 2 * h * (idx - countE)
-        out.append(("E" if elim else "U", j))
-    return out
+    return shim.cr_level(N, h, updates=not (h == first_level == 1))[0]
 
 
 @pytest.mark.parametrize("first_level", [1, 2])
@@ -55,9 +46,9 @@ def test_every_block_is_eliminated_once_and_in_order(first_level):
         h = hf
         while h >= 1:
             final = h == hf
-            count = 1 if final else ((N // h) + 1) // 2
+            count = shim.cr_back_count(N, h)
             for idx in range(count):
-                j = 0 if final else h * (2 * idx + 1)
+                j = shim.cr_back_block(N, h, idx)
                 assert eliminated_at[j] == h
                 if not final:
                     for jn in (j - h, j + h):
@@ -66,6 +57,36 @@ def test_every_block_is_eliminated_once_and_in_order(first_level):
                 solved.add(j)
             h >>= 1
         assert len(solved) == N + 1
+
+
+def test_one_tile_path_eliminates_every_block_once():
+    """cr_forward of the one-tile kernels: k_assemble has eliminated levels 1 and 2 (blocks 1, 2, 3 mod 4) when level 2
+    is not the final one (N >= 2), so the first level here is 4; its U tasks are deferred to level 8 when there is one
+    (hfinal >= 8), where every task absorbs all it is owed in one go.  N = 1: only level 1 is done on entry."""
+    for N in range(1, 260):
+        hf = hfinal_of(N)
+        assert hf & (hf - 1) == 0 and hf > N >= hf // 2      # the first power of two above N
+        h0 = 4 if N >= 2 else 2
+        eliminated_at = {j: (1 if j % 2 else 2) for j in range(N + 1) if (j % 4 if N >= 2 else j % 2)}
+        h = h0
+        while h <= hf:
+            updates = not (h0 == 4 and hf >= 8 and h == 4)
+            tasks, (countE, countU, final) = shim.cr_level(N, h, updates)
+            assert final == (h == hf) and len(tasks) == countE + countU
+            assert updates or countU == 0
+            blocks = [j for _, j in tasks]
+            assert len(set(blocks)) == len(blocks) and all(0 <= j <= N for j in blocks), (N, h)
+            for kind, j in tasks:
+                assert j % h == 0 or h == hf
+                if kind == "E":
+                    assert j not in eliminated_at, (N, h, j)
+                    eliminated_at[j] = h
+                else:
+                    assert j % (2 * h) == 0 and j not in eliminated_at, (N, h, j)
+            if updates and not final:     # every block that stays in the tree is brought up to date
+                assert sorted(j for k, j in tasks if k == "U") == list(range(0, N + 1, 2 * h)), (N, h)
+            h <<= 1
+        assert sorted(eliminated_at) == list(range(N + 1)), N
 
 
 def test_wide_split_tail_groups_cover_every_block():
