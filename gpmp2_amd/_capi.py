@@ -146,6 +146,22 @@ def declare_score(lib):
         getattr(lib, name).restype = i
 
 
+def declare_posterior(lib):
+    """argtypes of the posterior entry points (include/gpmp2mi.h "posterior"); the `_dev` forms take device addresses."""
+    vp, i, d, ip = C.c_void_p, C.c_int, c_double_p, c_int_p
+    decl = {
+        "gpmp2mi_block_tridiag_marginals": [i, i, i, d, d, d, d, ip],
+        "gpmp2mi_block_tridiag_sample": [i, i, i, i, d, d, d, d, ip],
+        "gpmp2mi_plan_marginals": [vp, d, d, d, ip],
+        "gpmp2mi_plan_marginals_dev": [vp, vp, vp, vp, vp],
+        "gpmp2mi_plan_sample_posterior": [vp, i, d, d, ip],
+        "gpmp2mi_plan_sample_posterior_dev": [vp, i, vp, vp, vp, vp],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

@@ -62,6 +62,21 @@ int fetch_all(const Bufs&... bufs) {
   return rc;
 }
 
+// A device workspace that only grows (the scoring and posterior workspaces of a plan, the score records of a robot
+// handle).  hipFree waits for the device, so whatever still reads the old block is done before it goes; a call whose
+// shape the block already holds neither allocates nor synchronises.
+constexpr size_t WS_ALIGN = 256;
+inline size_t ws_round(size_t bytes) { return (bytes + WS_ALIGN - 1) / WS_ALIGN * WS_ALIGN; }
+inline int ws_reserve(void** ws, size_t* have, size_t need) {
+  if (need <= *have) return GPMP2MI_OK;
+  if (*ws) (void)hipFree(*ws);
+  *ws = nullptr;
+  *have = 0;
+  G2_TRY(dev_malloc(ws, need));
+  *have = need;
+  return GPMP2MI_OK;
+}
+
 // handles.hip
 int ensure_device();
 void gp_winv(double dt, double W[4]);
@@ -226,6 +241,10 @@ struct gpmp2mi_plan {
   // call for an inter_step and kept (grown when a later call needs more)
   void* score_ws = nullptr;
   size_t score_ws_bytes = 0;
+  // posterior (posterior.hip): the exported normal equations and the factor scratch of k_posterior, taken at the first
+  // marginals / sample call and kept
+  void* post_ws = nullptr;
+  size_t post_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -301,6 +320,9 @@ int plan_get_result(gpmp2mi_plan* p, double* traj, int* iters, double* ferr, int
                     hipMemcpyKind kind, hipStream_t st);
 // `io`: M and the ten arrays of the queue run; `host`: they are host arrays, staged here
 int plan_optimize_queue(gpmp2mi_plan* p, QueueRun io, bool host, hipStream_t st);
+// linearize `traj` into record buffer `bufsel` of every (active) trajectory, extra factors included
+int plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st,
+                   double* dst = nullptr, int pass = 0, bool trial = false);
 int spin_wait_flag(const volatile int* flag, bool st_valid, hipStream_t st, double timeout_s, int* count);
 
 // score.hip: the per-row outputs of a score call and the selection of a select call (any pointer may be null)

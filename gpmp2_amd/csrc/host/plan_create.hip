@@ -89,6 +89,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   flags_release(flagbuf);
   if (qws) (void)hipFree(qws);
   if (score_ws) (void)hipFree(score_ws);
+  if (post_ws) (void)hipFree(post_ws);
   flags_release(qflags);
 }
 

@@ -11,8 +11,8 @@ using namespace g2;
 // then -- only for plans that carry extra factors -- the workspace / self-collision factor kernels on the support
 // states and their accumulation into the unary records
 // dst / pass: fused finish (launch_linearize); the extra-factor kernels then run on the NEW states in dst
-static int plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st,
-                          double* dst = nullptr, int pass = 0, bool trial = false) {
+int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st, double* dst,
+                       int pass, bool trial) {
   const PlanParams& P = p->hp;
   G2_TRY(launch_linearize(p->robot->h, p->robot->d, p->sdf->h, P, p->pb, traj, bufsel, active, st, dst, pass, trial));
   if (!p->has_extras) return GPMP2MI_OK;

@@ -10,21 +10,6 @@ using namespace g2;
 
 namespace {
 
-constexpr size_t WS_ALIGN = 256;
-size_t ws_round(size_t bytes) { return (bytes + WS_ALIGN - 1) / WS_ALIGN * WS_ALIGN; }
-
-// A workspace that only grows.  hipFree waits for the device, so whatever still reads the old block is done before it
-// goes; a call whose shape the block already holds neither allocates nor synchronises.
-int ws_reserve(void** ws, size_t* have, size_t need) {
-  if (need <= *have) return GPMP2MI_OK;
-  if (*ws) (void)hipFree(*ws);
-  *ws = nullptr;
-  *have = 0;
-  G2_TRY(dev_malloc(ws, need));
-  *have = need;
-  return GPMP2MI_OK;
-}
-
 int check_score_args(int inter, int B, int total_step, double delta_t) {
   G2_CHECK(inter >= 0, GPMP2MI_ERR_INVALID, "inter_step must be >= 0");
   G2_CHECK(B >= 0, GPMP2MI_ERR_INVALID, "B must be >= 0");

@@ -214,5 +214,17 @@ int launch_export_normal_eq(const PlanParams& hp, const PlanBuffers& pb, const d
                             double* Hdiag, double* Hoff, double* g, hipStream_t st, const int* active = nullptr);
 int launch_block_tridiag_solve(int B, int nblk, int n, const double* Hd, const double* Ho,
                                const double* b, double* x, int* ok, double* scratch, hipStream_t st);
+// posterior_kernels.hip: Sigma = H^-1 on the band and samples delta = L^-T z of B block-tridiagonal systems (layouts of
+// launch_block_tridiag_solve).  Sd / So null: no marginals; K = 0: no samples; ok may be null.
+struct PosteriorArgs {
+  int nblk, K;
+  const double *Hd, *Ho;   // [B][nblk][n][n], [B][nblk-1][n][n] block (i+1, i)
+  const double* z;         // [B][K][nblk][n]
+  double *Sd, *So;         // as Hd, Ho
+  double* delta;           // as z
+  int* ok;                 // [B]
+  double* fac;             // [B][nblk][512] factor scratch
+};
+int launch_posterior(int B, int n, const PosteriorArgs& a, hipStream_t st);
 
 }  // namespace g2

@@ -42,6 +42,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_queue(lib)
     _capi.declare_multi(lib)
     _capi.declare_score(lib)
+    _capi.declare_posterior(lib)
     return lib
 
 
@@ -320,6 +321,30 @@ class Engine:
         self._ck(self.lib.gpmp2mi_block_tridiag_solve(B, nblk, n, dptr(Hd), dptr(Ho), dptr(b), dptr(x), iptr(ok)))
         return x, ok
 
+    # ---------------------------------------------------------------- posterior (include/gpmp2mi.h "posterior")
+    def block_tridiag_marginals(self, Hd, Ho, want=("Sdiag", "Soff", "ok")):
+        """Sigma = H^-1 on the band of B block-tridiagonal SPD systems (layouts of block_tridiag_solve) ->
+        dict(Sdiag [B][nblk][n][n], Soff [B][nblk-1][n][n] = block (i+1, i), ok [B]); want: the outputs to compute."""
+        Hd, Ho = f64(Hd), f64(Ho)
+        B, nblk, n = Hd.shape[0], Hd.shape[1], Hd.shape[2]
+        o = dict(Sdiag=np.zeros((B, nblk, n, n)) if "Sdiag" in want else None,
+                 Soff=np.zeros((B, nblk - 1, n, n)) if "Soff" in want else None,
+                 ok=np.zeros(B, dtype=np.int32) if "ok" in want else None)
+        self._ck(self.lib.gpmp2mi_block_tridiag_marginals(B, nblk, n, dptr(Hd), dptr(Ho), dptr(o["Sdiag"]),
+                                                          dptr(o["Soff"]), iptr(o["ok"])))
+        return o
+
+    def block_tridiag_sample(self, Hd, Ho, z):
+        """delta = L^-T z with H = L L^T, so cov(delta) = H^-1 for z ~ N(0, I): z [B][K][nblk][n] -> (delta, ok [B])"""
+        Hd, Ho, z = f64(Hd), f64(Ho), f64(z)
+        B, nblk, n = Hd.shape[0], Hd.shape[1], Hd.shape[2]
+        if z.ndim != 4 or z.shape[0] != B or z.shape[2:] != (nblk, n):
+            raise ValueError(f"z: expected [{B}][K][{nblk}][{n}], got {list(z.shape)}")
+        delta, ok = np.zeros_like(z), np.zeros(B, dtype=np.int32)
+        self._ck(self.lib.gpmp2mi_block_tridiag_sample(B, nblk, n, z.shape[1], dptr(Hd), dptr(Ho), dptr(z), dptr(delta),
+                                                       iptr(ok)))
+        return delta, ok
+
     def collision_cost(self, robot, sdf, total_step, traj):
         t = f64(traj).reshape(-1, total_step + 1, 2 * robot.dof)
         cost = np.zeros(t.shape[0])
@@ -556,6 +581,45 @@ class Plan:
         g, err = np.zeros((B, nb, n)), np.zeros(B)
         self.eng._ck(self.eng.lib.gpmp2mi_plan_linearize(self.h.ptr, dptr(t), dptr(Hd), dptr(Ho), dptr(g), dptr(err)))
         return Hd, Ho, g, err
+
+    # ---- the posterior at the estimate (include/gpmp2mi.h "posterior")
+    def marginals(self, traj=None):
+        """Sigma = H^-1 of the plan's graph at `traj` ([B][N+1][2D]; None: the current estimate) ->
+        dict(Sdiag [B][N+1][2D][2D], Soff [B][N][2D][2D] = block (i+1, i), ok [B])."""
+        B, n, nb = self.B, 2 * self.D, self.N + 1
+        t = None if traj is None else f64(traj).reshape(B, nb, n)
+        Sd, So, ok = np.zeros((B, nb, n, n)), np.zeros((B, nb - 1, n, n)), np.zeros(B, dtype=np.int32)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_marginals(self.h.ptr, dptr(t), dptr(Sd), dptr(So), iptr(ok)))
+        return dict(Sdiag=Sd, Soff=So, ok=ok)
+
+    def marginals_dev(self, Sdiag=None, Soff=None, ok=None, stream=None):
+        """The same at the current estimate into device buffers (torch tensors or raw pointers, any may be None); no host
+        synchronisation."""
+        B, n, nb = self.B, 2 * self.D, self.N + 1
+        args = [_dev_arg("Sdiag", Sdiag, (B, nb, n, n)), _dev_arg("Soff", Soff, (B, nb - 1, n, n)),
+                _dev_arg("ok", ok, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_marginals_dev(self.h.ptr, *args, C.c_void_p(stream or 0)))
+
+    def sample_posterior(self, z):
+        """z [B][K][N+1][2D] -> delta of the same shape, delta = L^-T z (H = L L^T at the current estimate): for
+        z ~ N(0, I), perturbations of the estimate drawn from the posterior."""
+        B, n, nb = self.B, 2 * self.D, self.N + 1
+        z = f64(z)
+        if z.ndim != 4 or z.shape[0] != B or z.shape[1] < 1 or z.shape[2:] != (nb, n):
+            raise ValueError(f"z: expected [{B}][K][{nb}][{n}] with K >= 1, got {list(z.shape)}")
+        delta = np.zeros_like(z)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_posterior(self.h.ptr, z.shape[1], dptr(z), dptr(delta), None))
+        return delta
+
+    def sample_posterior_dev(self, K, z, delta, ok=None, stream=None):
+        """The same on device buffers: z, delta [B][K][N+1][2D], ok int32 [B] or None; no host synchronisation."""
+        B, n, nb, K = self.B, 2 * self.D, self.N + 1, int(K)
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        if z is None or delta is None:
+            raise ValueError("z and delta are required")
+        args = [_dev_arg("z", z, (B, K, nb, n)), _dev_arg("delta", delta, (B, K, nb, n)), _dev_arg("ok", ok, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_posterior_dev(self.h.ptr, K, *args, C.c_void_p(stream or 0)))
 
     # ---- incremental replanning (ISAM2TrajOptimizer's role; see include/gpmp2mi.h)
     def fix_state(self, b, state_idx, conf, vel):

@@ -279,6 +279,25 @@ class _ISAM2TrajOptimizer:
     def values(self):
         return values_from_traj(self.opt_values_) if self.as_values_ else self.opt_values_
 
+    def jointMarginalCovariance(self, state_idx):
+        """gtsam::ISAM2::marginalCovariance of (x_i, v_i) together: the 2D x 2D block of Sigma = H^-1 at the current
+        estimate (Plan.marginals), ordered [x_i; v_i]; tangent space for Pose2 robots."""
+        if self.opt_values_ is None:
+            raise RuntimeError("[ISAM2TrajOptimizer] initValues must come first")
+        i = int(state_idx)
+        if not 0 <= i <= self.setting_.total_step:
+            raise IndexError(f"state_idx {i} is outside 0..{self.setting_.total_step}")
+        m = self.plan_.marginals()
+        if m["ok"][0] != 1:
+            raise RuntimeError("IndeterminantLinearSystemException")
+        return m["Sdiag"][0, i].copy()
+
+    def marginalCovariance(self, state_idx, velocity=False):
+        """gtsam::ISAM2::marginalCovariance(Symbol('x', i)) (velocity: Symbol('v', i)): the D x D block"""
+        D = self.setting_.dof
+        S = self.jointMarginalCovariance(state_idx)
+        return S[D:, D:].copy() if velocity else S[:D, :D].copy()
+
 
 class ISAM2TrajOptimizer2DArm(_ISAM2TrajOptimizer):
     """gpmp2/planner/ISAM2TrajOptimizer.h:143-147"""

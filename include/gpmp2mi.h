@@ -593,6 +593,41 @@ int gpmp2mi_joint_limit_factor(int dof, const double* down, const double* up, co
 int gpmp2mi_block_tridiag_solve(int B, int nblk, int n, const double* Hdiag, const double* Hoff,
                                 const double* b, double* x, int* ok);
 
+/* ---- posterior: marginal covariances and samples, on the device -------------------------------------
+ * The MAP trajectory of a plan is the mean of a Gaussian posterior whose covariance is Sigma = H^-1, H the
+ * Gauss-Newton Hessian of the graph at that trajectory: what gtsam::Marginals(graph, values).marginalCovariance(key)
+ * and ISAM2::marginalCovariance(key) return.  H is block tridiagonal (block n = 2D, z_i = [x_i; v_i]); one kernel
+ * eliminates it forward as the solvers do (H = L L^T, L^T block upper bidiagonal) and sweeps back
+ * (Rauch-Tung-Striebel) for the blocks of Sigma on the band, or back-substitutes K vectors z for
+ * delta = L^-T z: with z ~ N(0, I), delta ~ N(0, Sigma), a perturbation of the trajectory drawn from the posterior.
+ *
+ * Sigma = H^-1 of B block-tridiagonal SPD systems (layouts of gpmp2mi_block_tridiag_solve):
+ * Sdiag [B][nblk][n][n] = Sigma_ii (exactly symmetric), Soff [B][nblk-1][n][n] = block (i+1,i) = Sigma_{i,i+1}^T,
+ * ok [B] (0: a pivot was not positive; that system's outputs are then unspecified).  Any output may be NULL.
+ * n = 1..15 (GPMP2MI_ERR_UNSUPPORTED above). */
+int gpmp2mi_block_tridiag_marginals(int B, int nblk, int n, const double* Hdiag, const double* Hoff,
+                                    double* Sdiag, double* Soff, int* ok);
+/* delta = L^-T z, H = L L^T:  z, delta [B][K][nblk][n], K >= 1; ok may be NULL */
+int gpmp2mi_block_tridiag_sample(int B, int nblk, int n, int K, const double* Hdiag, const double* Hoff,
+                                 const double* z, double* delta, int* ok);
+/* the plan's graph linearized (Gauss-Newton Hessian, no damping; start/goal and state priors and extra
+ * factors included) at `traj` (host, [B][N+1][2D]) or, traj == NULL, at the plan's current estimate (the result of
+ * the last optimize / update; the initial values if there is none); tangent space at that estimate for Pose2 robots,
+ * as gtsam::Marginals.  Sdiag [B][N+1][2D][2D], Soff [B][N][2D][2D], ok [B]; any output may be NULL.
+ * The optimizer's state is not touched: a gpmp2mi_plan_update after these calls gives what it gives without them.
+ * Errors: GPMP2MI_ERR_INVALID for a NULL plan, before gpmp2mi_plan_set_problem, K < 1 or a NULL z / delta;
+ * GPMP2MI_ERR_TIMEOUT for a poisoned plan, before anything is enqueued; GPMP2MI_ERR_UNSUPPORTED for 2D > 15 (the wide
+ * and dense plans, dof >= 8): one 16 x 16 tile per block is the limit of this kernel.
+ * Memory: the exported H (2 (2D)^2 doubles per state) and 512 doubles of factors per state are taken at the first call
+ * and kept with the plan, as the scoring workspace is.  The `_dev` forms (device pointers, current estimate) enqueue
+ * on `stream` and return without a host synchronisation; calls on one plan belong in stream order. */
+int gpmp2mi_plan_marginals(gpmp2mi_plan* p, const double* traj, double* Sdiag, double* Soff, int* ok);
+int gpmp2mi_plan_marginals_dev(gpmp2mi_plan* p, double* Sdiag, double* Soff, int* ok, void* stream);
+/* z, delta [B][K][N+1][2D]: delta ~ N(0, Sigma) for z ~ N(0, I); retract delta onto the estimate for samples of the
+ * trajectory (vector-space robots: estimate + delta) */
+int gpmp2mi_plan_sample_posterior(gpmp2mi_plan* p, int K, const double* z, double* delta, int* ok);
+int gpmp2mi_plan_sample_posterior_dev(gpmp2mi_plan* p, int K, const double* z, double* delta, int* ok, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 const char* gpmp2mi_last_error(void);  /* thread-local message of the last failing call */
 int gpmp2mi_device_count(void);

@@ -667,6 +667,27 @@ class ISAM2TrajOptimizer {
           "gpmp2mi_plan_add_state_estimate");
   }
   const Trajectory& values() const { return opt_values_; }
+  /// gtsam::ISAM2::marginalCovariance of (x_i, v_i) together: the 2 dof x 2 dof block of Sigma = H^-1 at the current
+  /// estimate (gpmp2mi_plan_marginals), row-major, ordered [x_i; v_i]
+  Vector jointMarginalCovariance(std::size_t state_idx) const {
+    if (opt_values_.data.empty()) throw std::runtime_error("[ISAM2TrajOptimizer] initValues must come first");
+    if (state_idx > setting_.total_step) throw std::runtime_error("[ISAM2TrajOptimizer] state_idx is past total_step");
+    const std::size_t nn = 4 * dof_ * dof_;
+    Vector all((setting_.total_step + 1) * nn);
+    int ok = 0;
+    check(gpmp2mi_plan_marginals(plan_, nullptr, all.data(), nullptr, &ok), "gpmp2mi_plan_marginals");
+    if (!ok) throw std::runtime_error("[gpmp2mi] IndeterminantLinearSystemException");
+    return Vector(all.begin() + state_idx * nn, all.begin() + (state_idx + 1) * nn);
+  }
+  /// gtsam::ISAM2::marginalCovariance(Symbol('x', i)) (velocity: Symbol('v', i)): row-major [dof][dof]
+  Vector marginalCovariance(std::size_t state_idx, bool velocity = false) const {
+    const Vector J = jointMarginalCovariance(state_idx);
+    const std::size_t o = velocity ? dof_ : 0;
+    Vector out(dof_ * dof_);
+    for (std::size_t r = 0; r < dof_; r++)
+      for (std::size_t c = 0; c < dof_; c++) out[r * dof_ + c] = J[(o + r) * 2 * dof_ + o + c];
+    return out;
+  }
 
  private:
   void fits(const Vector& v) const {
@@ -683,6 +704,49 @@ class ISAM2TrajOptimizer {
 /// gpmp2/planner/ISAM2TrajOptimizer.h:143-156
 typedef internal::ISAM2TrajOptimizer<ArmModel, PlanarSDF> ISAM2TrajOptimizer2DArm;
 typedef internal::ISAM2TrajOptimizer<ArmModel, SignedDistanceField> ISAM2TrajOptimizer3DArm;
+
+/// The posterior around a result (include/gpmp2mi.h "posterior"): Sigma = H^-1 of the BatchTrajOptimize graph
+/// linearized at `result`, what gtsam::Marginals(graph, result) holds.  diag [total_step+1][2 dof][2 dof] = the blocks
+/// of (x_i, v_i), off [total_step][2 dof][2 dof] = block (i+1, i), both row-major.
+struct TrajectoryCovariance {
+  std::size_t dof = 0, total_step = 0;
+  Vector diag, off;
+  /// the [2 dof][2 dof] block of state i
+  Vector joint(std::size_t i) const {
+    const std::size_t nn = 4 * dof * dof;
+    return Vector(diag.begin() + i * nn, diag.begin() + (i + 1) * nn);
+  }
+};
+/// ROBOT: a robot model of at most 7 dof (one tile per block; wider ones throw); SDF: SignedDistanceField or PlanarSDF.
+template <class ROBOT, class SDF>
+inline TrajectoryCovariance TrajectoryMarginals(const ROBOT& robot, const SDF& sdf, const Trajectory& result,
+                                                const Vector& start_conf, const Vector& start_vel, const Vector& end_conf,
+                                                const Vector& end_vel, const TrajOptimizerSetting& setting) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[TrajectoryMarginals] result does not match dof / total_step");
+  for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+    if (v->size() != robot.dof()) throw std::runtime_error("[TrajectoryMarginals] vector dim does not fit dof");
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, 1, &plan), "gpmp2mi_plan_create");
+  TrajectoryCovariance out;
+  out.dof = robot.dof(), out.total_step = setting.total_step;
+  const std::size_t nn = 4 * out.dof * out.dof;
+  out.diag.assign((out.total_step + 1) * nn, 0.0);
+  out.off.assign(out.total_step * nn, 0.0);
+  int ok = 0;
+  int rc = gpmp2mi_plan_set_problem(plan, start_conf.data(), start_vel.data(), end_conf.data(), end_vel.data(),
+                                    result.data.data());
+  const char* what = "gpmp2mi_plan_set_problem";
+  if (!rc) {
+    rc = gpmp2mi_plan_marginals(plan, result.data.data(), out.diag.data(), out.off.data(), &ok);
+    what = "gpmp2mi_plan_marginals";
+  }
+  gpmp2mi_plan_destroy(plan);
+  check(rc, what);
+  if (!ok) throw std::runtime_error("[gpmp2mi] IndeterminantLinearSystemException");
+  return out;
+}
 
 /// B independent BatchTrajOptimize problems of one robot, field and setting, sharded over several GPUs of this process
 /// (gpmp2mi_multi_plan, include/gpmp2mi.h): shard k of `devices` holds a contiguous share of the rows, repeats allowed.
