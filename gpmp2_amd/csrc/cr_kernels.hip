@@ -46,8 +46,8 @@ namespace g2 {
 #define G2_TSTAMP(q) do {} while (0)
 #endif
 #ifdef G2_STAMPS
-#define G2_ASTAMP(k) do { if (i == 1 && lane == 0 && pb.iters[b] == G2_STAMP_ITER) pb.stamps[(size_t)b * 64 + 32 + (k)] = __builtin_amdgcn_s_memtime(); \
-                          if (i == 2 && lane == 0 && pb.iters[b] == G2_STAMP_ITER) pb.stamps[(size_t)b * 64 + 40 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define G2_ASTAMP(k) do { if (v == 5 && lane == 0 && pb.iters[b] == G2_STAMP_ITER) pb.stamps[(size_t)b * 64 + 32 + (k)] = __builtin_amdgcn_s_memtime(); \
+                          if (v == 6 && lane == 0 && pb.iters[b] == G2_STAMP_ITER) pb.stamps[(size_t)b * 64 + 40 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define G2_ASTAMP(k) do {} while (0)
 #endif
@@ -105,11 +105,16 @@ __device__ __forceinline__ Tile coupling(const Tile& A, const Tile& B, int lane)
 }
 
 // =============================================================================== assemble
-// One workgroup = 4 wavefronts = the 4 consecutive blocks 4q .. 4q+3 of one trajectory; wavefront r
-// forms block i = 4q + r.  Levels 1 AND 2 of the cyclic reduction happen here, spread over the whole
+// Blocks are named by their index in the rooted tree of cr_schedule.h, v = state + 1 in [1, N + 1]; everything keyed by
+// the state -- the staged intervals, build_tiles, epart / gvec / htiles, and the per-block storage tiles / fac / xg --
+// keeps the state index j = v - 1, so the debug readers and k_ghg see the layout they always saw.
+// One workgroup = 4 wavefronts = the 4 consecutive tree blocks 4q .. 4q+3 of one trajectory (states 4q-1 .. 4q+2);
+// wavefront r forms block v = 4q + r.  Levels 1 AND 2 of the cyclic reduction happen here, spread over the whole
 // chip: odd blocks (r = 1, 3) are eliminated as soon as they are formed; block 4q + 2 then absorbs
 // their Schur complements (handed over through LDS), gets its fill-in couplings to 4q and 4q + 4 and is
-// eliminated too.  The per-trajectory solve kernels start at level 4 (cr_forward).
+// eliminated too.  The per-trajectory solve kernels start at level 4 (cr_forward).  Block 0 does not exist: wavefront 0
+// of group 0 shadows state 0 up to the barriers (as the idle wavefronts of the last group shadow state N), group 0 folds
+// nothing into S(4q) and the pair (0, 4) has no coupling.
 //
 // Round 3: everything the eliminated blocks of the group owe to the surviving multiples of 4 is FOLDED here as well,
 // on matrix cores that this (vector-issue bound) kernel leaves idle, instead of in the per-trajectory step kernel whose
@@ -133,7 +138,7 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   using Asm = Assembler<D, LIE>;
   const PlanParams& P = *pp;
   const int N = P.N;
-  const int groups = (N + ASM_WAVES) / ASM_WAVES;  // ceil((N + 1) / 4)
+  const int groups = crr_groups(N, ASM_WAVES);     // tree indices 0 .. N + 1 in fours
   const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
   if (active && !active[b]) return;
   // Early stop (Gauss-Newton fast driver): the graph error at these states is already known -- k_linearize_arm left its
@@ -146,13 +151,14 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   // Dogleg retries (phase 1: same linearization, smaller trust region) need no new factorisation
   if (active && dogleg_retry(P, pb, b)) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int i = ASM_WAVES * q + wv;
-  const bool live = i <= N;             // the last group may be partly empty
-  const int ic = live ? i : N;          // idle wavefronts shadow block N up to the barriers
+  const int v = ASM_WAVES * q + wv, i = v - 1;   // tree index, state
+  const bool live = v >= 1 && i <= N;   // the last group may be partly empty; v = 0 does not exist
+  const int ic = min(max(i, 0), N);     // idle wavefronts shadow a real state up to the barriers
   extern __shared__ __attribute__((aligned(16))) double asm_smem[];
-  // the 4 blocks of the group need the 5 intervals 4q .. 4q+4; every interval is staged once, into a slot all
-  // wavefronts can read: wavefront wv stages interval 4q + wv (the last one also 4q + 4) and then uses slots
-  // wv (interval i) and wv + 1 (interval i + 1)
+  // the 4 blocks of the group need the 5 intervals 4q-1 .. 4q+3; every interval is staged once, into a slot all
+  // wavefronts can read: wavefront wv stages interval i = 4q-1 + wv (the last one also 4q + 3) and then uses slots
+  // wv (interval i) and wv + 1 (interval i + 1).  (There is no interval -1: the wavefront without a block stages
+  // interval 0 into the slot nobody else reads.)
   // hand-over tiles: [0] W_l, [1] W_r of block 4q+1; [2] W_l, [3] W_r of block 4q+3; S of block 4q goes where only its
   // own wavefront has read -- record slot 0 -- when a slot holds a tile, otherwise into a fifth tile
   const int slotd = Asm::slot_doubles(P.I, P.RECS, P.GPS);
@@ -163,11 +169,11 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   Asm as(P, pb, rec, gpu, b, lane);
   G2_ASTAMP(0);
   const typename Asm::Slot slot0 = as.make_slot(asm_smem, wv), slot1 = as.make_slot(asm_smem, wv + 1);
-  as.stage2(i, slot0, slot1, wv == ASM_WAVES - 1 ? 2 : 1);
+  as.stage2(max(i, 0), slot0, slot1, wv == ASM_WAVES - 1 ? 2 : 1);
   __syncthreads();
   G2_ASTAMP(1);
-  const bool odd = (i & 1) != 0;
-  const bool fuse2 = N >= 2;            // level 2 is fused here unless it is the final level (N < 2)
+  const bool odd = (v & 1) != 0;
+  const bool fuse2 = N >= 3;            // level 2 is fused here unless it is the top level (N + 1 < 4)
   const bool lvl2 = fuse2 && wv == 2 && live;
   Tile S, Cl, Cr;
   double err_acc = as.build_tiles(ic, slot0, slot1, traj + ((size_t)b * (N + 1) + ic) * n, S, Cl, Cr,
@@ -220,41 +226,44 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   __syncthreads();
   G2_ASTAMP(6);
   if (wv != 2) return;
-  // wavefront 2: level h = 2 for block j = 4q + 2 (an odd multiple of 2; the E task of cr_forward with the neighbours'
+  // wavefront 2: level h = 2 for block v = 4q + 2 (an odd multiple of 2; the E task of cr_forward with the neighbours'
   // factor tiles taken from LDS) when that block exists, and the folding for block 4q / the next group either way
-  const int j0 = ASM_WAVES * q;
-  const bool next = j0 + 4 <= N;
-  Tile Sp = tile_load(xs0, lane);                             // S of block 4q
+  const int v0 = ASM_WAVES * q, M = N + 1;
+  const bool has0 = q >= 1;                                   // block 4q exists
+  const bool next = v0 + 4 <= M;
+  Tile Sp = tile_zero();
+  if (has0) Sp = tile_load(xs0, lane);                        // S of block 4q
   // what the odd blocks owe: W_l(4q+1)^T W_l(4q+1) to block 4q, W_r(4q+3)^T W_r(4q+3) to block 4q + 4.  The products are
   // issued here, in front of the level-2 elimination, and only masked / applied behind it: the matrix cores work through
   // them while the pivot loop runs on the vector ALU.
   Tile A1 = tile_zero(), R = tile_zero();
-  if (j0 + 1 <= N) {
+  if (has0 && v0 + 1 <= M) {
     const Tile Wl1 = tile_load(xch, lane);
     A1 = tile_atb(Wl1, Wl1);
   }
-  if (next && j0 + 3 <= N) {
+  if (next) {
     const Tile Wr3 = tile_load(xch + 3 * TILE_DBL, lane);
     R = tile_atb(Wr3, Wr3);
   }
   if (live) {
-    const int j = i;
-    const Tile Wr_m = tile_load(xch + TILE_DBL, lane);       // block j - 1: W_r
+    const Tile Wr_m = tile_load(xch + TILE_DBL, lane);       // block v - 1: W_r
     schur_sub<n>(S, Wr_m, lane);
-    const Tile Wl_m = tile_load(xch, lane);                  // block j - 1: W_l
-    Tile C2l = coupling<n>(Wr_m, Wl_m, lane);                // rows j, cols j - 2
-    Tile C2r = tile_zero();
-    if (j + 1 <= N) {
-      const Tile Wl_p = tile_load(xch + 2 * TILE_DBL, lane); // block j + 1: W_l
+    Tile C2l = tile_zero(), C2r = tile_zero();
+    if (has0) {
+      const Tile Wl_m = tile_load(xch, lane);                // block v - 1: W_l
+      C2l = coupling<n>(Wr_m, Wl_m, lane);                   // rows v, cols v - 2
+    }
+    if (v + 1 <= M) {
+      const Tile Wl_p = tile_load(xch + 2 * TILE_DBL, lane); // block v + 1: W_l
       schur_sub<n>(S, Wl_p, lane);
-      if (j + 2 <= N) {
+      if (v + 2 <= M) {
         const Tile Wr_p = tile_load(xch + 3 * TILE_DBL, lane);
-        C2r = coupling<n>(Wl_p, Wr_p, lane);                 // rows j, cols j + 2
+        C2r = coupling<n>(Wl_p, Wr_p, lane);                 // rows v, cols v + 2
       }
     }
     Tile V;
     const bool ok = tile_eliminate_cv<n>(S, C2l, C2r, V, lane);
-    double* f = pb.fac + ((size_t)b * (N + 1) + j) * 3 * TILE_DBL;
+    double* f = pb.fac + ((size_t)b * (N + 1) + i) * 3 * TILE_DBL;
     tile_store_rows<n>(f, C2l, lane);
     tile_store_rows<n>(f + TILE_DBL, C2r, lane);
     tile_store_transposed<n>(f + 2 * TILE_DBL, V, lane);
@@ -266,24 +275,27 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
       const Tile B2 = tile_atb(C2r, C2r);                    // W_r(j)^T W_r(j): owed by block 4q + 4
 #pragma unroll
       for (int k = 0; k < 4; k++) R.r[k] += B2.r[k];
-      // fill-in between 4q and 4q + 4: rows of the one that level 4 eliminates
-      const Tile K = (q & 1) ? coupling<n>(C2l, C2r, lane) : coupling<n>(C2r, C2l, lane);
-      tile_store_rows<n>(pb.coup + ((size_t)b * groups + q) * TILE_DBL, K, lane);
+      if (has0) {   // fill-in between 4q and 4q + 4: rows of the one that level 4 eliminates
+        const Tile K = (q & 1) ? coupling<n>(C2l, C2r, lane) : coupling<n>(C2r, C2l, lane);
+        tile_store_rows<n>(pb.coup + ((size_t)b * groups + q) * TILE_DBL, K, lane);
+      }
     }
     G2_ASTAMP(7);
   }
   schur_keep<n>(A1);                                          // real rows, matrix + rhs columns (as schur_sub)
   schur_keep<n>(R);
+  if (has0) {
 #pragma unroll
-  for (int k = 0; k < 4; k++) Sp.r[k] -= A1.r[k];
-  tile_store_rows<n>(tiles + ((size_t)b * (N + 1) + j0) * TILE_DBL, Sp, lane);
+    for (int k = 0; k < 4; k++) Sp.r[k] -= A1.r[k];
+    tile_store_rows<n>(tiles + ((size_t)b * (N + 1) + v0 - 1) * TILE_DBL, Sp, lane);
+  }
   if (next) tile_store_rows<n>(pb.pend + ((size_t)b * groups + q) * TILE_DBL, R, lane);
 }
 
 int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel,
                     const int* active, hipStream_t st, bool early_stop) {
   const int es = early_stop ? 1 : 0;
-  const dim3 grid(hp.B * ((hp.N + ASM_WAVES) / ASM_WAVES)), block(64 * ASM_WAVES);
+  const dim3 grid(hp.B * crr_groups(hp.N, ASM_WAVES)), block(64 * ASM_WAVES);
   const size_t slotd = (size_t)(hp.I + 1) * hp.RECS + hp.GPS + 24 * hp.I;
   const size_t shmem = ((ASM_WAVES + 1) * slotd + (slotd >= TILE_DBL ? 4 : 5) * TILE_DBL) * sizeof(double);
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
@@ -302,7 +314,8 @@ constexpr int CR_WAVES = G2_CR_WAVES;
 
 
 
-// Forward elimination (levels h >= 2; level 1 was done by k_assemble) of one trajectory's system.
+// Forward elimination (levels h >= 2; level 1 was done by k_assemble) of one trajectory's system, down the rooted tree of
+// cr_schedule.h: a task's block is a tree index v in [1, N + 1] and lives at state v - 1 in tiles / fac.
 // All CR_WAVES wavefronts of the workgroup take part; returns false (per wavefront) on a bad pivot.
 template <int n>
 __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, int tid) {
@@ -316,21 +329,21 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
   double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;  // per block: Wl, Wr, V
   bool ok = true;
   G2_STAMP_DECL;
-  const int hfinal = cr_hfinal(N);
-  // levels 1 and 2 were done by k_assemble (level 2 only when it is not the final one, N >= 2), including
+  const int htop = crr_top(N), M = N + 1;
+  // levels 1 and 2 were done by k_assemble (level 2 only when it is not the top one, N >= 3), including
   // their Schur complements on the surviving blocks (multiples of 4) and the level-4 couplings
-  const int h0 = (N >= 2) ? 4 : 2;
+  const int h0 = (N >= 3) ? 4 : 2;
   // Level 4 would be 13 E + 13 U tasks on 16 wavefronts (two rounds) for N = 100: its U tasks (the blocks that
   // are multiples of 8) are deferred -- at level 8 every task absorbs the Schur complements of its level-1,
   // level-2 and level-4 neighbours in one go, so both levels take a single round.
-  const bool defer4 = (h0 == 4) && (hfinal >= 8);
-  for (int h = h0; h <= hfinal; h <<= 1) {
-    const CrLevel level = cr_level(N, h, !(defer4 && h == 4));
-    const bool final = level.final;
+  const bool defer4 = (h0 == 4) && (htop >= 8);
+  // (the top level is a level like any other: its single block has no neighbour at distance h, so it gets no coupling)
+  for (int h = h0; h <= htop; h <<= 1) {
+    const CrrLevel level = crr_level(N, h, !(defer4 && h == 4));
     const int hh = h >> 1;
     for (int idx = w; idx < level.tasks(); idx += CR_WAVES) {
       const bool elim = level.elim(idx);
-      const int j = level.block(idx);
+      const int v = level.block(idx), j = v - 1;
       // every tile this task needs is requested before the first product: the level-1 / level-2 factors come from
       // the previous kernel (other XCDs' L2 -> Infinity Cache / HBM latency), and one latency is paid instead of
       // one per neighbour
@@ -340,11 +353,11 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
       // ready-made.  Every tile is requested before the first product (one latency per task, not one per neighbour).
       const bool first = h0 == 4 && (h == 4 || (defer4 && h == 8));
       const bool ready = h0 == 4 && h == 4;          // level-2 neighbours already absorbed, couplings precomputed
-      const int jm = j - hh, jp = j + hh, qj = j >> 2;
-      const bool em = jm >= 0, ep = jp <= N;
-      const bool cm = em && elim && !final, cp = ep && elim && !final && j + h <= N;
+      const int jm = j - hh, jp = j + hh, qj = v >> 2;     // states of the neighbours v -+ h/2 (v - h/2 >= 1 always)
+      const bool ep = v + hh <= M;
+      const bool cm = elim && v - h >= 1, cp = elim && v + h <= M;
       auto facp = [&](int blk, int which) { return fac + ((size_t)blk * 3 + which) * TILE_DBL; };
-      const int groups = (N + 4) / 4;
+      const int groups = crr_groups(N, 4);
       const double* pend = pb.pend + (size_t)b * groups * TILE_DBL;
       const double* coup = pb.coup + (size_t)b * groups * TILE_DBL;
       G2_TSTAMP(0);
@@ -352,12 +365,12 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
       Tile Pd = tile_zero();
       Tile Wr_m = tile_zero(), Wl_m = tile_zero(), Wl_p = tile_zero(), Wr_p = tile_zero();
       Tile Cl = tile_zero(), Cr = tile_zero();
-      if (first && qj >= 1) Pd = tile_load_rows<n>(pend + (size_t)(qj - 1) * TILE_DBL, lane);
+      if (first) Pd = tile_load_rows<n>(pend + (size_t)(qj - 1) * TILE_DBL, lane);   // v = 4 qj, qj >= 1
       if (ready) {
         if (cm) Cl = tile_load_rows<n>(coup + (size_t)(qj - 1) * TILE_DBL, lane);
         if (cp) Cr = tile_load_rows<n>(coup + (size_t)qj * TILE_DBL, lane);
       } else {
-        if (em) Wr_m = tile_load_rows<n>(facp(jm, 1), lane);
+        Wr_m = tile_load_rows<n>(facp(jm, 1), lane);
         if (cm) Wl_m = tile_load_rows<n>(facp(jm, 0), lane);
         if (ep) Wl_p = tile_load_rows<n>(facp(jp, 0), lane);
         if (cp) Wr_p = tile_load_rows<n>(facp(jp, 1), lane);
@@ -369,10 +382,10 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
 #pragma unroll
       for (int k = 0; k < 4; k++) S.r[k] -= Pd.r[k];
       if (!ready) {
-        if (em) schur_sub<n>(S, Wr_m, lane);
-        if (cm) Cl = coupling<n>(Wr_m, Wl_m, lane);  // rows j, cols j - h
+        schur_sub<n>(S, Wr_m, lane);
+        if (cm) Cl = coupling<n>(Wr_m, Wl_m, lane);  // rows v, cols v - h
         if (ep) schur_sub<n>(S, Wl_p, lane);
-        if (cp) Cr = coupling<n>(Wl_p, Wr_p, lane);  // rows j, cols j + h
+        if (cp) Cr = coupling<n>(Wl_p, Wr_p, lane);  // rows v, cols v + h
       }
       if (!elim) {
         tile_store_rows<n>(tiles + (size_t)j * TILE_DBL, S, lane);
@@ -401,31 +414,30 @@ __device__ __forceinline__ bool cr_forward(const PlanBuffers& pb, int b, int N, 
   return ok;
 }
 
-// Back-substitution down the same tree, levels hfinal .. hmin; leaves x of every block it reaches in
-// xs[(N+1)][16] (LDS).
+// Back-substitution down the same tree, levels top .. hmin; leaves x of every block it reaches in
+// xs[(N+1)][16] (LDS), addressed by the state v - 1 like tiles / fac.
 template <int n>
 __device__ __forceinline__ void cr_backward(const PlanBuffers& pb, int b, int N, int tid, double* xs, int hmin = 1) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, c = lane & 15, g = lane >> 4;
   const double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;
   G2_STAMP_DECL;
-  const int hfinal = cr_hfinal(N);
+  const int htop = crr_top(N), M = N + 1;
   // the factor tiles of a wavefront's first task of a level do not depend on the level above: they are requested
   // BEFORE the barrier that publishes that level's solutions, so their latency hides behind it
   Tile pWl = tile_zero(), pWr = tile_zero(), pV = tile_zero();
   auto prefetch = [&](int h) {
-    if (h >= hmin && w < cr_back_count(N, h)) {
-      const double* f = fac + (size_t)cr_back_block(N, h, w) * 3 * TILE_DBL;
+    if (h >= hmin && w < crr_back_count(N, h)) {
+      const double* f = fac + (size_t)(crr_back_block(N, h, w) - 1) * 3 * TILE_DBL;
       pWl = tile_load_rows<n>(f, lane);
       pWr = tile_load_rows<n>(f + TILE_DBL, lane);
       pV = load_v<n>(f + 2 * TILE_DBL, h, N, lane);
     }
   };
-  prefetch(hfinal);
-  for (int h = hfinal; h >= hmin; h >>= 1) {
-    const bool final = (h == hfinal);
-    const int count = cr_back_count(N, h);
+  prefetch(htop);
+  for (int h = htop; h >= hmin; h >>= 1) {
+    const int count = crr_back_count(N, h);
     for (int idx = w; idx < count; idx += CR_WAVES) {
-      const int j = cr_back_block(N, h, idx);
+      const int v = crr_back_block(N, h, idx), j = v - 1;
       Tile Wl = pWl, Wr = pWr, V = pV;
       if (idx != w) {
         const double* f = fac + (size_t)j * 3 * TILE_DBL;
@@ -434,8 +446,8 @@ __device__ __forceinline__ void cr_backward(const PlanBuffers& pb, int b, int N,
         V = load_v<n>(f + 2 * TILE_DBL, h, N, lane);
       }
       const int jl = j - h, jr = j + h;
-      const double xl = (!final && jl >= 0) ? xs[jl * 16 + c] : 0.0;
-      const double xr = (!final && jr <= N) ? xs[jr * 16 + c] : 0.0;
+      const double xl = (v - h >= 1) ? xs[jl * 16 + c] : 0.0;
+      const double xr = (v + h <= M) ? xs[jr * 16 + c] : 0.0;
       const double x = cr_backsolve<n>(Wl, Wr, V, xl, xr, lane);
       if (g == 0) xs[j * 16 + c] = (c < n) ? x : 0.0;
     }
@@ -534,12 +546,12 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
 
   if (P.split_back) {
     // the three widest back-substitution levels (88 of the 101 blocks) and the retract run chip-wide in
-    // k_finish_step; this kernel only solves the blocks that are multiples of 8 and hands them over
+    // k_finish_step; this kernel only solves the blocks whose tree index is a multiple of 8 and hands them over
     cr_backward<n>(pb, b, N, tid, xs, FIN_BLOCKS);
     G2_STAMP(3);
     double* xg = pb.xg + (size_t)b * (N + 1) * 16;
-    for (int k = tid; k < (N / FIN_BLOCKS + 1) * 16; k += blockDim.x) {
-      const size_t o = (size_t)(k >> 4) * FIN_BLOCKS * 16 + (k & 15);
+    for (int k = tid; k < ((N + 1) / FIN_BLOCKS) * 16; k += blockDim.x) {
+      const size_t o = ((size_t)((k >> 4) + 1) * FIN_BLOCKS - 1) * 16 + (k & 15);   // state 8 (k / 16 + 1) - 1
       xg[o] = xs[o];
     }
     G2_STAMP(4);
@@ -576,15 +588,16 @@ __global__ __launch_bounds__(64 * CR_WAVES) void k_gn_step_cr(const PlanParams* 
   if (threadIdx.x == 0) publish_pass_count(pb, pass);
 }
 
-// Chip-wide tail of a Gauss-Newton pass (split path): one workgroup of 8 wavefronts per (trajectory, blocks
-// 8q .. 8q+7).  Block 8q+4 is back-substituted from x_{8q}, x_{8q+8} (level 4), then 8q+2 / 8q+6 (level 2), then the
-// odd blocks (level 1); every wavefront then retracts its own state: last = cur; cur = cur (+) x.
+// Chip-wide tail of a Gauss-Newton pass (split path): one workgroup of 8 wavefronts per (trajectory, tree blocks
+// v = 8q .. 8q+7, i.e. states 8q-1 .. 8q+6; v = 0 does not exist).  Block 8q+4 is back-substituted from x_{8q}, x_{8q+8}
+// (level 4), then 8q+2 / 8q+6 (level 2), then the odd blocks (level 1); every wavefront then retracts its own state:
+// last = cur; cur = cur (+) x.
 // (FIN_BLOCKS is declared next to CR_WAVES: the step kernels stop their back-substitution at the multiples of it.)
 template <int D>
 struct FinishGroup {
   static constexpr int n = 2 * D;
   Tile Wl, Wr, V;
-  int b, q, wv, lane, c, g, i, N;
+  int b, q, wv, lane, c, g, v, i, N;   // v: tree index, i = v - 1: state
   bool live;
   // loads of the wavefront's factor tiles are requested right away, so they are in flight while the levels above
   // are being solved
@@ -594,8 +607,9 @@ struct FinishGroup {
     lane = threadIdx.x & 63;
     c = lane & 15;
     g = lane >> 4;
-    i = FIN_BLOCKS * q + wv;
-    live = i <= N;
+    v = FIN_BLOCKS * q + wv;
+    i = v - 1;
+    live = v >= 1 && i <= N;
     const double* xg = pb.xg + (size_t)b * (N + 1) * 16;
     const double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;
     Wl = Wr = V = tile_zero();
@@ -603,16 +617,16 @@ struct FinishGroup {
       const double* f = fac + (size_t)i * 3 * TILE_DBL;
       Wl = tile_load_rows<n>(f, lane);
       Wr = tile_load_rows<n>(f + TILE_DBL, lane);
-      V = load_v<n>(f + 2 * TILE_DBL, (i & 3) ? 1 : 4, N, lane);   // blocks 8q + 4 were eliminated by the step kernel (level 4)
+      V = load_v<n>(f + 2 * TILE_DBL, (v & 3) ? 1 : 4, N, lane);   // blocks 8q + 4 were eliminated by the step kernel (level 4)
     }
-    if (wv == 0 && lane < 16) xl_[0][lane] = xg[(size_t)(FIN_BLOCKS * q) * 16 + lane];
+    if (wv == 0 && lane < 16) xl_[0][lane] = live ? xg[(size_t)i * 16 + lane] : 0.0;
     if (wv == 1 && lane < 16)
-      xl_[FIN_BLOCKS][lane] = (FIN_BLOCKS * q + FIN_BLOCKS <= N) ? xg[(size_t)(FIN_BLOCKS * q + FIN_BLOCKS) * 16 + lane] : 0.0;
+      xl_[FIN_BLOCKS][lane] = (FIN_BLOCKS * q + FIN_BLOCKS <= N + 1) ? xg[(size_t)(FIN_BLOCKS * q + FIN_BLOCKS - 1) * 16 + lane] : 0.0;
   }
   __device__ __forceinline__ void solve(int h, double (*xl_)[16]) const {
-    const int jl = i - h, jr = i + h;
-    const double xl = (jl >= 0) ? xl_[jl - FIN_BLOCKS * q][c] : 0.0;
-    const double xr = (jr <= N) ? xl_[jr - FIN_BLOCKS * q][c] : 0.0;
+    const int vl = v - h, vr = v + h;
+    const double xl = (vl >= 1) ? xl_[vl - FIN_BLOCKS * q][c] : 0.0;
+    const double xr = (vr <= N + 1) ? xl_[vr - FIN_BLOCKS * q][c] : 0.0;
     const double x = cr_backsolve<n>(Wl, Wr, V, xl, xr, lane);
     if (g == 0) xl_[wv][c] = (c < n) ? x : 0.0;
   }
@@ -633,7 +647,7 @@ __global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_step(const PlanParam
   constexpr int n = 2 * D;
   const PlanParams& P = *pp;
   const int N = P.N;
-  const int groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
+  const int groups = crr_groups(N, FIN_BLOCKS);
   const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
   if (pb.stepped[b] != pass + 1) return;
   __shared__ double xl_[FIN_BLOCKS + 1][16];
@@ -651,27 +665,27 @@ __global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_step(const PlanParam
 }
 
 int launch_finish_step(const PlanParams& hp, const PlanBuffers& pb, int pass, hipStream_t st) {
-  const dim3 grid(hp.B * ((hp.N + FIN_BLOCKS) / FIN_BLOCKS)), block(64 * FIN_BLOCKS);
+  const dim3 grid(hp.B * crr_groups(hp.N, FIN_BLOCKS)), block(64 * FIN_BLOCKS);
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
     k_finish_step<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb, pass);
   });
 }
 
-// Group tail of k_finish_trial / k_finish_trial_wide, once the workgroup (FIN_BLOCKS wavefronts, blocks
-// FIN_BLOCKS q ..) has solved its blocks: wavefront wv writes the step x of its block i = FIN_BLOCKS q + wv (x: LDS,
+// Group tail of k_finish_trial / k_finish_trial_wide, once the workgroup (FIN_BLOCKS wavefronts, states
+// i0 ..; group q of P.spart_groups) has solved its blocks: wavefront wv writes the step x of its state i = i0 + wv (x: LDS,
 // in the layout of gvec rows of stride X) to `delta` and the trial point cur (+) x to `trial` (cur stays), and the
 // workgroup leaves its share of g.delta, |delta|^2, |g|^2 in spart for the step control (k_decide sums them in group
 // order).
 template <int D, int X>
-__device__ __forceinline__ void finish_trial_group(const PlanParams& P, const PlanBuffers& pb, int b, int q,
+__device__ __forceinline__ void finish_trial_group(const PlanParams& P, const PlanBuffers& pb, int b, int q, int i0,
                                                    const double* x) {
   constexpr int n = 2 * D;
   __shared__ double psum[FIN_BLOCKS][3];
-  const int N = P.N, groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
+  const int N = P.N, groups = P.spart_groups;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int i = FIN_BLOCKS * q + wv;
+  const int i = i0 + wv;
   double gd = 0.0, dd = 0.0, gg = 0.0;
-  if (i <= N && lane < n) {
+  if (i >= 0 && i <= N && lane < n) {
     const size_t k = ((size_t)b * (N + 1) + i) * n + lane;
     const double* zs = pb.cur + ((size_t)b * (N + 1) + i) * n;
     const double xk = x[lane], gk = pb.gvec[((size_t)b * (N + 1) + i) * X + lane];
@@ -704,17 +718,17 @@ template <int D>
 __global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_trial(const PlanParams* __restrict__ pp, PlanBuffers pb) {
   const PlanParams& P = *pp;
   const int N = P.N;
-  const int groups = (N + FIN_BLOCKS) / FIN_BLOCKS;
+  const int groups = crr_groups(N, FIN_BLOCKS);
   const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
   if (!pb.active[b] || pb.stepped[b] != 1) return;
   __shared__ double xl_[FIN_BLOCKS + 1][16];
   const FinishGroup<D> fg(pb, N, b, q, xl_);
   fg.solve_all(xl_);
-  finish_trial_group<D, 16>(P, pb, b, q, xl_[fg.wv]);
+  finish_trial_group<D, 16>(P, pb, b, q, FIN_BLOCKS * q - 1, xl_[fg.wv]);
 }
 
 int launch_finish_trial(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {
-  const dim3 grid(hp.B * ((hp.N + FIN_BLOCKS) / FIN_BLOCKS)), block(64 * FIN_BLOCKS);
+  const dim3 grid(hp.B * crr_groups(hp.N, FIN_BLOCKS)), block(64 * FIN_BLOCKS);
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
     k_finish_trial<decltype(d)::value><<<grid, block, 0, st>>>(pb.params, pb);
   });
@@ -740,6 +754,9 @@ int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hip
 template <int D_>
 struct CrForm {   // one 16 x 16 tile per block (dof <= 7)
   static constexpr int D = D_, n = 2 * D, WAVES = CR_WAVES, X = 16;
+  // split form: the states whose step the solve kernel hands to the finish kernels (tree indices 8, 16, ..)
+  static __device__ __forceinline__ int handed(int N) { return (N + 1) / FIN_BLOCKS; }
+  static __device__ __forceinline__ int handed_state(int k) { return (k + 1) * FIN_BLOCKS - 1; }
   static __device__ __forceinline__ bool forward(const PlanParams& P, const PlanBuffers& pb, int b, int tid) {
     return cr_forward<n>(pb, b, P.N, tid);
   }
@@ -750,6 +767,8 @@ struct CrForm {   // one 16 x 16 tile per block (dof <= 7)
 template <int D_>
 struct WcrForm {  // 2 x 2 tiles per block (8 <= dof <= 11, wide_cr.h); levels below P.wide_h0 ran in k_cr_level_wide
   static constexpr int D = D_, n = 2 * D, WAVES = WCR_WAVES, X = WX;
+  static __device__ __forceinline__ int handed(int N) { return N / FIN_BLOCKS + 1; }   // blocks 0, 8, 16, ..
+  static __device__ __forceinline__ int handed_state(int k) { return k * FIN_BLOCKS; }
   static __device__ __forceinline__ bool forward(const PlanParams& P, const PlanBuffers& pb, int b, int tid) {
     return wcr_forward<n>(pb, b, P.N, tid, P.wide_h0);
   }
@@ -800,8 +819,8 @@ __global__ __launch_bounds__(64 * F::WAVES) void k_solve_step(const PlanParams* 
       // k_finish_trial (k_finish_trial_wide)
       F::backward(pb, b, N, tid, xs, FIN_BLOCKS);
       double* xg = pb.xg + (size_t)b * (N + 1) * X;
-      for (int k = tid; k < (N / FIN_BLOCKS + 1) * X; k += blockDim.x) {
-        const size_t o = (size_t)(k / X) * FIN_BLOCKS * X + (k % X);
+      for (int k = tid; k < F::handed(N) * X; k += blockDim.x) {
+        const size_t o = (size_t)F::handed_state(k / X) * X + (k % X);
         xg[o] = xs[o];
       }
       if (tid == 0) pb.stepped[b] = 1;

@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "host.h"
+#include "../cr_schedule.h"
 
 namespace g2 {
 // Host-mapped pass-flag arrays are recycled across plans: pinning and unpinning host memory costs more than the
@@ -154,7 +155,7 @@ static int choose_forms(const RobotDev& h, const gpmp2mi_settings& s, int B, con
   // fused finish (k_linearize_arm applies the step: GN fast path, LM / GN trial steps); the trial-step shares then come
   // per chunk of 64 of the 1 + N (I + 1) evaluation points instead of per group of 8 blocks (k_finish_trial)
   F.fuse_finish = F.lin_split == 4 && F.split_back && !F.wide && !f.no_fused_finish;
-  F.spart_groups = F.fuse_finish ? (1 + N * (I + 1) + 63) / 64 : (N + 8) / 8;
+  F.spart_groups = F.fuse_finish ? (1 + N * (I + 1) + 63) / 64 : F.wide ? (N + 8) / 8 : crr_groups(N, 8);
   F.generic_gn = f.generic_gn != 0;
   F.no_early_stop = f.no_early_stop != 0;
   *out = F;
@@ -343,7 +344,7 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
   for (double** q : {&pb.gpu, &pb.gpu2}) G2_TRY(plan_alloc(p, q, (size_t)B * P.GPS * P.Npad));
   G2_TRY(plan_alloc(p, &pb.tiles, (size_t)B * (P.N + 1) * 256 * tq));
   G2_TRY(plan_alloc(p, &pb.fac, (size_t)B * (P.N + 1) * 768 * tq));
-  for (double** q : {&pb.pend, &pb.coup}) G2_TRY(plan_alloc(p, q, (size_t)B * ((P.N + 4) / 4) * 256));
+  for (double** q : {&pb.pend, &pb.coup}) G2_TRY(plan_alloc(p, q, (size_t)B * crr_groups(P.N, 4) * 256));
   for (double** q : {&pb.cur_err, &pb.prev_err, &pb.last_err, &pb.final_err, &pb.lambda}) G2_TRY(plan_alloc(p, q, B));
   G2_TRY(plan_alloc(p, &pb.trace, (size_t)B * (P.rules.max_iter + 1)));
   for (int** q : {&pb.iters, &pb.status, &pb.active, &pb.phase, &pb.notspd}) G2_TRY(plan_alloc(p, q, B));

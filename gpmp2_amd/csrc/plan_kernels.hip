@@ -19,6 +19,7 @@
 #include "plan.h"
 #include "tiles.h"
 #include "assembler.h"
+#include "cr_schedule.h"
 #include "plan_device.h"
 
 namespace g2 {
@@ -303,9 +304,10 @@ __global__ __launch_bounds__(64 * NSPLIT, KIND == GPMP2MI_ROBOT_ARM ? 2 : 1) voi
 // 7 joints + 8 spheres, and 168 VGPRs leave room for three wavefronts per SIMD: 640 workgroups x 4 wavefronts of the
 // 64-restart batch are resident at once.
 // Fused finish (Gauss-Newton fast path, `dst` != nullptr): the kernel first APPLIES the step the previous pass solved.  The
-// step kernel left the solution of the blocks that are multiples of 8 (pb.xg); every workgroup here back-substitutes levels
+// step kernel left the solution of the blocks whose tree index v = state + 1 (cr_schedule.h, rooted schedule) is a multiple of
+// 8 (pb.xg); every workgroup here back-substitutes levels
 // 4, 2, 1 for the 12 - 18 states its 64 points touch -- only the blocks those states need, found with bit masks over a window
-// of <= 40 blocks; what k_finish_step did chip-wide in a launch of its own (7 - 8 us) --, adds the step to the states it
+// of <= 40 tree indices that starts at a multiple of 8 (bit k: v = w0 + k, state w0 + k - 1; v = 0 is never valid); what k_finish_step did chip-wide in a launch of its own (7 - 8 us) --, adds the step to the states it
 // reads from `traj` (the buffer of the previous pass, which nobody writes during this kernel), keeps the new states in
 // LDS for its own points and writes those whose unary point lies in its chunk to `dst`.  The two state buffers of a
 // plan (cur / last) swap roles from pass to pass, so `last` is simply the buffer the step started from.
@@ -367,20 +369,16 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
   if (apply) {
     const double* fac = pb.fac + (size_t)b * (N + 1) * 3 * TILE_DBL;
     const double* xg = pb.xg + (size_t)b * (N + 1) * 16;
-    const int w0 = s0 & ~7, c = lane & 15, g = lane >> 4;
+    // window in tree indices: the states s0 .. s1 are v = s0 + 1 .. s1 + 1 <= w0 + 7 + ZNS, their neighbours at distance 1, 2, 4
+    // reach no further than the next multiple of 8, w0 + 32 < FXS
+    const int w0 = (s0 + 1) & ~7, M = N + 1, c = lane & 15, g = lane >> 4;
     using u64 = unsigned long long;
-    auto bits = [](int lo, int hi) -> u64 { return (hi < lo) ? 0ull : ((~0ull >> (63 - (hi - lo))) << lo); };   // [lo, hi], hi <= 63
-    const u64 valid = bits(0, min(N - w0, FXS - 1)), inr = bits(s0 - w0, s1 - w0);
-    const u64 L1 = 0xAAAAAAAAAAAAAAAAull, L2 = 0x4444444444444444ull, L4 = 0x1010101010101010ull, L8 = 0x0101010101010101ull;
-    // a block of level h needs its neighbours at distance h, which belong to higher levels
-    const u64 need1 = inr & L1 & valid, nb1 = (need1 << 1) | (need1 >> 1);
-    const u64 need2 = (inr | nb1) & L2 & valid, nb2 = (need2 << 2) | (need2 >> 2);
-    const u64 need4 = (inr | nb1 | nb2) & L4 & valid, nb4 = (need4 << 4) | (need4 >> 4);
-    const u64 need8 = (inr | nb1 | nb2 | nb4) & L8 & valid;
+    const CrrWindow win = crr_window(N, s0, s1, FXS);   // the blocks of levels 1, 2, 4 to solve here, the multiples of 8 to fetch
+    const u64 need1 = win.need1, need2 = win.need2, need4 = win.need4, need8 = win.need8;
     // multiples of 8: solved by the step kernel
     for (u64 m = need8; m; m &= m - 1) {
       const int k = __builtin_ctzll(m);
-      if (wv == ((k >> 3) & (NW - 1)) && lane < 16) fx[k][lane] = xg[(size_t)(w0 + k) * 16 + lane];
+      if (wv == ((k >> 3) & (NW - 1)) && lane < 16) fx[k][lane] = xg[(size_t)(w0 + k - 1) * 16 + lane];
     }
     __syncthreads();
     // Task t of a level (the t-th needed block) belongs to wavefront t % NW.  (Requesting the factor tiles ahead -- all twelve
@@ -389,12 +387,12 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
       int t = 0;
       for (u64 m = need; m; m &= m - 1, t++) {
         if ((t & (NW - 1)) != wv) continue;
-        const int k = __builtin_ctzll(m), jb = w0 + k;
-        const double* f = fac + (size_t)jb * 3 * TILE_DBL;
+        const int k = __builtin_ctzll(m), vb = w0 + k;
+        const double* f = fac + (size_t)(vb - 1) * 3 * TILE_DBL;
         const Tile Wl = tile_load_rows<n>(f, lane), Wr = tile_load_rows<n>(f + TILE_DBL, lane);
         const Tile V = load_v<n>(f + 2 * TILE_DBL, h, N, lane);
-        const double xl = (k - h >= 0) ? fx[k - h][c] : 0.0;          // (k - h < 0 cannot happen: w0 is a multiple of 8)
-        const double xr = (jb + h <= N) ? fx[k + h][c] : 0.0;
+        const double xl = (vb - h >= 1) ? fx[k - h][c] : 0.0;         // (k - h < 0 cannot happen: w0 is a multiple of 8)
+        const double xr = (vb + h <= M) ? fx[k + h][c] : 0.0;
         const double x = cr_backsolve<n>(Wl, Wr, V, xl, xr, lane);
         if (g == 0) fx[k][c] = (c < n) ? x : 0.0;
       }
@@ -411,7 +409,7 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     const int t = e / n, rho = e - t * n, st = s0 + t;
     const size_t k = ((size_t)b * (N + 1) + st) * n + rho;
     double z = traj[k];
-    const double x = apply ? fx[st - (s0 & ~7)][rho] : 0.0;
+    const double x = apply ? fx[st + 1 - ((s0 + 1) & ~7)][rho] : 0.0;
     z += x;                                       // Values::retract of a vector-valued state
     zn[t][rho] = z;
     const int pu = st * (I + 1);                  // the state's unary evaluation point: its owner writes the state

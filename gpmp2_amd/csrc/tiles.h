@@ -522,11 +522,12 @@ __device__ __forceinline__ double cr_backsolve(const Tile& Wl, const Tile& Wr, c
 #endif
 }
 
-// The third factor tile of a block eliminated at level h: k_assemble (level 1, and level 2 when N >= 2) stores V, the
+// The third factor tile of a block eliminated at level h: k_assemble (level 1, and level 2 when N >= 3, where it is not
+// the top level of the rooted tree) stores V, the
 // levels the step kernels run themselves store Vt (see tile_load_transposed)
 template <int n>
 __device__ __forceinline__ Tile load_v(const double* p, int h, int N, int lane) {
-  const int h0 = (N >= 2) ? 4 : 2;   // first level of cr_forward
+  const int h0 = (N >= 3) ? 4 : 2;   // first level of cr_forward
   return (h >= h0) ? tile_load_transposed<n>(p, lane) : tile_load_rows<n>(p, lane);
 }
 

@@ -662,7 +662,7 @@ __global__ __launch_bounds__(64 * FIN_BLOCKS) void k_finish_trial_wide(const Pla
   __syncthreads();
   if ((wv & 1) && live) solve(1);
   __syncthreads();
-  finish_trial_group<D, WX>(P, pb, b, q, xl_[wv]);
+  finish_trial_group<D, WX>(P, pb, b, q, FIN_BLOCKS * q, xl_[wv]);
 }
 
 int launch_finish_trial_wide(const PlanParams& hp, const PlanBuffers& pb, hipStream_t st) {

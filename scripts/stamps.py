@@ -40,12 +40,12 @@ for b in (0, 33):
     print(f"trajectory {b}")
     print("   linearize wavefront 0 (chunk 1), k_linearize_arm: fused finish (levels 4, 2, 1 of the previous step for its states) + state loads + interpolation + sin/cos + barrier | chain walk (wavefront 0) + barrier | "
           "its 4 spheres | wait for the others + tree sum | record store | (gp prior: last wavefront)", d(raw[48:64]))
-    print("   assemble wave i=1 (odd block): stage / build / misc / eliminate / store", d(raw[32:38]))
-    print("   build_tiles i=1: owner rows / constants + unary / sub-step loop / replanner priors + shuffles", d(raw[24:29]))
+    print("   assemble wave v=5 (odd block, state 4): stage / build / misc / eliminate / store", d(raw[32:38]))
+    print("   build_tiles v=5: owner rows / constants + unary / sub-step loop / replanner priors + shuffles", d(raw[24:29]))
     t2 = raw[40:48]
-    print("   assemble wave i=2 (level 2): stage / build / ... / wait for the odd blocks / products + eliminate + store", d(t2))
+    print("   assemble wave v=6 (level 2, state 5): stage / build / ... / wait for the odd blocks / products + eliminate + store", d(t2))
     if raw[47] > 0 and raw[32] > 0:
-        print("   assemble i=1 start -> i=2 end:", int(raw[47] - raw[32]))
+        print("   assemble v=5 start -> v=6 end:", int(raw[47] - raw[32]))
     if raw[4] > raw[0] > 0:
         print("   step kernel: control", int(raw[1] - raw[0]), "forward", int(raw[2] - raw[1]), "backward", int(raw[3] - raw[2]),
               "hand-over", int(raw[4] - raw[3]), "total", int(raw[4] - raw[0]))
@@ -59,4 +59,4 @@ for b in (0, 33):
     fw = [raw[1]] + [raw[5 + k] for k in range(1, 9) if raw[5 + k] > 0]
     print("   forward levels h = 4, 8, ..:", [int(x) for x in np.diff(fw)])
     bw = [raw[2]] + [raw[16 + k] for k in range(7, -1, -1) if raw[16 + k] > 0]
-    print("   backward levels h = final, ..:", [int(x) for x in np.diff(bw)])
+    print("   backward levels h = top, ..:", [int(x) for x in np.diff(bw)])
