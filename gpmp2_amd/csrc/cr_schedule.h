@@ -8,7 +8,7 @@
 // is alone.  Backward level h solves the blocks eliminated at level h from x_{j-h}, x_{j+h}.  (The 2 x 2-tile and
 // dense paths: wide_cr.h, dense_kernels.hip.)
 //
-// The ROOTED schedule (crr_*; the one-tile path, cr_kernels.hip and the fused finish of plan_kernels.hip) numbers the
+// The ROOTED schedule (crr_*; the one-tile path, cr_kernels.hip and the fused finish of linearize_kernels.hip) numbers the
 // same blocks v = j + 1 = 1 .. N + 1 and there is no block v = 0.  A block belongs to the level of the lowest set bit
 // of v: level h eliminates the odd multiples of h in [1, N + 1], the even multiples are its U tasks.  A coupling to
 // v - h = 0 or to v + h > N + 1 does not exist, so the first E block of every level has no left coupling, and the top
@@ -72,11 +72,15 @@ G2_PURE int crr_back_block(int, int h, int idx) { return h * (2 * idx + 1); }
 // the first group, so that every group is aligned with the tree
 G2_PURE int crr_groups(int N, int g) { return (N + 1) / g + 1; }
 
+constexpr int ZNS = 24, FXS = 40;   // states a chunk of 64 evaluation points may read; slots of its step window
+// the most states a chunk reads with I sub-steps per interval: 63 / (I + 1) + 2 that its points belong to, and the one before
+G2_PURE constexpr int chunk_states(int I) { return 63 / (I + 1) + 3; }
+
 // The blocks a workgroup must back-substitute itself (levels 4, 2, 1) to know the step of the states s0 .. s1, once the
 // solve kernel has handed over the multiples of 8 (fused finish, k_linearize_arm): bit k of a mask is the tree index
 // v = w0 + k, w0 the multiple of 8 at or below s0 + 1.  A block of level h needs its neighbours at distance h, which
-// belong to higher levels; need8 are the handed-over blocks to fetch.  s1 - s0 < 24: every bit lies below w0 + 33, and
-// `span` (<= 64) is the number of window slots the caller has.
+// belong to higher levels; need8 are the handed-over blocks to fetch.  s1 - s0 < ZNS: every bit lies below w0 + 33, and
+// `span` (<= 64; FXS in the kernel) is the number of window slots the caller has.
 struct CrrWindow {
   int w0;
   unsigned long long need1, need2, need4, need8;

@@ -1,7 +1,7 @@
 // factor_kernels.hip -- factor-level kernels behind the evaluateError-style C ABI entry points
 // (include/gpmp2mi.h "factor-level entry points").  One lane per evaluation; these exist for
 // parity testing and for callers that embed single factors; the planner's hot loop uses the
-// fused kernels in plan_kernels.hip.
+// fused kernels in linearize_kernels.hip and plan_kernels.hip.
 #include "device_math.h"
 #include "dispatch.h"
 #include "launch.h"

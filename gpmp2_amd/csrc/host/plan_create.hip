@@ -131,7 +131,8 @@ static int choose_forms(const RobotDev& h, const gpmp2mi_settings& s, int B, con
   const bool fixed_arm = h.kind == GPMP2MI_ROBOT_ARM;
   G2_CHECK(f.lin_split == 0 || f.lin_split == 1 || (fixed_arm && (f.lin_split == 2 || f.lin_split == 4)), GPMP2MI_ERR_UNSUPPORTED,
            "forced lin_split: 1, or 2 / 4 on a fixed-base arm");
-  // (the four-wavefront form keeps the <= 24 states of a chunk in LDS: two or more sub-steps per interval)
+  // (the four-wavefront form keeps the <= ZNS states of a chunk in LDS: two or more sub-steps per interval)
+  static_assert(chunk_states(2) <= ZNS && chunk_states(1) > ZNS, "the I >= 2 below and at the default choice");
   G2_CHECK(f.lin_split != 4 || I >= 2, GPMP2MI_ERR_UNSUPPORTED, "forced lin_split 4: needs obs_check_inter >= 2");
   PlanForms F;
   F.wide = 2 * D > 15;

@@ -1,5 +1,5 @@
 // plan.h -- device-resident state of a batch of trajectory problems (gpmp2mi_plan) and the
-// launchers of the fused hot-path kernels in plan_kernels.hip.
+// launchers of the fused hot-path kernels (linearize_kernels.hip, plan_kernels.hip, cr_kernels.hip, dense_kernels.hip).
 #pragma once
 #include "common.h"
 #include "step_control.h"

@@ -484,7 +484,7 @@ __device__ __forceinline__ bool chain_solve(int nblk, BlockSrc&& next_block, dou
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// back-substitution of one block of the cyclic reduction (cr_kernels.hip: cr_backward, k_finish_step; plan_kernels.hip:
+// back-substitution of one block of the cyclic reduction (cr_kernels.hip: cr_backward, k_finish_step; linearize_kernels.hip:
 // the fused finish of k_linearize_arm)
 // sum over the 16 lanes of a DPP row, result in every lane of the row
 __device__ __forceinline__ double row_sum16(double v) {

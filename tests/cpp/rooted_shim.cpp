@@ -24,6 +24,10 @@ int shim_crr_level(int N, int h, int updates, int* elim, int* block, int* counts
 int shim_crr_back_count(int N, int h) { return crr_back_count(N, h); }
 int shim_crr_back_block(int N, int h, int idx) { return crr_back_block(N, h, idx); }
 int shim_crr_groups(int N, int g) { return crr_groups(N, g); }
+// the fused finish's bounds: states per chunk, slots of the step window; the most states a chunk reads
+int shim_zns() { return ZNS; }
+int shim_fxs() { return FXS; }
+int shim_chunk_states(int I) { return chunk_states(I); }
 // out = {need1, need2, need4, need8}; returns w0
 int shim_crr_window(int N, int s0, int s1, int span, unsigned long long* out) {
   const CrrWindow w = crr_window(N, s0, s1, span);

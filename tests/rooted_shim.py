@@ -29,6 +29,7 @@ def lib():
         L.shim_crr_back_count.argtypes = [i, i]
         L.shim_crr_back_block.argtypes = [i, i, i]
         L.shim_crr_groups.argtypes = [i, i]
+        L.shim_chunk_states.argtypes = [i]
         L.shim_crr_window.argtypes = [i, i, i, i, C.POINTER(C.c_ulonglong)]
         _lib = L
     return _lib
@@ -67,8 +68,23 @@ def groups(N, g):
     return lib().shim_crr_groups(N, g)
 
 
-def window(N, s0, s1, span=40):
-    """-> w0, {h: set of tree indices v} for h = 1, 2, 4 (to solve) and 8 (to fetch)"""
+def zns():
+    """states a chunk of 64 evaluation points may read (k_linearize_arm keeps them in LDS)"""
+    return lib().shim_zns()
+
+
+def fxs():
+    """slots of the step window of the fused finish"""
+    return lib().shim_fxs()
+
+
+def chunk_states(I):
+    return lib().shim_chunk_states(I)
+
+
+def window(N, s0, s1, span=None):
+    """-> w0, {h: set of tree indices v} for h = 1, 2, 4 (to solve) and 8 (to fetch); span: the kernel's window, FXS"""
+    span = fxs() if span is None else span
     out = (C.c_ulonglong * 4)()
     w0 = lib().shim_crr_window(N, s0, s1, span, out)
     return w0, {h: {w0 + k for k in range(64) if (out[t] >> k) & 1} for t, h in enumerate((1, 2, 4, 8))}

@@ -166,8 +166,11 @@ def test_finish_groups_of_eight_cover_every_state_once():
 
 
 def test_fused_finish_windows_cover_every_state_once():
-    """k_linearize_arm: the chunk of 64 evaluation points reads the states s0 .. s1 (<= 24) and owns those whose unary
-    point lies in it; the window of 40 tree indices from the multiple of 8 below holds every block it must solve"""
+    """k_linearize_arm: the chunk of 64 evaluation points reads the states s0 .. s1 (<= ZNS) and owns those whose unary
+    point lies in it; the window of FXS tree indices from the multiple of 8 below holds every block it must solve"""
+    ZNS, FXS = shim.zns(), shim.fxs()
+    assert (ZNS, FXS) == (24, 40)
+    assert shim.chunk_states(2) <= ZNS < shim.chunk_states(1)        # the four-wavefront form needs obs_check_inter >= 2
     for I in (2, 3, 5, 10):
         for N in list(range(16, 131)) + [255, 256, 260]:
             M, P = N + 1, 1 + N * (I + 1)
@@ -176,17 +179,17 @@ def test_fused_finish_windows_cover_every_state_once():
             for chunk in range((P + 63) // 64):
                 p_lo, p_hi = chunk * 64, min(chunk * 64 + 63, P - 1)
                 s1, s0 = state_of(p_hi), max(0, state_of(p_lo) - 1)
-                assert s1 - s0 + 1 <= 24
+                assert s1 - s0 + 1 <= min(ZNS, shim.chunk_states(I))
                 w0, need = shim.window(N, s0, s1)
                 assert w0 % 8 == 0 and w0 <= s0 + 1
                 have = set(need[8])
                 assert all(v % 8 == 0 and 8 <= v <= M for v in have)
                 for h in (4, 2, 1):
-                    assert all((v & -v) == h and 1 <= v <= M and 0 <= v - w0 < 40 for v in need[h]), (N, I, chunk)
+                    assert all((v & -v) == h and 1 <= v <= M and 0 <= v - w0 < FXS for v in need[h]), (N, I, chunk)
                     for v in need[h]:
                         for vn in (v - h, v + h):
                             if 1 <= vn <= M:
-                                assert vn in have and 0 <= vn - w0 < 40, (N, I, chunk, v, vn)
+                                assert vn in have and 0 <= vn - w0 < FXS, (N, I, chunk, v, vn)
                     have |= need[h]
                 assert set(range(s0 + 1, s1 + 2)) <= have, (N, I, chunk)
                 owned += [s for s in range(s0, s1 + 1) if p_lo <= s * (I + 1) <= p_lo + 63]

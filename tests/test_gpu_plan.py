@@ -640,18 +640,21 @@ def test_every_block_width_of_the_one_tile_path(engine, oracle, D, opt):
     check_contract(engine, oracle, p, label=p.name, final_error_rtol=1e-8)
 
 
-@pytest.mark.parametrize("case", ["wam3d", "planar3", "planar5"])
+@pytest.mark.parametrize("case", ["wam3d", "planar3", "planar5", "wam3d_two_chunks"])
 def test_every_linearization_form_of_fixed_base_arms(engine, oracle, case):
     """Fixed-base arms have three forms of the linearization kernel: one wavefront per 64 points (forms lin_split=1), two
     wavefronts that both walk the chain (2; the default above 256 trajectories) and four that share one walk through LDS
-    (4: k_linearize_arm, the default up to 256).  All three against the oracle's normal equations, and against each other."""
+    (4: k_linearize_arm, the default up to 256).  All three against the oracle's normal equations, and against each other.
+    The first three cases have 56 and 53 evaluation points, one partly filled chunk of 64; wam3d_two_chunks has 81: a full
+    chunk and a tail of 17, so the point decode crosses a chunk boundary and the record store is predicated in the last
+    chunk (4 + 2 states per chunk: form 4 is legal; the 0.05 noise of wam3d meets the precondition asserted below)."""
     import gpmp2_amd as g
     from gpmp2_amd import datasets
     from gpmp2_amd.settings import TrajOptimizerSetting
     from gpmp2_amd.trajutils import initArmTrajStraightLine
     rng = np.random.default_rng(12)
-    if case == "wam3d":
-        p = problems.wam_restarts(B=3, total_step=11, obs_check_inter=4, opt="GN", sdf="40")
+    if case.startswith("wam3d"):
+        p = problems.wam_restarts(B=3, total_step=16 if case == "wam3d_two_chunks" else 11, obs_check_inter=4, opt="GN", sdf="40")
         traj = p.init + 0.05 * rng.normal(size=p.init.shape)
     else:
         D = int(case[-1])
