@@ -162,6 +162,30 @@ def declare_posterior(lib):
         getattr(lib, name).restype = i
 
 
+RNG_RESTARTS, RNG_POSTERIOR = 1, 2
+
+
+def declare_seed(lib):
+    """argtypes of the seeding entry points (include/gpmp2mi.h "seeding") and their debug read-out; the `_dev` forms take
+    device addresses."""
+    vp, i, d, ip, f, u64 = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double, C.c_uint64
+    decl = {
+        "gpmp2mi_normal_fill": [u64, i, i, i, i, i, i, i, d],
+        "gpmp2mi_normal_fill_dev": [u64, i, i, i, i, i, i, i, vp, vp],
+        "gpmp2mi_plan_seed_restarts": [vp, i, u64, i, f, i, d, d, d, d],
+        "gpmp2mi_plan_seed_restarts_dev": [vp, i, u64, i, f, i, vp, vp, vp, vp, vp],
+        "gpmp2mi_plan_optimize_queue_seeded": [vp, i, u64, i, f, i, d, d, d, d, d, d, ip, d, ip, d, d],
+        "gpmp2mi_plan_optimize_queue_seeded_dev": [vp, i, u64, i, f, i] + [vp] * 12,
+        "gpmp2mi_multi_plan_optimize_queue_seeded": [vp, i, u64, i, f, i, d, d, d, d, d, d, ip, d, ip, d, d],
+        "gpmp2mi_plan_sample_posterior_seeded": [vp, i, u64, i, i, d, ip],
+        "gpmp2mi_plan_sample_posterior_seeded_dev": [vp, i, u64, i, i, vp, vp, vp],
+        "gpmp2mi_debug_plan_seed_prior": [vp, d, d],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

@@ -245,6 +245,12 @@ struct gpmp2mi_plan {
   // marginals / sample call and kept
   void* post_ws = nullptr;
   size_t post_ws_bytes = 0;
+  // seeding (seed.hip): H_seed of the plan's linear prior graph on the host (built at the first seeded call or read-out),
+  // and on the device with its factors (uploaded and factored at the first seeded call, then kept)
+  std::vector<double> seed_Hd, seed_Ho;
+  void* seed_ws = nullptr;
+  size_t seed_ws_bytes = 0;
+  bool seed_ready = false;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -303,7 +309,8 @@ struct QueueStage {
   QueueRun q{};   // M and the ten array pointers
   size_t D = 0, tr = 0, T = 0;
   int alloc(int M, const QueueRun& io, int D_, size_t trow, int T_);
-  int upload(const QueueRun& io, size_t j, hipStream_t st) const;
+  // with_init = false: the four end arrays only (the seeded queue makes the inits on the device)
+  int upload(const QueueRun& io, size_t j, hipStream_t st, bool with_init = true) const;
   int download(const QueueRun& io, size_t j, hipStream_t st) const;
   void leak() { base = nullptr; }   // a hung kernel may still write the slab: it goes with the poisoned plan
   void release() {                  // hipFree waits for the whole device
@@ -324,6 +331,15 @@ int plan_optimize_queue(gpmp2mi_plan* p, QueueRun io, bool host, hipStream_t st)
 int plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st,
                    double* dst = nullptr, int pass = 0, bool trial = false);
 int spin_wait_flag(const volatile int* flag, bool st_valid, hipStream_t st, double timeout_s, int* count);
+
+// posterior.hip: linearize -> export -> factor-only k_posterior at the plan's current estimate on `st`; *fac: the factor
+// scratch it leaves, [B][N+1][512] (V at +0, W at +256), valid until the next posterior call on the plan
+int plan_posterior_factor(gpmp2mi_plan* p, int* ok, const double** fac, hipStream_t st);
+// seed.hip: the checks of a seeded restart call (arguments, liveness, the limits), then M restarts of problems
+// first .. first + M - 1 into `init` on `st` (device pointers; mean null: the straight line from sc to ec)
+int plan_seed_check(gpmp2mi_plan* p, int M, int first, double scale);
+int plan_seed_restarts(gpmp2mi_plan* p, int M, uint64_t seed, int first, double scale, int keep_first, const double* sc,
+                       const double* ec, const double* mean, double* init, hipStream_t st);
 
 // score.hip: the per-row outputs of a score call and the selection of a select call (any pointer may be null)
 struct ScoreOut {

@@ -154,6 +154,66 @@ static int on_shard(gpmp2mi_multi_plan* m, int k, F f) {
   return rc == GPMP2MI_OK ? rc : shard_error(m, k, rc, last_error());
 }
 
+// A queue run over the shards, the one body of the plain and the seeded entry point: the split, the staging, the run, the
+// drain after a failure and the statistics.  With `make_inits` the caller's `io.init` is null: only the four end arrays
+// are uploaded, and make_inits(k, row0, stage, extra, stream) fills shard k's staged inits on its stream; `extra` is
+// `extra_row` doubles a problem of further device staging (null when 0), freed with the rest.
+using MakeInits = std::function<int(int, int, const QueueStage&, double*, hipStream_t)>;
+static int multi_queue(gpmp2mi_multi_plan* m, const QueueRun& io, size_t extra_row, const MakeInits& make_inits) {
+  const int n = (int)m->shards.size();
+  std::vector<int> row0, rows;
+  split_rows(io.M, n, row0, rows);
+  std::vector<char> work(n);
+  for (int k = 0; k < n; k++) work[k] = rows[k] > 0;
+  DeviceGuard guard;
+  // Staging for every shard with problems, allocated before any shard starts and freed after all have joined: hipFree
+  // waits for the whole device, so it would stall the other shards there.  Leaked with a shard that timed out.
+  struct StageSet {
+    gpmp2mi_multi_plan* m;
+    std::vector<QueueStage> st;
+    std::vector<void*> extra;
+    ~StageSet() {
+      for (size_t k = 0; k < st.size(); k++) {
+        if (m->shards[k].poisoned()) {
+          st[k].leak();
+          continue;
+        }
+        if ((st[k].base || extra[k]) && hipSetDevice(m->shards[k].device) == hipSuccess) {
+          st[k].release();
+          if (extra[k]) (void)hipFree(extra[k]);
+        }
+      }
+    }
+  } stage{m, std::vector<QueueStage>(n), std::vector<void*>(n, nullptr)};
+  for (int k = 0; k < n; k++) {
+    if (!work[k]) continue;
+    G2_TRY(on_shard(m, k, [&]() -> int {
+      G2_TRY(stage.st[k].alloc(rows[k], io, m->D, m->trow(), m->T));
+      return extra_row ? dev_malloc(&stage.extra[k], rows[k] * extra_row * sizeof(double)) : GPMP2MI_OK;
+    }));
+  }
+  m->problem_set = m->optimized = m->queue_ran = false;
+  const int rc = run_shards(m, work, [&](int k) -> int {
+    const QueueStage& g = stage.st[k];
+    hipStream_t st = m->shards[k].stream;
+    G2_TRY(g.upload(io, row0[k], st, !make_inits));
+    if (make_inits) G2_TRY(make_inits(k, row0[k], g, (double*)stage.extra[k], st));
+    G2_TRY(plan_optimize_queue(m->shards[k].plan, g.q, false, st));
+    G2_TRY(g.download(io, row0[k], st));
+    G2_HIP(hipStreamSynchronize(st));
+    return GPMP2MI_OK;
+  });
+  if (rc != GPMP2MI_OK) {
+    // a shard's stream may still hold copies if it failed half-way: wait for them before the staging is freed
+    for (const MultiShard& sh : m->shards)
+      if (!sh.poisoned()) (void)hipStreamSynchronize(sh.stream);
+    return rc;
+  }
+  for (int k = 0; k < n; k++) m->shards[k].qstats = work[k] ? m->shards[k].plan->qstats : gpmp2mi_queue_stats{};
+  m->queue_ran = true;
+  return GPMP2MI_OK;
+}
+
 extern "C" {
 
 int gpmp2mi_multi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const gpmp2mi_settings* s,
@@ -324,48 +384,29 @@ int gpmp2mi_multi_plan_optimize_queue(gpmp2mi_multi_plan* m, int M, const double
   G2_MULTI_LIVE(m);
   G2_CHECK(M >= 1, GPMP2MI_ERR_INVALID, "queue: M must be >= 1");
   G2_CHECK(sc && sv && ec && ev && init, GPMP2MI_ERR_INVALID, "queue: null input");
-  const int n = (int)m->shards.size();
-  const QueueRun io{M, 0, sc, sv, ec, ev, init, traj, iters, ferr, status, trace};
-  std::vector<int> row0, rows;
-  split_rows(M, n, row0, rows);
-  std::vector<char> work(n);
-  for (int k = 0; k < n; k++) work[k] = rows[k] > 0;
-  DeviceGuard guard;
-  // Staging for every shard with problems, allocated before any shard starts and freed after all have joined: hipFree
-  // waits for the whole device, so it would stall the other shards there.  Leaked with a shard that timed out.
-  struct StageSet {
-    gpmp2mi_multi_plan* m;
-    std::vector<QueueStage> st;
-    ~StageSet() {
-      for (size_t k = 0; k < st.size(); k++) {
-        if (m->shards[k].poisoned()) st[k].leak();
-        else if (st[k].base && hipSetDevice(m->shards[k].device) == hipSuccess) st[k].release();
-      }
-    }
-  } stage{m, std::vector<QueueStage>(n)};
-  for (int k = 0; k < n; k++) {
-    if (!work[k]) continue;
-    G2_TRY(on_shard(m, k, [&] { return stage.st[k].alloc(rows[k], io, m->D, m->trow(), m->T); }));
-  }
-  m->problem_set = m->optimized = m->queue_ran = false;
-  const int rc = run_shards(m, work, [&](int k) -> int {
-    const QueueStage& g = stage.st[k];
-    hipStream_t st = m->shards[k].stream;
-    G2_TRY(g.upload(io, row0[k], st));
-    G2_TRY(plan_optimize_queue(m->shards[k].plan, g.q, false, st));
-    G2_TRY(g.download(io, row0[k], st));
-    G2_HIP(hipStreamSynchronize(st));
-    return GPMP2MI_OK;
-  });
-  if (rc != GPMP2MI_OK) {
-    // a shard's stream may still hold copies if it failed half-way: wait for them before the staging is freed
-    for (const MultiShard& sh : m->shards)
-      if (!sh.poisoned()) (void)hipStreamSynchronize(sh.stream);
-    return rc;
-  }
-  for (int k = 0; k < n; k++) m->shards[k].qstats = work[k] ? m->shards[k].plan->qstats : gpmp2mi_queue_stats{};
-  m->queue_ran = true;
-  return GPMP2MI_OK;
+  return multi_queue(m, QueueRun{M, 0, sc, sv, ec, ev, init, traj, iters, ferr, status, trace}, 0, nullptr);
+}
+
+// The queue with its initial values made on the device (include/gpmp2mi.h "seeding"): shard k draws the problems
+// first + row0 .. from the same function, so the rows are those of one plan.  The extra staging holds the rows of a
+// caller's mean.
+int gpmp2mi_multi_plan_optimize_queue_seeded(gpmp2mi_multi_plan* m, int M, uint64_t seed, int first, double scale,
+                                             int keep_first, const double* sc, const double* sv, const double* ec,
+                                             const double* ev, const double* mean, double* traj, int* iters, double* ferr,
+                                             int* status, double* trace, double* init_out) {
+  G2_MULTI_LIVE(m);
+  G2_CHECK(sc && sv && ec && ev, GPMP2MI_ERR_INVALID, "queue: null input");
+  G2_TRY(plan_seed_check(m->shards[0].plan, M, first, scale));   // the shards' plans share the setting and the robot
+  const size_t trow = m->trow();
+  return multi_queue(m, QueueRun{M, 0, sc, sv, ec, ev, nullptr, traj, iters, ferr, status, trace}, mean ? trow : 0,
+                     [&](int k, int row0, const QueueStage& g, double* dmean, hipStream_t st) -> int {
+                       const size_t bytes = (size_t)g.q.M * trow * sizeof(double);
+                       if (mean) G2_HIP(hipMemcpyAsync(dmean, mean + row0 * trow, bytes, hipMemcpyHostToDevice, st));
+                       G2_TRY(plan_seed_restarts(m->shards[k].plan, g.q.M, seed, first + row0, scale, keep_first,
+                                                 g.q.start_conf, g.q.end_conf, dmean, (double*)g.q.init, st));
+                       if (init_out) G2_HIP(hipMemcpyAsync(init_out + row0 * trow, g.q.init, bytes, hipMemcpyDeviceToHost, st));
+                       return GPMP2MI_OK;
+                     });
 }
 
 int gpmp2mi_multi_plan_queue_stats(const gpmp2mi_multi_plan* m, int shard, gpmp2mi_queue_stats* out) {

@@ -91,6 +91,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (qws) (void)hipFree(qws);
   if (score_ws) (void)hipFree(score_ws);
   if (post_ws) (void)hipFree(post_ws);
+  if (seed_ws) (void)hipFree(seed_ws);
   flags_release(qflags);
 }
 

@@ -409,13 +409,13 @@ int QueueStage::alloc(int M, const QueueRun& io, int D_, size_t trow, int T_) {
   if (io.status) q.status = i;
   return GPMP2MI_OK;
 }
-int QueueStage::upload(const QueueRun& io, size_t j, hipStream_t st) const {
+int QueueStage::upload(const QueueRun& io, size_t j, hipStream_t st, bool with_init) const {
   const size_t md = (size_t)q.M * D * sizeof(double);
   G2_HIP(hipMemcpyAsync((void*)q.start_conf, io.start_conf + j * D, md, hipMemcpyHostToDevice, st));
   G2_HIP(hipMemcpyAsync((void*)q.start_vel, io.start_vel + j * D, md, hipMemcpyHostToDevice, st));
   G2_HIP(hipMemcpyAsync((void*)q.end_conf, io.end_conf + j * D, md, hipMemcpyHostToDevice, st));
   G2_HIP(hipMemcpyAsync((void*)q.end_vel, io.end_vel + j * D, md, hipMemcpyHostToDevice, st));
-  G2_HIP(hipMemcpyAsync((void*)q.init, io.init + j * tr, q.M * tr * sizeof(double), hipMemcpyHostToDevice, st));
+  if (with_init) G2_HIP(hipMemcpyAsync((void*)q.init, io.init + j * tr, q.M * tr * sizeof(double), hipMemcpyHostToDevice, st));
   return GPMP2MI_OK;
 }
 int QueueStage::download(const QueueRun& io, size_t j, hipStream_t st) const {

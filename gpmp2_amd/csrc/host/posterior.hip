@@ -108,6 +108,12 @@ int plan_posterior_host(gpmp2mi_plan* p, const double* traj, int K, const double
 
 }  // namespace
 
+int g2::plan_posterior_factor(gpmp2mi_plan* p, int* ok, const double** fac, hipStream_t st) {
+  G2_TRY(plan_posterior_dev(p, nullptr, 0, nullptr, nullptr, nullptr, nullptr, ok, st));
+  *fac = post_ws_layout((char*)p->post_ws, p->hp).fac;
+  return GPMP2MI_OK;
+}
+
 extern "C" {
 
 int gpmp2mi_block_tridiag_marginals(int B, int nblk, int n, const double* Hdiag, const double* Hoff, double* Sdiag,

@@ -1,6 +1,8 @@
 // plan.h -- device-resident state of a batch of trajectory problems (gpmp2mi_plan) and the
 // launchers of the fused hot-path kernels (linearize_kernels.hip, plan_kernels.hip, cr_kernels.hip, dense_kernels.hip).
 #pragma once
+#include <cstdint>
+
 #include "common.h"
 #include "step_control.h"
 
@@ -226,5 +228,27 @@ struct PosteriorArgs {
   double* fac;             // [B][nblk][512] factor scratch
 };
 int launch_posterior(int B, int n, const PosteriorArgs& a, hipStream_t st);
+// seed_kernels.hip: normals of rng.h, and samples whose z is made in registers (include/gpmp2mi.h "seeding")
+struct NormalFillArgs {
+  uint64_t seed;
+  uint32_t stream;
+  int a_first, a_count, b_first, b_count, nblk, n;
+  double* out;             // [a_count][b_count][nblk][n]
+};
+int launch_normal_fill(const NormalFillArgs& a, hipStream_t st);
+struct SeedSampleArgs {
+  uint64_t seed;
+  uint32_t stream;
+  int nblk, count;         // blocks of a system; columns (restarts, or samples per system)
+  int a_first, b_first;    // shared: column s is problem (a_first + s, 0); else sample (a_first + system, b_first + s)
+  const double* fac;       // [1 or systems][nblk][512] factor scratch of a factor-only launch_posterior
+  double* out;             // shared: [count][nblk][n] = mean + scale delta; else [systems][count][nblk][n] = delta
+  // restarts (shared) only
+  double scale;
+  int keep_first, D;       // keep_first: problem 0 gets delta = 0; n = 2 D
+  const double* mean;      // [count][nblk][n], or null: the straight line from start_conf to end_conf
+  const double *start_conf, *end_conf;   // [count][D], read when mean is null
+};
+int launch_sample_seeded(int systems, int n, bool shared, const SeedSampleArgs& a, hipStream_t st);
 
 }  // namespace g2

@@ -43,7 +43,22 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_multi(lib)
     _capi.declare_score(lib)
     _capi.declare_posterior(lib)
+    _capi.declare_seed(lib)
     return lib
+
+
+def seed_inputs(D, N, start_conf, end_conf, mean, M=None):
+    """The rows of a seeded call as contiguous float64 arrays: start_conf, end_conf [M][D] (both may be None when a mean
+    is given), mean [M][N+1][2D] or None -> (M, start_conf, end_conf, mean); ValueError when they disagree on M."""
+    sc = None if start_conf is None else f64(start_conf).reshape(-1, D)
+    ec = None if end_conf is None else f64(end_conf).reshape(-1, D)
+    mu = None if mean is None else f64(mean).reshape(-1, N + 1, 2 * D)
+    if mu is None and (sc is None or ec is None):
+        raise ValueError("start_conf and end_conf are required when no mean is given")
+    counts = [x.shape[0] for x in (sc, ec, mu) if x is not None] + ([] if M is None else [int(M)])
+    if len(set(counts)) != 1 or counts[0] < 1:
+        raise ValueError(f"seeded inputs disagree on the number of problems: {counts}")
+    return counts[0], sc, ec, mu
 
 
 def queue_inputs(D, N, start_conf, start_vel, end_conf, end_vel, init):
@@ -345,6 +360,24 @@ class Engine:
                                                        iptr(ok)))
         return delta, ok
 
+    # ---------------------------------------------------------------- seeding (include/gpmp2mi.h "seeding")
+    def normal_fill(self, seed, stream, a_first, a_count, b_first, b_count, nblk, n):
+        """out [a_count][b_count][nblk][n] = normal(seed, stream, a_first + a, b_first + b, i, r): the library's counter
+        RNG (gpmp2_amd/csrc/rng.h), evaluated on the device.  stream: _capi.RNG_RESTARTS / RNG_POSTERIOR or any id < 2^24."""
+        out = np.zeros((int(a_count), int(b_count), int(nblk), int(n)))
+        self._ck(self.lib.gpmp2mi_normal_fill(int(seed), int(stream), int(a_first), int(a_count), int(b_first),
+                                              int(b_count), int(nblk), int(n), dptr(out)))
+        return out
+
+    def normal_fill_dev(self, seed, stream_id, a_first, a_count, b_first, b_count, nblk, n, out, stream=None):
+        """The same into a device buffer (a torch tensor of that shape or a raw pointer); no host synchronisation."""
+        shape = (int(a_count), int(b_count), int(nblk), int(n))
+        if out is None:
+            raise ValueError("out is required")
+        self._ck(self.lib.gpmp2mi_normal_fill_dev(int(seed), int(stream_id), int(a_first), shape[0], int(b_first),
+                                                  shape[1], shape[2], shape[3], _dev_arg("out", out, shape),
+                                                  C.c_void_p(stream or 0)))
+
     def collision_cost(self, robot, sdf, total_step, traj):
         t = f64(traj).reshape(-1, total_step + 1, 2 * robot.dof)
         cost = np.zeros(t.shape[0])
@@ -516,6 +549,78 @@ class Plan:
             args.append(C.c_void_p(int(x)))
         self.eng._ck(self.eng.lib.gpmp2mi_plan_optimize_queue_dev(self.h.ptr, M, *args, C.c_void_p(stream or 0)))
 
+    # ---- restarts drawn on the device from the GP prior (include/gpmp2mi.h "seeding")
+    def seed_restarts(self, M, seed, start_conf=None, end_conf=None, mean=None, first=0, scale=1.0, keep_first=False):
+        """init [M][N+1][2D]: problem j = first + row gets mean_j + scale * L^-T z_j, z_j from the counter RNG at
+        (seed, j); mean None: the straight line from start_conf[row] to end_conf[row] ([M][D])."""
+        M, sc, ec, mu = seed_inputs(self.D, self.N, start_conf, end_conf, mean, M)
+        init = np.zeros((M, self.N + 1, 2 * self.D))
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_seed_restarts(self.h.ptr, M, int(seed), int(first), float(scale),
+                                                             int(bool(keep_first)), dptr(sc), dptr(ec), dptr(mu),
+                                                             dptr(init)))
+        return init
+
+    def seed_restarts_dev(self, M, seed, init, start_conf=None, end_conf=None, mean=None, first=0, scale=1.0,
+                          keep_first=False, stream=None):
+        """The same on device buffers (torch tensors or raw pointers); no host synchronisation after the plan's first
+        seeded call."""
+        D, N, M = self.D, self.N, int(M)
+        if M < 1:
+            raise ValueError("M must be >= 1")
+        if init is None or (mean is None and (start_conf is None or end_conf is None)):
+            raise ValueError("init, and start_conf / end_conf unless a mean is given, are required")
+        args = [_dev_arg("start_conf", start_conf, (M, D)), _dev_arg("end_conf", end_conf, (M, D)),
+                _dev_arg("mean", mean, (M, N + 1, 2 * D)), _dev_arg("init", init, (M, N + 1, 2 * D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_seed_restarts_dev(self.h.ptr, M, int(seed), int(first), float(scale),
+                                                                 int(bool(keep_first)), *args, C.c_void_p(stream or 0)))
+
+    def optimize_queue_seeded(self, seed, start_conf, start_vel, end_conf, end_vel, mean=None, first=0, scale=1.0,
+                              keep_first=False, want_init=False):
+        """optimize_queue on M restarts made on the device (seed_restarts followed by optimize_queue, without the inits
+        crossing to the host): the result() dict with M rows, plus `init` when want_init."""
+        D, N = self.D, self.N
+        rows = [f64(x).reshape(-1, D) for x in (start_conf, start_vel, end_conf, end_vel)]
+        M, sc, ec, mu = seed_inputs(D, N, rows[0], rows[2], mean)
+        if any(x.shape[0] != M for x in rows):
+            raise ValueError(f"queue inputs disagree on the number of problems: {[x.shape[0] for x in rows]}")
+        traj = np.zeros((M, N + 1, 2 * D))
+        iters, status = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        ferr, trace = np.zeros(M), np.zeros((M, self.setting.max_iter + 1))
+        init = np.zeros((M, N + 1, 2 * D)) if want_init else None
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_optimize_queue_seeded(
+            self.h.ptr, M, int(seed), int(first), float(scale), int(bool(keep_first)), dptr(sc), dptr(rows[1]), dptr(ec),
+            dptr(rows[3]), dptr(mu), dptr(traj), iptr(iters), dptr(ferr), iptr(status), dptr(trace), dptr(init)))
+        out = dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+        if want_init:
+            out["init"] = init
+        return out
+
+    def optimize_queue_seeded_dev(self, M, seed, start_conf, start_vel, end_conf, end_vel, mean=None, traj=None,
+                                  iters=None, final_error=None, status=None, error_trace=None, init_out=None, first=0,
+                                  scale=1.0, keep_first=False, stream=None):
+        """The same on device buffers (torch tensors or raw pointers); outputs and mean may be None."""
+        D, N, T, M = self.D, self.N, self.setting.max_iter + 1, int(M)
+        if M < 1:
+            raise ValueError("M must be >= 1")
+        if any(x is None for x in (start_conf, start_vel, end_conf, end_vel)):
+            raise ValueError("start_conf, start_vel, end_conf and end_vel are required")
+        t = (M, N + 1, 2 * D)
+        args = [_dev_arg("start_conf", start_conf, (M, D)), _dev_arg("start_vel", start_vel, (M, D)),
+                _dev_arg("end_conf", end_conf, (M, D)), _dev_arg("end_vel", end_vel, (M, D)), _dev_arg("mean", mean, t),
+                _dev_arg("traj", traj, t), _dev_arg("iters", iters, (M,), True),
+                _dev_arg("final_error", final_error, (M,)), _dev_arg("status", status, (M,), True),
+                _dev_arg("error_trace", error_trace, (M, T)), _dev_arg("init_out", init_out, t)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_optimize_queue_seeded_dev(
+            self.h.ptr, M, int(seed), int(first), float(scale), int(bool(keep_first)), *args, C.c_void_p(stream or 0)))
+
+    def seed_prior(self):
+        """(Hdiag [N+1][2D][2D], Hoff [N][2D][2D] = block (i+1, i)): the precision H_seed the restarts are drawn from
+        (gpmp2mi_debug_plan_seed_prior)."""
+        n, nb = 2 * self.D, self.N + 1
+        Hd, Ho = np.zeros((nb, n, n)), np.zeros((nb - 1, n, n))
+        self.eng._ck(self.eng.lib.gpmp2mi_debug_plan_seed_prior(self.h.ptr, dptr(Hd), dptr(Ho)))
+        return Hd, Ho
+
     def queue_stats(self):
         """of the last queue run: passes, slot_passes (B * passes), busy_slot_passes (slots that held a problem)."""
         st = _capi.QueueStats()
@@ -620,6 +725,28 @@ class Plan:
             raise ValueError("z and delta are required")
         args = [_dev_arg("z", z, (B, K, nb, n)), _dev_arg("delta", delta, (B, K, nb, n)), _dev_arg("ok", ok, (B,), True)]
         self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_posterior_dev(self.h.ptr, K, *args, C.c_void_p(stream or 0)))
+
+    def sample_posterior_seeded(self, K, seed, row_first=0, sample_first=0):
+        """sample_posterior with z made on the device: (delta [B][K][N+1][2D], ok [B]); z of (row b, sample s) is the
+        counter RNG at (seed, row_first + b, sample_first + s)."""
+        B, n, nb, K = self.B, 2 * self.D, self.N + 1, int(K)
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        delta, ok = np.zeros((B, K, nb, n)), np.zeros(B, dtype=np.int32)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_posterior_seeded(self.h.ptr, K, int(seed), int(row_first),
+                                                                       int(sample_first), dptr(delta), iptr(ok)))
+        return delta, ok
+
+    def sample_posterior_seeded_dev(self, K, seed, delta, ok=None, row_first=0, sample_first=0, stream=None):
+        """The same into device buffers: delta [B][K][N+1][2D], ok int32 [B] or None; no host synchronisation."""
+        B, n, nb, K = self.B, 2 * self.D, self.N + 1, int(K)
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        if delta is None:
+            raise ValueError("delta is required")
+        args = [_dev_arg("delta", delta, (B, K, nb, n)), _dev_arg("ok", ok, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_posterior_seeded_dev(
+            self.h.ptr, K, int(seed), int(row_first), int(sample_first), *args, C.c_void_p(stream or 0)))
 
     # ---- incremental replanning (ISAM2TrajOptimizer's role; see include/gpmp2mi.h)
     def fix_state(self, b, state_idx, conf, vel):
@@ -745,6 +872,26 @@ class MultiPlan:
                                                                     dptr(t), dptr(traj), iptr(iters), dptr(ferr),
                                                                     iptr(status), dptr(trace)))
         return dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+
+    def optimize_queue_seeded(self, seed, start_conf, start_vel, end_conf, end_vel, mean=None, first=0, scale=1.0,
+                              keep_first=False, want_init=False):
+        """Plan.optimize_queue_seeded split over the shards: the same rows as one plan returns."""
+        D, N = self.D, self.N
+        rows = [f64(x).reshape(-1, D) for x in (start_conf, start_vel, end_conf, end_vel)]
+        M, sc, ec, mu = seed_inputs(D, N, rows[0], rows[2], mean)
+        if any(x.shape[0] != M for x in rows):
+            raise ValueError(f"queue inputs disagree on the number of problems: {[x.shape[0] for x in rows]}")
+        traj = np.zeros((M, N + 1, 2 * D))
+        iters, status = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        ferr, trace = np.zeros(M), np.zeros((M, self.T))
+        init = np.zeros((M, N + 1, 2 * D)) if want_init else None
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_optimize_queue_seeded(
+            self.h.ptr, M, int(seed), int(first), float(scale), int(bool(keep_first)), dptr(sc), dptr(rows[1]), dptr(ec),
+            dptr(rows[3]), dptr(mu), dptr(traj), iptr(iters), dptr(ferr), iptr(status), dptr(trace), dptr(init)))
+        out = dict(traj=traj, iters=iters, final_error=ferr, status=status, error_trace=trace)
+        if want_init:
+            out["init"] = init
+        return out
 
     def score(self, inter_step, out=None):
         """Plan.score over all shards, rows in batch order."""

@@ -238,7 +238,8 @@ void gpmp2mi_graph_opts_default(gpmp2mi_graph_opts* o);
  * optimizer loop planner/BatchTrajOptimizer.cpp:212-308) for B independent problems sharing one
  * robot, one SDF and one setting.  The plan owns all device workspace; nothing is allocated in
  * the optimize call, so it can be enqueued repeatedly (receding horizon).  (The scoring calls take their workspace
- * at their first use for an inter_step and keep it: see "scoring" below.) */
+ * at their first use for an inter_step and keep it: see "scoring" below; so do the posterior calls and the seeded
+ * calls at their first use: see "posterior" and "seeding".) */
 typedef struct gpmp2mi_plan gpmp2mi_plan;
 int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
                         const gpmp2mi_settings* setting, const gpmp2mi_graph_opts* opts /*NULL ok*/,
@@ -627,6 +628,73 @@ int gpmp2mi_plan_marginals_dev(gpmp2mi_plan* p, double* Sdiag, double* Soff, int
  * trajectory (vector-space robots: estimate + delta) */
 int gpmp2mi_plan_sample_posterior(gpmp2mi_plan* p, int K, const double* z, double* delta, int* ok);
 int gpmp2mi_plan_sample_posterior_dev(gpmp2mi_plan* p, int K, const double* z, double* delta, int* ok, void* stream);
+
+/* ---- seeding: restarts and samples from a counter RNG, on the device ------------------------------------
+ * The random function.  normal(seed, stream, a, b, i, r) is a standard normal that is a pure function of its arguments
+ * (gpmp2_amd/csrc/rng.h states it once, for the kernels and for a host compiler alike): Philox4x32-10 keyed by the 64-bit
+ * seed on the counter (a, b, i, stream << 8 | pair), Box-Muller in fp64 on the two 53-bit uniforms of a block;
+ * coordinates r and r + 4 (bit 2 of r clear) are the cosine and sine member of one pair; r = 0..15, stream < 2^24.
+ * Every value is finite, |z| <= 8.57.  `stream` separates the uses: the library draws restarts from
+ * GPMP2MI_RNG_RESTARTS and posterior samples from GPMP2MI_RNG_POSTERIOR.
+ * Determinism: a problem's numbers depend on (seed, problem index) alone -- not on M, B, the slot, the shard, or the
+ * entry point that asked.
+ *
+ * out [a_count][b_count][nblk][n] = normal(seed, stream, a_first + a, b_first + b, i, r), n = 1..16. */
+enum { GPMP2MI_RNG_RESTARTS = 1, GPMP2MI_RNG_POSTERIOR = 2 };
+int gpmp2mi_normal_fill(uint64_t seed, int stream, int a_first, int a_count, int b_first, int b_count, int nblk, int n,
+                        double* out);   /* host out; runs on the device */
+int gpmp2mi_normal_fill_dev(uint64_t seed, int stream, int a_first, int a_count, int b_first, int b_count, int nblk,
+                            int n, double* out, void* hip_stream);
+/* Restarts from the GP prior.  Problem j = first + row (row < M) gets
+ *     init_j = mean_j + scale * L^-T z_j,     z_j[i][r] = normal(seed, GPMP2MI_RNG_RESTARTS, j, 0, i, r),
+ * H_seed = L L^T the block-tridiagonal precision of the plan's LINEAR PRIOR GRAPH: the PriorFactors on x_0, v_0, x_N, v_N
+ * (conf_prior_sigma, vel_prior_sigma) and the N GaussianProcessPriorLinear factors (Qc, delta_t = total_time / N).
+ * Both end priors are always in it; end_conf_prior_off, obstacle, limit, workspace and self-collision factors are not:
+ * it is a proposal (smooth trajectories pinned at both ends, velocities consistent with positions), not the posterior.
+ * keep_first != 0: problem j == 0 gets exactly its mean.  mean [M][N+1][2D], or NULL: the straight line of
+ * gpmp2::initArmTrajStraightLine from start_conf[row] to end_conf[row] ([M][D]), bit for bit.  init [M][N+1][2D].
+ * H_seed does not depend on the problem: it is built on the host, uploaded and factored once per plan at the first
+ * seeded call (which therefore waits for its stream once), and kept with the plan -- with the scoring and posterior
+ * workspaces the third exception to "nothing is allocated after gpmp2mi_plan_create": 2 (2D)^2 + 512 doubles per state.
+ * The queue forms make the M inits on the device and run gpmp2mi_plan_optimize_queue(_dev) on them: the results equal
+ * seed_restarts followed by optimize_queue, the refusals are those of optimize_queue; init_out ([M][N+1][2D], NULL ok)
+ * receives the inits.  Shard k of a multi plan draws problems first + row_begin_k .., so a multi plan returns what one
+ * plan returns.
+ * Errors: GPMP2MI_ERR_INVALID for a NULL plan or required pointer (start_conf / end_conf may be NULL for seed_restarts
+ * when a mean is given), M < 1, first < 0, a negative or non-finite scale; GPMP2MI_ERR_UNSUPPORTED for 2D > 15 (one
+ * 16 x 16 tile per block) and for the Pose2 robot kinds (a bridge in the tangent space is not built);
+ * GPMP2MI_ERR_TIMEOUT for a poisoned plan, before anything is enqueued.  The `_dev` forms take device pointers and
+ * enqueue on `stream`; seed_restarts_dev returns without a host synchronisation (after the plan's first seeded call). */
+int gpmp2mi_plan_seed_restarts(gpmp2mi_plan* p, int M, uint64_t seed, int first, double scale, int keep_first,
+                               const double* start_conf, const double* end_conf, const double* mean /*NULL ok*/,
+                               double* init);
+int gpmp2mi_plan_seed_restarts_dev(gpmp2mi_plan* p, int M, uint64_t seed, int first, double scale, int keep_first,
+                                   const double* start_conf, const double* end_conf, const double* mean /*NULL ok*/,
+                                   double* init, void* stream);
+int gpmp2mi_plan_optimize_queue_seeded(gpmp2mi_plan* p, int M, uint64_t seed, int first, double scale, int keep_first,
+                                       const double* start_conf, const double* start_vel, const double* end_conf,
+                                       const double* end_vel, const double* mean /*NULL ok*/, double* traj, int* iters,
+                                       double* final_error, int* status, double* error_trace,
+                                       double* init_out /*NULL ok*/);
+int gpmp2mi_plan_optimize_queue_seeded_dev(gpmp2mi_plan* p, int M, uint64_t seed, int first, double scale,
+                                           int keep_first, const double* start_conf, const double* start_vel,
+                                           const double* end_conf, const double* end_vel, const double* mean /*NULL ok*/,
+                                           double* traj, int* iters, double* final_error, int* status,
+                                           double* error_trace, double* init_out /*NULL ok*/, void* stream);
+int gpmp2mi_multi_plan_optimize_queue_seeded(gpmp2mi_multi_plan* m, int M, uint64_t seed, int first, double scale,
+                                             int keep_first, const double* start_conf, const double* start_vel,
+                                             const double* end_conf, const double* end_vel,
+                                             const double* mean /*NULL ok*/, double* traj, int* iters,
+                                             double* final_error, int* status, double* error_trace,
+                                             double* init_out /*NULL ok*/);
+/* gpmp2mi_plan_sample_posterior with z made in registers: delta [B][K][N+1][2D] = L^-T z at the current estimate,
+ * z of (row b, sample s) = normal(seed, GPMP2MI_RNG_POSTERIOR, row_first + b, sample_first + s, i, r); one wavefront
+ * per (16 samples, row).  ok [B] may be NULL.  Errors as above, and GPMP2MI_ERR_INVALID for K < 1, negative row_first /
+ * sample_first, or before gpmp2mi_plan_set_problem.  The optimizer's state is not touched. */
+int gpmp2mi_plan_sample_posterior_seeded(gpmp2mi_plan* p, int K, uint64_t seed, int row_first, int sample_first,
+                                         double* delta, int* ok);
+int gpmp2mi_plan_sample_posterior_seeded_dev(gpmp2mi_plan* p, int K, uint64_t seed, int row_first, int sample_first,
+                                             double* delta, int* ok, void* stream);
 
 /* ---- misc ---------------------------------------------------------------------------------- */
 const char* gpmp2mi_last_error(void);  /* thread-local message of the last failing call */

@@ -43,6 +43,10 @@ int gpmp2mi_debug_replica_counts(long* robots, long* sdfs);
  * that thread's current device in *current (multi-plan calls must leave it as they found it). */
 int gpmp2mi_debug_current_device(int set_to, int* current);
 
+/* Test hook: the precision H_seed of the plan's linear prior graph as the plan built it for the seeded calls
+ * (include/gpmp2mi.h "seeding"): Hdiag [N+1][2D][2D], Hoff [N][2D][2D] = block (i+1, i).  Either may be NULL. */
+int gpmp2mi_debug_plan_seed_prior(gpmp2mi_plan* p, double* Hdiag, double* Hoff);
+
 /* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
 int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);
 /* Diagnostic: scalars of trajectory b's last LM / Dogleg trial step, out17 = {g.delta, |delta|^2, g.g, g^T H g,

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <array>
 #include <cstddef>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -748,6 +749,113 @@ inline TrajectoryCovariance TrajectoryMarginals(const ROBOT& robot, const SDF& s
   return out;
 }
 
+/// Seeding on the device (include/gpmp2mi.h "seeding").  Not in the reference, where restarts are the caller's business.
+/// out [a_count][b_count][nblk][n] of the library's counter RNG: normal(seed, stream, a_first + a, b_first + b, i, r)
+inline Vector NormalFill(std::uint64_t seed, int stream, int a_first, int a_count, int b_first, int b_count, int nblk, int n) {
+  Vector out(static_cast<std::size_t>(a_count) * b_count * nblk * n);
+  check(gpmp2mi_normal_fill(seed, stream, a_first, a_count, b_first, b_count, nblk, n, out.data()), "gpmp2mi_normal_fill");
+  return out;
+}
+/// M restarts from start_conf to end_conf and what the optimizer made of them: restart j = first + row starts from the
+/// straight line plus scale * (a draw from the plan's GP-prior bridge, a function of (seed, j) alone); keep_first:
+/// restart 0 is the straight line itself.  `init` is filled by SeedRestarts and, on request, by BatchTrajOptimizeSeeded.
+struct SeededRestarts {
+  std::vector<Trajectory> init, traj;
+  std::vector<int> iterations, status;
+  Vector final_error;
+};
+namespace internal {
+inline std::vector<Trajectory> split_rows(const Vector& flat, std::size_t M, std::size_t dof, std::size_t total_step) {
+  const std::size_t T = (total_step + 1) * 2 * dof;
+  std::vector<Trajectory> out(M, Trajectory(dof, total_step));
+  for (std::size_t m = 0; m < M; m++) std::copy(flat.begin() + m * T, flat.begin() + (m + 1) * T, out[m].data.begin());
+  return out;
+}
+inline Vector repeat_rows(const Vector& v, std::size_t M) {
+  Vector out(M * v.size());
+  for (std::size_t m = 0; m < M; m++) std::copy(v.begin(), v.end(), out.begin() + m * v.size());
+  return out;
+}
+}  // namespace internal
+/// ROBOT: a vector-space robot model of at most 7 dof (others throw); SDF: SignedDistanceField or PlanarSDF.
+template <class ROBOT, class SDF>
+inline std::vector<Trajectory> SeedRestarts(const ROBOT& robot, const SDF& sdf, const Vector& start_conf,
+                                            const Vector& end_conf, const TrajOptimizerSetting& setting, std::size_t M,
+                                            std::uint64_t seed, double scale = 1.0, bool keep_first = true, int first = 0) {
+  if (start_conf.size() != robot.dof() || end_conf.size() != robot.dof())
+    throw std::runtime_error("[SeedRestarts] vector dim does not fit dof");
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, 1, &plan), "gpmp2mi_plan_create");
+  const Vector sc = internal::repeat_rows(start_conf, M), ec = internal::repeat_rows(end_conf, M);
+  Vector init(M * (setting.total_step + 1) * 2 * robot.dof());
+  const int rc = gpmp2mi_plan_seed_restarts(plan, static_cast<int>(M), seed, first, scale, keep_first ? 1 : 0, sc.data(),
+                                            ec.data(), nullptr, init.data());
+  gpmp2mi_plan_destroy(plan);
+  check(rc, "gpmp2mi_plan_seed_restarts");
+  return internal::split_rows(init, M, robot.dof(), setting.total_step);
+}
+/// The M restarts through a plan of `slots` slots (gpmp2mi_plan_optimize_queue_seeded): no trajectory crosses to the
+/// device.  The rows equal SeedRestarts followed by one BatchTrajOptimize per row.
+template <class ROBOT, class SDF>
+inline SeededRestarts BatchTrajOptimizeSeeded(const ROBOT& robot, const SDF& sdf, const Vector& start_conf,
+                                              const Vector& start_vel, const Vector& end_conf, const Vector& end_vel,
+                                              const TrajOptimizerSetting& setting, std::size_t M, std::size_t slots,
+                                              std::uint64_t seed, double scale = 1.0, bool keep_first = true,
+                                              bool want_init = false, int first = 0) {
+  for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+    if (v->size() != robot.dof()) throw std::runtime_error("[BatchTrajOptimizeSeeded] vector dim does not fit dof");
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, static_cast<int>(slots), &plan), "gpmp2mi_plan_create");
+  const Vector sc = internal::repeat_rows(start_conf, M), sv = internal::repeat_rows(start_vel, M),
+               ec = internal::repeat_rows(end_conf, M), ev = internal::repeat_rows(end_vel, M);
+  const std::size_t T = (setting.total_step + 1) * 2 * robot.dof();
+  Vector traj(M * T), init(want_init ? M * T : 0);
+  SeededRestarts out;
+  out.iterations.assign(M, 0);
+  out.status.assign(M, 0);
+  out.final_error.assign(M, 0.0);
+  const int rc = gpmp2mi_plan_optimize_queue_seeded(plan, static_cast<int>(M), seed, first, scale, keep_first ? 1 : 0,
+                                                    sc.data(), sv.data(), ec.data(), ev.data(), nullptr, traj.data(),
+                                                    out.iterations.data(), out.final_error.data(), out.status.data(),
+                                                    nullptr, want_init ? init.data() : nullptr);
+  gpmp2mi_plan_destroy(plan);
+  check(rc, "gpmp2mi_plan_optimize_queue_seeded");
+  out.traj = internal::split_rows(traj, M, robot.dof(), setting.total_step);
+  if (want_init) out.init = internal::split_rows(init, M, robot.dof(), setting.total_step);
+  return out;
+}
+/// K perturbations delta ~ N(0, Sigma) of `result` (TrajectoryMarginals' Sigma), drawn on the device: sample s is a
+/// function of (seed, sample_first + s) alone.  result + delta is a trajectory drawn from the posterior.
+template <class ROBOT, class SDF>
+inline std::vector<Trajectory> TrajectoryPosteriorSamples(const ROBOT& robot, const SDF& sdf, const Trajectory& result,
+                                                          const Vector& start_conf, const Vector& start_vel,
+                                                          const Vector& end_conf, const Vector& end_vel,
+                                                          const TrajOptimizerSetting& setting, std::size_t K,
+                                                          std::uint64_t seed, int sample_first = 0) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[TrajectoryPosteriorSamples] result does not match dof / total_step");
+  for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+    if (v->size() != robot.dof()) throw std::runtime_error("[TrajectoryPosteriorSamples] vector dim does not fit dof");
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, 1, &plan), "gpmp2mi_plan_create");
+  Vector delta(K * result.data.size());
+  int ok = 0;
+  int rc = gpmp2mi_plan_set_problem(plan, start_conf.data(), start_vel.data(), end_conf.data(), end_vel.data(),
+                                    result.data.data());
+  const char* what = "gpmp2mi_plan_set_problem";
+  if (!rc) {
+    rc = gpmp2mi_plan_sample_posterior_seeded(plan, static_cast<int>(K), seed, 0, sample_first, delta.data(), &ok);
+    what = "gpmp2mi_plan_sample_posterior_seeded";
+  }
+  gpmp2mi_plan_destroy(plan);
+  check(rc, what);
+  if (!ok) throw std::runtime_error("[gpmp2mi] IndeterminantLinearSystemException");
+  return internal::split_rows(delta, K, robot.dof(), setting.total_step);
+}
+
 /// B independent BatchTrajOptimize problems of one robot, field and setting, sharded over several GPUs of this process
 /// (gpmp2mi_multi_plan, include/gpmp2mi.h): shard k of `devices` holds a contiguous share of the rows, repeats allowed.
 /// The robot model and the field must outlive the planner.  Not in the reference (one problem per call there).
@@ -802,6 +910,28 @@ class MultiDeviceBatchPlanner {
           "gpmp2mi_multi_plan_get_result");
     std::vector<Trajectory> out(B_, Trajectory(D, setting_.total_step));
     for (std::size_t b = 0; b < B_; b++) std::copy(traj.begin() + b * T, traj.begin() + (b + 1) * T, out[b].data.begin());
+    return out;
+  }
+  /// BatchTrajOptimizeSeeded over the shards (gpmp2mi_multi_plan_optimize_queue_seeded): M restarts of one problem, the
+  /// rows those of one plan
+  SeededRestarts optimizeSeeded(const Vector& start_conf, const Vector& start_vel, const Vector& end_conf,
+                                const Vector& end_vel, std::size_t M, std::uint64_t seed, double scale = 1.0,
+                                bool keep_first = true, int first = 0) {
+    for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+      if (v->size() != dof_) throw std::runtime_error("[MultiDeviceBatchPlanner] vector dim does not fit dof");
+    const Vector sc = internal::repeat_rows(start_conf, M), sv = internal::repeat_rows(start_vel, M),
+                 ec = internal::repeat_rows(end_conf, M), ev = internal::repeat_rows(end_vel, M);
+    Vector traj(M * (setting_.total_step + 1) * 2 * dof_);
+    SeededRestarts out;
+    out.iterations.assign(M, 0);
+    out.status.assign(M, 0);
+    out.final_error.assign(M, 0.0);
+    check(gpmp2mi_multi_plan_optimize_queue_seeded(plan_, static_cast<int>(M), seed, first, scale, keep_first ? 1 : 0,
+                                                   sc.data(), sv.data(), ec.data(), ev.data(), nullptr, traj.data(),
+                                                   out.iterations.data(), out.final_error.data(), out.status.data(),
+                                                   nullptr, nullptr),
+          "gpmp2mi_multi_plan_optimize_queue_seeded");
+    out.traj = internal::split_rows(traj, M, dof_, setting_.total_step);
     return out;
   }
   /// of the last optimize, per problem: GTSAM iterations() and GPMP2MI_TRAJ_* status

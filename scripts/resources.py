@@ -1,6 +1,6 @@
 """Build-time resource table of every shipped kernel: VGPRs, SGPRs, spills, scratch, LDS, occupancy, as the compiler
 reports them (hipcc -Rpass-analysis=kernel-resource-usage on the product sources with the product flags).
-usage: python scripts/resources.py > profiles/rNN_resources.txt        (compiles the eight .hip files with kernels, a few minutes)"""
+usage: python scripts/resources.py > profiles/rNN_resources.txt        (compiles the .hip files with kernels, a few minutes)"""
 import concurrent.futures
 import os
 import re
@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "gpmp2_amd", "csrc")
 FILES = ["host/debug.hip", "sdf_kernels.hip", "factor_kernels.hip", "linearize_kernels.hip", "plan_kernels.hip", "cr_kernels.hip", "dense_kernels.hip",
-         "score_kernels.hip"]
+         "score_kernels.hip", "posterior_kernels.hip", "seed_kernels.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage", "-c"]
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]",
         "Occupancy [waves/SIMD]"]
