@@ -162,6 +162,25 @@ def declare_posterior(lib):
         getattr(lib, name).restype = i
 
 
+def declare_risk(lib):
+    """argtypes of the entry points of the posterior on the executed timeline (include/gpmp2mi.h); the `_dev` forms take
+    device addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_gp_interpolate_cov": [i, d, f, i, i, i, d, d, d],
+        "gpmp2mi_gp_interpolate_cov_dev": [i, vp, f, i, i, i, vp, vp, vp, vp],
+        "gpmp2mi_risk_traj": [vp, vp, d, f, i, i, i, d, d, d, ip, f, d, ip, d, ip, d],
+        "gpmp2mi_risk_traj_dev": [vp, vp, vp, f, i, i, i, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, vp],
+        "gpmp2mi_plan_marginals_dense": [vp, i, d, ip],
+        "gpmp2mi_plan_marginals_dense_dev": [vp, i, vp, vp, vp],
+        "gpmp2mi_plan_risk": [vp, i, f, d, ip, d, ip, d, ip],
+        "gpmp2mi_plan_risk_dev": [vp, i, f, vp, vp, vp, vp, vp, vp, vp],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 RNG_RESTARTS, RNG_POSTERIOR = 1, 2
 
 

@@ -251,6 +251,13 @@ struct gpmp2mi_plan {
   void* seed_ws = nullptr;
   size_t seed_ws_bytes = 0;
   bool seed_ready = false;
+  // posterior on the executed timeline (risk.hip): the band of Sigma, ok and the records of k_risk, taken at the first
+  // marginals_dense / risk call and kept (grown when a later inter_step needs more records); Qc of the setting, on the
+  // host from creation and on the device from that first call
+  void* risk_ws = nullptr;
+  size_t risk_ws_bytes = 0;
+  std::vector<double> Qc;
+  double* risk_qc = nullptr;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -335,6 +342,10 @@ int spin_wait_flag(const volatile int* flag, bool st_valid, hipStream_t st, doub
 // posterior.hip: linearize -> export -> factor-only k_posterior at the plan's current estimate on `st`; *fac: the factor
 // scratch it leaves, [B][N+1][512] (V at +0, W at +256), valid until the next posterior call on the plan
 int plan_posterior_factor(gpmp2mi_plan* p, int* ok, const double** fac, hipStream_t st);
+// the state rules of the plan posterior calls (null, poisoned, no problem, blocks wider than one tile), and the band of
+// Sigma at the current estimate into device arrays on `st` (risk.hip: the plan's band workspace)
+int plan_posterior_check(gpmp2mi_plan* p);
+int plan_posterior_band(gpmp2mi_plan* p, double* Sd, double* So, int* ok, hipStream_t st);
 // seed.hip: the checks of a seeded restart call (arguments, liveness, the limits), then M restarts of problems
 // first .. first + M - 1 into `init` on `st` (device pointers; mean null: the straight line from sc to ec)
 int plan_seed_check(gpmp2mi_plan* p, int M, int first, double scale);

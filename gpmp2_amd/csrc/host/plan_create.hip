@@ -92,6 +92,8 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (score_ws) (void)hipFree(score_ws);
   if (post_ws) (void)hipFree(post_ws);
   if (seed_ws) (void)hipFree(seed_ws);
+  if (risk_ws) (void)hipFree(risk_ws);
+  if (risk_qc) (void)hipFree(risk_qc);
   flags_release(qflags);
 }
 
@@ -446,6 +448,9 @@ int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf
   G2_HIP(hipGetDevice(&p->device));
   G2_TRY(fill_params(robot->h, s, o, F, B, p->hp));
   p->n_active_len = p->hp.max_pass;
+  p->Qc.assign((size_t)D * D, 0.0);
+  for (int i = 0; i < D; i++) p->Qc[(size_t)i * D + i] = 1.0;
+  if (s->Qc) std::copy(s->Qc, s->Qc + (size_t)D * D, p->Qc.begin());
   ExtrasHost hx;
   G2_TRY(check_extras(robot->h, o, p->hp.N, p->ex, hx));
   p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0;

@@ -114,6 +114,11 @@ int g2::plan_posterior_factor(gpmp2mi_plan* p, int* ok, const double** fac, hipS
   return GPMP2MI_OK;
 }
 
+int g2::plan_posterior_check(gpmp2mi_plan* p) { return check_plan(p); }
+int g2::plan_posterior_band(gpmp2mi_plan* p, double* Sd, double* So, int* ok, hipStream_t st) {
+  return plan_posterior_dev(p, nullptr, 0, nullptr, Sd, So, nullptr, ok, st);
+}
+
 extern "C" {
 
 int gpmp2mi_block_tridiag_marginals(int B, int nblk, int n, const double* Hdiag, const double* Hoff, double* Sdiag,

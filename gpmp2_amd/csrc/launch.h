@@ -72,4 +72,27 @@ int launch_score(const RobotDev& h, const RobotDev* R, const SdfDev& s, double d
                  const double* traj, ScoreRec* recs, hipStream_t st);
 int launch_score_finish(const ScoreFinish& a, hipStream_t st);
 
+// risk_kernels.hip
+// what one workgroup of k_risk leaves for k_risk_finish; k = s = INT_MAX: no pair of the tile was in range
+struct RiskRec {
+  double c, sigma;   // the smallest clearance - kappa sigma of the tile, and sigma at that pair
+  int k, s, oor, pad;
+};
+// arguments of k_risk_finish; every output may be null
+struct RiskFinish {
+  int B, nblk;
+  const RiskRec* recs;   // [B][nblk]
+  const int* ok;         // null: every row is fine
+  double *robust, *sigma_worst;
+  int *worst, *oor;
+};
+// Sd [B][N+1][n][n], So [B][N][n][n] -> cov [B][N (inter + 1) + 1][n][n], n = 2 D; Qc [D][D] or null (identity)
+int launch_gp_interp_cov(int D, const double* Qc, double dt, int inter, int B, int N, const double* Sd, const double* So,
+                         double* cov, hipStream_t st);
+// records per row: score_blocks.  sigma: [B][Md][S] or null
+int launch_risk(const RobotDev& h, const RobotDev* R, const SdfDev& s, const double* Qc, double dt, int inter, int B,
+                int N, double kappa, const double* traj, const double* Sd, const double* So, const int* ok, double* sigma,
+                RiskRec* recs, hipStream_t st);
+int launch_risk_finish(const RiskFinish& a, hipStream_t st);
+
 }  // namespace g2

@@ -43,6 +43,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_multi(lib)
     _capi.declare_score(lib)
     _capi.declare_posterior(lib)
+    _capi.declare_risk(lib)
     _capi.declare_seed(lib)
     return lib
 
@@ -104,6 +105,35 @@ def _score_args(inter_step):
 def _score_ptrs(o):
     return (dptr(o["support_cost"]), dptr(o["dense_cost"]), dptr(o["min_clearance"]), iptr(o["worst"]),
             iptr(o["out_of_range"]))
+
+
+def _kappa_arg(kappa):
+    kappa = float(kappa)
+    if not (np.isfinite(kappa) and kappa >= 0.0):
+        raise ValueError("kappa must be finite and >= 0")
+    return kappa
+
+
+def band_inputs(D, Sdiag, Soff, Qc=None):
+    """The band of a posterior as contiguous float64 arrays: Sdiag [B][N+1][2D][2D], Soff [B][N][2D][2D] (one row may
+    come without the batch axis), Qc [D][D] or None -> (B, N, Sdiag, Soff, Qc); ValueError when the shapes disagree."""
+    n = 2 * int(D)
+    Sd, So = f64(Sdiag), f64(Soff)
+    if Sd.ndim == 3:
+        Sd = Sd.reshape((1,) + Sd.shape)
+    if So.ndim == 3:
+        So = So.reshape((1,) + So.shape)
+    if Sd.ndim != 4 or Sd.shape[1] < 2 or Sd.shape[2:] != (n, n):
+        raise ValueError(f"Sdiag: expected [B][N+1][{n}][{n}] with N >= 1, got {list(Sd.shape)}")
+    B, N = Sd.shape[0], Sd.shape[1] - 1
+    if So.shape != (B, N, n, n):
+        raise ValueError(f"Soff: expected [{B}][{N}][{n}][{n}], got {list(So.shape)}")
+    q = None
+    if Qc is not None:
+        q = f64(Qc)
+        if q.shape != (D, D):
+            raise ValueError(f"Qc: expected [{D}][{D}], got {list(q.shape)}")
+    return B, N, Sd, So, q
 
 
 def multi_plan_args(B, devices):
@@ -359,6 +389,45 @@ class Engine:
         self._ck(self.lib.gpmp2mi_block_tridiag_sample(B, nblk, n, z.shape[1], dptr(Hd), dptr(Ho), dptr(z), dptr(delta),
                                                        iptr(ok)))
         return delta, ok
+
+    # ------------------------------------------- the posterior on the executed timeline (include/gpmp2mi.h)
+    def gp_interpolate_cov(self, dof, Qc, delta_t, inter_step, Sdiag, Soff):
+        """The band of a posterior, Sdiag [B][N+1][2D][2D] and Soff [B][N][2D][2D] = block (i+1, i), carried to the
+        Md = N (inter_step + 1) + 1 checked states: cov [B][Md][2D][2D], exactly symmetric, support states copied.
+        Qc [D][D] or None (identity).  ValueError for mis-shaped arrays."""
+        dof, inter_step = int(dof), _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N, Sd, So, q = band_inputs(dof, Sdiag, Soff, Qc)
+        cov = np.zeros((B, scoring.checked_states(N, inter_step), 2 * dof, 2 * dof))
+        self._ck(self.lib.gpmp2mi_gp_interpolate_cov(dof, dptr(q), float(delta_t), inter_step, B, N, dptr(Sd), dptr(So),
+                                                     dptr(cov)))
+        return cov
+
+    def risk_traj(self, robot, sdf, Qc, delta_t, inter_step, traj, Sdiag, Soff, kappa, ok=None, want_sigma=True):
+        """traj [B][N+1][2D] with the band of its posterior -> dict(robust_clearance [B] = min over the in-range pairs
+        of clearance - kappa sigma, worst [B][2] = (checked state, sphere), sigma_worst [B], out_of_range [B],
+        sigma [B][Md][S] or None); ok [B] or None: rows with ok == 0 answer NaN.  ValueError for mis-shaped arrays."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step, kappa = _score_args(inter_step), _kappa_arg(kappa)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N, Sd, So, q = band_inputs(robot.dof, Sdiag, Soff, Qc)
+        if t.shape[0] != B or t.shape[1] != N + 1:
+            raise ValueError(f"traj: expected [{B}][{N + 1}][{2 * robot.dof}] to fit the band, got {list(t.shape)}")
+        k = None
+        if ok is not None:
+            k = np.ascontiguousarray(ok, dtype=np.int32)
+            if k.shape != (B,):
+                raise ValueError(f"ok: expected [{B}], got {list(k.shape)}")
+        Md = scoring.checked_states(N, inter_step)
+        o = dict(robust_clearance=np.zeros(B), worst=np.zeros((B, 2), dtype=np.int32), sigma_worst=np.zeros(B),
+                 out_of_range=np.zeros(B, dtype=np.int32), sigma=np.zeros((B, Md, robot.S)) if want_sigma else None)
+        self._ck(self.lib.gpmp2mi_risk_traj(robot.ptr, sdf.ptr, dptr(q), float(delta_t), inter_step, B, N, dptr(t),
+                                            dptr(Sd), dptr(So), iptr(k), kappa, dptr(o["robust_clearance"]),
+                                            iptr(o["worst"]), dptr(o["sigma_worst"]), iptr(o["out_of_range"]),
+                                            dptr(o["sigma"])))
+        return o
 
     # ---------------------------------------------------------------- seeding (include/gpmp2mi.h "seeding")
     def normal_fill(self, seed, stream, a_first, a_count, b_first, b_count, nblk, n):
@@ -704,6 +773,47 @@ class Plan:
         args = [_dev_arg("Sdiag", Sdiag, (B, nb, n, n)), _dev_arg("Soff", Soff, (B, nb - 1, n, n)),
                 _dev_arg("ok", ok, (B,), True)]
         self.eng._ck(self.eng.lib.gpmp2mi_plan_marginals_dev(self.h.ptr, *args, C.c_void_p(stream or 0)))
+
+    # ---- the posterior on the executed timeline (include/gpmp2mi.h)
+    def marginals_dense(self, inter_step):
+        """The posterior at the current estimate carried to the Md = N (inter_step + 1) + 1 checked states:
+        dict(cov [B][Md][2D][2D], ok [B])."""
+        inter_step = _score_args(inter_step)
+        B, n, Md = self.B, 2 * self.D, scoring.checked_states(self.N, inter_step)
+        cov, ok = np.zeros((B, Md, n, n)), np.zeros(B, dtype=np.int32)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_marginals_dense(self.h.ptr, inter_step, dptr(cov), iptr(ok)))
+        return dict(cov=cov, ok=ok)
+
+    def marginals_dense_dev(self, inter_step, cov=None, ok=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        inter_step = _score_args(inter_step)
+        B, n, Md = self.B, 2 * self.D, scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("cov", cov, (B, Md, n, n)), _dev_arg("ok", ok, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_marginals_dense_dev(self.h.ptr, inter_step, *args,
+                                                                   C.c_void_p(stream or 0)))
+
+    def risk(self, inter_step, kappa, want_sigma=True):
+        """The k-sigma clearance of the plan's current estimate, B rows: dict(robust_clearance, worst [B][2],
+        sigma_worst, out_of_range, sigma [B][Md][S] or None, ok)."""
+        inter_step, kappa = _score_args(inter_step), _kappa_arg(kappa)
+        B, Md = self.B, scoring.checked_states(self.N, inter_step)
+        o = dict(robust_clearance=np.zeros(B), worst=np.zeros((B, 2), dtype=np.int32), sigma_worst=np.zeros(B),
+                 out_of_range=np.zeros(B, dtype=np.int32),
+                 sigma=np.zeros((B, Md, self.robot.S)) if want_sigma else None, ok=np.zeros(B, dtype=np.int32))
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_risk(self.h.ptr, inter_step, kappa, dptr(o["robust_clearance"]),
+                                                    iptr(o["worst"]), dptr(o["sigma_worst"]), iptr(o["out_of_range"]),
+                                                    dptr(o["sigma"]), iptr(o["ok"])))
+        return o
+
+    def risk_dev(self, inter_step, kappa, robust_clearance=None, worst=None, sigma_worst=None, out_of_range=None,
+                 sigma=None, ok=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        inter_step, kappa = _score_args(inter_step), _kappa_arg(kappa)
+        B, Md = self.B, scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("robust_clearance", robust_clearance, (B,)), _dev_arg("worst", worst, (B, 2), True),
+                _dev_arg("sigma_worst", sigma_worst, (B,)), _dev_arg("out_of_range", out_of_range, (B,), True),
+                _dev_arg("sigma", sigma, (B, Md, self.robot.S)), _dev_arg("ok", ok, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_risk_dev(self.h.ptr, inter_step, kappa, *args, C.c_void_p(stream or 0)))
 
     def sample_posterior(self, z):
         """z [B][K][N+1][2D] -> delta of the same shape, delta = L^-T z (H = L L^T at the current estimate): for

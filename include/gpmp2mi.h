@@ -629,6 +629,77 @@ int gpmp2mi_plan_marginals_dev(gpmp2mi_plan* p, double* Sdiag, double* Soff, int
 int gpmp2mi_plan_sample_posterior(gpmp2mi_plan* p, int K, const double* z, double* delta, int* ok);
 int gpmp2mi_plan_sample_posterior_dev(gpmp2mi_plan* p, int K, const double* z, double* delta, int* ok, void* stream);
 
+/* ---- posterior on the executed timeline: dense covariances and the k-sigma clearance, on the device -----------
+ * gpmp2mi_plan_score checks the Md = N (J + 1) + 1 executed states deterministically; gpmp2mi_plan_marginals gives
+ * Sigma = H^-1 at the N + 1 support states only.  These calls carry the posterior to the executed states and ask how
+ * sure the planner is that they clear the obstacles.
+ *
+ * Setting: vector-space robots (the fixed-base arm and the point robot), state z = [x; v], n = 2D, the linear
+ * constant-velocity GP, Delta = delta_t, J = inter_step >= 0.
+ *  - Checked states as in "scoring": state m has interval i = m / (J+1), sub-step j = m % (J+1), tau = j (Delta / (J+1)).
+ *  - Support posterior: Sdiag[i] = Sigma_ii, Soff[i] = Sigma_{i+1,i} (rows of i+1, columns of i), as
+ *    gpmp2mi_plan_marginals returns them.
+ *  - Covariance of a checked state.  j = 0: Sigma(m) = Sigma_ii, copied bit for bit.  j > 0: with
+ *    Lambda = Lambda_2(tau) (x) I_D, Psi = Psi_2(tau) (x) I_D (the scalars of gpmp2mi_gp_interpolate) and C = Sigma_{i+1,i},
+ *        Sigma(m) = Lambda Sigma_ii Lambda^T + Psi Sigma_{i+1,i+1} Psi^T + Psi C Lambda^T + (Psi C Lambda^T)^T
+ *                   + Q_c(tau) (x) Qc,
+ *    Q_c(tau) the 2 x 2 conditional covariance of the prior bridge, evaluated in factored form with t = tau:
+ *        [0][0] = t^3 (Delta-t)^3 / (3 Delta^3),   [0][1] = [1][0] = t^2 (Delta-t)^2 (Delta-2t) / (2 Delta^3),
+ *        [1][1] = t (Delta-t) (Delta^2 - 3 t Delta + 3 t^2) / Delta^3      (= Q(t) - Psi_2 Q(Delta) Psi_2^T).
+ *    Qc is row-major [D][D], SPD, NULL = identity; a plan uses the Qc of its setting.  This is the exact posterior of
+ *    z(tau): every factor of the graph, the GP obstacle factors included, depends on the support states only, so
+ *    p(z(tau) | data) is the prior conditional integrated over the support posterior.
+ *  - Clearance deviation, for checked state m and sphere s with centre, field lookup, in-range rule and clearance(m, s)
+ *    exactly as in "scoring": h = grad d . d centre / d x (1 x D; planar fields use x and y only),
+ *    sigma^2(m, s) = h Sigma_xx(m) h^T with Sigma_xx the top-left D x D block of Sigma(m), sigma = sqrt(max(sigma^2, 0)).
+ *  - Robust clearance, kappa >= 0 finite: c_kappa(m, s) = clearance(m, s) - kappa sigma(m, s).  robust_clearance [B] is
+ *    its minimum over the in-range pairs, +inf if there is none; worst [B][2] the (m, s) attaining it, ties as in
+ *    "scoring", (-1, -1) if none; sigma_worst [B] is sigma at that pair (0 if none); out_of_range [B] as in "scoring".
+ *    No division, no special case for sigma = 0.  sigma [B][Md][S] (sphere ids in the order of the robot description)
+ *    is the map of sigma(m, s); NaN at pairs that are out of range.
+ *  - Rows that are not SPD (ok[b] == 0): robust_clearance = sigma_worst = NaN, worst = (-1, -1), and the row's sigma
+ *    map is NaN where in range.  gpmp2mi_select_best never picks a NaN clearance, so robust_clearance can be passed to
+ *    gpmp2mi_select_best(_dev) as its min_clearance with required_clearance = 0: no further selection rule is needed.
+ *  - Determinism as in "scoring": a row's outputs are a function of that row, the robot, the field, Delta, J, kappa and
+ *    the row's band alone; sums are taken in a fixed order, without floating-point atomics.
+ * Every output may be NULL.  The `_dev` forms take device pointers (Qc and ok included) and a stream, enqueue, and
+ * return without a host synchronisation.
+ * Errors, before any device work: GPMP2MI_ERR_INVALID for a NULL handle or input, inter_step < 0, B < 0 (B == 0 is
+ * fine and does nothing), total_step < 1, delta_t <= 0, kappa negative or not finite, dof outside
+ * 1..GPMP2MI_MAX_DOF.  gpmp2mi_risk_traj and the plan forms return GPMP2MI_ERR_UNSUPPORTED for dof >= 8 (the limit of
+ * the posterior kernel, with its message) and for the Pose2 robot kinds (the covariance of the tangent-space
+ * interpolation is not built; the seeded calls refuse these kinds in the same way).
+ * Memory: gpmp2mi_risk_traj_dev keeps one 32-byte record per 64 checked states and row with the robot handle, in the
+ * block gpmp2mi_score_traj_dev uses and under its rule (calls on one handle in stream order, the handle's device
+ * current).  A plan takes the band (2 (2D)^2 doubles per state), ok and its records at the first call below and keeps
+ * them, and puts its Qc on the device then (that first call waits for the copy): with the scoring, posterior and
+ * seeding workspaces the fourth exception to "nothing is allocated after gpmp2mi_plan_create". */
+
+/* cov [B][Md][n][n] from a band, any dof <= GPMP2MI_MAX_DOF (the interpolation is Kronecker: no tile layout).  cov is
+ * exactly symmetric between support states (one triangle is computed and mirrored); support states are copies of Sdiag. */
+int gpmp2mi_gp_interpolate_cov(int dof, const double* Qc, double delta_t, int inter_step, int B, int total_step,
+                               const double* Sdiag, const double* Soff, double* cov);
+int gpmp2mi_gp_interpolate_cov_dev(int dof, const double* Qc, double delta_t, int inter_step, int B, int total_step,
+                                   const double* Sdiag, const double* Soff, double* cov, void* stream);
+/* traj [B][total_step+1][2D] with its band; ok [B] or NULL = all fine */
+int gpmp2mi_risk_traj(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const double* Qc, double delta_t,
+                      int inter_step, int B, int total_step, const double* traj, const double* Sdiag,
+                      const double* Soff, const int* ok, double kappa, double* robust_clearance, int* worst,
+                      double* sigma_worst, int* out_of_range, double* sigma);
+int gpmp2mi_risk_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const double* Qc, double delta_t,
+                          int inter_step, int B, int total_step, const double* traj, const double* Sdiag,
+                          const double* Soff, const int* ok, double kappa, double* robust_clearance, int* worst,
+                          double* sigma_worst, int* out_of_range, double* sigma, void* stream);
+/* The plan at its current estimate, with the state rules of gpmp2mi_plan_marginals (a problem is set, the plan is not
+ * poisoned): linearize -> export -> the posterior sweep into the plan's band workspace, then the kernels above.  The
+ * optimizer's records, factors and estimate are not touched.  ok [B] as gpmp2mi_plan_marginals. */
+int gpmp2mi_plan_marginals_dense(gpmp2mi_plan* p, int inter_step, double* cov, int* ok);
+int gpmp2mi_plan_marginals_dense_dev(gpmp2mi_plan* p, int inter_step, double* cov, int* ok, void* stream);
+int gpmp2mi_plan_risk(gpmp2mi_plan* p, int inter_step, double kappa, double* robust_clearance, int* worst,
+                      double* sigma_worst, int* out_of_range, double* sigma, int* ok);
+int gpmp2mi_plan_risk_dev(gpmp2mi_plan* p, int inter_step, double kappa, double* robust_clearance, int* worst,
+                          double* sigma_worst, int* out_of_range, double* sigma, int* ok, void* stream);
+
 /* ---- seeding: restarts and samples from a counter RNG, on the device ------------------------------------
  * The random function.  normal(seed, stream, a, b, i, r) is a standard normal that is a pure function of its arguments
  * (gpmp2_amd/csrc/rng.h states it once, for the kernels and for a host compiler alike): Philox4x32-10 keyed by the 64-bit

@@ -749,6 +749,54 @@ inline TrajectoryCovariance TrajectoryMarginals(const ROBOT& robot, const SDF& s
   return out;
 }
 
+/// The posterior on the executed timeline (include/gpmp2mi.h): how sure the planner is that the inter_step-up-sampled
+/// `result` clears the obstacles.  robust_clearance = min over the in-range (checked state, sphere) pairs of
+/// clearance - kappa sigma, sigma the first-order standard deviation of the clearance under TrajectoryMarginals' Sigma
+/// carried to the checked states; worst_state / worst_sphere attain it (-1 if no pair is in range), sigma_worst is sigma
+/// there; sigma [Md][nr_body_spheres], Md = total_step (inter_step + 1) + 1, NaN at pairs out of range.
+/// The function below has the struct's name, as the entry point has: write `auto r = TrajectoryRisk(...)`.
+struct TrajectoryRisk {
+  std::size_t checked_states = 0, nr_spheres = 0;
+  double robust_clearance = 0.0, sigma_worst = 0.0;
+  int worst_state = -1, worst_sphere = -1, out_of_range = 0;
+  Vector sigma;
+  double sigma_at(std::size_t state, std::size_t sphere) const { return sigma[state * nr_spheres + sphere]; }
+};
+/// ROBOT: a vector-space robot model of at most 7 dof (wider ones and the Pose2 kinds throw); SDF: SignedDistanceField
+/// or PlanarSDF.
+template <class ROBOT, class SDF>
+inline struct TrajectoryRisk TrajectoryRisk(const ROBOT& robot, const SDF& sdf, const Trajectory& result,
+                                            const Vector& start_conf, const Vector& start_vel, const Vector& end_conf,
+                                            const Vector& end_vel, const TrajOptimizerSetting& setting,
+                                            std::size_t inter_step, double kappa) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[TrajectoryRisk] result does not match dof / total_step");
+  for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+    if (v->size() != robot.dof()) throw std::runtime_error("[TrajectoryRisk] vector dim does not fit dof");
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, 1, &plan), "gpmp2mi_plan_create");
+  struct TrajectoryRisk out;
+  out.checked_states = setting.total_step * (inter_step + 1) + 1;
+  out.nr_spheres = robot.nr_body_spheres();
+  out.sigma.assign(out.checked_states * out.nr_spheres, 0.0);
+  int ok = 0, worst[2] = {-1, -1};
+  // the initial values of a plan that has not been optimized are its current estimate
+  int rc = gpmp2mi_plan_set_problem(plan, start_conf.data(), start_vel.data(), end_conf.data(), end_vel.data(),
+                                    result.data.data());
+  const char* what = "gpmp2mi_plan_set_problem";
+  if (!rc) {
+    rc = gpmp2mi_plan_risk(plan, static_cast<int>(inter_step), kappa, &out.robust_clearance, worst, &out.sigma_worst,
+                           &out.out_of_range, out.sigma.data(), &ok);
+    what = "gpmp2mi_plan_risk";
+  }
+  gpmp2mi_plan_destroy(plan);
+  check(rc, what);
+  if (!ok) throw std::runtime_error("[gpmp2mi] IndeterminantLinearSystemException");
+  out.worst_state = worst[0], out.worst_sphere = worst[1];
+  return out;
+}
+
 /// Seeding on the device (include/gpmp2mi.h "seeding").  Not in the reference, where restarts are the caller's business.
 /// out [a_count][b_count][nblk][n] of the library's counter RNG: normal(seed, stream, a_first + a, b_first + b, i, r)
 inline Vector NormalFill(std::uint64_t seed, int stream, int a_first, int a_count, int b_first, int b_count, int nblk, int n) {
