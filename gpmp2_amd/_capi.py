@@ -205,6 +205,28 @@ def declare_seed(lib):
         getattr(lib, name).restype = i
 
 
+RNG_BRIDGE = 3
+
+
+def declare_sampled(lib):
+    """argtypes of the sampled-clearance entry points (include/gpmp2mi.h "sampled clearance") and their debug hook; the
+    `_dev` forms take device addresses, except Qc, which stays a host array."""
+    vp, i, d, ip, f, u64 = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double, C.c_uint64
+    head = [vp, vp, d, f, i, i, i, i]
+    decl = {
+        "gpmp2mi_sampled_clearance_traj": head + [d, d, ip, u64, i, i, i, f, ip, d, d, ip, d, ip, ip, d],
+        "gpmp2mi_sampled_clearance_traj_dev": head + [vp, vp, vp, u64, i, i, i, f] + [vp] * 9,
+        "gpmp2mi_plan_collision_probability": [vp, i, i, u64, i, i, i, f, ip, d, d, ip, d, ip, ip, ip],
+        "gpmp2mi_plan_collision_probability_dev": [vp, i, i, u64, i, i, i, f] + [vp] * 9,
+        "gpmp2mi_plan_sample_dense_seeded": [vp, i, i, u64, i, i, i, d, ip],
+        "gpmp2mi_plan_sample_dense_seeded_dev": [vp, i, i, u64, i, i, i, vp, vp, vp],
+        "gpmp2mi_debug_sampled_chunk_bytes": [C.c_size_t],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

@@ -77,6 +77,27 @@ inline int ws_reserve(void** ws, size_t* have, size_t need) {
   return GPMP2MI_OK;
 }
 
+// The two lower Cholesky factors of the sampled clearance (sampled.hip; include/gpmp2mi.h "sampled clearance"): formed on
+// the host for a key (Qc, delta_t, inter_step, dof), kept on the host and the device.  A handle keeps the factors of its
+// last SAMPLED_FAC_KEYS keys, so calls that alternate between a few inter_steps neither copy nor wait; a new key takes the
+// oldest entry's place.
+constexpr int SAMPLED_FAC_KEYS = 4;
+struct SampledFacEntry {
+  double* dev = nullptr;      // Lp packed by rows at +0 (room for inter_step = SAMPLED_MAX_INTER), C [D][D] behind it
+  std::vector<double> host;   // what `dev` holds
+  std::vector<double> qc;     // the key: Qc (empty: identity), delta_t, inter_step, dof
+  double dt = 0.0;
+  int inter = -1, dof = 0;
+};
+struct SampledFac {
+  SampledFacEntry e[SAMPLED_FAC_KEYS];
+  int next = 0;               // the entry a new key replaces
+  void release() {            // by the owner's destructor (a poisoned plan leaks its blocks: hipFree would wait for it)
+    for (auto& x : e)
+      if (x.dev) (void)hipFree(x.dev);
+  }
+};
+
 // handles.hip
 int ensure_device();
 void gp_winv(double dt, double W[4]);
@@ -98,9 +119,12 @@ struct gpmp2mi_robot {
   mutable std::mutex score_mu;
   mutable void* score_ws = nullptr;
   mutable size_t score_ws_bytes = 0;
+  // the bridge factors of gpmp2mi_sampled_clearance_traj(_dev) calls on this handle, under the same guard and rule
+  mutable g2::SampledFac sampled_fac;
   ~gpmp2mi_robot() {
     if (d) (void)hipFree(d);
     if (score_ws) (void)hipFree(score_ws);
+    sampled_fac.release();
     if (replica) g2::g_robot_replicas.fetch_sub(1);
   }
 };
@@ -258,6 +282,11 @@ struct gpmp2mi_plan {
   size_t risk_ws_bytes = 0;
   std::vector<double> Qc;
   double* risk_qc = nullptr;
+  // sampled clearance (sampled.hip): a chunk of delta, its records, the carried counts and ok, taken at the first
+  // collision_probability / sample_dense_seeded call and kept; the bridge factors of the last (inter_step) asked for
+  void* sampled_ws = nullptr;
+  size_t sampled_ws_bytes = 0;
+  g2::SampledFac sampled_fac;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }

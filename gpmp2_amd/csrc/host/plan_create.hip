@@ -94,6 +94,8 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (seed_ws) (void)hipFree(seed_ws);
   if (risk_ws) (void)hipFree(risk_ws);
   if (risk_qc) (void)hipFree(risk_qc);
+  if (sampled_ws) (void)hipFree(sampled_ws);
+  sampled_fac.release();
   flags_release(qflags);
 }
 

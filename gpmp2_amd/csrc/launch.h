@@ -1,5 +1,7 @@
 // launch.h -- host-callable launchers implemented in the .hip translation units.
 #pragma once
+#include <cstdint>
+
 #include "common.h"
 
 namespace g2 {
@@ -94,5 +96,48 @@ int launch_risk(const RobotDev& h, const RobotDev* R, const SdfDev& s, const dou
                 int N, double kappa, const double* traj, const double* Sd, const double* So, const int* ok, double* sigma,
                 RiskRec* recs, hipStream_t st);
 int launch_risk_finish(const RiskFinish& a, hipStream_t st);
+
+// sample_clearance_kernels.hip (include/gpmp2mi.h "sampled clearance")
+constexpr int SAMPLED_MAX_INTER = 63;                 // inter_step limit: Lp is (J + 1) J / 2 <= 2 016 doubles of LDS
+#ifndef G2_SAMPLED_PER_WG
+#define G2_SAMPLED_PER_WG 8                           // -DG2_SAMPLED_PER_WG=4 / 16: the builds scripts/sampled_throughput.py compares
+#endif
+constexpr int SAMPLED_PER_WG = G2_SAMPLED_PER_WG;     // samples a workgroup of k_sampled_clearance loops over (4, 8 and 16
+                                                      // measured: profiles/sampled_throughput.json)
+constexpr size_t SAMPLED_CHUNK_BYTES = 256ull << 20;  // byte budget of a plan's delta chunk (host/sampled.hip)
+// what one wavefront of k_sampled_clearance leaves for k_sampled_finish per (row, sample, tile); k = s = INT_MAX: no
+// pair of the tile was in range.  32 bytes.
+struct SampledRec {
+  double c;
+  int k, s, oor, pad0, pad1, pad2;   // oor: 1 when a pair of the tile was out of range
+};
+// arguments of k_sampled_clearance: one chunk of `cnt` samples, s0 .. s0 + cnt - 1 of the call's K.  Outputs may be null.
+struct SampledArgs {
+  double dt, required;
+  uint64_t seed;
+  int inter, B, N, Md, nblk;
+  int K, s0, cnt;                    // K: the call's samples = the sample stride of the outputs
+  int row_first, sample_first, bridge;
+  const double* est;                 // [B][N+1][2D]
+  const double* delta;               // [B][cnt][N+1][2D]
+  const int* ok;                     // [B] or null
+  const double *Lp, *C;              // packed lower factor of the bridge (row j, column j' at (j-1) j / 2 + j' - 1); [D][D]
+  SampledRec* recs;                  // [B][cnt][nblk]
+  double* state_clearance;           // [B][K][Md]
+  int* state_hits;                   // [B][Md], zeroed ahead of the first chunk
+  double* conf;                      // [B][K][Md][D]
+};
+// arguments of k_sampled_finish for the same chunk; first / last: the call's first / last chunk
+struct SampledFinish {
+  int B, Md, nblk, K, s0, cnt, first, last;
+  double required;
+  const SampledRec* recs;
+  const int* ok;
+  int* acc;                          // [B][2]: hits and oor_samples so far
+  int *hits, *worst, *state_hits, *oor_samples;
+  double *probability, *clearance;
+};
+int launch_sampled_clearance(const RobotDev& h, const RobotDev* R, const SdfDev& s, const SampledArgs& a, hipStream_t st);
+int launch_sampled_finish(const SampledFinish& a, hipStream_t st);
 
 }  // namespace g2

@@ -45,6 +45,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
     _capi.declare_seed(lib)
+    _capi.declare_sampled(lib)
     return lib
 
 
@@ -112,6 +113,40 @@ def _kappa_arg(kappa):
     if not (np.isfinite(kappa) and kappa >= 0.0):
         raise ValueError("kappa must be finite and >= 0")
     return kappa
+
+
+def sampled_args(inter_step, K, row_first, sample_first, required_clearance=0.0):
+    """The scalars of a sampled-clearance call, checked: (inter_step, K, row_first, sample_first, required_clearance)."""
+    inter_step, K, row_first, sample_first = _score_args(inter_step), int(K), int(row_first), int(sample_first)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if row_first < 0 or sample_first < 0:
+        raise ValueError("row_first and sample_first must be >= 0")
+    required_clearance = float(required_clearance)
+    if np.isnan(required_clearance):
+        raise ValueError("required_clearance must not be NaN")
+    return inter_step, K, row_first, sample_first, required_clearance
+
+
+def sampled_outputs(B, K, Md, D, want_maps=True, want_conf=False):
+    """Fresh host arrays for the outputs of a sampled-clearance call (state_clearance / conf: None unless wanted)."""
+    return dict(hits=np.zeros(B, dtype=np.int32), probability=np.zeros(B), clearance=np.zeros((B, K)),
+                worst=np.zeros((B, K, 2), dtype=np.int32),
+                state_clearance=np.zeros((B, K, Md)) if want_maps else None,
+                state_hits=np.zeros((B, Md), dtype=np.int32), oor_samples=np.zeros(B, dtype=np.int32),
+                conf=np.zeros((B, K, Md, D)) if want_conf else None)
+
+
+def _sampled_ptrs(o):
+    return (iptr(o["hits"]), dptr(o["probability"]), dptr(o["clearance"]), iptr(o["worst"]), dptr(o["state_clearance"]),
+            iptr(o["state_hits"]), iptr(o["oor_samples"]))
+
+
+def _sampled_dev_args(B, K, Md, hits, probability, clearance, worst, state_clearance, state_hits, oor_samples):
+    return [_dev_arg("hits", hits, (B,), True), _dev_arg("probability", probability, (B,)),
+            _dev_arg("clearance", clearance, (B, K)), _dev_arg("worst", worst, (B, K, 2), True),
+            _dev_arg("state_clearance", state_clearance, (B, K, Md)), _dev_arg("state_hits", state_hits, (B, Md), True),
+            _dev_arg("oor_samples", oor_samples, (B,), True)]
 
 
 def band_inputs(D, Sdiag, Soff, Qc=None):
@@ -428,6 +463,43 @@ class Engine:
                                             iptr(o["worst"]), dptr(o["sigma_worst"]), iptr(o["out_of_range"]),
                                             dptr(o["sigma"])))
         return o
+
+    # ---------------------------------------------------------------- sampled clearance (include/gpmp2mi.h)
+    def sampled_clearance_traj(self, robot, sdf, Qc, delta_t, inter_step, traj, delta, seed, required_clearance=0.0,
+                               ok=None, row_first=0, sample_first=0, bridge=True, want_maps=True, want_conf=False):
+        """traj [B][N+1][2D] with K support samples delta [B][K][N+1][2D] of its posterior -> dict(hits [B],
+        probability [B], clearance [B][K], worst [B][K][2], state_clearance [B][K][Md] or None, state_hits [B][Md],
+        oor_samples [B], conf [B][K][Md][D] or None): every sample carried to the Md checked states (bridge: with the
+        noise of the prior bridge) and put through the collision check.  ok [B] or None: rows with ok == 0 answer -1 / NaN.
+        ValueError for mis-shaped arrays."""
+        t = scoring.traj_rows(traj, robot.dof)
+        B, N, D = t.shape[0], t.shape[1] - 1, robot.dof
+        de = f64(delta)
+        if de.ndim != 4 or de.shape[0] != B or de.shape[1] < 1 or de.shape[2:] != (N + 1, 2 * D):
+            raise ValueError(f"delta: expected [{B}][K][{N + 1}][{2 * D}] with K >= 1, got {list(de.shape)}")
+        inter_step, K, row_first, sample_first, required_clearance = sampled_args(
+            inter_step, de.shape[1], row_first, sample_first, required_clearance)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        q = None
+        if Qc is not None:
+            q = f64(Qc)
+            if q.shape != (D, D):
+                raise ValueError(f"Qc: expected [{D}][{D}], got {list(q.shape)}")
+        k = None
+        if ok is not None:
+            k = np.ascontiguousarray(ok, dtype=np.int32)
+            if k.shape != (B,):
+                raise ValueError(f"ok: expected [{B}], got {list(k.shape)}")
+        o = sampled_outputs(B, K, scoring.checked_states(N, inter_step), D, want_maps, want_conf)
+        self._ck(self.lib.gpmp2mi_sampled_clearance_traj(
+            robot.ptr, sdf.ptr, dptr(q), float(delta_t), inter_step, B, N, K, dptr(t), dptr(de), iptr(k), int(seed),
+            row_first, sample_first, int(bool(bridge)), required_clearance, *_sampled_ptrs(o), dptr(o["conf"])))
+        return o
+
+    def sampled_chunk_bytes(self, nbytes=0):
+        """Test hook: the byte budget of the delta chunk of Plan.collision_probability / sample_dense_seeded (0: default)."""
+        self._ck(self.lib.gpmp2mi_debug_sampled_chunk_bytes(int(nbytes)))
 
     # ---------------------------------------------------------------- seeding (include/gpmp2mi.h "seeding")
     def normal_fill(self, seed, stream, a_first, a_count, b_first, b_count, nblk, n):
@@ -857,6 +929,57 @@ class Plan:
         args = [_dev_arg("delta", delta, (B, K, nb, n)), _dev_arg("ok", ok, (B,), True)]
         self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_posterior_seeded_dev(
             self.h.ptr, K, int(seed), int(row_first), int(sample_first), *args, C.c_void_p(stream or 0)))
+
+    # ---- sampled clearance (include/gpmp2mi.h "sampled clearance")
+    def collision_probability(self, inter_step, K, seed, required_clearance=0.0, row_first=0, sample_first=0, bridge=True,
+                              want_maps=True):
+        """K joint draws of the executed trajectory per row from the posterior at the current estimate, each through the
+        collision check: dict(hits [B], probability [B] = hits / K, clearance [B][K], worst [B][K][2],
+        state_clearance [B][K][Md] or None, state_hits [B][Md], oor_samples [B], ok [B])."""
+        inter_step, K, row_first, sample_first, required_clearance = sampled_args(
+            inter_step, K, row_first, sample_first, required_clearance)
+        o = sampled_outputs(self.B, K, scoring.checked_states(self.N, inter_step), self.D, want_maps)
+        del o["conf"]
+        o["ok"] = np.zeros(self.B, dtype=np.int32)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_collision_probability(
+            self.h.ptr, inter_step, K, int(seed), row_first, sample_first, int(bool(bridge)), required_clearance,
+            *_sampled_ptrs(o), iptr(o["ok"])))
+        return o
+
+    def collision_probability_dev(self, inter_step, K, seed, required_clearance=0.0, row_first=0, sample_first=0,
+                                  bridge=True, hits=None, probability=None, clearance=None, worst=None,
+                                  state_clearance=None, state_hits=None, oor_samples=None, ok=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation once the
+        plan holds the bridge factors of this inter_step."""
+        inter_step, K, row_first, sample_first, required_clearance = sampled_args(
+            inter_step, K, row_first, sample_first, required_clearance)
+        B, Md = self.B, scoring.checked_states(self.N, inter_step)
+        args = _sampled_dev_args(B, K, Md, hits, probability, clearance, worst, state_clearance, state_hits, oor_samples)
+        args.append(_dev_arg("ok", ok, (B,), True))
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_collision_probability_dev(
+            self.h.ptr, inter_step, K, int(seed), row_first, sample_first, int(bool(bridge)), required_clearance, *args,
+            C.c_void_p(stream or 0)))
+
+    def sample_dense_seeded(self, inter_step, K, seed, row_first=0, sample_first=0, bridge=True):
+        """(conf [B][K][Md][D], ok [B]): the sampled configurations on the executed timeline alone."""
+        inter_step, K, row_first, sample_first, _ = sampled_args(inter_step, K, row_first, sample_first)
+        conf = np.zeros((self.B, K, scoring.checked_states(self.N, inter_step), self.D))
+        ok = np.zeros(self.B, dtype=np.int32)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_dense_seeded(
+            self.h.ptr, inter_step, K, int(seed), row_first, sample_first, int(bool(bridge)), dptr(conf), iptr(ok)))
+        return conf, ok
+
+    def sample_dense_seeded_dev(self, inter_step, K, seed, conf, ok=None, row_first=0, sample_first=0, bridge=True,
+                                stream=None):
+        """The same into device buffers: conf [B][K][Md][D], ok int32 [B] or None."""
+        inter_step, K, row_first, sample_first, _ = sampled_args(inter_step, K, row_first, sample_first)
+        if conf is None:
+            raise ValueError("conf is required")
+        B, Md = self.B, scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("conf", conf, (B, K, Md, self.D)), _dev_arg("ok", ok, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_sample_dense_seeded_dev(
+            self.h.ptr, inter_step, K, int(seed), row_first, sample_first, int(bool(bridge)), *args,
+            C.c_void_p(stream or 0)))
 
     # ---- incremental replanning (ISAM2TrajOptimizer's role; see include/gpmp2mi.h)
     def fix_state(self, b, state_idx, conf, vel):

@@ -238,8 +238,8 @@ void gpmp2mi_graph_opts_default(gpmp2mi_graph_opts* o);
  * optimizer loop planner/BatchTrajOptimizer.cpp:212-308) for B independent problems sharing one
  * robot, one SDF and one setting.  The plan owns all device workspace; nothing is allocated in
  * the optimize call, so it can be enqueued repeatedly (receding horizon).  (The scoring calls take their workspace
- * at their first use for an inter_step and keep it: see "scoring" below; so do the posterior calls and the seeded
- * calls at their first use: see "posterior" and "seeding".) */
+ * at their first use for an inter_step and keep it: see "scoring" below; so do the posterior calls, the seeded
+ * calls and the sampled-clearance calls at their first use: see "posterior", "seeding" and "sampled clearance".) */
 typedef struct gpmp2mi_plan gpmp2mi_plan;
 int gpmp2mi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf,
                         const gpmp2mi_settings* setting, const gpmp2mi_graph_opts* opts /*NULL ok*/,
@@ -766,6 +766,95 @@ int gpmp2mi_plan_sample_posterior_seeded(gpmp2mi_plan* p, int K, uint64_t seed, 
                                          double* delta, int* ok);
 int gpmp2mi_plan_sample_posterior_seeded_dev(gpmp2mi_plan* p, int K, uint64_t seed, int row_first, int sample_first,
                                              double* delta, int* ok, void* stream);
+
+/* ---- sampled clearance: the collision probability of a plan from posterior samples, on the device ------------
+ * gpmp2mi_plan_risk answers with a first-order number, clearance - kappa sigma, pair by pair.  These calls draw K whole
+ * trajectories per row from the posterior ON THE EXECUTED TIMELINE, put each through the collision check of "scoring",
+ * and count: how likely is the trajectory as a whole to come closer to an obstacle than required_clearance?
+ *
+ * Setting: that of "posterior on the executed timeline": vector-space robots with 2D <= 15, state [x; v],
+ * Delta = delta_t, J = inter_step, 0 <= J <= 63, Md = N (J+1) + 1 checked states; state m has interval i = m / (J+1),
+ * sub-step j = m % (J+1) and tau_j = j (Delta / (J+1)).
+ *  - Indices.  Row b and sample s of a call have the global indices r = row_first + b and q = sample_first + s.
+ *  - Support sample.  delta [N+1][2D] = L^-T z with z[i][rho] = normal(seed, GPMP2MI_RNG_POSTERIOR, r, q, i, rho): exactly
+ *    the delta of gpmp2mi_plan_sample_posterior_seeded (the stand-alone call takes delta from the caller).
+ *    zeta_i = est_i + delta_i, one rounded addition per coordinate.
+ *  - Sampled configuration x_s(m) [D]: the configuration half of gpmp2mi_interpolate_traj(inter_step = J) applied to zeta,
+ *    with the arithmetic of "scoring" (zeta is rounded, then interpolated); for bridge != 0 and j > 0, plus eps(i, j).
+ *  - Bridge noise.  A sample between support states is not the interpolation of a support sample: it also carries the
+ *    noise of the prior bridge, jointly over the sub-steps of an interval.
+ *        eps(i, j) = sum_{j' = 1..j} Lp[j][j'] (C xi_{i,j'}),
+ *        xi_{i,j'}[d] = normal(seed, GPMP2MI_RNG_BRIDGE, r, q, i (J+1) + j', d),  d < D.
+ *    C is the lower Cholesky factor of Qc ([D][D] row-major, SPD, NULL = identity; a plan uses its setting's Qc) and Lp
+ *    the lower Cholesky factor of the J x J matrix P: for s = tau_a <= t = tau_b,
+ *        P[a][b] = P[b][a] = s^2 (Delta - t)^2 (3 t Delta - s Delta - 2 s t) / (6 Delta^3),
+ *    the position-position part of K0(s,t) - K0(s,Delta) Q(Delta)^-1 K0(Delta,t) with K0(s,t) = Q(s) Phi(t-s)^T; at a = b
+ *    it is t^3 (Delta-t)^3 / (3 Delta^3) = Q_c(tau)[0][0] of "posterior on the executed timeline".  Both factors are
+ *    formed on the host in fp64 by row-wise Cholesky without pivoting -- for each row a and b = 0..a:
+ *    s = A[a][b] - sum_{k<b} L[a][k] L[b][k], L[a][b] = s / L[b][b] below the diagonal and sqrt(s) on it -- and uploaded
+ *    once per key (Qc, delta_t, J); a plan or robot handle keeps the factors of its last 4 keys, and only a call with a
+ *    new key waits for the copy.  A new key takes the place of the oldest one with a copy on the calling stream: calls on
+ *    one handle must be in stream order (as for the records, see Memory), or a kernel still queued on another stream
+ *    could read a block while it is replaced.  eps of
+ *    different intervals, rows or samples are independent, and eps is independent of delta.
+ *  - Law of the samples.  The x_s(.) of one sample are a joint draw of the configurations on the executed timeline from
+ *    the Gaussian posterior; the marginal covariance of x_s(m) is the Sigma_xx(m) of gpmp2mi_plan_marginals_dense.
+ *    Velocities are not sampled.
+ *  - Per sample: clearance_s(m, sphere) as in "scoring" at x_s(m) (in-range rule, planar fields and non-finite centres
+ *    as there); state_clearance [B][K][Md] = its minimum over the in-range spheres, +inf if none; clearance [B][K] = c_s =
+ *    the minimum over m; worst [B][K][2] the (m, sphere) attaining it with the ties of "scoring", (-1, -1) if none.
+ *  - Per row: hits [B] = #{s : c_s < required_clearance}, an exact integer; probability [B] = hits / K, one fp64 division;
+ *    state_hits [B][Md] = #{s : state_clearance[s][m] < required_clearance}; oor_samples [B] = #{s with at least one
+ *    out-of-range pair}.  conf [B][K][Md][D] receives the sampled configurations.
+ *  - bridge = 0, or J = 0: c_s and worst[s] are bit for bit the min_clearance and worst of gpmp2mi_score_traj on zeta.
+ *  - Rows with ok[b] == 0: hits = state_hits = oor_samples = -1, probability = clearance = state_clearance = conf = NaN,
+ *    worst = (-1, -1).
+ *  - Determinism: every output of (row, sample) is a function of the row's estimate and factorisation, the robot, the
+ *    field, Delta, J, bridge, seed, r and q alone -- not of B, K, the chunking below, the entry point or the device.
+ *    Counts are integers, so hits and state_hits of a sample range are the sums over any split of it.  No floating-point
+ *    atomics.
+ * Every output may be NULL.  The `_dev` forms take device pointers (ok included; Qc stays a HOST array, read before the
+ * call returns) and a stream, enqueue, and return.
+ * Errors, before any device work: GPMP2MI_ERR_INVALID for a NULL handle or required input, K < 1, B < 0 (B == 0 is fine
+ * and does nothing), total_step < 1, delta_t <= 0, inter_step < 0, a negative first index or overflow of first + count, a
+ * required_clearance that is NaN, a plan without a problem, a Qc that is not SPD; GPMP2MI_ERR_UNSUPPORTED, the limit in
+ * the message, for inter_step > 63, 2D > 15 and the Pose2 robot kinds; GPMP2MI_ERR_TIMEOUT for a poisoned plan.  The
+ * stand-alone call takes at most 524 280 samples per call (one launch); the plan forms have no such limit.
+ * Memory: the plan forms run linearize -> export -> the factor-only posterior sweep, then, chunk after chunk on the one
+ * stream, the seeded back-substitution into a delta workspace and the kernels of this section.  The chunk is the largest
+ * multiple of 16 samples whose delta fits 256 MiB; that workspace (delta chunk, one 32-byte record per sample and 64
+ * checked states, the factors Lp and C) is taken at the first call and kept: with the scoring, posterior, seeding and
+ * band workspaces the fifth exception to "nothing is allocated after gpmp2mi_plan_create".  The optimizer's records,
+ * factors and estimate are not touched.  gpmp2mi_sampled_clearance_traj_dev keeps its records and factors with the robot
+ * handle, in the block gpmp2mi_score_traj_dev uses and under its rule. */
+enum { GPMP2MI_RNG_BRIDGE = 3 };
+/* caller's trajectories and support samples (e.g. from gpmp2mi_block_tridiag_sample or
+ * gpmp2mi_plan_sample_posterior_seeded): traj [B][N+1][2D], delta [B][K][N+1][2D], ok [B] or NULL */
+int gpmp2mi_sampled_clearance_traj(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const double* Qc, double delta_t,
+                                   int inter_step, int B, int total_step, int K, const double* traj, const double* delta,
+                                   const int* ok, uint64_t seed, int row_first, int sample_first, int bridge,
+                                   double required_clearance, int* hits, double* probability, double* clearance,
+                                   int* worst, double* state_clearance, int* state_hits, int* oor_samples, double* conf);
+int gpmp2mi_sampled_clearance_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, const double* Qc,
+                                       double delta_t, int inter_step, int B, int total_step, int K, const double* traj,
+                                       const double* delta, const int* ok, uint64_t seed, int row_first,
+                                       int sample_first, int bridge, double required_clearance, int* hits,
+                                       double* probability, double* clearance, int* worst, double* state_clearance,
+                                       int* state_hits, int* oor_samples, double* conf, void* stream);
+/* the plan at its current estimate, state rules of gpmp2mi_plan_sample_posterior_seeded; ok [B] as there */
+int gpmp2mi_plan_collision_probability(gpmp2mi_plan* p, int inter_step, int K, uint64_t seed, int row_first,
+                                       int sample_first, int bridge, double required_clearance, int* hits,
+                                       double* probability, double* clearance, int* worst, double* state_clearance,
+                                       int* state_hits, int* oor_samples, int* ok);
+int gpmp2mi_plan_collision_probability_dev(gpmp2mi_plan* p, int inter_step, int K, uint64_t seed, int row_first,
+                                           int sample_first, int bridge, double required_clearance, int* hits,
+                                           double* probability, double* clearance, int* worst, double* state_clearance,
+                                           int* state_hits, int* oor_samples, int* ok, void* stream);
+/* the sampled configurations alone: conf [B][K][Md][D] */
+int gpmp2mi_plan_sample_dense_seeded(gpmp2mi_plan* p, int inter_step, int K, uint64_t seed, int row_first,
+                                     int sample_first, int bridge, double* conf, int* ok);
+int gpmp2mi_plan_sample_dense_seeded_dev(gpmp2mi_plan* p, int inter_step, int K, uint64_t seed, int row_first,
+                                         int sample_first, int bridge, double* conf, int* ok, void* stream);
 
 /* ---- misc ---------------------------------------------------------------------------------- */
 const char* gpmp2mi_last_error(void);  /* thread-local message of the last failing call */

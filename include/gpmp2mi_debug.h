@@ -9,6 +9,8 @@
 #ifndef GPMP2MI_DEBUG_H
 #define GPMP2MI_DEBUG_H
 
+#include <stddef.h>
+
 #include "gpmp2mi.h"
 
 #ifdef __cplusplus
@@ -46,6 +48,11 @@ int gpmp2mi_debug_current_device(int set_to, int* current);
 /* Test hook: the precision H_seed of the plan's linear prior graph as the plan built it for the seeded calls
  * (include/gpmp2mi.h "seeding"): Hdiag [N+1][2D][2D], Hoff [N][2D][2D] = block (i+1, i).  Either may be NULL. */
 int gpmp2mi_debug_plan_seed_prior(gpmp2mi_plan* p, double* Hdiag, double* Hoff);
+
+/* Test hook (works without a GPU): the byte budget of the delta chunk of the plan forms of "sampled clearance"
+ * (include/gpmp2mi.h), for every plan of the process; 0 = the default (256 MiB).  A chunk is never smaller than 16 samples,
+ * so a small budget lets a test cross chunk borders at small K. */
+int gpmp2mi_debug_sampled_chunk_bytes(size_t bytes);
 
 /* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
 int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);

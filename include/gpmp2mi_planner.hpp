@@ -797,6 +797,59 @@ inline struct TrajectoryRisk TrajectoryRisk(const ROBOT& robot, const SDF& sdf, 
   return out;
 }
 
+/// The sampled clearance (include/gpmp2mi.h "sampled clearance"): K joint draws of the inter_step-up-sampled trajectory
+/// from the posterior at `result`, each through the collision check.  hits = the samples whose minimum clearance lies
+/// below required_clearance, probability = hits / K; clearance [K] and worst [K][2] per sample, state_hits [Md] per
+/// checked state, Md = total_step (inter_step + 1) + 1; oor_samples = the samples with a pair out of range.
+/// probability (or -hits) can be handed to SelectBest as a score by the caller.
+/// The function below has the struct's name, as TrajectoryRisk: write `auto r = SampledClearance(...)`.
+struct SampledClearance {
+  std::size_t checked_states = 0, samples = 0;
+  int hits = 0, oor_samples = 0;
+  double probability = 0.0;
+  Vector clearance;
+  std::vector<int> worst, state_hits;
+};
+/// ROBOT, SDF as for TrajectoryRisk; inter_step <= 63.
+template <class ROBOT, class SDF>
+inline struct SampledClearance SampledClearance(const ROBOT& robot, const SDF& sdf, const Trajectory& result,
+                                                const Vector& start_conf, const Vector& start_vel,
+                                                const Vector& end_conf, const Vector& end_vel,
+                                                const TrajOptimizerSetting& setting, std::size_t inter_step,
+                                                std::size_t K, std::uint64_t seed, double required_clearance,
+                                                bool bridge = true, int row_first = 0, int sample_first = 0) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[SampledClearance] result does not match dof / total_step");
+  for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+    if (v->size() != robot.dof()) throw std::runtime_error("[SampledClearance] vector dim does not fit dof");
+  if (K < 1) throw std::runtime_error("[SampledClearance] K must be >= 1");
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, 1, &plan), "gpmp2mi_plan_create");
+  struct SampledClearance out;
+  out.checked_states = setting.total_step * (inter_step + 1) + 1;
+  out.samples = K;
+  out.clearance.assign(K, 0.0);
+  out.worst.assign(2 * K, -1);
+  out.state_hits.assign(out.checked_states, 0);
+  int ok = 0;
+  // the initial values of a plan that has not been optimized are its current estimate
+  int rc = gpmp2mi_plan_set_problem(plan, start_conf.data(), start_vel.data(), end_conf.data(), end_vel.data(),
+                                    result.data.data());
+  const char* what = "gpmp2mi_plan_set_problem";
+  if (!rc) {
+    rc = gpmp2mi_plan_collision_probability(plan, static_cast<int>(inter_step), static_cast<int>(K), seed, row_first,
+                                            sample_first, bridge ? 1 : 0, required_clearance, &out.hits,
+                                            &out.probability, out.clearance.data(), out.worst.data(), nullptr,
+                                            out.state_hits.data(), &out.oor_samples, &ok);
+    what = "gpmp2mi_plan_collision_probability";
+  }
+  gpmp2mi_plan_destroy(plan);
+  check(rc, what);
+  if (!ok) throw std::runtime_error("[gpmp2mi] IndeterminantLinearSystemException");
+  return out;
+}
+
 /// Seeding on the device (include/gpmp2mi.h "seeding").  Not in the reference, where restarts are the caller's business.
 /// out [a_count][b_count][nblk][n] of the library's counter RNG: normal(seed, stream, a_first + a, b_first + b, i, r)
 inline Vector NormalFill(std::uint64_t seed, int stream, int a_first, int a_count, int b_first, int b_count, int nblk, int n) {
