@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's matlab/WAMPlannerExample.m with gpmp2_amd: 7-DOF WAM arm in the desk scene, signed distance
-field built on the GPU, batch trajectory optimisation, dense up-sampling, collision cost, dense collision check and best-of-restarts
-selection on the device, then one replanning step (matlab/WAMReplannerExample.m:102-126).  Runs on an MI355X; there is no CPU path."""
+field built on the GPU, batch trajectory optimisation, dense up-sampling, collision cost, dense collision and self-collision check and
+best-of-restarts selection on the device, then one replanning step (matlab/WAMReplannerExample.m:102-126).  Runs on an MI355X; there is no CPU path."""
 import os
 import sys
 import time
@@ -64,14 +64,19 @@ robot = eng.robot(arm)
 plan = eng.plan(robot, sdf.handle(), opt_setting, B)
 plan.set_problem(*[np.repeat(v[None], B, axis=0) for v in (start_conf, zero, end_conf, zero)], inits)
 plan.optimize()
-scores, pick = plan.score(9), plan.select(9, required_clearance=0.0, require_in_range=True)
+# the robot must clear itself too: every sphere pair two joints apart or more that does not touch at the zero configuration
+pairs = eng.generate_self_pairs(robot, min_joint_gap=2, ref_conf=np.zeros(7))
+scores, self_scores = plan.score(9), plan.self_score(pairs, 9)
+pick = plan.select_checked(9, pairs, required_clearance=0.0, require_in_range=True, required_self_clearance=0.0)
 hidden = int(((scores["support_cost"] == 0) & (scores["dense_cost"] > 0)).sum())
-print(f"{B} restarts: {pick['n_eligible']} collision-free when up-sampled, {hidden} clean at the support states only; "
-      f"best = restart {pick['best']}")
+touching = int((self_scores["min_self_clearance"] < 0).sum())
+print(f"{B} restarts: {pick['n_eligible']} clear of the obstacles and of themselves when up-sampled, {hidden} clean at the "
+      f"support states only, {touching} in self-collision ({pairs.P} pairs); best = restart {pick['best']}")
 if pick["best"] >= 0:
     b = pick["best"]
     print(f"  support cost {scores['support_cost'][b]:.4f}, dense cost {scores['dense_cost'][b]:.4f}, clearance "
-          f"{scores['min_clearance'][b]:.4f} m; {pick['dense_best'].shape[0]} states ready to execute")
+          f"{scores['min_clearance'][b]:.4f} m, self clearance {self_scores['min_self_clearance'][b]:.4f} m; "
+          f"{pick['dense_best'].shape[0]} states ready to execute")
 plan.close()
 
 # ---- replanning: execute to state 5, the goal moves (WAMReplannerExample.m:102-126)

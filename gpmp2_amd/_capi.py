@@ -146,6 +146,29 @@ def declare_score(lib):
         getattr(lib, name).restype = i
 
 
+def declare_self(lib):
+    """argtypes of the self-collision check (include/gpmp2mi.h "self-collision check"); the `_dev` forms take device
+    addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_self_pairs_create": [vp, i, d, vp],
+        "gpmp2mi_self_pairs_generate": [vp, i, i, d, f, f, vp],
+        "gpmp2mi_self_pairs_count": [vp],
+        "gpmp2mi_self_pairs_get": [vp, d],
+        "gpmp2mi_self_score_traj": [vp, vp, f, i, i, i, d, d, d, d, ip, ip],
+        "gpmp2mi_self_score_traj_dev": [vp, vp, f, i, i, i] + [vp] * 7,
+        "gpmp2mi_plan_self_score": [vp, vp, i, d, d, d, ip, ip],
+        "gpmp2mi_plan_self_score_dev": [vp, vp, i] + [vp] * 6,
+        "gpmp2mi_plan_select_checked": [vp, i, f, i, vp, f, ip, ip, d, d],
+        "gpmp2mi_plan_select_checked_dev": [vp, i, f, i, vp, f] + [vp] * 5,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_self_pairs_destroy.argtypes = [vp]
+    lib.gpmp2mi_self_pairs_destroy.restype = None
+
+
 def declare_posterior(lib):
     """argtypes of the posterior entry points (include/gpmp2mi.h "posterior"); the `_dev` forms take device addresses."""
     vp, i, d, ip = C.c_void_p, C.c_int, c_double_p, c_int_p

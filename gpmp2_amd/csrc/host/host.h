@@ -141,6 +141,23 @@ struct gpmp2mi_sdf {
   }
 };
 
+// A pair table of the self-collision check (self_score.hip; include/gpmp2mi.h "self-collision check"), bound to the
+// sphere model of the robot it was made for.  An empty table holds nothing on the device.
+struct gpmp2mi_self_pairs {
+  int P = 0, S = 0, dof = 0, kind = 0;
+  int device = -1;            // the device `d` lives on (-1: empty table)
+  std::vector<double> data;   // [P][4] as the caller gave it
+  g2::SelfPair* d = nullptr;  // [P]
+  // records of gpmp2mi_self_score_traj(_dev) calls with this table, by the rules of gpmp2mi_robot::score_ws
+  mutable std::mutex mu;
+  mutable void* ws = nullptr;
+  mutable size_t ws_bytes = 0;
+  ~gpmp2mi_self_pairs() {
+    if (d) (void)hipFree(d);
+    if (ws) (void)hipFree(ws);
+  }
+};
+
 namespace g2 {
 // geometry + device storage of a field handle; the caller fills s->plain ([nz][ny][nx]) and packs (handles.hip)
 int sdf_alloc(int dim, const double origin[3], double cell, int nx, int ny, int nz, std::unique_ptr<gpmp2mi_sdf>& s);
@@ -287,6 +304,10 @@ struct gpmp2mi_plan {
   void* sampled_ws = nullptr;
   size_t sampled_ws_bytes = 0;
   g2::SampledFac sampled_fac;
+  // self-collision check (self_score.hip): the records of k_self_clearance, those of k_score for select_checked and
+  // the staging of the host-pointer forms, taken at the first self_score / select_checked call and kept
+  void* self_ws = nullptr;
+  size_t self_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -397,6 +418,8 @@ struct ScoreSel {
 // host: the outputs are host arrays (staged in the plan's scoring workspace, copied back, `st` synchronised);
 // otherwise device pointers, and the call returns without a host synchronisation.
 int plan_score(gpmp2mi_plan* p, int inter, const ScoreOut& out, const ScoreSel* sel, bool host, hipStream_t st);
+// the argument rules the score calls share (inter_step, B, total_step, delta_t, the launch limits)
+int check_score_args(int inter, int B, int total_step, double delta_t);
 // B comparisons on the host: the rule of gpmp2mi_select_best
 void select_rule_host(int B, const double* ferr, const int* status, const double* clearance, const int* oor,
                       double required_clearance, int require_in_range, int* best, int* n_eligible);

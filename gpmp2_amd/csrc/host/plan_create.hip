@@ -95,6 +95,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (risk_ws) (void)hipFree(risk_ws);
   if (risk_qc) (void)hipFree(risk_qc);
   if (sampled_ws) (void)hipFree(sampled_ws);
+  if (self_ws) (void)hipFree(self_ws);
   sampled_fac.release();
   flags_release(qflags);
 }

@@ -8,9 +8,7 @@
 
 using namespace g2;
 
-namespace {
-
-int check_score_args(int inter, int B, int total_step, double delta_t) {
+int g2::check_score_args(int inter, int B, int total_step, double delta_t) {
   G2_CHECK(inter >= 0, GPMP2MI_ERR_INVALID, "inter_step must be >= 0");
   G2_CHECK(B >= 0, GPMP2MI_ERR_INVALID, "B must be >= 0");
   G2_CHECK(total_step >= 1, GPMP2MI_ERR_INVALID, "total_step must be >= 1");
@@ -20,6 +18,8 @@ int check_score_args(int inter, int B, int total_step, double delta_t) {
            GPMP2MI_ERR_INVALID, "too many checked states for one launch");
   return GPMP2MI_OK;
 }
+
+namespace {
 
 // k_score over `traj` into `recs`, then k_score_finish with the outputs (and the selection) of `f`
 int enqueue_score(const gpmp2mi_robot* r, const gpmp2mi_sdf* s, double dt, int inter, int B, int N, const double* traj,

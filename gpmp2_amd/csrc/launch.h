@@ -74,6 +74,31 @@ int launch_score(const RobotDev& h, const RobotDev* R, const SdfDev& s, double d
                  const double* traj, ScoreRec* recs, hipStream_t st);
 int launch_score_finish(const ScoreFinish& a, hipStream_t st);
 
+// self_clearance_kernels.hip (include/gpmp2mi.h "self-collision check")
+// one row of a pair table on the device: sorted-order sphere indices and radius_A + radius_B + epsilon.  16 bytes.
+struct SelfPair {
+  double total_eps;
+  int a, b;
+};
+// Checked states per workgroup of k_self_clearance: LDS holds 24 S bytes per state, so the tile shrinks as the sphere
+// model grows.  A function of S alone (it fixes the summation order); a power of two <= 64.
+inline int self_tile(int S) { return S <= 32 ? 64 : S <= 64 ? 32 : 16; }
+inline int self_blocks(int Md, int S) { return (Md + self_tile(S) - 1) / self_tile(S); }   // records per row
+// arguments of k_self_finish.  The records of k_self_clearance are ScoreRecs: s is the row of the caller's pair table,
+// oor the number of invalid (state, pair)s.  `sel` carries the selection (sel.select) with the records of k_score for
+// the same rows (sel.recs, sel.nblk) and the shape of the trajectories; its per-row outputs are not written.
+struct SelfFinish {
+  ScoreFinish sel;
+  const ScoreRec* recs;   // [B][nblk]
+  int nblk;
+  double *support, *dense, *clearance;
+  int *worst, *invalid;
+  double required_self_clearance;
+};
+int launch_self_clearance(const RobotDev& h, const RobotDev* R, const SelfPair* pairs, int P, double dt, int inter, int B,
+                          int N, const double* traj, ScoreRec* recs, hipStream_t st);
+int launch_self_finish(const SelfFinish& a, hipStream_t st);
+
 // risk_kernels.hip
 // what one workgroup of k_risk leaves for k_risk_finish; k = s = INT_MAX: no pair of the tile was in range
 struct RiskRec {

@@ -18,18 +18,9 @@
 #include "device_math.h"
 #include "dispatch.h"
 #include "launch.h"
+#include "score_select.h"
 
 namespace g2 {
-
-// (clearance, state, sphere) compared lexicographically: the minimum and where it occurs travel together, exact ties
-// go to the lowest state, then the lowest sphere.  "none" is (+inf, INT_MAX, INT_MAX).
-struct ScoreKey {
-  double c;
-  int k, s;
-};
-__device__ __forceinline__ bool key_less(const ScoreKey& a, const ScoreKey& b) {
-  return a.c < b.c || (a.c == b.c && (a.k < b.k || (a.k == b.k && a.s < b.s)));
-}
 
 template <int KIND, int AD, int AD2, int SDIM>
 __global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, SdfDev sdf, double dt, int inter, int N,
@@ -120,61 +111,18 @@ __global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, 
   }
 }
 
-// One output state of interpolateArmTraj / interpolatePose2MobileArmTraj, coordinate k: the expressions of
-// k_interpolate_traj (factor_kernels.hip) element by element.  s0 / s1: the support states around it.
-__device__ __forceinline__ void score_dense_coord(bool lie, double dt, int inter, int D, int j, int k, const double* s0,
-                                                  double* o) {
-  if (j == 0) {
-    o[k] = s0[k];
-    o[D + k] = s0[D + k];
-    return;
-  }
-  const double* s1 = s0 + 2 * D;
-  const GpCoef gc = gp_coef_dev(dt, (double)j * (dt / (double)(inter + 1)));
-  if (lie) {
-    double r, qk;
-    if (k < 3) {
-      double x0[3], w0[3], x1[3], w1[3], qp[3], lg[3];
-#pragma unroll
-      for (int i = 0; i < 3; i++) { x0[i] = s0[i]; w0[i] = s0[D + i]; x1[i] = s1[i]; w1[i] = s1[D + i]; }
-      lie_interpolate<3>(gc, x0, w0, x1, w1, qp, nullptr);
-      pose2_logmap(pose2_between(P2{x0[0], x0[1], x0[2]}, P2{x1[0], x1[1], x1[2]}), lg);
-      qk = k == 0 ? qp[0] : k == 1 ? qp[1] : qp[2];
-      r = k == 0 ? lg[0] : k == 1 ? lg[1] : lg[2];
-    } else {
-      qk = s0[k] + (gc.l12 * s0[D + k] + gc.p11 * (s1[k] - s0[k]) + gc.p12 * s1[D + k]);
-      r = s1[k] - s0[k];
-    }
-    o[k] = qk;
-    o[D + k] = gc.l22 * s0[D + k] + gc.p21 * r + gc.p22 * s1[D + k];
-  } else {
-    o[k] = gc.l11 * s0[k] + gc.l12 * s0[D + k] + gc.p11 * s1[k] + gc.p12 * s1[D + k];
-    o[D + k] = gc.l21 * s0[k] + gc.l22 * s0[D + k] + gc.p21 * s1[k] + gc.p22 * s1[D + k];
-  }
-}
-
 // Second stage.  Rows are taken by thread (row = thread id + multiple of the thread count): a row's records are summed
 // in index order.  With a.select the grid is one workgroup: every thread keeps the best (final_error, row) of its rows,
-// the workgroup reduces them through LDS, then all its threads copy the chosen row.  a.recs == nullptr: selection over
-// given scores (gpmp2mi_select_best_dev).
+// the workgroup reduces them through LDS, then all its threads copy the chosen row (select_finish, score_select.h).
+// a.recs == nullptr: selection over given scores (gpmp2mi_select_best_dev).
 __global__ __launch_bounds__(256) void k_score_finish(ScoreFinish a) {
-  __shared__ double s_err[256];
-  __shared__ int s_row[256], s_cnt[256];
   double my_err = HUGE_VAL;
   int my_row = INT_MAX, my_cnt = 0;
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
     double clr;
     int oor;
     if (a.recs) {
-      const ScoreRec* r = a.recs + (size_t)b * a.nblk;
-      ScoreRec t = r[0];
-      for (int i = 1; i < a.nblk; i++) {   // records in index order
-        t.support += r[i].support;
-        t.dense += r[i].dense;
-        t.oor += r[i].oor;
-        const ScoreKey x{r[i].clearance, r[i].k, r[i].s}, c{t.clearance, t.k, t.s};
-        if (key_less(x, c)) { t.clearance = x.c; t.k = x.k; t.s = x.s; }
-      }
+      const ScoreRec t = reduce_records(a.recs + (size_t)b * a.nblk, a.nblk);
       const bool none = t.k == INT_MAX;
       if (a.support) a.support[b] = t.support;
       if (a.dense) a.dense[b] = t.dense;
@@ -202,38 +150,7 @@ __global__ __launch_bounds__(256) void k_score_finish(ScoreFinish a) {
     }
   }
   if (!a.select) return;
-  s_err[threadIdx.x] = my_err;
-  s_row[threadIdx.x] = my_row;
-  s_cnt[threadIdx.x] = my_cnt;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      const int o = threadIdx.x + h;
-      if (s_err[o] < s_err[threadIdx.x] || (s_err[o] == s_err[threadIdx.x] && s_row[o] < s_row[threadIdx.x])) {
-        s_err[threadIdx.x] = s_err[o];
-        s_row[threadIdx.x] = s_row[o];
-      }
-      s_cnt[threadIdx.x] += s_cnt[o];
-    }
-    __syncthreads();
-  }
-  const int best = s_row[0] == INT_MAX ? -1 : s_row[0];
-  if (threadIdx.x == 0) {
-    if (a.best) *a.best = best;
-    if (a.n_eligible) *a.n_eligible = s_cnt[0];
-  }
-  if (best < 0) return;   // the trajectory outputs are left untouched
-  if (threadIdx.x == 0 && a.best_err) *a.best_err = s_err[0];
-  const size_t trow = (size_t)(a.N + 1) * 2 * a.D;
-  const double* row = a.traj + (size_t)best * trow;
-  if (a.traj_best)
-    for (size_t i = threadIdx.x; i < trow; i += blockDim.x) a.traj_best[i] = row[i];
-  if (a.dense_best)
-    for (int e = threadIdx.x; e < a.Md * a.D; e += blockDim.x) {
-      const int m = e / a.D, k = e % a.D;
-      const int seg = m / (a.inter + 1), j = m % (a.inter + 1);
-      score_dense_coord(a.lie != 0, a.dt, a.inter, a.D, j, k, row + (size_t)seg * 2 * a.D, a.dense_best + (size_t)m * 2 * a.D);
-    }
+  select_finish(a, my_err, my_row, my_cnt);
 }
 
 int score_blocks(int Md) { return (Md + SCORE_TILE - 1) / SCORE_TILE; }

@@ -42,6 +42,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_queue(lib)
     _capi.declare_multi(lib)
     _capi.declare_score(lib)
+    _capi.declare_self(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
     _capi.declare_seed(lib)
@@ -106,6 +107,11 @@ def _score_args(inter_step):
 def _score_ptrs(o):
     return (dptr(o["support_cost"]), dptr(o["dense_cost"]), dptr(o["min_clearance"]), iptr(o["worst"]),
             iptr(o["out_of_range"]))
+
+
+def _self_ptrs(o):
+    return (dptr(o["self_support_cost"]), dptr(o["self_dense_cost"]), dptr(o["min_self_clearance"]), iptr(o["worst"]),
+            iptr(o["invalid"]))
 
 
 def _kappa_arg(kappa):
@@ -549,6 +555,46 @@ class Engine:
                                               int(bool(require_in_range)), C.byref(best), C.byref(n)))
         return best.value, n.value
 
+    # ---------------------------------------------------------------- self-collision check (include/gpmp2mi.h)
+    def _pairs_handle(self, out):
+        h = _Handle(out, self.lib.gpmp2mi_self_pairs_destroy)
+        h.P = int(self.lib.gpmp2mi_self_pairs_count(out))
+        h.data = np.zeros((h.P, 4))
+        self._ck(self.lib.gpmp2mi_self_pairs_get(out, dptr(h.data)))
+        return h
+
+    def self_pairs(self, robot, data):
+        """A device-resident pair table for `robot` from data [P][4] = (sphere A, sphere B, epsilon, sigma): a handle
+        with .P and .data.  An empty table is fine."""
+        t = scoring.pair_table(data, getattr(robot, "S", None))
+        out = C.c_void_p()
+        self._ck(self.lib.gpmp2mi_self_pairs_create(robot.ptr, t.shape[0], dptr(t), C.byref(out)))
+        return self._pairs_handle(out)
+
+    def generate_self_pairs(self, robot, min_joint_gap=2, ref_conf=None, epsilon=0.0, sigma=1.0):
+        """The table of all sphere pairs whose links are at least min_joint_gap joints apart in the robot's kinematic
+        tree, less those that overlap at any of the reference configurations ref_conf [n][D] (None: none given)."""
+        if int(min_joint_gap) < 1:
+            raise ValueError("min_joint_gap must be >= 1")
+        ref = np.zeros((0, robot.dof)) if ref_conf is None else f64(ref_conf).reshape(-1, robot.dof)
+        out = C.c_void_p()
+        self._ck(self.lib.gpmp2mi_self_pairs_generate(robot.ptr, int(min_joint_gap), ref.shape[0], dptr(ref),
+                                                      float(epsilon), float(sigma), C.byref(out)))
+        return self._pairs_handle(out)
+
+    def self_score_traj(self, robot, pairs, delta_t, inter_step, traj, out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) -> dict(self_support_cost [B], self_dense_cost [B], min_self_clearance [B],
+        worst [B][2] = (checked state, row of the table), invalid [B]) of the inter_step-up-sampled trajectories."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        o = scoring.score_outputs(B, out, scoring.SELF_NAMES)
+        self._ck(self.lib.gpmp2mi_self_score_traj(robot.ptr, pairs.ptr, float(delta_t), inter_step, B, N, dptr(t),
+                                                  *_self_ptrs(o)))
+        return o
+
     # ---------------------------------------------------------------- plans
     def plan(self, robot, sdf, setting, B, forms=None):
         return Plan(self, robot, sdf, setting, B, forms)
@@ -813,6 +859,51 @@ class Plan:
                 _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
         self.eng._ck(self.eng.lib.gpmp2mi_plan_select_dev(self.h.ptr, inter_step, float(required_clearance),
                                                           int(bool(require_in_range)), *args, C.c_void_p(stream or 0)))
+
+    # ---- the same against the robot itself (include/gpmp2mi.h "self-collision check")
+    def self_score(self, pairs, inter_step, out=None):
+        """dict(self_support_cost, self_dense_cost, min_self_clearance, worst, invalid) of the plan's result, B rows."""
+        inter_step = _score_args(inter_step)
+        o = scoring.score_outputs(self.B, out, scoring.SELF_NAMES)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_self_score(self.h.ptr, pairs.ptr, inter_step, *_self_ptrs(o)))
+        return o
+
+    def self_score_dev(self, pairs, inter_step, self_support_cost=None, self_dense_cost=None, min_self_clearance=None,
+                       worst=None, invalid=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        B = self.B
+        args = [_dev_arg("self_support_cost", self_support_cost, (B,)), _dev_arg("self_dense_cost", self_dense_cost, (B,)),
+                _dev_arg("min_self_clearance", min_self_clearance, (B,)), _dev_arg("worst", worst, (B, 2), True),
+                _dev_arg("invalid", invalid, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_self_score_dev(self.h.ptr, pairs.ptr, _score_args(inter_step), *args,
+                                                              C.c_void_p(stream or 0)))
+
+    def select_checked(self, inter_step, pairs, required_clearance=0.0, require_in_range=False,
+                       required_self_clearance=0.0):
+        """select() with the rule that also asks for required_self_clearance against the pairs of `pairs` and no invalid
+        pair: dict(best, n_eligible, traj_best, dense_best); best = -1: the two trajectories are None."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D))
+        best, n = C.c_int(-1), C.c_int(0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_checked(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)), pairs.ptr,
+            float(required_self_clearance), C.byref(best), C.byref(n), dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_checked_dev(self, inter_step, pairs, required_clearance=0.0, require_in_range=False,
+                           required_self_clearance=0.0, best=None, n_eligible=None, traj_best=None, dense_best=None,
+                           stream=None):
+        """The same with device outputs, as select_dev.  One enqueue on `stream`, no host synchronisation."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_checked_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)), pairs.ptr,
+            float(required_self_clearance), *args, C.c_void_p(stream or 0)))
 
     def graph_error(self, traj):
         t = f64(traj).reshape(self.B, self.N + 1, 2 * self.D)

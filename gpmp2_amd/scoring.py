@@ -13,8 +13,11 @@ def checked_states(total_step, inter_step):
     return int(total_step) * (int(inter_step) + 1) + 1
 
 
-def eligible(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False):
-    """Boolean mask [B] of the rows the rule may choose (status None: all fine; out_of_range None: all in range)."""
+def eligible(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+             min_self_clearance=None, invalid=None, required_self_clearance=0.0):
+    """Boolean mask [B] of the rows the rule may choose (status None: all fine; out_of_range None: all in range).
+    min_self_clearance / invalid (include/gpmp2mi.h "self-collision check"): the row must also keep
+    required_self_clearance from itself and have no invalid pair; None: not asked."""
     fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
     clr = np.asarray(min_clearance, dtype=np.float64).reshape(-1)
     ok = np.isfinite(fe)
@@ -24,13 +27,20 @@ def eligible(final_error, status, min_clearance, out_of_range, required_clearanc
         ok &= clr >= required_clearance          # False for a NaN clearance
     if require_in_range and out_of_range is not None:
         ok &= np.asarray(out_of_range).reshape(-1) == 0
+    if min_self_clearance is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= np.asarray(min_self_clearance, dtype=np.float64).reshape(-1) >= required_self_clearance
+    if invalid is not None:
+        ok &= np.asarray(invalid).reshape(-1) == 0
     return ok
 
 
-def select_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False):
+def select_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+                min_self_clearance=None, invalid=None, required_self_clearance=0.0):
     """(best, n_eligible): the eligible row with the smallest final_error, the lowest row on ties; (-1, 0) if none."""
     fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range)
+    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+                  invalid, required_self_clearance)
     rows = np.flatnonzero(ok)
     if rows.size == 0:
         return -1, 0
@@ -63,11 +73,33 @@ def traj_rows(traj, D, total_step=None):
     return t
 
 
-def score_outputs(B, out=None):
+SCORE_NAMES = ("support_cost", "dense_cost", "min_clearance", "worst", "out_of_range")
+SELF_NAMES = ("self_support_cost", "self_dense_cost", "min_self_clearance", "worst", "invalid")
+
+
+def pair_table(data, S=None):
+    """A pair table as contiguous float64 [P][4] (sphere A, sphere B, epsilon, sigma); [P][2] / [P][3] rows are completed
+    with epsilon 0, sigma 1.  ValueError for another shape, or (S given) ids that are not distinct integers in [0, S)."""
+    t = np.asarray(data, dtype=np.float64)
+    if t.size == 0:
+        return np.zeros((0, 4))
+    if t.ndim != 2 or t.shape[1] not in (2, 3, 4):
+        raise ValueError(f"pair table: expected [P][4], got {list(t.shape)}")
+    full = np.zeros((t.shape[0], 4))
+    full[:, 3] = 1.0
+    full[:, :t.shape[1]] = t
+    ids = full[:, :2]
+    if S is not None and not ((ids == np.floor(ids)).all() and (ids >= 0).all() and (ids < S).all()
+                              and (ids[:, 0] != ids[:, 1]).all()):
+        raise ValueError(f"pair table: sphere ids must be distinct integers in [0, {S})")
+    return np.ascontiguousarray(full)
+
+
+def score_outputs(B, out=None, names=SCORE_NAMES):
     """The five per-row outputs of a score call: fresh arrays, or the caller's (a dict with any of the five names),
-    checked for dtype, contiguity and length."""
-    want = dict(support_cost=((B,), np.float64), dense_cost=((B,), np.float64), min_clearance=((B,), np.float64),
-                worst=((B, 2), np.int32), out_of_range=((B,), np.int32))
+    checked for dtype, contiguity and length.  names: SCORE_NAMES, or SELF_NAMES for the self-collision check."""
+    shapes = (((B,), np.float64), ((B,), np.float64), ((B,), np.float64), ((B, 2), np.int32), ((B,), np.int32))
+    want = dict(zip(names, shapes))
     res = {}
     out = out or {}
     unknown = set(out) - set(want)

@@ -496,6 +496,80 @@ int gpmp2mi_multi_plan_score(gpmp2mi_multi_plan* m, int inter_step, double* supp
 int gpmp2mi_multi_plan_select(gpmp2mi_multi_plan* m, int inter_step, double required_clearance, int require_in_range,
                               int* best, int* n_eligible, double* traj_best, double* dense_best);
 
+/* ---- self-collision check: the executed trajectory against the robot itself, on the device ----------------------
+ * The calls of "scoring" test the body spheres against the signed-distance field only, and the in-plan SelfCollision
+ * factor holds at most GPMP2MI_MAX_SELF_COLLISION_PAIRS rows on support states.  These calls test every checked state
+ * of "scoring" against a pair table of any size, and let the selection ask for both clearances.
+ *
+ * Definitions:
+ *  - Pair table: data [P][4] doubles, the matrix of gpmp2::SelfCollision (obstacle/SelfCollision.h:39-45) that
+ *    gpmp2mi_self_collision_factor takes: sphere A id, sphere B id (ids in the order of the robot description), epsilon,
+ *    sigma.  Column 3 is not read.  total_eps_p = radius_A + radius_B + epsilon_p, evaluated in that order on the host
+ *    in fp64 (SelfCollision.h:89).
+ *  - Checked states: exactly those of "scoring" for one trajectory, delta_t and inter_step = J: Md = N (J+1) + 1 states;
+ *    Pose2 robot kinds go through the Pose2 interpolator; only the configuration half is used.
+ *  - For checked state k and pair p: dist = |c_A - c_B| with the centres of sphereCenters(conf_k);
+ *    clearance(k, p) = dist - total_eps_p; hinge = dist > total_eps_p ? 0 : total_eps_p - dist (SelfCollision.h:114-127).
+ *    A pair whose dist is not finite is invalid: it adds nothing to the sums or the minimum, and it is counted.
+ *  - self_support_cost [B]: the hinge sum over support states = the sum of the unwhitened
+ *    gpmp2mi_self_collision_factor errors at those states.  self_dense_cost [B]: the same sum over all Md states.
+ *    min_self_clearance [B]: min of clearance(k, p) over the valid (k, p), +inf if there is none.  worst [B][2]: the
+ *    (k, p) attaining it, p the row of the caller's table; on exact ties the lowest k, then the lowest p; (-1, -1) if
+ *    none.  invalid [B]: number of invalid (k, p).  Any output may be NULL.
+ *  - Determinism as in "scoring": a row's results are a function of that row, the robot, the table, delta_t and J alone;
+ *    sums are taken in an order fixed by (N, J, S, P) and the table's order, without floating-point atomics: a row scores
+ *    bit-identically alone, in any batch, through the trajectory form or the plan form.
+ *  - Selection: the rule of "scoring" with one more condition,
+ *      eligible(b) = <the rule of "scoring"> && invalid[b] == 0 && min_self_clearance[b] >= required_self_clearance;
+ *    everything else as there, the lowest row on ties included.
+ * Errors: GPMP2MI_ERR_INVALID (checked before any device work) for a NULL argument, the argument errors of "scoring",
+ * and a table made for a robot with another sphere count, dof or kind.
+ * Memory: the workspace rules of "scoring".  A plan keeps the records (one 40-byte record per tile of checked states of
+ * every row: 64 states for S <= 32 spheres, 32 for S <= 64, 16 above) with the staging of its host-pointer forms, taken
+ * at the first call and kept; gpmp2mi_self_score_traj_dev keeps them with the PAIR TABLE, not with the robot handle, so
+ * calls that share a table belong on one stream, or in stream order.
+ * Not here: gpmp2mi_multi_plan_* twins, a self-collision term in the risk / collision-probability calls. */
+typedef struct gpmp2mi_self_pairs gpmp2mi_self_pairs;   /* device-resident table, bound to the robot's sphere model */
+
+/* GPMP2MI_ERR_INVALID, before any device work, for a NULL argument, P < 0, an id that is not an integer in
+ * [0, nr_spheres), or A == B.  P == 0 is a valid, empty table (data may be NULL): every row then has costs 0,
+ * clearance +inf and worst (-1, -1).  A non-empty table lives on the current device, which must be the robot's. */
+int gpmp2mi_self_pairs_create(const gpmp2mi_robot* robot, int P, const double* data /*[P][4]*/, gpmp2mi_self_pairs** out);
+/* All pairs A < B, in lexicographic order, whose links are at least min_joint_gap (>= 1) joints apart in the kinematic
+ * tree of the robot's kind: link 0 is the vehicle of the mobile kinds, link 1 the torso of the lift kinds, the first
+ * links of both arms of a two-arm kind are children of the same parent; for a fixed-base arm the distance is the
+ * difference of the link indices; a point robot yields no pair.  Less the pairs whose clearance with epsilon 0 is
+ * negative at any of the n_ref reference configurations ref_conf [n_ref][D] (n_ref may be 0): spheres that overlap by
+ * construction.  Every row gets (epsilon, sigma). */
+int gpmp2mi_self_pairs_generate(const gpmp2mi_robot* robot, int min_joint_gap, int n_ref, const double* ref_conf,
+                                double epsilon, double sigma, gpmp2mi_self_pairs** out);
+int gpmp2mi_self_pairs_count(const gpmp2mi_self_pairs* pairs);   /* -1 for NULL */
+int gpmp2mi_self_pairs_get(const gpmp2mi_self_pairs* pairs, double* data /*[P][4]*/);
+void gpmp2mi_self_pairs_destroy(gpmp2mi_self_pairs* pairs);      /* NULL: no-op */
+
+/* caller buffers; traj [B][total_step+1][2D].  The device of the robot handle and the table must be current. */
+int gpmp2mi_self_score_traj(const gpmp2mi_robot* robot, const gpmp2mi_self_pairs* pairs, double delta_t, int inter_step,
+                            int B, int total_step, const double* traj, double* self_support_cost,
+                            double* self_dense_cost, double* min_self_clearance, int* worst, int* invalid);
+int gpmp2mi_self_score_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_self_pairs* pairs, double delta_t,
+                                int inter_step, int B, int total_step, const double* traj, double* self_support_cost,
+                                double* self_dense_cost, double* min_self_clearance, int* worst, int* invalid,
+                                void* stream);
+/* The plan's resident result; preconditions and errors as gpmp2mi_plan_score. */
+int gpmp2mi_plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* pairs, int inter_step, double* self_support_cost,
+                            double* self_dense_cost, double* min_self_clearance, int* worst, int* invalid);
+int gpmp2mi_plan_self_score_dev(gpmp2mi_plan* p, const gpmp2mi_self_pairs* pairs, int inter_step,
+                                double* self_support_cost, double* self_dense_cost, double* min_self_clearance,
+                                int* worst, int* invalid, void* stream);
+/* gpmp2mi_plan_select with the extended rule, one enqueue: the obstacle scores, the self scores, then one finish that
+ * reads both.  Outputs as gpmp2mi_plan_select. */
+int gpmp2mi_plan_select_checked(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                const gpmp2mi_self_pairs* pairs, double required_self_clearance, int* best,
+                                int* n_eligible, double* traj_best, double* dense_best);
+int gpmp2mi_plan_select_checked_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                    const gpmp2mi_self_pairs* pairs, double required_self_clearance, int* best,
+                                    int* n_eligible, double* traj_best, double* dense_best, void* stream);
+
 /* ---- factor-level entry points (the GTSAM plug-in contract: evaluateError(x..., H...)) -----
  * All batched over M independent evaluations, host pointers, Jacobian outputs may be NULL. */
 

@@ -21,6 +21,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -560,6 +561,94 @@ inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int
         "gpmp2mi_select_best");
   if (n_eligible) *n_eligible = static_cast<std::size_t>(n);
   return best;
+}
+
+/// A pair table of the self-collision check (include/gpmp2mi.h "self-collision check"), resident on the device and bound
+/// to the sphere model of `robot`: rows (sphere A, sphere B, epsilon, sigma) as gpmp2::SelfCollision takes them, or
+/// generated from the robot's kinematic tree (all pairs at least min_joint_gap joints apart, less those that overlap at
+/// a reference configuration).  Move-only.
+class SelfCollisionPairs {
+ public:
+  template <class ROBOT>
+  SelfCollisionPairs(const ROBOT& robot, const Vector& data_row_major) {
+    if (data_row_major.size() % 4) throw std::runtime_error("[SelfCollisionPairs] data must have 4 columns");
+    check(gpmp2mi_self_pairs_create(robot.handle(), static_cast<int>(data_row_major.size() / 4), data_row_major.data(), &h_),
+          "gpmp2mi_self_pairs_create");
+  }
+  /// ref_conf: n reference configurations back to back (may be empty)
+  template <class ROBOT>
+  static SelfCollisionPairs Generate(const ROBOT& robot, int min_joint_gap = 2, const Vector& ref_conf = {},
+                                     double epsilon = 0.0, double sigma = 1.0) {
+    if (ref_conf.size() % robot.dof()) throw std::runtime_error("[SelfCollisionPairs] ref_conf does not fit the dof");
+    SelfCollisionPairs t;
+    check(gpmp2mi_self_pairs_generate(robot.handle(), min_joint_gap, static_cast<int>(ref_conf.size() / robot.dof()),
+                                      ref_conf.empty() ? nullptr : ref_conf.data(), epsilon, sigma, &t.h_),
+          "gpmp2mi_self_pairs_generate");
+    return t;
+  }
+  SelfCollisionPairs(SelfCollisionPairs&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  SelfCollisionPairs& operator=(SelfCollisionPairs&& o) noexcept {
+    if (this != &o) {
+      gpmp2mi_self_pairs_destroy(h_);
+      h_ = o.h_;
+      o.h_ = nullptr;
+    }
+    return *this;
+  }
+  SelfCollisionPairs(const SelfCollisionPairs&) = delete;
+  SelfCollisionPairs& operator=(const SelfCollisionPairs&) = delete;
+  ~SelfCollisionPairs() { gpmp2mi_self_pairs_destroy(h_); }
+  std::size_t size() const { return static_cast<std::size_t>(gpmp2mi_self_pairs_count(h_)); }
+  /// the rows, [size()][4] row-major
+  Vector data() const {
+    Vector d(size() * 4);
+    check(gpmp2mi_self_pairs_get(h_, d.data()), "gpmp2mi_self_pairs_get");
+    return d;
+  }
+  const gpmp2mi_self_pairs* handle() const { return h_; }
+
+ private:
+  SelfCollisionPairs() = default;
+  gpmp2mi_self_pairs* h_ = nullptr;
+};
+
+/// What the executed trajectory looks like to the robot itself: the SelfCollision hinge summed over the support states
+/// and over the up-sampled states, the smallest pair clearance with the checked state and table row where it occurs
+/// ((-1, -1) and +inf for an empty table) and the number of (state, pair)s whose distance is not finite.
+struct TrajectorySelfScore {
+  double support_cost = 0.0, dense_cost = 0.0, min_clearance = 0.0;
+  int worst_state = -1, worst_pair = -1, invalid = 0;
+};
+template <class ROBOT>
+inline TrajectorySelfScore SelfScoreTrajectory(const ROBOT& robot, const SelfCollisionPairs& pairs, const Trajectory& result,
+                                               const TrajOptimizerSetting& setting, std::size_t inter_step) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[SelfScoreTrajectory] result does not match dof / total_step");
+  TrajectorySelfScore sc;
+  int worst[2] = {-1, -1};
+  check(gpmp2mi_self_score_traj(robot.handle(), pairs.handle(), setting.total_time / static_cast<double>(setting.total_step),
+                                static_cast<int>(inter_step), 1, static_cast<int>(result.total_step), result.data.data(),
+                                &sc.support_cost, &sc.dense_cost, &sc.min_clearance, worst, &sc.invalid),
+        "gpmp2mi_self_score_traj");
+  sc.worst_state = worst[0];
+  sc.worst_pair = worst[1];
+  return sc;
+}
+/// SelectBestTrajectory that also looks at the robot itself: a result is eligible when the SMALLER of its two clearances
+/// (obstacles, itself) reaches required_clearance and none of its pairs is invalid; the rest as above.  Host code.
+inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int>& status,
+                                const std::vector<TrajectoryScore>& scores, const std::vector<TrajectorySelfScore>& self_scores,
+                                double required_clearance = 0.0, bool require_in_range = false,
+                                std::size_t* n_eligible = nullptr) {
+  if (self_scores.size() != scores.size())
+    throw std::runtime_error("[SelectBestTrajectory] scores and self_scores differ in length");
+  std::vector<TrajectoryScore> both(scores);
+  for (std::size_t b = 0; b < both.size(); b++) {
+    // std::min keeps a NaN first argument, and a NaN clearance is never eligible
+    both[b].min_clearance = self_scores[b].invalid != 0 ? std::nan("") : std::min(scores[b].min_clearance, self_scores[b].min_clearance);
+    if (self_scores[b].min_clearance != self_scores[b].min_clearance) both[b].min_clearance = std::nan("");
+  }
+  return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
 }
 
 namespace internal {
