@@ -169,6 +169,24 @@ def declare_self(lib):
     lib.gpmp2mi_self_pairs_destroy.restype = None
 
 
+def declare_group(lib):
+    """include/gpmp2mi.h "distinct alternatives"; `weights` is a host array in every form"""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_traj_distances": [i, i, i, d, d, i, d],
+        "gpmp2mi_traj_distances_dev": [i, i, i, vp, d, i, vp, vp],
+        "gpmp2mi_group_rows": [i, d, d, ip, f, ip, ip, ip, ip],
+        "gpmp2mi_group_rows_dev": [i, vp, vp, vp, f] + [vp] * 5,
+        "gpmp2mi_group_traj": [i, i, i, d, d, i, f, d, ip, ip, ip, ip, ip],
+        "gpmp2mi_group_traj_dev": [i, i, i, vp, d, i, f] + [vp] * 7,
+        "gpmp2mi_plan_select_distinct": [vp, i, f, i, vp, f, i, d, f, i, ip, ip, ip, ip, d, ip, d, d],
+        "gpmp2mi_plan_select_distinct_dev": [vp, i, f, i, vp, f, i, d, f, i] + [vp] * 9,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def declare_posterior(lib):
     """argtypes of the posterior entry points (include/gpmp2mi.h "posterior"); the `_dev` forms take device addresses."""
     vp, i, d, ip = C.c_void_p, C.c_int, c_double_p, c_int_p

@@ -308,6 +308,10 @@ struct gpmp2mi_plan {
   // the staging of the host-pointer forms, taken at the first self_score / select_checked call and kept
   void* self_ws = nullptr;
   size_t self_ws_bytes = 0;
+  // distinct alternatives (group.hip): the bit matrix of k_traj_pairs, the per-row scores the rule reads, what
+  // k_group_rule leaves and the staging of the host-pointer form, taken at the first select_distinct call and kept
+  void* group_ws = nullptr;
+  size_t group_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -418,6 +422,13 @@ struct ScoreSel {
 // host: the outputs are host arrays (staged in the plan's scoring workspace, copied back, `st` synchronised);
 // otherwise device pointers, and the call returns without a host synchronisation.
 int plan_score(gpmp2mi_plan* p, int inter, const ScoreOut& out, const ScoreSel* sel, bool host, hipStream_t st);
+// self_score.hip: the same for the self-collision check against `t` (out.oor: invalid); sel adds k_score for the same
+// rows and the rule with both clearances
+struct SelfSel : ScoreSel {
+  double required_self_clearance = 0.0;
+};
+int plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, const ScoreOut& out, const SelfSel* sel,
+                    bool host, hipStream_t st);
 // the argument rules the score calls share (inter_step, B, total_step, delta_t, the launch limits)
 int check_score_args(int inter, int B, int total_step, double delta_t);
 // B comparisons on the host: the rule of gpmp2mi_select_best

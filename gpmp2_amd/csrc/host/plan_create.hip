@@ -96,6 +96,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (risk_qc) (void)hipFree(risk_qc);
   if (sampled_ws) (void)hipFree(sampled_ws);
   if (self_ws) (void)hipFree(self_ws);
+  if (group_ws) (void)hipFree(group_ws);
   sampled_fac.release();
   flags_release(qflags);
 }

@@ -73,13 +73,11 @@ PlanSelfWs plan_ws_layout(char* base, int B, int N, int D, int S, int inter) {
   return w;
 }
 
-struct SelfSel : ScoreSel {
-  double required_self_clearance = 0.0;
-};
+}  // namespace
 
 // Scores the plan's resident result against `t` on `st`; sel != null: k_score for the same rows first, then the rule
 // with both clearances and the copy of the chosen row.  host / out / sel as plan_score (score.hip); out.oor: invalid.
-int plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, const ScoreOut& out, const SelfSel* sel,
+int g2::plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, const ScoreOut& out, const SelfSel* sel,
                     bool host, hipStream_t st) {
   G2_CHECK(p && t, GPMP2MI_ERR_INVALID, "null argument");
   G2_PLAN_LIVE(p);   // before anything is enqueued
@@ -155,6 +153,8 @@ int plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, con
   p->mark_clean(st);
   return GPMP2MI_OK;
 }
+
+namespace {
 
 // the table as the kernels read it: sorted-order sphere indices and total_eps
 int upload_pairs(const gpmp2mi_robot* r, gpmp2mi_self_pairs* t) {

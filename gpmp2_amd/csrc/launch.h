@@ -99,6 +99,52 @@ int launch_self_clearance(const RobotDev& h, const RobotDev* R, const SelfPair* 
                           int N, const double* traj, ScoreRec* recs, hipStream_t st);
 int launch_self_finish(const SelfFinish& a, hipStream_t st);
 
+// group_kernels.hip (include/gpmp2mi.h "distinct alternatives")
+constexpr int GROUP_TILE = 64;          // k_traj_pairs: one workgroup per 64 x 64 tile of pairs
+constexpr int GROUP_CHUNK_ELEMS = 32;   // configuration doubles of a row staged through LDS at a time
+// support states per LDS chunk: whole states only, so that s_i closes inside a chunk
+constexpr int group_chunk_states(int D) { return D >= GROUP_CHUNK_ELEMS ? 1 : GROUP_CHUNK_ELEMS / D; }
+// arguments of k_traj_pairs; dist [B][B] and bits [B][ceil(B/64)] are both optional
+struct PairArgs {
+  int B, N, D, metric;
+  const double* traj;           // [B][N+1][2D]
+  double w[GPMP2MI_MAX_DOF];    // the weights, 1 where the caller gave none
+  double radius;
+  double* dist;
+  unsigned long long* bits;
+};
+int launch_traj_pairs(const PairArgs& a, hipStream_t st);
+// arguments of k_group_rule (one workgroup).  Adjacency: `bits`, or dist <= radius for a given matrix.  Eligibility:
+// `eligible` (null: all 1), or with `plan_rule` the rule of "scoring" over status / ferr (= score) / clearance / oor,
+// extended by the self scores when self_clearance is given.  Every output may be null.
+struct GroupRule {
+  int B, plan_rule, require_in_range;
+  double radius, required_clearance, required_self_clearance;
+  const double* dist;
+  const unsigned long long* bits;
+  const double* score;
+  const int* eligible;
+  const int* status;
+  const double* clearance;
+  const int* oor;
+  const double* self_clearance;
+  const int* self_invalid;
+  int *mode, *leaders, *sizes, *n_modes, *n_eligible;
+};
+int launch_group_rule(const GroupRule& a, hipStream_t st);
+// arguments of k_group_copy: one workgroup per alternative, reading what k_group_rule left
+struct GroupCopy {
+  int N, D, lie, inter, Md, max_alt;
+  double dt;
+  const double* traj;   // [B][N+1][2D]
+  const double* ferr;
+  const int *leaders, *sizes, *n_modes, *n_eligible;
+  int *out_n_modes, *out_n_eligible;   // the caller's copies of the two counts
+  int *alt, *alt_size;
+  double *alt_error, *traj_alt, *dense_alt;
+};
+int launch_group_copy(const GroupCopy& a, hipStream_t st);
+
 // risk_kernels.hip
 // what one workgroup of k_risk leaves for k_risk_finish; k = s = INT_MAX: no pair of the tile was in range
 struct RiskRec {

@@ -140,8 +140,8 @@ __global__ __launch_bounds__(256) void k_score_finish(ScoreFinish a) {
     }
     if (!a.select) continue;
     const double fe = a.ferr[b];
-    const bool ok = (!a.status || a.status[b] != GPMP2MI_TRAJ_NOT_SPD) && isfinite(fe) && clr >= a.required_clearance &&
-                    (!a.require_in_range || oor == 0);
+    const bool ok = score_eligible(!a.status || a.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, clr, a.required_clearance,
+                                   a.require_in_range, oor);
     if (!ok) continue;
     my_cnt++;
     if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row

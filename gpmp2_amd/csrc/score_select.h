@@ -20,6 +20,12 @@ __device__ __forceinline__ bool key_less(const ScoreKey& a, const ScoreKey& b) {
   return a.c < b.c || (a.c == b.c && (a.k < b.k || (a.k == b.k && a.s < b.s)));
 }
 
+// eligible(b) of "scoring" (include/gpmp2mi.h) for one row; status_ok: status[b] != GPMP2MI_TRAJ_NOT_SPD, or no status
+__device__ __forceinline__ bool score_eligible(bool status_ok, double final_error, double clearance,
+                                               double required_clearance, int require_in_range, int oor) {
+  return status_ok && isfinite(final_error) && clearance >= required_clearance && (!require_in_range || oor == 0);
+}
+
 // the nblk records of one row, in index order
 __device__ __forceinline__ ScoreRec reduce_records(const ScoreRec* r, int nblk) {
   ScoreRec t = r[0];

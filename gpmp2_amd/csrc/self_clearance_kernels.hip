@@ -151,9 +151,9 @@ __global__ __launch_bounds__(256) void k_self_finish(SelfFinish a) {
     if (!f.select) continue;
     const ScoreRec o = reduce_records(f.recs + (size_t)b * f.nblk, f.nblk);
     const double fe = f.ferr[b];
-    const bool ok = (!f.status || f.status[b] != GPMP2MI_TRAJ_NOT_SPD) && isfinite(fe) &&
-                    o.clearance >= f.required_clearance && (!f.require_in_range || o.oor == 0) && t.oor == 0 &&
-                    t.clearance >= a.required_self_clearance;
+    const bool ok = score_eligible(!f.status || f.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, o.clearance,
+                                   f.required_clearance, f.require_in_range, o.oor) &&
+                    t.oor == 0 && t.clearance >= a.required_self_clearance;
     if (!ok) continue;
     my_cnt++;
     if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row

@@ -43,6 +43,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_multi(lib)
     _capi.declare_score(lib)
     _capi.declare_self(lib)
+    _capi.declare_group(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
     _capi.declare_seed(lib)
@@ -595,6 +596,74 @@ class Engine:
                                                   *_self_ptrs(o)))
         return o
 
+    # ---------------------------------------------------------------- distinct alternatives (include/gpmp2mi.h)
+    def traj_distances(self, dof, traj, weights=None, metric=scoring.DIST_MAX_STATE):
+        """traj [B][N+1][2 dof] -> dist [B][B] between the configuration halves (scoring.DIST_MAX_STATE / DIST_RMS)."""
+        t = scoring.traj_rows(traj, dof)
+        w, metric = scoring.group_weights(weights, dof), scoring.group_metric(metric)
+        B, N = t.shape[0], t.shape[1] - 1
+        dist = np.zeros((B, B))
+        self._ck(self.lib.gpmp2mi_traj_distances(dof, B, N, dptr(t), dptr(w), metric, dptr(dist)))
+        return dist
+
+    def traj_distances_dev(self, dof, B, total_step, traj, dist, weights=None, metric=scoring.DIST_MAX_STATE, stream=None):
+        """The same between device buffers (torch tensors or raw pointers); weights stays a host array."""
+        w, metric = scoring.group_weights(weights, dof), scoring.group_metric(metric)
+        B, N = int(B), int(total_step)
+        args = [_dev_arg("traj", traj, (B, N + 1, 2 * dof)), dptr(w), metric, _dev_arg("dist", dist, (B, B))]
+        self._ck(self.lib.gpmp2mi_traj_distances_dev(dof, B, N, *args, C.c_void_p(stream or 0)))
+
+    def group_rows(self, dist, score, eligible=None, radius=0.0):
+        """The leader rule (scoring.group_rule states it) on a given matrix; host arrays, no device needed:
+        dict(mode [B], leaders [B], sizes [B], n_modes)."""
+        B = int(np.shape(score)[0]) if np.ndim(score) == 1 else -1
+        sc, el, d = scoring.group_inputs(B, score, eligible, dist, limit=False)
+        radius = scoring.group_radius(radius)
+        o, n = scoring.group_outputs(B), C.c_int(0)
+        self._ck(self.lib.gpmp2mi_group_rows(B, dptr(d), dptr(sc), iptr(el), radius, iptr(o["mode"]), iptr(o["leaders"]),
+                                             iptr(o["sizes"]), C.byref(n)))
+        o["n_modes"] = n.value
+        return o
+
+    def group_rows_dev(self, B, dist, score, eligible=None, radius=0.0, mode=None, leaders=None, sizes=None, n_modes=None,
+                       stream=None):
+        """The same on device buffers, one kernel: dist [B][B], score [B], eligible int32 [B] or None; outputs int32
+        mode / leaders / sizes [B], n_modes [1], any may be None."""
+        B = int(B)
+        if B > scoring.MAX_GROUP_ROWS:
+            raise ValueError(f"at most {scoring.MAX_GROUP_ROWS} rows can be grouped, got {B}")
+        args = [_dev_arg("dist", dist, (B, B)), _dev_arg("score", score, (B,)), _dev_arg("eligible", eligible, (B,), True),
+                scoring.group_radius(radius), _dev_arg("mode", mode, (B,), True), _dev_arg("leaders", leaders, (B,), True),
+                _dev_arg("sizes", sizes, (B,), True), _dev_arg("n_modes", n_modes, (1,), True)]
+        self._ck(self.lib.gpmp2mi_group_rows_dev(B, *args, C.c_void_p(stream or 0)))
+
+    def group_traj(self, dof, traj, score, eligible=None, radius=0.0, weights=None, metric=scoring.DIST_MAX_STATE):
+        """Distances and rule on the device, without the [B][B] matrix: dict(mode, leaders, sizes, n_modes)."""
+        t = scoring.traj_rows(traj, dof)
+        w, metric = scoring.group_weights(weights, dof), scoring.group_metric(metric)
+        B, N = t.shape[0], t.shape[1] - 1
+        sc, el = scoring.group_inputs(B, score, eligible)
+        radius = scoring.group_radius(radius)
+        o, n = scoring.group_outputs(B), C.c_int(0)
+        self._ck(self.lib.gpmp2mi_group_traj(dof, B, N, dptr(t), dptr(w), metric, radius, dptr(sc), iptr(el),
+                                             iptr(o["mode"]), iptr(o["leaders"]), iptr(o["sizes"]), C.byref(n)))
+        o["n_modes"] = n.value
+        return o
+
+    def group_traj_dev(self, dof, B, total_step, traj, score, eligible=None, radius=0.0, weights=None,
+                       metric=scoring.DIST_MAX_STATE, mode=None, leaders=None, sizes=None, n_modes=None, stream=None):
+        """The same on device buffers.  The bit matrix is allocated and freed inside the call: one synchronising
+        allocation per call."""
+        w, metric = scoring.group_weights(weights, dof), scoring.group_metric(metric)
+        B, N = int(B), int(total_step)
+        if B > scoring.MAX_GROUP_ROWS:
+            raise ValueError(f"at most {scoring.MAX_GROUP_ROWS} rows can be grouped, got {B}")
+        args = [_dev_arg("traj", traj, (B, N + 1, 2 * dof)), dptr(w), metric, scoring.group_radius(radius),
+                _dev_arg("score", score, (B,)), _dev_arg("eligible", eligible, (B,), True),
+                _dev_arg("mode", mode, (B,), True), _dev_arg("leaders", leaders, (B,), True),
+                _dev_arg("sizes", sizes, (B,), True), _dev_arg("n_modes", n_modes, (1,), True)]
+        self._ck(self.lib.gpmp2mi_group_traj_dev(dof, B, N, *args, C.c_void_p(stream or 0)))
+
     # ---------------------------------------------------------------- plans
     def plan(self, robot, sdf, setting, B, forms=None):
         return Plan(self, robot, sdf, setting, B, forms)
@@ -904,6 +973,55 @@ class Plan:
         self.eng._ck(self.eng.lib.gpmp2mi_plan_select_checked_dev(
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)), pairs.ptr,
             float(required_self_clearance), *args, C.c_void_p(stream or 0)))
+
+    # ---- one representative per mode of the resident result (include/gpmp2mi.h "distinct alternatives")
+    def _distinct_args(self, inter_step, radius, weights, metric, max_alt):
+        max_alt = int(max_alt)
+        if not 1 <= max_alt <= scoring.MAX_ALTERNATIVES:
+            raise ValueError(f"max_alt must be in 1..{scoring.MAX_ALTERNATIVES}")
+        if self.B > scoring.MAX_GROUP_ROWS:
+            raise ValueError(f"at most {scoring.MAX_GROUP_ROWS} rows can be grouped, got {self.B}")
+        return (_score_args(inter_step), scoring.group_radius(radius), scoring.group_weights(weights, self.D),
+                scoring.group_metric(metric), max_alt)
+
+    def select_distinct(self, inter_step, radius, max_alt=8, required_clearance=0.0, require_in_range=False, pairs=None,
+                        required_self_clearance=0.0, weights=None, metric=scoring.DIST_MAX_STATE, fill=np.nan):
+        """Score, apply the rule of select() (of select_checked() when `pairs` is given), group the eligible rows by the
+        leader rule with final_error as the score, fetch one row per mode: dict(n_modes, n_eligible, alt [max_alt],
+        alt_size [max_alt], alt_error [max_alt], mode [B], traj_alt [max_alt][N+1][2D], dense_alt [max_alt][Md][2D]).
+        n_modes counts all modes; entries beyond min(n_modes, max_alt) are -1 / 0 / `fill`."""
+        inter_step, radius, w, metric, max_alt = self._distinct_args(inter_step, radius, weights, metric, max_alt)
+        Md = scoring.checked_states(self.N, inter_step)
+        nm, ne = C.c_int(0), C.c_int(0)
+        alt, size = np.full(max_alt, -1, dtype=np.int32), np.zeros(max_alt, dtype=np.int32)
+        err, mode = np.full(max_alt, float(fill)), np.full(self.B, -1, dtype=np.int32)
+        ta = np.full((max_alt, self.N + 1, 2 * self.D), float(fill))
+        da = np.full((max_alt, Md, 2 * self.D), float(fill))
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_distinct(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), metric, dptr(w), radius, max_alt,
+            C.byref(nm), C.byref(ne), iptr(alt), iptr(size), dptr(err), iptr(mode), dptr(ta), dptr(da)))
+        return dict(n_modes=nm.value, n_eligible=ne.value, alt=alt, alt_size=size, alt_error=err, mode=mode, traj_alt=ta,
+                    dense_alt=da)
+
+    def select_distinct_dev(self, inter_step, radius, max_alt=8, required_clearance=0.0, require_in_range=False,
+                            pairs=None, required_self_clearance=0.0, weights=None, metric=scoring.DIST_MAX_STATE,
+                            n_modes=None, n_eligible=None, alt=None, alt_size=None, alt_error=None, mode=None,
+                            traj_alt=None, dense_alt=None, stream=None):
+        """The same with device outputs (torch tensors or raw pointers, any may be None): n_modes / n_eligible int32 [1],
+        alt / alt_size int32 [max_alt], alt_error [max_alt], mode int32 [B], traj_alt [max_alt][N+1][2D], dense_alt
+        [max_alt][Md][2D].  weights stays a host array.  One enqueue on `stream`, no host synchronisation."""
+        inter_step, radius, w, metric, max_alt = self._distinct_args(inter_step, radius, weights, metric, max_alt)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("n_modes", n_modes, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("alt", alt, (max_alt,), True), _dev_arg("alt_size", alt_size, (max_alt,), True),
+                _dev_arg("alt_error", alt_error, (max_alt,)), _dev_arg("mode", mode, (self.B,), True),
+                _dev_arg("traj_alt", traj_alt, (max_alt, self.N + 1, 2 * self.D)),
+                _dev_arg("dense_alt", dense_alt, (max_alt, Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_distinct_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), metric, dptr(w), radius, max_alt,
+            *args, C.c_void_p(stream or 0)))
 
     def graph_error(self, traj):
         t = f64(traj).reshape(self.B, self.N + 1, 2 * self.D)

@@ -114,3 +114,91 @@ def score_outputs(B, out=None, names=SCORE_NAMES):
                              f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
         res[name] = x
     return res
+
+
+# ---- distinct alternatives (include/gpmp2mi.h): the grouping rule in numpy terms and the shape checks of its wrappers
+DIST_MAX_STATE, DIST_RMS = 0, 1
+MAX_GROUP_ROWS = 8192       # GPMP2MI_MAX_GROUP_ROWS
+MAX_ALTERNATIVES = 64       # GPMP2MI_MAX_ALTERNATIVES
+
+
+def group_rule(dist, score, eligible, radius):
+    """The leader rule: (mode [B], leaders [B], sizes [B], n_modes).  A row takes part iff it is eligible (None: all
+    are) and its score is finite; the participating rows are visited by ascending score, the lowest row on ties, and
+    each joins the first leader, in leader order, with dist[leader][row] <= radius, or becomes the next leader.  A NaN
+    distance is never within the radius.  mode is -1 for rows that do not take part; leaders is -1 and sizes 0 beyond
+    n_modes."""
+    sc = np.asarray(score, dtype=np.float64).reshape(-1)
+    B = sc.size
+    d = np.asarray(dist, dtype=np.float64).reshape(B, B)
+    part = np.isfinite(sc)
+    if eligible is not None:
+        part &= np.asarray(eligible).reshape(-1) != 0
+    mode = np.full(B, -1, dtype=np.int32)
+    leaders = np.full(B, -1, dtype=np.int32)
+    sizes = np.zeros(B, dtype=np.int32)
+    rows = np.flatnonzero(part)
+    order = rows[np.argsort(sc[rows], kind="stable")]   # stable: equal scores keep ascending rows
+    n = 0
+    for b in order:
+        with np.errstate(invalid="ignore"):
+            near = np.flatnonzero(d[leaders[:n], b] <= radius)
+        k = int(near[0]) if near.size else n
+        if k == n:
+            leaders[n] = b
+            n += 1
+        mode[b] = k
+        sizes[k] += 1
+    return mode, leaders, sizes, n
+
+
+def group_metric(metric):
+    """GPMP2MI_DIST_MAX_STATE / GPMP2MI_DIST_RMS from 0 / 1 or "max_state" / "rms"; ValueError otherwise."""
+    names = {"max_state": DIST_MAX_STATE, "rms": DIST_RMS}
+    m = names.get(metric, metric) if isinstance(metric, str) else metric
+    if m not in (DIST_MAX_STATE, DIST_RMS):
+        raise ValueError(f"metric: expected 0 / 'max_state' or 1 / 'rms', got {metric!r}")
+    return int(m)
+
+
+def group_weights(weights, D):
+    """weights as contiguous float64 [D] of finite values >= 0, or None; ValueError otherwise."""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (D,) or not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError(f"weights: expected [{D}] finite values >= 0, got {list(np.shape(weights))}")
+    return w
+
+
+def group_radius(radius):
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be >= 0")
+    return radius
+
+
+def group_inputs(B, score, eligible, dist=None, limit=True):
+    """score float64 [B], eligible int32 [B] or None, dist float64 [B][B] or None, contiguous; ValueError for other
+    shapes or, with `limit` (the forms that use the device), B > MAX_GROUP_ROWS."""
+    if limit and B > MAX_GROUP_ROWS:
+        raise ValueError(f"at most {MAX_GROUP_ROWS} rows can be grouped, got {B}")
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    if sc.shape != (B,):
+        raise ValueError(f"score: expected [{B}], got {list(sc.shape)}")
+    el = None
+    if eligible is not None:
+        el = np.ascontiguousarray(np.asarray(eligible) != 0, dtype=np.int32)
+        if el.shape != (B,):
+            raise ValueError(f"eligible: expected [{B}], got {list(el.shape)}")
+    if dist is None:
+        return sc, el
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    if d.shape != (B, B):
+        raise ValueError(f"dist: expected [{B}][{B}], got {list(d.shape)}")
+    return sc, el, d
+
+
+def group_outputs(B):
+    return dict(mode=np.full(B, -1, dtype=np.int32), leaders=np.full(B, -1, dtype=np.int32),
+                sizes=np.zeros(B, dtype=np.int32))

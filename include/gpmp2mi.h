@@ -570,6 +570,103 @@ int gpmp2mi_plan_select_checked_dev(gpmp2mi_plan* p, int inter_step, double requ
                                     const gpmp2mi_self_pairs* pairs, double required_self_clearance, int* best,
                                     int* n_eligible, double* traj_best, double* dense_best, void* stream);
 
+/* ---- distinct alternatives: how many different solutions the restarts found, one row per mode, on the device ------
+ * The calls of "scoring" answer with one row.  These calls say how many different trajectories a batch holds and hand
+ * over one representative of each, best first, without the trajectories leaving the device: the fallback when the
+ * best row is refused downstream, the count of modes, and the rows to run gpmp2mi_plan_risk /
+ * gpmp2mi_plan_collision_probability on.
+ *
+ * Definitions:
+ *  - Rows and metric.  A row is one trajectory [N+1][2D]; only the configuration half of each state is read.  For rows
+ *    b and c, state i and weights w[d] >= 0 (finite; NULL = all 1):
+ *      s_i(b, c) = sum over d = 0 .. D-1, ascending, of w[d] * (x_b[i][d] - x_c[i][d])^2
+ *    GPMP2MI_DIST_MAX_STATE: dist = sqrt(max_i s_i) -- two trajectories are "the same" if at every support state their
+ *    configurations are within `radius`: the metric to reason about in joint space.
+ *    GPMP2MI_DIST_RMS: dist = sqrt((sum over i, ascending, of s_i) / (N+1)).
+ *    No angle is wrapped: the theta of the Pose2 kinds is compared as stored, and a base that arrives a full turn
+ *    later is a different execution.
+ *  - dist is exactly symmetric; the diagonal and any pair of bit-identical finite rows are exactly 0.  A pair's value
+ *    is a function of those two rows, w, N, D and the metric alone: not of B, of where the rows sit in the batch, of
+ *    the tile they fall in or of the entry point.  Every operation is rounded once, in the order written above
+ *    (difference, square, one fused multiply-add per coordinate; then the max or the sum, the division, the root).  A row
+ *    with a non-finite coordinate has NaN distances wherever that arithmetic gives one (a NaN s_i stays in the max).
+ *  - Grouping rule ("leader" rule) over score [B], eligible [B] (ints, NULL = all 1) and radius >= 0 (+inf allowed):
+ *    a row takes part iff eligible[b] != 0 && isfinite(score[b]).  The participating rows are visited in rank order:
+ *    ascending score, the lowest row on ties.  A visited row joins the mode of the first leader, in leader order, with
+ *    dist(row, leader) <= radius; if there is none it becomes the next leader.  A comparison with NaN is false, so a
+ *    participating row with NaN distances leads a mode of its own.  A given matrix is taken to be symmetric: the entry
+ *    read is dist[leader][row].
+ *  - Outputs: mode [B]: index of the row's mode, in leader order, -1 for rows that do not take part.  n_modes: number
+ *    of modes.  leaders [B]: leaders[k] is the leader of mode k for k < n_modes (by construction the best-ranked row
+ *    of its mode), -1 beyond.  sizes [B]: number of members of mode k, 0 beyond.  leaders[0] is the row the selection
+ *    rule of "scoring" picks from the same score / eligible.  Any output may be NULL.
+ *  - Determinism: the rule is a function of its inputs; no floating-point atomics anywhere.  The device forms evaluate
+ *    it in n_modes rounds (argmin over the undecided rows, then every undecided row within radius of that leader is
+ *    decided), which gives the answer of the sequential rule.  gpmp2mi_group_traj and the plan form use exactly
+ *    dist <= radius with the dist gpmp2mi_traj_distances writes: one kernel computes both, leaving one bit per pair
+ *    instead of a B x B matrix of doubles.
+ * Errors, before any device work: GPMP2MI_ERR_INVALID for a NULL handle or required pointer (traj; dist for the distance
+ * calls and, with B > 0, for gpmp2mi_group_rows*; score for the grouping calls), B < 0 (B == 0 is fine and does
+ * nothing, n_modes = 0), total_step < 1, dof outside 1..GPMP2MI_MAX_DOF, an unknown metric, a negative or NaN radius, a
+ * negative or non-finite weight, max_alt outside 1..GPMP2MI_MAX_ALTERNATIVES, and the argument and state errors of
+ * gpmp2mi_plan_select for the plan forms; GPMP2MI_ERR_UNSUPPORTED, the limit in the message, for
+ * B > GPMP2MI_MAX_GROUP_ROWS (every call of this section that uses the device; the host form gpmp2mi_group_rows has
+ * no row limit); GPMP2MI_ERR_TIMEOUT for a poisoned plan.  A refused call writes nothing.
+ * Memory: `weights` is a HOST array in every form, read before the call returns (as Qc in "sampled clearance").  The
+ * bit matrix is B * ceil(B/64) 64-bit words.  A plan takes it, with a few [B] arrays and the staging of its
+ * host-pointer form, at the first call and keeps it (grown when a later call needs more): with the scoring, posterior,
+ * seeding, band and sampled workspaces the sixth exception to "nothing is allocated after gpmp2mi_plan_create".
+ * gpmp2mi_group_traj_dev has no handle to keep a workspace with: it allocates the bit matrix, and waits for `stream`
+ * before it frees it again -- ONE synchronising allocation per call.  The stream-ordered allocator is deliberately
+ * not used: it draws on a per-device pool the host application (PyTorch) tunes and trims for itself, it needs a second
+ * path for devices without pool support, and the caller who must not wait has the plan form.  gpmp2mi_traj_distances_dev,
+ * gpmp2mi_group_rows_dev and gpmp2mi_plan_select_distinct_dev (once its workspaces hold the shape) enqueue and return
+ * without a host synchronisation.  Calls on one plan belong in stream order.  The optimizer's state is not touched: a
+ * gpmp2mi_plan_update afterwards gives what it gives without the call.
+ * Not here: gpmp2mi_multi_plan_* twins, time-warp-invariant or workspace (end-effector) metrics, more than
+ * GPMP2MI_MAX_GROUP_ROWS rows, a distinctness term inside gpmp2mi_plan_select itself. */
+enum { GPMP2MI_DIST_MAX_STATE = 0, GPMP2MI_DIST_RMS = 1 };
+#define GPMP2MI_MAX_GROUP_ROWS 8192
+#define GPMP2MI_MAX_ALTERNATIVES 64
+
+/* dist [B][B]; traj [B][total_step+1][2 dof] */
+int gpmp2mi_traj_distances(int dof, int B, int total_step, const double* traj, const double* weights, int metric,
+                           double* dist);
+int gpmp2mi_traj_distances_dev(int dof, int B, int total_step, const double* traj, const double* weights, int metric,
+                               double* dist, void* stream);
+/* The rule on a given matrix.  Host pointers: runs on the host, no device needed (as gpmp2mi_select_best).
+ * _dev: device pointers, one kernel. */
+int gpmp2mi_group_rows(int B, const double* dist, const double* score, const int* eligible, double radius, int* mode,
+                       int* leaders, int* sizes, int* n_modes);
+int gpmp2mi_group_rows_dev(int B, const double* dist, const double* score, const int* eligible, double radius, int* mode,
+                           int* leaders, int* sizes, int* n_modes, void* stream);
+/* Distances and rule in one enqueue (two kernels), without a B x B matrix of doubles. */
+int gpmp2mi_group_traj(int dof, int B, int total_step, const double* traj, const double* weights, int metric,
+                       double radius, const double* score, const int* eligible, int* mode, int* leaders, int* sizes,
+                       int* n_modes);
+int gpmp2mi_group_traj_dev(int dof, int B, int total_step, const double* traj, const double* weights, int metric,
+                           double radius, const double* score, const int* eligible, int* mode, int* leaders, int* sizes,
+                           int* n_modes, void* stream);
+/* The plan's resident result, one enqueue: the scores of gpmp2mi_plan_score (and of gpmp2mi_plan_self_score when pairs
+ * != NULL), eligibility by the rule of "scoring" (extended as in "self-collision check" when pairs != NULL), score =
+ * the plan's final_error, then the grouping, then the copies.
+ * alt [max_alt], alt_size [max_alt]: leader and size of the first min(n_modes, max_alt) modes, -1 / 0 beyond; alt_error
+ * [max_alt]: their final_error (untouched beyond); mode [B]; traj_alt [max_alt][N+1][2D], dense_alt [max_alt][Md][2D]:
+ * slab k as gpmp2mi_plan_select writes traj_best / dense_best for row alt[k]; slabs k >= n_modes untouched.  n_modes
+ * counts ALL modes, also beyond max_alt.  alt[0] and n_eligible are the best / n_eligible of gpmp2mi_plan_select (of
+ * gpmp2mi_plan_select_checked when pairs is given) for the same arguments; mode, alt and alt_size are what
+ * gpmp2mi_group_traj gives on the plan's result with that eligibility.  Any output may be NULL. */
+int gpmp2mi_plan_select_distinct(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                 const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                 int metric, const double* weights, double radius, int max_alt, int* n_modes,
+                                 int* n_eligible, int* alt, int* alt_size, double* alt_error, int* mode,
+                                 double* traj_alt, double* dense_alt);
+int gpmp2mi_plan_select_distinct_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                     const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                     int metric, const double* weights, double radius, int max_alt, int* n_modes,
+                                     int* n_eligible, int* alt, int* alt_size, double* alt_error, int* mode,
+                                     double* traj_alt, double* dense_alt, void* stream);
+
 /* ---- factor-level entry points (the GTSAM plug-in contract: evaluateError(x..., H...)) -----
  * All batched over M independent evaluations, host pointers, Jacobian outputs may be NULL. */
 

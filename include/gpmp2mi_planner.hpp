@@ -1046,6 +1046,139 @@ inline std::vector<Trajectory> TrajectoryPosteriorSamples(const ROBOT& robot, co
   return internal::split_rows(delta, K, robot.dof(), setting.total_step);
 }
 
+/// The modes among several results (include/gpmp2mi.h "distinct alternatives"): mode[b] is the mode of result b in leader
+/// order (-1: the row does not take part), leaders[k] the best-ranked row of mode k, sizes[k] its member count.
+struct TrajectoryGroups {
+  std::vector<int> mode, leaders, sizes;   // leaders / sizes hold n_modes entries
+  std::size_t n_modes = 0;
+};
+namespace internal {
+inline void trim_groups(TrajectoryGroups& g, int n_modes) {
+  g.n_modes = static_cast<std::size_t>(n_modes);
+  g.leaders.resize(g.n_modes);
+  g.sizes.resize(g.n_modes);
+}
+}  // namespace internal
+/// The leader rule on a given symmetric distance matrix dist [B][B] row-major: results are visited by ascending score
+/// (the lowest index on ties) and join the first leader within `radius`, or become the next leader.  eligible may be
+/// empty (all take part); a non-finite score does not take part.  Host code.
+inline TrajectoryGroups GroupRows(const Vector& dist, const Vector& score, const std::vector<int>& eligible, double radius) {
+  const std::size_t B = score.size();
+  if (dist.size() != B * B || (!eligible.empty() && eligible.size() != B))
+    throw std::runtime_error("[GroupRows] dist, score and eligible differ in size");
+  TrajectoryGroups g;
+  g.mode.assign(B, -1);
+  g.leaders.assign(B, -1);
+  g.sizes.assign(B, 0);
+  int n = 0;
+  check(gpmp2mi_group_rows(static_cast<int>(B), dist.data(), score.data(), eligible.empty() ? nullptr : eligible.data(),
+                           radius, g.mode.data(), g.leaders.data(), g.sizes.data(), &n),
+        "gpmp2mi_group_rows");
+  internal::trim_groups(g, n);
+  return g;
+}
+/// The same from the trajectories themselves, distances and rule on the device: metric GPMP2MI_DIST_MAX_STATE (the
+/// largest weighted configuration distance over the support states) or GPMP2MI_DIST_RMS; weights may be empty (all 1).
+inline TrajectoryGroups GroupTrajectories(const std::vector<Trajectory>& results, const Vector& score,
+                                          const std::vector<int>& eligible, double radius,
+                                          int metric = GPMP2MI_DIST_MAX_STATE, const Vector& weights = {}) {
+  const std::size_t B = results.size();
+  if (B == 0 || score.size() != B || (!eligible.empty() && eligible.size() != B))
+    throw std::runtime_error("[GroupTrajectories] results, score and eligible differ in length");
+  const std::size_t dof = results[0].dof, N = results[0].total_step;
+  if (!weights.empty() && weights.size() != dof) throw std::runtime_error("[GroupTrajectories] weights dim does not fit dof");
+  Vector flat;
+  for (const Trajectory& t : results) {
+    if (t.dof != dof || t.total_step != N) throw std::runtime_error("[GroupTrajectories] results differ in shape");
+    flat.insert(flat.end(), t.data.begin(), t.data.end());
+  }
+  TrajectoryGroups g;
+  g.mode.assign(B, -1);
+  g.leaders.assign(B, -1);
+  g.sizes.assign(B, 0);
+  int n = 0;
+  check(gpmp2mi_group_traj(static_cast<int>(dof), static_cast<int>(B), static_cast<int>(N), flat.data(),
+                           weights.empty() ? nullptr : weights.data(), metric, radius, score.data(),
+                           eligible.empty() ? nullptr : eligible.data(), g.mode.data(), g.leaders.data(), g.sizes.data(), &n),
+        "gpmp2mi_group_traj");
+  internal::trim_groups(g, n);
+  return g;
+}
+/// One representative per mode of a batch of restarts, best first (gpmp2mi_plan_select_distinct): alt[k] is the restart
+/// leading mode k, alt_size[k] its member count, alt_error[k] its final error, traj[k] / dense[k] its trajectory and the
+/// inter_step-up-sampled form; n_modes counts all modes, the vectors hold min(n_modes, max_alt) entries.
+struct DistinctAlternatives {
+  std::size_t n_modes = 0, n_eligible = 0;
+  std::vector<int> alt, alt_size, mode;
+  Vector alt_error;
+  std::vector<Trajectory> traj, dense;
+};
+/// BatchTrajOptimize from every row of init_values, then the dense collision check, the selection rule of
+/// SelectBestTrajectory and the grouping of the eligible results, all on the device; alt[0] is the result
+/// SelectBestTrajectory picks.  pairs (may be null) adds the self-collision rule.
+template <class ROBOT, class SDF>
+inline DistinctAlternatives BatchTrajOptimizeDistinct(const ROBOT& robot, const SDF& sdf, const Vector& start_conf,
+                                                      const Vector& start_vel, const Vector& end_conf, const Vector& end_vel,
+                                                      const std::vector<Trajectory>& init_values,
+                                                      const TrajOptimizerSetting& setting, std::size_t inter_step,
+                                                      double radius, std::size_t max_alt = 8, double required_clearance = 0.0,
+                                                      bool require_in_range = false, int metric = GPMP2MI_DIST_MAX_STATE,
+                                                      const Vector& weights = {}, const SelfCollisionPairs* pairs = nullptr,
+                                                      double required_self_clearance = 0.0) {
+  const std::size_t B = init_values.size(), dof = robot.dof(), N = setting.total_step;
+  for (const Vector* v : {&start_conf, &start_vel, &end_conf, &end_vel})
+    if (v->size() != dof) throw std::runtime_error("[BatchTrajOptimizeDistinct] vector dim does not fit dof");
+  if (B == 0 || (!weights.empty() && weights.size() != dof))
+    throw std::runtime_error("[BatchTrajOptimizeDistinct] no initial values, or weights dim does not fit dof");
+  if (max_alt < 1 || max_alt > GPMP2MI_MAX_ALTERNATIVES)
+    throw std::runtime_error("[BatchTrajOptimizeDistinct] max_alt must be in 1..GPMP2MI_MAX_ALTERNATIVES");
+  Vector init;
+  for (const Trajectory& t : init_values) {
+    if (t.dof != dof || t.total_step != N) throw std::runtime_error("[BatchTrajOptimizeDistinct] init does not match dof / total_step");
+    init.insert(init.end(), t.data.begin(), t.data.end());
+  }
+  const gpmp2mi_settings s = setting.c_struct();
+  gpmp2mi_plan* plan = nullptr;
+  check(gpmp2mi_plan_create(robot.handle(), sdf.handle(), &s, nullptr, static_cast<int>(B), &plan), "gpmp2mi_plan_create");
+  const Vector sc = internal::repeat_rows(start_conf, B), sv = internal::repeat_rows(start_vel, B),
+               ec = internal::repeat_rows(end_conf, B), ev = internal::repeat_rows(end_vel, B);
+  const std::size_t Md = N * (inter_step + 1) + 1;
+  DistinctAlternatives out;
+  out.alt.assign(max_alt, -1);
+  out.alt_size.assign(max_alt, 0);
+  out.alt_error.assign(max_alt, 0.0);
+  out.mode.assign(B, -1);
+  Vector ta(max_alt * (N + 1) * 2 * dof), da(max_alt * Md * 2 * dof);
+  int nm = 0, ne = 0;
+  int rc = gpmp2mi_plan_set_problem(plan, sc.data(), sv.data(), ec.data(), ev.data(), init.data());
+  const char* what = "gpmp2mi_plan_set_problem";
+  if (!rc) {
+    rc = gpmp2mi_plan_optimize(plan, nullptr);
+    what = "gpmp2mi_plan_optimize";
+  }
+  if (!rc) {
+    rc = gpmp2mi_plan_select_distinct(plan, static_cast<int>(inter_step), required_clearance, require_in_range ? 1 : 0,
+                                      pairs ? pairs->handle() : nullptr, required_self_clearance, metric,
+                                      weights.empty() ? nullptr : weights.data(), radius, static_cast<int>(max_alt), &nm, &ne,
+                                      out.alt.data(), out.alt_size.data(), out.alt_error.data(), out.mode.data(), ta.data(),
+                                      da.data());
+    what = "gpmp2mi_plan_select_distinct";
+  }
+  gpmp2mi_plan_destroy(plan);
+  check(rc, what);
+  out.n_modes = static_cast<std::size_t>(nm);
+  out.n_eligible = static_cast<std::size_t>(ne);
+  const std::size_t k = std::min(out.n_modes, max_alt);
+  out.alt.resize(k);
+  out.alt_size.resize(k);
+  out.alt_error.resize(k);
+  ta.resize(k * (N + 1) * 2 * dof);
+  da.resize(k * Md * 2 * dof);
+  out.traj = internal::split_rows(ta, k, dof, N);
+  out.dense = internal::split_rows(da, k, dof, Md - 1);
+  return out;
+}
+
 /// B independent BatchTrajOptimize problems of one robot, field and setting, sharded over several GPUs of this process
 /// (gpmp2mi_multi_plan, include/gpmp2mi.h): shard k of `devices` holds a contiguous share of the rows, repeats allowed.
 /// The robot model and the field must outlive the planner.  Not in the reference (one problem per call there).
