@@ -77,7 +77,6 @@ if pick["best"] >= 0:
     print(f"  support cost {scores['support_cost'][b]:.4f}, dense cost {scores['dense_cost'][b]:.4f}, clearance "
           f"{scores['min_clearance'][b]:.4f} m, self clearance {self_scores['min_self_clearance'][b]:.4f} m; "
           f"{pick['dense_best'].shape[0]} states ready to execute")
-plan.close()
 
 # ---- replanning: execute to state 5, the goal moves (WAMReplannerExample.m:102-126)
 isam = g.ISAM2TrajOptimizer3DArm(arm, sdf, opt_setting)
@@ -92,3 +91,17 @@ isam.update()
 replanned = isam.values()
 print(f"replanned: goal reached {np.round(replanned[('x', total_time_step)], 3)}, "
       f"state 5 moved by {np.abs(replanned[('x', 5)] - values[('x', 5)]).max():.1e}")
+
+# ---- can the arm execute it?  The Barrett WAM's joint ranges, 2 rad/s, 20 rad/s^2 and 1.5 m/s for any point of the body: the
+# best row that stays inside its joint ranges, and the factor by which its duration must be stretched to meet the rates
+limits = engine.MotionLimits(7, pos_down=[-2.6, -2.0, -2.8, -0.9, -4.76, -1.6, -3.0],
+                             pos_up=[2.6, 2.0, 2.8, 3.1, 1.24, 1.6, 3.0], vel=2.0, acc=20.0, point_speed=1.5)
+motion = plan.motion_score(limits, 9)
+feasible = plan.select_feasible(9, limits, required_pos_margin=0.0, max_time_scale=np.inf, require_in_range=True, pairs=pairs)
+print(f"{int((motion['pos_margin'] < 0).sum())} restarts leave the joint ranges, {int((motion['time_scale'] > 1).sum())} are "
+      f"too fast as planned; executable: {feasible['n_eligible']}, best = restart {feasible['best']}")
+if feasible["best"] >= 0:
+    s = feasible["time_scale_best"]
+    print(f"  time_scale {s:.3f}: run it over {max(s, 1.0) * total_time_sec:.2f} s instead of {total_time_sec:.2f} s "
+          f"(velocities divided by {max(s, 1.0):.3f})")
+plan.close()

@@ -169,6 +169,32 @@ def declare_self(lib):
     lib.gpmp2mi_self_pairs_destroy.restype = None
 
 
+class MotionLimitsC(C.Structure):
+    """gpmp2mi_motion_limits (include/gpmp2mi.h "motion limits"): host arrays [dof] or NULL, and the Cartesian speed."""
+    _fields_ = [("pos_down", c_double_p), ("pos_up", c_double_p), ("vel", c_double_p), ("acc", c_double_p),
+                ("point_speed", C.c_double)]
+
+
+def declare_motion(lib):
+    """argtypes of the motion-limit entry points (include/gpmp2mi.h "motion limits"); `limits` is a host struct in every
+    form, the `_dev` forms take device addresses for everything else."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    lp = C.POINTER(MotionLimitsC)
+    decl = {
+        "gpmp2mi_motion_score_traj": [vp, lp, f, i, i, i, d, d, d, d, d, d, ip, ip],
+        "gpmp2mi_motion_score_traj_dev": [vp, lp, f, i, i, i] + [vp] * 9,
+        "gpmp2mi_plan_motion_score": [vp, lp, i, d, d, d, d, d, ip, ip],
+        "gpmp2mi_plan_motion_score_dev": [vp, lp, i] + [vp] * 8,
+        "gpmp2mi_plan_select_feasible": [vp, i, f, i, vp, f, lp, f, f, ip, ip, d, d, d],
+        "gpmp2mi_plan_select_feasible_dev": [vp, i, f, i, vp, f, lp, f, f] + [vp] * 6,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_motion_limits_default.argtypes = [lp]
+    lib.gpmp2mi_motion_limits_default.restype = None
+
+
 def declare_group(lib):
     """include/gpmp2mi.h "distinct alternatives"; `weights` is a host array in every form"""
     vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double

@@ -337,8 +337,36 @@ struct Kin {
     }
   }
 
+  // J v for the point of jacobian(): out = sum over k < tag.value of J[k] v[k], the columns of jacobian() formed one at
+  // a time and added in ascending k, so that no J[DOF][3] stays in registers (k_motion, motion_kernels.hip).
+  template <class Tag>
+  __device__ __forceinline__ static void jacobian_times(const Axes& A, const double (&p)[3], Tag, const double (&v)[DOF],
+                                                        double (&out)[3]) {
+    constexpr int NC = Tag::value, FIRST = Tag::first;
+    if constexpr (KIND == GPMP2MI_ROBOT_POINT) {
+      out[0] = v[0]; out[1] = v[1]; out[2] = 0.0;
+    } else {
+      out[0] = out[1] = out[2] = 0.0;
+      if constexpr (MOBILE) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) out[i] = A.bx[i] * v[0] + A.by[i] * v[1];
+        out[0] += -(p[1] - A.vt[1]) * v[2];  // z x (p - t_veh)
+        out[1] += (p[0] - A.vt[0]) * v[2];
+        if constexpr (LIFT == 1 && NC > 3) out[2] += A.lift_sign * v[3];
+      }
+#pragma unroll
+      for (int k = FIRST; k < NC; k++) {
+        const int jn = k - NB;
+        const double rx = p[0] - A.org[jn][0], ry = p[1] - A.org[jn][1], rz = p[2] - A.org[jn][2];
+        out[0] += (A.zax[jn][1] * rz - A.zax[jn][2] * ry) * v[k];
+        out[1] += (A.zax[jn][2] * rx - A.zax[jn][0] * rz) * v[k];
+        out[2] += (A.zax[jn][0] * ry - A.zax[jn][1] * rx) * v[k];
+      }
+    }
+  }
+
   // Visitor over the body spheres (sorted by link):
-  //   pre(s, p) -> bool      : called with the sphere centre; return true if the Jacobian is wanted
+  //   pre(s, p) -> bool     : called with the sphere centre; return true if the Jacobian is wanted
   //   post(s, p, J, nc)      : J[k] = d p / d q_k for k < nc.value (compile time),
   //                            zero for k >= nc.value -- a sphere depends on the joints below its link only
   template <class Pre, class Post>

@@ -121,9 +121,13 @@ struct gpmp2mi_robot {
   mutable size_t score_ws_bytes = 0;
   // the bridge factors of gpmp2mi_sampled_clearance_traj(_dev) calls on this handle, under the same guard and rule
   mutable g2::SampledFac sampled_fac;
+  // the records of gpmp2mi_motion_score_traj(_dev) calls on this handle (motion_score.hip), under the same guard and rule
+  mutable void* motion_ws = nullptr;
+  mutable size_t motion_ws_bytes = 0;
   ~gpmp2mi_robot() {
     if (d) (void)hipFree(d);
     if (score_ws) (void)hipFree(score_ws);
+    if (motion_ws) (void)hipFree(motion_ws);
     sampled_fac.release();
     if (replica) g2::g_robot_replicas.fetch_sub(1);
   }
@@ -312,6 +316,11 @@ struct gpmp2mi_plan {
   // k_group_rule leaves and the staging of the host-pointer form, taken at the first select_distinct call and kept
   void* group_ws = nullptr;
   size_t group_ws_bytes = 0;
+  // motion limits (motion_score.hip): the records of k_motion, the per-row scores of the existing stages that
+  // select_feasible's rule reads and the staging of the host-pointer forms, taken at the first motion_score /
+  // select_feasible call and kept
+  void* motion_ws = nullptr;
+  size_t motion_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }

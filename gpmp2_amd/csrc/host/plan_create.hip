@@ -97,6 +97,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (sampled_ws) (void)hipFree(sampled_ws);
   if (self_ws) (void)hipFree(self_ws);
   if (group_ws) (void)hipFree(group_ws);
+  if (motion_ws) (void)hipFree(motion_ws);
   sampled_fac.release();
   flags_release(qflags);
 }

@@ -99,6 +99,40 @@ int launch_self_clearance(const RobotDev& h, const RobotDev* R, const SelfPair* 
                           int N, const double* traj, ScoreRec* recs, hipStream_t st);
 int launch_self_finish(const SelfFinish& a, hipStream_t st);
 
+// motion_kernels.hip (include/gpmp2mi.h "motion limits")
+// the limits as k_motion reads them, a kernel argument: +-inf where there is none
+struct MotionLimitsDev {
+  double down[GPMP2MI_MAX_DOF], up[GPMP2MI_MAX_DOF], vel[GPMP2MI_MAX_DOF], acc[GPMP2MI_MAX_DOF];
+};
+// What one workgroup of k_motion leaves for k_motion_finish: the four extrema of its tile of SCORE_TILE checked states,
+// each with its two indices, and the count of non-finite quantities.  v[0]: the smallest position margin; v[1..3]: MINUS
+// the largest velocity ratio, acceleration ratio and point speed, so that all four are minima under key_less
+// (score_select.h) and exact ties go to the lowest indices.  ij = INT_MAX: none.  72 bytes.
+struct MotionRec {
+  double v[4];
+  int ij[4][2];
+  int invalid, pad;
+};
+// arguments of k_motion_finish; every output may be null.  `sel` carries the selection (sel.select) and the shape of the
+// trajectories; the rule reads the per-row scores the existing stages left: clearance / oor (k_score_finish) and, when
+// self_clearance is given, self_clearance / self_invalid (k_self_finish).
+struct MotionFinish {
+  ScoreFinish sel;
+  const MotionRec* recs;   // [B][nblk]
+  int nblk;
+  double limit_point_speed;
+  double *pos_margin, *vel_ratio, *acc_ratio, *point_speed, *time_scale;
+  int *worst, *invalid;    // [B][4][2], [B]
+  const double *clearance, *self_clearance;
+  const int *oor, *self_invalid;
+  double required_self_clearance, required_pos_margin, max_time_scale;
+  double* time_scale_best;
+};
+// records per row: score_blocks
+int launch_motion(const RobotDev& h, const RobotDev* R, const MotionLimitsDev& lim, double dt, int inter, int B, int N,
+                  const double* traj, MotionRec* recs, hipStream_t st);
+int launch_motion_finish(const MotionFinish& a, hipStream_t st);
+
 // group_kernels.hip (include/gpmp2mi.h "distinct alternatives")
 constexpr int GROUP_TILE = 64;          // k_traj_pairs: one workgroup per 64 x 64 tile of pairs
 constexpr int GROUP_CHUNK_ELEMS = 32;   // configuration doubles of a row staged through LDS at a time

@@ -43,6 +43,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_multi(lib)
     _capi.declare_score(lib)
     _capi.declare_self(lib)
+    _capi.declare_motion(lib)
     _capi.declare_group(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
@@ -113,6 +114,35 @@ def _score_ptrs(o):
 def _self_ptrs(o):
     return (dptr(o["self_support_cost"]), dptr(o["self_dense_cost"]), dptr(o["min_self_clearance"]), iptr(o["worst"]),
             iptr(o["invalid"]))
+
+
+def _motion_ptrs(o):
+    return (dptr(o["pos_margin"]), dptr(o["vel_ratio"]), dptr(o["acc_ratio"]), dptr(o["point_speed"]),
+            dptr(o["time_scale"]), iptr(o["worst"]), iptr(o["invalid"]))
+
+
+class MotionLimits:
+    """gpmp2mi_motion_limits for a robot of `dof` coordinates (include/gpmp2mi.h "motion limits"): pos_down / pos_up /
+    vel / acc are [dof] arrays, scalars (spread over the coordinates) or None = no limit of that kind; infinite entries
+    mean no limit for that coordinate; point_speed in m/s, inf = none.  Validated as the C side validates
+    (ValueError); the arrays live as long as this object."""
+
+    def __init__(self, dof, pos_down=None, pos_up=None, vel=None, acc=None, point_speed=np.inf):
+        self.dof = int(dof)
+        self.pos_down, self.pos_up, self.vel, self.acc, self.point_speed = scoring.motion_limits(
+            self.dof, pos_down, pos_up, vel, acc, point_speed)
+        self.c = _capi.MotionLimitsC(dptr(self.pos_down), dptr(self.pos_up), dptr(self.vel), dptr(self.acc),
+                                     self.point_speed)
+
+    def ref(self, dof):
+        if dof != self.dof:
+            raise ValueError(f"these limits are for dof {self.dof}, not {dof}")
+        return C.byref(self.c)
+
+
+def _limits_arg(limits, dof):
+    """limits: a MotionLimits, or None = no limit at all"""
+    return (limits if limits is not None else MotionLimits(dof)).ref(dof)
 
 
 def _kappa_arg(kappa):
@@ -596,6 +626,22 @@ class Engine:
                                                   *_self_ptrs(o)))
         return o
 
+    # ---------------------------------------------------------------- motion limits (include/gpmp2mi.h)
+    def motion_score_traj(self, robot, limits, delta_t, inter_step, traj, out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) -> dict(pos_margin [B], vel_ratio [B], acc_ratio [B], point_speed [B],
+        time_scale [B], worst [B][4][2], invalid [B]) of the inter_step-up-sampled trajectories against `limits` (a
+        MotionLimits; None: no limit)."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        o = scoring.motion_outputs(B, out)
+        lim = _limits_arg(limits, robot.dof)
+        self._ck(self.lib.gpmp2mi_motion_score_traj(robot.ptr, lim, float(delta_t), inter_step, B, N, dptr(t),
+                                                    *_motion_ptrs(o)))
+        return o
+
     # ---------------------------------------------------------------- distinct alternatives (include/gpmp2mi.h)
     def traj_distances(self, dof, traj, weights=None, metric=scoring.DIST_MAX_STATE):
         """traj [B][N+1][2 dof] -> dist [B][B] between the configuration halves (scoring.DIST_MAX_STATE / DIST_RMS)."""
@@ -973,6 +1019,65 @@ class Plan:
         self.eng._ck(self.eng.lib.gpmp2mi_plan_select_checked_dev(
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)), pairs.ptr,
             float(required_self_clearance), *args, C.c_void_p(stream or 0)))
+
+    # ---- can the robot execute it (include/gpmp2mi.h "motion limits")
+    def motion_score(self, limits, inter_step, out=None):
+        """dict(pos_margin, vel_ratio, acc_ratio, point_speed, time_scale, worst, invalid) of the plan's result, B rows."""
+        inter_step = _score_args(inter_step)
+        o = scoring.motion_outputs(self.B, out)
+        lim = _limits_arg(limits, self.D)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_motion_score(self.h.ptr, lim, inter_step, *_motion_ptrs(o)))
+        return o
+
+    def motion_score_dev(self, limits, inter_step, pos_margin=None, vel_ratio=None, acc_ratio=None, point_speed=None,
+                         time_scale=None, worst=None, invalid=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        B = self.B
+        args = [_dev_arg("pos_margin", pos_margin, (B,)), _dev_arg("vel_ratio", vel_ratio, (B,)),
+                _dev_arg("acc_ratio", acc_ratio, (B,)), _dev_arg("point_speed", point_speed, (B,)),
+                _dev_arg("time_scale", time_scale, (B,)), _dev_arg("worst", worst, (B, 4, 2), True),
+                _dev_arg("invalid", invalid, (B,), True)]
+        lim, inter_step = _limits_arg(limits, self.D), _score_args(inter_step)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_motion_score_dev(self.h.ptr, lim, inter_step, *args,
+                                                                C.c_void_p(stream or 0)))
+
+    def select_feasible(self, inter_step, limits, required_pos_margin=0.0, max_time_scale=1.0, required_clearance=0.0,
+                        require_in_range=False, pairs=None, required_self_clearance=0.0):
+        """select() (select_checked() when `pairs` is given) with the rule that also asks for no non-finite motion
+        quantity, pos_margin >= required_pos_margin and time_scale <= max_time_scale against `limits`:
+        dict(best, n_eligible, time_scale_best, traj_best, dense_best); best = -1: the last three are None.  dense_best
+        is as planned: divide its velocities by time_scale_best when the row is run that much slower."""
+        inter_step = _score_args(inter_step)
+        rpm, mts = scoring.feasible_thresholds(required_pos_margin, max_time_scale)
+        lim = _limits_arg(limits, self.D)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D))
+        best, n, ts = C.c_int(-1), C.c_int(0), C.c_double(0.0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_feasible(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts,
+            C.byref(best), C.byref(n), C.cast(C.byref(ts), _capi.c_double_p), dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, time_scale_best=ts.value if hit else None,
+                    traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_feasible_dev(self, inter_step, limits, required_pos_margin=0.0, max_time_scale=1.0, required_clearance=0.0,
+                            require_in_range=False, pairs=None, required_self_clearance=0.0, best=None, n_eligible=None,
+                            time_scale_best=None, traj_best=None, dense_best=None, stream=None):
+        """The same with device outputs, as select_dev, plus time_scale_best float64 [1].  One enqueue on `stream`, no
+        host synchronisation once the plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        rpm, mts = scoring.feasible_thresholds(required_pos_margin, max_time_scale)
+        lim = _limits_arg(limits, self.D)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("time_scale_best", time_scale_best, (1,)),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_feasible_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts,
+            *args, C.c_void_p(stream or 0)))
 
     # ---- one representative per mode of the resident result (include/gpmp2mi.h "distinct alternatives")
     def _distinct_args(self, inter_step, radius, weights, metric, max_alt):

@@ -116,6 +116,83 @@ def score_outputs(B, out=None, names=SCORE_NAMES):
     return res
 
 
+# ---- motion limits (include/gpmp2mi.h "motion limits"): the extended rule and the checks of its wrappers
+MOTION_NAMES = ("pos_margin", "vel_ratio", "acc_ratio", "point_speed", "time_scale", "worst", "invalid")
+
+
+def feasible_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+                  min_self_clearance=None, invalid=None, required_self_clearance=0.0, pos_margin=None, time_scale=None,
+                  motion_invalid=None, required_pos_margin=0.0, max_time_scale=np.inf):
+    """(best, n_eligible) by the rule of select_rule with three more conditions: no non-finite motion quantity,
+    pos_margin >= required_pos_margin, time_scale <= max_time_scale (each None: not asked)."""
+    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
+    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+                  invalid, required_self_clearance)
+    if motion_invalid is not None:
+        ok &= np.asarray(motion_invalid).reshape(-1) == 0
+    with np.errstate(invalid="ignore"):
+        if pos_margin is not None:
+            ok &= np.asarray(pos_margin, dtype=np.float64).reshape(-1) >= required_pos_margin
+        if time_scale is not None:
+            ok &= np.asarray(time_scale, dtype=np.float64).reshape(-1) <= max_time_scale
+    rows = np.flatnonzero(ok)
+    if rows.size == 0:
+        return -1, 0
+    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+
+
+def motion_limits(D, pos_down=None, pos_up=None, vel=None, acc=None, point_speed=np.inf):
+    """The limits as the C side takes them: contiguous float64 [D] arrays or None (a scalar is spread over the D
+    coordinates), checked as the C side checks them; ValueError otherwise."""
+    def vec(name, x):
+        if x is None:
+            return None
+        a = np.asarray(x, dtype=np.float64)
+        a = np.full(D, float(a)) if a.ndim == 0 else np.ascontiguousarray(a)
+        if a.shape != (D,) or np.isnan(a).any():
+            raise ValueError(f"{name}: expected [{D}] values that are not NaN, got {list(np.shape(x))}")
+        return a
+    lo, hi, v, a = vec("pos_down", pos_down), vec("pos_up", pos_up), vec("vel", vel), vec("acc", acc)
+    if (lo is None) != (hi is None):
+        raise ValueError("pos_down and pos_up are given together or not at all")
+    if lo is not None and (lo > hi).any():
+        raise ValueError("pos_down > pos_up")
+    for name, x in (("vel", v), ("acc", a)):
+        if x is not None and not (x > 0).all():
+            raise ValueError(f"{name}: entries must be > 0")
+    point_speed = float(point_speed)
+    if not point_speed > 0:
+        raise ValueError("point_speed must be > 0 (inf: no limit)")
+    return lo, hi, v, a, point_speed
+
+
+def motion_outputs(B, out=None):
+    """The seven per-row outputs of a motion-score call: fresh arrays, or the caller's (checked as score_outputs does)."""
+    f, i = np.float64, np.int32
+    want = dict(zip(MOTION_NAMES, (((B,), f), ((B,), f), ((B,), f), ((B,), f), ((B,), f), ((B, 4, 2), i), ((B,), i))))
+    res = {}
+    out = out or {}
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"unknown motion outputs: {sorted(unknown)}")
+    for name, (shape, dt) in want.items():
+        x = out.get(name)
+        if x is None:
+            x = np.zeros(shape, dtype=dt)
+        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
+            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
+                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
+        res[name] = x
+    return res
+
+
+def feasible_thresholds(required_pos_margin, max_time_scale):
+    required_pos_margin, max_time_scale = float(required_pos_margin), float(max_time_scale)
+    if np.isnan(required_pos_margin) or np.isnan(max_time_scale):
+        raise ValueError("required_pos_margin / max_time_scale must not be NaN")
+    return required_pos_margin, max_time_scale
+
+
 # ---- distinct alternatives (include/gpmp2mi.h): the grouping rule in numpy terms and the shape checks of its wrappers
 DIST_MAX_STATE, DIST_RMS = 0, 1
 MAX_GROUP_ROWS = 8192       # GPMP2MI_MAX_GROUP_ROWS

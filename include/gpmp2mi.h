@@ -570,6 +570,107 @@ int gpmp2mi_plan_select_checked_dev(gpmp2mi_plan* p, int inter_step, double requ
                                     const gpmp2mi_self_pairs* pairs, double required_self_clearance, int* best,
                                     int* n_eligible, double* traj_best, double* dense_best, void* stream);
 
+/* ---- motion limits: can the robot execute the trajectory, and how much slower must it run, on the device ---------
+ * The calls of "scoring" and "self-collision check" ask whether the executed trajectory is free of collisions.  GPMP2's
+ * joint and velocity limits are soft hinge factors on support states, off by default; nothing bounds acceleration or
+ * Cartesian speed, and between two support states the GP mean is a cubic whose velocity peaks where no factor looks.
+ * These calls test every checked state of "scoring" against joint ranges, joint speeds, joint accelerations and a
+ * Cartesian speed of the body spheres, give the factor by which a row's duration must be stretched to become
+ * executable, and let the selection ask for both.
+ *
+ * Definitions, for one trajectory traj [N+1][2D], delta_t = dt and inter_step = J >= 0:
+ *  - Checked states: exactly those of "scoring", Md = N (J+1) + 1 states; BOTH halves of gpmp2mi_interpolate_traj are
+ *    used: configuration q_k and velocity v_k (the linear GP for vector-space robots, the Pose2 interpolator for the
+ *    mobile kinds; support states are copies).
+ *  - Limits: gpmp2mi_motion_limits, HOST pointers, each [dof] or NULL, and one scalar.  An infinite entry or a NULL array
+ *    means no limit of that kind for that coordinate; pos_down / pos_up are both NULL or both given; coordinate d has a
+ *    position limit iff pos_down[d] or pos_up[d] is finite.  point_speed = +inf: no Cartesian limit.
+ *    gpmp2mi_motion_limits_default fills "no limit".  The arrays are read before the call returns.
+ *  - Mobile kinds: position limits and acceleration limits on coordinates 0..2 are not applied (the former as
+ *    JointLimitFactorPose2Vector does); velocity limits on 0..2 apply to the velocity half as stored (body frame).
+ *  - pos_margin [B]: min over (k, d) with a position limit of min(q_k[d] - down[d], up[d] - q_k[d]), an infinite side
+ *    left out.  Negative: outside.  +inf if nothing is limited.
+ *  - vel_ratio [B]: max over (k, d) with a finite vel[d] of |v_k[d]| / vel[d]; 0 if nothing is limited.
+ *  - acc_ratio [B]: max over interval i < N, end e in {0, 1} and d with a finite acc[d] of |a_i,e[d]| / acc[d], with the
+ *    acceleration of the interpolated mean inside interval i (support states x0 v0, x1 v1) at its two ends,
+ *      a_i,0 = 6 (x1 - x0) / dt^2 - (4 v0 + 2 v1) / dt,    a_i,1 = -6 (x1 - x0) / dt^2 + (2 v0 + 4 v1) / dt.
+ *    The mean is a cubic Hermite in every vector coordinate, so its acceleration is linear in time and these 2N values
+ *    bound it over continuous time; acc_ratio does not depend on J.  0 if nothing is limited.
+ *  - point_speed [B]: max over (k, s) of |J_s(q_k) v_k|, J_s the 3 x D Jacobian of sphereCenters as
+ *    gpmp2mi_sphere_centers returns it, s in the order of the robot description.  Computed whatever the limits are.
+ *  - time_scale [B] = max(vel_ratio, sqrt(acc_ratio), point_speed / limits.point_speed): the smallest factor s such that
+ *    the same path run over s * total_time meets every rate limit (velocities and point speeds scale by 1/s,
+ *    accelerations by 1/s^2); s <= 1: executable as planned.  Position limits cannot be bought with time.
+ *  - worst [B][4][2]: the (k, d), (k, d), (2i+e, d), (k, s) attaining the four extrema, on exact ties the lowest first
+ *    index, then the lowest second; (-1, -1) if none.
+ *  - invalid [B]: the number of evaluated quantities (margins and ratios of limited coordinates, every point speed) that
+ *    are not finite.  Such a quantity enters no extremum.  Every quantity is evaluated per coordinate: a non-finite
+ *    coordinate of a support state makes that coordinate non-finite in the checked states of the two intervals around
+ *    it and leaves the other coordinates alone, and a sphere's speed is the sum over the Jacobian columns of the
+ *    joints its link hangs from only (the others are zero), so a non-finite joint further out leaves it finite.  Any
+ *    output may be NULL.
+ *  - Determinism: every output is an extremum with an index key: no sums, no atomics.  A row's results are a function of
+ *    the row, the robot, the limits, delta_t and J alone: bit-identical alone, in any batch, through the trajectory form
+ *    or the plan form.
+ *  - Selection: the rule of "scoring", extended as in "self-collision check" when pairs != NULL, and then
+ *      eligible(b) = <that rule> && invalid[b] == 0 && pos_margin[b] >= required_pos_margin
+ *                    && time_scale[b] <= max_time_scale;
+ *    the ranking stays final_error, the lowest row on ties.  With all limits off and max_time_scale = +inf the answer is
+ *    that of gpmp2mi_plan_select / gpmp2mi_plan_select_checked for rows without a non-finite coordinate.
+ *    time_scale_best: time_scale of the chosen row (untouched when none is).  dense_best is not rescaled: the caller
+ *    divides its velocities by time_scale_best.
+ * Errors, before any device work: GPMP2MI_ERR_INVALID for a NULL robot / limits / traj / plan, the argument errors of
+ * "scoring", a NaN limit, down > up, a vel / acc / point_speed entry <= 0, one of pos_down / pos_up alone, a NaN
+ * required_pos_margin / max_time_scale, and a pair table made for another robot; GPMP2MI_ERR_TIMEOUT for a poisoned
+ * plan.  A refused call writes nothing and leaves the plan usable.
+ * Memory: the workspace rules of "scoring": one 72-byte record per 64 checked states of every row.  A plan takes the
+ * records, a few [B] arrays and the staging of its host-pointer forms at the first call and keeps them (grown when a
+ * later call needs more): one more exception to "nothing is allocated after gpmp2mi_plan_create".
+ * gpmp2mi_motion_score_traj_dev keeps its records with the robot handle, under the stream-order rule of
+ * gpmp2mi_score_traj_dev.  The `_dev` forms enqueue and return.  The plan forms read the plan's resident result and
+ * delta_t, have the preconditions of gpmp2mi_plan_score and leave the optimizer's state untouched.
+ * Not here: gpmp2mi_multi_plan_* twins, a motion term inside gpmp2mi_plan_select_distinct, the acceleration of the Pose2
+ * coordinates (the acceleration of the tangent-space interpolation is not built), exact continuous-time velocity maxima
+ * between checked states, jerk limits, per-interval re-timing (time_scale is one uniform factor per row). */
+typedef struct gpmp2mi_motion_limits {
+  const double* pos_down;   /* [dof] or NULL (then pos_up is NULL too) */
+  const double* pos_up;
+  const double* vel;        /* [dof] or NULL, entries > 0 */
+  const double* acc;        /* [dof] or NULL, entries > 0 */
+  double point_speed;       /* > 0; +inf: no Cartesian limit */
+} gpmp2mi_motion_limits;
+void gpmp2mi_motion_limits_default(gpmp2mi_motion_limits* limits);
+
+/* caller buffers; traj [B][total_step+1][2D].  The device of the robot handle must be current. */
+int gpmp2mi_motion_score_traj(const gpmp2mi_robot* robot, const gpmp2mi_motion_limits* limits, double delta_t,
+                              int inter_step, int B, int total_step, const double* traj, double* pos_margin,
+                              double* vel_ratio, double* acc_ratio, double* point_speed, double* time_scale, int* worst,
+                              int* invalid);
+int gpmp2mi_motion_score_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_motion_limits* limits, double delta_t,
+                                  int inter_step, int B, int total_step, const double* traj, double* pos_margin,
+                                  double* vel_ratio, double* acc_ratio, double* point_speed, double* time_scale,
+                                  int* worst, int* invalid, void* stream);
+/* The plan's resident result; preconditions and errors as gpmp2mi_plan_score. */
+int gpmp2mi_plan_motion_score(gpmp2mi_plan* p, const gpmp2mi_motion_limits* limits, int inter_step, double* pos_margin,
+                              double* vel_ratio, double* acc_ratio, double* point_speed, double* time_scale, int* worst,
+                              int* invalid);
+int gpmp2mi_plan_motion_score_dev(gpmp2mi_plan* p, const gpmp2mi_motion_limits* limits, int inter_step,
+                                  double* pos_margin, double* vel_ratio, double* acc_ratio, double* point_speed,
+                                  double* time_scale, int* worst, int* invalid, void* stream);
+/* gpmp2mi_plan_select (gpmp2mi_plan_select_checked when pairs != NULL) with the extended rule, one enqueue: the existing
+ * score stages, the motion scores, then one finish that reads them all.  Outputs as gpmp2mi_plan_select, plus
+ * time_scale_best. */
+int gpmp2mi_plan_select_feasible(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                 const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                 const gpmp2mi_motion_limits* limits, double required_pos_margin, double max_time_scale,
+                                 int* best, int* n_eligible, double* time_scale_best, double* traj_best,
+                                 double* dense_best);
+int gpmp2mi_plan_select_feasible_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                     const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                     const gpmp2mi_motion_limits* limits, double required_pos_margin,
+                                     double max_time_scale, int* best, int* n_eligible, double* time_scale_best,
+                                     double* traj_best, double* dense_best, void* stream);
+
 /* ---- distinct alternatives: how many different solutions the restarts found, one row per mode, on the device ------
  * The calls of "scoring" answer with one row.  These calls say how many different trajectories a batch holds and hand
  * over one representative of each, best first, without the trajectories leaving the device: the fallback when the

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -647,6 +648,72 @@ inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int
     // std::min keeps a NaN first argument, and a NaN clearance is never eligible
     both[b].min_clearance = self_scores[b].invalid != 0 ? std::nan("") : std::min(scores[b].min_clearance, self_scores[b].min_clearance);
     if (self_scores[b].min_clearance != self_scores[b].min_clearance) both[b].min_clearance = std::nan("");
+  }
+  return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
+}
+
+/// The motion limits of a robot (include/gpmp2mi.h "motion limits"): joint ranges, joint speeds, joint accelerations,
+/// each empty (no limit of that kind) or one entry per coordinate with +-infinity where a coordinate has none, and the
+/// Cartesian speed limit of the body spheres (infinity: none).
+struct MotionLimits {
+  Vector pos_down, pos_up, vel, acc;
+  double point_speed = std::numeric_limits<double>::infinity();
+  /// the C struct over this object's arrays: valid while the object lives and is not modified
+  gpmp2mi_motion_limits c(std::size_t dof) const {
+    for (const Vector* v : {&pos_down, &pos_up, &vel, &acc})
+      if (!v->empty() && v->size() != dof) throw std::runtime_error("[MotionLimits] an array does not fit the dof");
+    gpmp2mi_motion_limits l;
+    l.pos_down = pos_down.empty() ? nullptr : pos_down.data();
+    l.pos_up = pos_up.empty() ? nullptr : pos_up.data();
+    l.vel = vel.empty() ? nullptr : vel.data();
+    l.acc = acc.empty() ? nullptr : acc.data();
+    l.point_speed = point_speed;
+    return l;
+  }
+};
+/// Whether the robot can execute the up-sampled trajectory: the smallest distance to a joint range (negative: outside),
+/// the largest joint speed and joint acceleration relative to their limits, the largest speed of a sphere centre, each
+/// with where it occurs ((-1, -1) if nothing is limited), the factor by which the duration must be stretched to meet
+/// every rate limit (<= 1: executable as planned) and the number of quantities that are not finite.
+struct TrajectoryMotionScore {
+  double pos_margin = 0.0, vel_ratio = 0.0, acc_ratio = 0.0, point_speed = 0.0, time_scale = 0.0;
+  int pos_state = -1, pos_coord = -1, vel_state = -1, vel_coord = -1, acc_end = -1, acc_coord = -1, speed_state = -1,
+      speed_sphere = -1, invalid = 0;
+};
+template <class ROBOT>
+inline TrajectoryMotionScore MotionScoreTrajectory(const ROBOT& robot, const MotionLimits& limits, const Trajectory& result,
+                                                   const TrajOptimizerSetting& setting, std::size_t inter_step) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[MotionScoreTrajectory] result does not match dof / total_step");
+  const gpmp2mi_motion_limits l = limits.c(robot.dof());
+  TrajectoryMotionScore sc;
+  int worst[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  check(gpmp2mi_motion_score_traj(robot.handle(), &l, setting.total_time / static_cast<double>(setting.total_step),
+                                  static_cast<int>(inter_step), 1, static_cast<int>(result.total_step), result.data.data(),
+                                  &sc.pos_margin, &sc.vel_ratio, &sc.acc_ratio, &sc.point_speed, &sc.time_scale, worst,
+                                  &sc.invalid),
+        "gpmp2mi_motion_score_traj");
+  sc.pos_state = worst[0]; sc.pos_coord = worst[1]; sc.vel_state = worst[2]; sc.vel_coord = worst[3];
+  sc.acc_end = worst[4]; sc.acc_coord = worst[5]; sc.speed_state = worst[6]; sc.speed_sphere = worst[7];
+  return sc;
+}
+/// SelectBestTrajectory that also asks whether the robot can execute the result: besides the rule above, no motion
+/// quantity may be non-finite, pos_margin must reach required_pos_margin and time_scale must not exceed max_time_scale.
+/// Host code.
+inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int>& status,
+                                const std::vector<TrajectoryScore>& scores,
+                                const std::vector<TrajectoryMotionScore>& motion_scores, double required_pos_margin,
+                                double max_time_scale, double required_clearance = 0.0, bool require_in_range = false,
+                                std::size_t* n_eligible = nullptr) {
+  if (motion_scores.size() != scores.size())
+    throw std::runtime_error("[SelectBestTrajectory] scores and motion_scores differ in length");
+  if (required_pos_margin != required_pos_margin || max_time_scale != max_time_scale)
+    throw std::runtime_error("[SelectBestTrajectory] required_pos_margin / max_time_scale is NaN");
+  std::vector<TrajectoryScore> both(scores);
+  for (std::size_t b = 0; b < both.size(); b++) {
+    const TrajectoryMotionScore& m = motion_scores[b];
+    const bool ok = m.invalid == 0 && m.pos_margin >= required_pos_margin && m.time_scale <= max_time_scale;
+    if (!ok) both[b].min_clearance = std::nan("");   // a NaN clearance is never eligible
   }
   return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
 }
