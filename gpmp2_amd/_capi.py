@@ -46,6 +46,7 @@ class Settings(C.Structure):
 
 
 MAX_WORKSPACE_FACTORS, MAX_SELF_COLLISION_PAIRS = 4, 16
+MAX_MOVING_SPHERES = 64
 WORKSPACE_POSITION, WORKSPACE_ORIENTATION, WORKSPACE_POSE = 0, 1, 2
 
 
@@ -64,7 +65,9 @@ class GraphOpts(C.Structure):
                 ("end_conf_prior_off", C.c_int), ("n_workspace", C.c_int),
                 ("workspace", WorkspaceFactor * MAX_WORKSPACE_FACTORS),
                 ("n_self_collision", C.c_int), ("self_collision_first", C.c_int), ("self_collision_last", C.c_int),
-                ("self_collision", (C.c_double * 4) * MAX_SELF_COLLISION_PAIRS)]
+                ("self_collision", (C.c_double * 4) * MAX_SELF_COLLISION_PAIRS),
+                ("max_moving_spheres", C.c_int), ("moving_first", C.c_int), ("moving_last", C.c_int),
+                ("moving_epsilon", C.c_double), ("moving_sigma", C.c_double)]
 
 
 class DebugForms(C.Structure):
@@ -193,6 +196,26 @@ def declare_motion(lib):
         getattr(lib, name).restype = i
     lib.gpmp2mi_motion_limits_default.argtypes = [lp]
     lib.gpmp2mi_motion_limits_default.restype = None
+
+
+def declare_moving(lib):
+    """argtypes of the moving-obstacle entry points (include/gpmp2mi.h "moving obstacles"); the `_dev` forms take device
+    addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_plan_set_moving_spheres": [vp, i, d, d],
+        "gpmp2mi_plan_set_moving_spheres_dev": [vp, i, vp, vp, vp],
+        "gpmp2mi_moving_sphere_factor": [vp, i, d, f, i, d, d, d, d],
+        "gpmp2mi_moving_score_traj": [vp, i, d, d, f, f, i, i, i, d, d, d, d, ip, ip],
+        "gpmp2mi_moving_score_traj_dev": [vp, i, vp, vp, f, f, i, i, i] + [vp] * 7,
+        "gpmp2mi_plan_moving_score": [vp, i, d, d, d, ip, ip],
+        "gpmp2mi_plan_moving_score_dev": [vp, i] + [vp] * 6,
+        "gpmp2mi_plan_select_moving": [vp, i, f, i, vp, f, f, ip, ip, d, d],
+        "gpmp2mi_plan_select_moving_dev": [vp, i, f, i, vp, f, f] + [vp] * 5,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
 
 
 def declare_group(lib):
@@ -403,4 +426,12 @@ def make_settings(setting):
         for k in range(sc.shape[0]):
             for t in range(4):
                 o.self_collision[k][t] = sc[k, t]
+    mv = getattr(setting, "moving_spheres", None)
+    if mv is not None:
+        if not 0 <= int(mv["capacity"]) <= MAX_MOVING_SPHERES:
+            raise ValueError("moving-sphere capacity outside 0..MAX_MOVING_SPHERES")
+        o.max_moving_spheres = int(mv["capacity"])
+        rng_ = mv.get("states") or (0, setting.total_step)
+        o.moving_first, o.moving_last = int(rng_[0]), int(rng_[1])
+        o.moving_epsilon, o.moving_sigma = float(mv["epsilon"]), float(mv["sigma"])
     return s, o, keep

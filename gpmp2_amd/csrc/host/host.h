@@ -124,10 +124,14 @@ struct gpmp2mi_robot {
   // the records of gpmp2mi_motion_score_traj(_dev) calls on this handle (motion_score.hip), under the same guard and rule
   mutable void* motion_ws = nullptr;
   mutable size_t motion_ws_bytes = 0;
+  // the records of gpmp2mi_moving_score_traj(_dev) calls on this handle (moving.hip), under the same guard and rule
+  mutable void* moving_ws = nullptr;
+  mutable size_t moving_ws_bytes = 0;
   ~gpmp2mi_robot() {
     if (d) (void)hipFree(d);
     if (score_ws) (void)hipFree(score_ws);
     if (motion_ws) (void)hipFree(motion_ws);
+    if (moving_ws) (void)hipFree(moving_ws);
     sampled_fac.release();
     if (replica) g2::g_robot_replicas.fetch_sub(1);
   }
@@ -321,6 +325,11 @@ struct gpmp2mi_plan {
   // select_feasible call and kept
   void* motion_ws = nullptr;
   size_t motion_ws_bytes = 0;
+  // moving obstacles (moving.hip): the records of k_moving_clearance, the per-row scores of the existing stages that
+  // select_moving's rule reads and the staging of the host-pointer forms, taken at the first moving_score /
+  // select_moving call and kept.  (The sphere set itself is part of `ex`, taken at creation.)
+  void* moving_ws = nullptr;
+  size_t moving_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }

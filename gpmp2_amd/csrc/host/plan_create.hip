@@ -1,5 +1,6 @@
 // plan_create.hip -- where a plan's memory comes from and goes back to (the pinned-flag pool, the arena-chunk pool,
 // plan_alloc), the choice of its kernel forms, and plan create / destroy.
+#include <cmath>
 #include <cstring>
 #include <mutex>
 
@@ -98,6 +99,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (self_ws) (void)hipFree(self_ws);
   if (group_ws) (void)hipFree(group_ws);
   if (motion_ws) (void)hipFree(motion_ws);
+  if (moving_ws) (void)hipFree(moving_ws);
   sampled_fac.release();
   flags_release(qflags);
 }
@@ -310,8 +312,23 @@ static int check_extras(const RobotDev& h, const gpmp2mi_graph_opts& o, int N, P
       for (int t = 0; t < 4; t++) hx.scd[4 * k + t] = o.self_collision[k][t];
       ex.sc_w[k] = 1.0 / (sg * sg);
     }
-    for (int sidx = 0; sidx < h.nr_spheres; sidx++) hx.radius[h.sph_orig[sidx]] = h.sph_r[sidx];
   }
+  G2_CHECK(o.max_moving_spheres >= 0 && o.max_moving_spheres <= GPMP2MI_MAX_MOVING_SPHERES, GPMP2MI_ERR_INVALID,
+           "max_moving_spheres outside 0..GPMP2MI_MAX_MOVING_SPHERES");
+  if (o.max_moving_spheres > 0) {
+    G2_CHECK(o.moving_sigma > 0 && std::isfinite(o.moving_sigma), GPMP2MI_ERR_INVALID, "moving spheres: sigma must be positive");
+    G2_CHECK(std::isfinite(o.moving_epsilon), GPMP2MI_ERR_INVALID, "moving spheres: epsilon must be finite");
+    G2_CHECK(o.moving_first >= 0 && o.moving_first <= o.moving_last && o.moving_last <= N, GPMP2MI_ERR_INVALID,
+             "moving spheres: bad state range");
+    ex.mv_cap = o.max_moving_spheres;
+    ex.mv_first = o.moving_first;
+    ex.mv_last = o.moving_last;
+    ex.mv_eps = o.moving_epsilon;
+    ex.mv_w = 1.0 / (o.moving_sigma * o.moving_sigma);
+  }
+  // the robot's radii in the caller's sphere order: read by the self-collision rows and the moving-sphere factor
+  if (ex.n_sc > 0 || ex.mv_cap > 0)
+    for (int sidx = 0; sidx < h.nr_spheres; sidx++) hx.radius[h.sph_orig[sidx]] = h.sph_r[sidx];
   return GPMP2MI_OK;
 }
 
@@ -374,6 +391,15 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
     G2_TRY(plan_alloc(p, &ex.sc_err, M * ex.n_sc));
     G2_TRY(plan_alloc(p, &ex.sc_H, M * ex.n_sc * D));
   }
+  if (ex.mv_cap > 0) {   // the centres and their Jacobians are shared with the self-collision rows
+    if (ex.n_sc == 0) {
+      G2_TRY(plan_alloc(p, &ex.radius, hx.radius.size()));
+      G2_TRY(plan_alloc(p, &ex.cen, M * h.nr_spheres * 3));
+      G2_TRY(plan_alloc(p, &ex.Jc, M * h.nr_spheres * 3 * D));
+    }
+    G2_TRY(plan_alloc(p, &ex.mv_radius, (size_t)ex.mv_cap));
+    G2_TRY(plan_alloc(p, &ex.mv_centers, (size_t)ex.mv_cap * (P.N + 1) * 3));
+  }
   G2_TRY(plan_alloc(p, &pb.n_active, p->n_active_len));
   G2_TRY(plan_alloc(p, &pb.stamps, (size_t)B * 128));   // rows 0..B-1: kernel phases, rows B..2B-1: one CR task per level
   G2_TRY(flags_acquire(p->n_active_len, &p->flagbuf));
@@ -391,8 +417,9 @@ static int upload_constants(gpmp2mi_plan* p, const ExtrasHost& hx) {
   if (ex.n_ws > 0) G2_HIP(hipMemcpy(ex.des, hx.des.data(), hx.des.size() * sizeof(double), hipMemcpyHostToDevice));
   if (ex.n_sc > 0) {
     G2_HIP(hipMemcpy(ex.sc_data, hx.scd.data(), hx.scd.size() * sizeof(double), hipMemcpyHostToDevice));
-    G2_HIP(hipMemcpy(ex.radius, hx.radius.data(), hx.radius.size() * sizeof(double), hipMemcpyHostToDevice));
   }
+  if (ex.n_sc > 0 || ex.mv_cap > 0)
+    G2_HIP(hipMemcpy(ex.radius, hx.radius.data(), hx.radius.size() * sizeof(double), hipMemcpyHostToDevice));
   G2_HIP(hipMemcpy(p->pb.params, &p->hp, sizeof(p->hp), hipMemcpyHostToDevice));
   // the zero fills of the arena chunks ran on the null stream: done before the caller may use any other stream
   G2_HIP(hipStreamSynchronize(nullptr));
@@ -458,7 +485,7 @@ int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf
   if (s->Qc) std::copy(s->Qc, s->Qc + (size_t)D * D, p->Qc.begin());
   ExtrasHost hx;
   G2_TRY(check_extras(robot->h, o, p->hp.N, p->ex, hx));
-  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0;
+  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0;
   p->h_xp_n.assign(B, 0);
   p->goal_removed.assign(B, 0);
   G2_TRY(alloc_buffers(p.get(), hx));

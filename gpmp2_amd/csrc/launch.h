@@ -133,6 +133,32 @@ int launch_motion(const RobotDev& h, const RobotDev* R, const MotionLimitsDev& l
                   const double* traj, MotionRec* recs, hipStream_t st);
 int launch_motion_finish(const MotionFinish& a, hipStream_t st);
 
+// moving_kernels.hip (include/gpmp2mi.h "moving obstacles"; the in-plan factor's launcher is in plan.h)
+// the factor on M evaluations: cen / Jc from launch_sphere_centers, robot_radius [S] in the caller's sphere order,
+// centers [M][K][3] -> err [M][S][K], H [M][S][K][D] or null
+int launch_moving_factor(int S, int D, int K, int M, const double* robot_radius, const double* radius, double eps,
+                         const double* centers, const double* cen, const double* Jc, double* err, double* H,
+                         hipStream_t st);
+// arguments of k_moving_finish.  The records of k_moving_clearance are ScoreRecs by the tiling of k_self_clearance
+// (self_tile, self_blocks): s is the pair index sphere * K + moving sphere, oor the number of invalid pairs.  `sel`
+// carries the selection (sel.select) and the shape of the trajectories; the rule reads the per-row scores the existing
+// stages left, as MotionFinish does.
+struct MovingFinish {
+  ScoreFinish sel;
+  const ScoreRec* recs;   // [B][nblk]
+  int nblk, K;
+  double *support, *dense, *min_clearance;
+  int *worst, *invalid;   // [B][3], [B]
+  const double *clearance, *self_clearance;
+  const int *oor, *self_invalid;
+  double required_self_clearance, required_moving_clearance;
+};
+// radius [K], centers [K][N+1][3]
+int launch_moving_clearance(const RobotDev& h, const RobotDev* R, int K, const double* radius, const double* centers,
+                            double eps, double dt, int inter, int B, int N, const double* traj, ScoreRec* recs,
+                            hipStream_t st);
+int launch_moving_finish(const MovingFinish& a, hipStream_t st);
+
 // group_kernels.hip (include/gpmp2mi.h "distinct alternatives")
 constexpr int GROUP_TILE = 64;          // k_traj_pairs: one workgroup per 64 x 64 tile of pairs
 constexpr int GROUP_CHUNK_ELEMS = 32;   // configuration doubles of a row staged through LDS at a time

@@ -67,6 +67,12 @@ struct PlanExtras {
   double* Jc;        // [M][S][3][D]
   double* sc_err;    // [M][n_sc]
   double* sc_H;      // [M][n_sc][D]
+  // moving spheres (include/gpmp2mi.h "moving obstacles"): the capacity, the factor's constants and the resident set.
+  // mv_K is the set's current size, a host value that every launch takes as an argument (moving_kernels.hip)
+  int mv_cap, mv_K, mv_first, mv_last;
+  double mv_eps, mv_w;   // epsilon, 1 / sigma^2
+  double* mv_radius;     // [mv_cap]
+  double* mv_centers;    // [mv_cap][N+1][3], the first mv_K spheres in use
 };
 
 // Per-plan device buffers.
@@ -181,6 +187,10 @@ int launch_linearize(const RobotDev& hrobot, const RobotDev* robot, const SdfDev
                      const int* active, hipStream_t st, double* dst = nullptr, int pass = 0, bool trial = false);
 int launch_extra_accumulate(const PlanParams& hp, const PlanBuffers& pb, const PlanExtras& ex, int L, int S, int bufsel,
                             const int* active, hipStream_t st);
+// moving_kernels.hip: the moving-sphere factor of the states ex.mv_first..mv_last, from ex.cen / ex.Jc and the resident
+// set (ex.mv_K > 0), straight into the unary records
+int launch_moving_accumulate(const PlanParams& hp, const PlanBuffers& pb, const PlanExtras& ex, int S, int bufsel,
+                             const int* active, hipStream_t st);
 int launch_set_mode(const PlanBuffers& pb, int opt_type, int fixed_iters, hipStream_t st);
 int launch_error_parts(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel, const int* active,
                        hipStream_t st);

@@ -44,6 +44,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_score(lib)
     _capi.declare_self(lib)
     _capi.declare_motion(lib)
+    _capi.declare_moving(lib)
     _capi.declare_group(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
@@ -114,6 +115,11 @@ def _score_ptrs(o):
 def _self_ptrs(o):
     return (dptr(o["self_support_cost"]), dptr(o["self_dense_cost"]), dptr(o["min_self_clearance"]), iptr(o["worst"]),
             iptr(o["invalid"]))
+
+
+def _moving_ptrs(o):
+    return (dptr(o["moving_support_cost"]), dptr(o["moving_dense_cost"]), dptr(o["min_moving_clearance"]),
+            iptr(o["worst"]), iptr(o["invalid"]))
 
 
 def _motion_ptrs(o):
@@ -413,6 +419,21 @@ class Engine:
         self._ck(self.lib.gpmp2mi_self_collision_factor(robot.ptr, n, dptr(d), M, dptr(q), dptr(err), dptr(H)))
         return err, H
 
+    def moving_sphere_factor(self, robot, radius, epsilon, conf, centers, jac=True):
+        """The moving-sphere hinge (include/gpmp2mi.h "moving obstacles"): radius [K], conf [M][D], centers [M][K][3]
+        (one centre set per evaluation) -> err [M][S][K], H [M][S][K][D]"""
+        q = f64(conf).reshape(-1, robot.dof)
+        M = q.shape[0]
+        r = f64(radius).reshape(-1)
+        K, S = r.size, int(robot.S)
+        if K > scoring.MAX_MOVING_SPHERES:
+            raise ValueError(f"{K} moving spheres, at most {scoring.MAX_MOVING_SPHERES}")
+        c = f64(centers).reshape(M, K, 3)
+        err, H = np.zeros((M, S, K)), (np.zeros((M, S, K, robot.dof)) if jac else None)
+        self._ck(self.lib.gpmp2mi_moving_sphere_factor(robot.ptr, K, dptr(r), float(epsilon), M, dptr(q), dptr(c),
+                                                       dptr(err), dptr(H)))
+        return err, H
+
     def vehicle_dynamics_factor(self, lie, conf, vel):
         """sliding velocity of an SE(2) base -> err [M], Hp [M][D], Hv [M][D]"""
         q, v = f64(conf), f64(vel)
@@ -640,6 +661,22 @@ class Engine:
         lim = _limits_arg(limits, robot.dof)
         self._ck(self.lib.gpmp2mi_motion_score_traj(robot.ptr, lim, float(delta_t), inter_step, B, N, dptr(t),
                                                     *_motion_ptrs(o)))
+        return o
+
+    # ---------------------------------------------------------------- moving obstacles (include/gpmp2mi.h)
+    def moving_score_traj(self, robot, radius, centers, epsilon, delta_t, inter_step, traj, out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) against the spheres radius [K], centers [K][N+1][3] -> dict(
+        moving_support_cost [B], moving_dense_cost [B], min_moving_clearance [B], worst [B][3] = (checked state, robot
+        sphere, moving sphere), invalid [B]) of the inter_step-up-sampled trajectories."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        K, r, c = scoring.moving_set(radius, centers, N + 1)
+        o = scoring.score_outputs(B, out, scoring.MOVING_NAMES)
+        self._ck(self.lib.gpmp2mi_moving_score_traj(robot.ptr, K, dptr(r), dptr(c), float(epsilon), float(delta_t),
+                                                    inter_step, B, N, dptr(t), *_moving_ptrs(o)))
         return o
 
     # ---------------------------------------------------------------- distinct alternatives (include/gpmp2mi.h)
@@ -1077,6 +1114,69 @@ class Plan:
         self.eng._ck(self.eng.lib.gpmp2mi_plan_select_feasible_dev(
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
             None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts,
+            *args, C.c_void_p(stream or 0)))
+
+    # ---- spheres that move with the support time (include/gpmp2mi.h "moving obstacles")
+    def set_moving_spheres(self, radius, centers):
+        """The plan's sphere set: radius [K], centers [K][N+1][3]; None / empty clears it.  May be repeated between
+        solves; the plan must have been created with room for K (TrajOptimizerSetting.set_moving_spheres)."""
+        K, r, c = scoring.moving_set(radius, centers, self.N + 1)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_moving_spheres(self.h.ptr, K, dptr(r), dptr(c)))
+
+    def set_moving_spheres_dev(self, K, radius, centers, stream=None):
+        """The same from device buffers (torch tensors or raw pointers); the copies are enqueued on `stream`."""
+        K = int(K)
+        args = [_dev_arg("radius", radius, (K,)), _dev_arg("centers", centers, (K, self.N + 1, 3))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_moving_spheres_dev(self.h.ptr, K, *args, C.c_void_p(stream or 0)))
+
+    def moving_score(self, inter_step, out=None):
+        """dict(moving_support_cost, moving_dense_cost, min_moving_clearance, worst [B][3], invalid) of the plan's result
+        against its resident sphere set, B rows."""
+        inter_step = _score_args(inter_step)
+        o = scoring.score_outputs(self.B, out, scoring.MOVING_NAMES)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_moving_score(self.h.ptr, inter_step, *_moving_ptrs(o)))
+        return o
+
+    def moving_score_dev(self, inter_step, moving_support_cost=None, moving_dense_cost=None, min_moving_clearance=None,
+                         worst=None, invalid=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        B = self.B
+        args = [_dev_arg("moving_support_cost", moving_support_cost, (B,)),
+                _dev_arg("moving_dense_cost", moving_dense_cost, (B,)),
+                _dev_arg("min_moving_clearance", min_moving_clearance, (B,)), _dev_arg("worst", worst, (B, 3), True),
+                _dev_arg("invalid", invalid, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_moving_score_dev(self.h.ptr, _score_args(inter_step), *args,
+                                                                C.c_void_p(stream or 0)))
+
+    def select_moving(self, inter_step, required_moving_clearance=0.0, required_clearance=0.0, require_in_range=False,
+                      pairs=None, required_self_clearance=0.0):
+        """select() (select_checked() when `pairs` is given) with the rule that also asks for no invalid pair and
+        required_moving_clearance against the plan's sphere set: dict(best, n_eligible, traj_best, dense_best);
+        best = -1: the two trajectories are None."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D))
+        best, n = C.c_int(-1), C.c_int(0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_moving(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), float(required_moving_clearance),
+            C.byref(best), C.byref(n), dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_moving_dev(self, inter_step, required_moving_clearance=0.0, required_clearance=0.0, require_in_range=False,
+                          pairs=None, required_self_clearance=0.0, best=None, n_eligible=None, traj_best=None,
+                          dense_best=None, stream=None):
+        """The same with device outputs, as select_dev.  One enqueue on `stream`, no host synchronisation once the
+        plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_moving_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), float(required_moving_clearance),
             *args, C.c_void_p(stream or 0)))
 
     # ---- one representative per mode of the resident result (include/gpmp2mi.h "distinct alternatives")

@@ -97,8 +97,10 @@ def pair_table(data, S=None):
 
 def score_outputs(B, out=None, names=SCORE_NAMES):
     """The five per-row outputs of a score call: fresh arrays, or the caller's (a dict with any of the five names),
-    checked for dtype, contiguity and length.  names: SCORE_NAMES, or SELF_NAMES for the self-collision check."""
-    shapes = (((B,), np.float64), ((B,), np.float64), ((B,), np.float64), ((B, 2), np.int32), ((B,), np.int32))
+    checked for dtype, contiguity and length.  names: SCORE_NAMES, SELF_NAMES for the self-collision check, or
+    MOVING_NAMES for the moving obstacles (worst [B][3])."""
+    nw = 3 if names is MOVING_NAMES else 2
+    shapes = (((B,), np.float64), ((B,), np.float64), ((B,), np.float64), ((B, nw), np.int32), ((B,), np.int32))
     want = dict(zip(names, shapes))
     res = {}
     out = out or {}
@@ -191,6 +193,43 @@ def feasible_thresholds(required_pos_margin, max_time_scale):
     if np.isnan(required_pos_margin) or np.isnan(max_time_scale):
         raise ValueError("required_pos_margin / max_time_scale must not be NaN")
     return required_pos_margin, max_time_scale
+
+
+# ---- moving obstacles (include/gpmp2mi.h "moving obstacles"): the output names, the extended rule, the sphere set
+MOVING_NAMES = ("moving_support_cost", "moving_dense_cost", "min_moving_clearance", "worst", "invalid")
+MAX_MOVING_SPHERES = 64     # GPMP2MI_MAX_MOVING_SPHERES
+
+
+def moving_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+                min_self_clearance=None, invalid=None, required_self_clearance=0.0, min_moving_clearance=None,
+                moving_invalid=None, required_moving_clearance=-np.inf):
+    """(best, n_eligible) by the rule of select_rule with two more conditions: no invalid (state, sphere, moving sphere)
+    and min_moving_clearance >= required_moving_clearance (each None: not asked)."""
+    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
+    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+                  invalid, required_self_clearance)
+    if moving_invalid is not None:
+        ok &= np.asarray(moving_invalid).reshape(-1) == 0
+    if min_moving_clearance is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= np.asarray(min_moving_clearance, dtype=np.float64).reshape(-1) >= required_moving_clearance
+    rows = np.flatnonzero(ok)
+    if rows.size == 0:
+        return -1, 0
+    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+
+
+def moving_set(radius, centers, states, capacity=MAX_MOVING_SPHERES):
+    """A sphere set as contiguous float64 (radius [K], centers [K][states][3]); None / empty: K = 0.  ValueError for
+    another shape or more than `capacity` spheres."""
+    r = np.zeros(0) if radius is None else np.ascontiguousarray(radius, dtype=np.float64).reshape(-1)
+    K = r.size
+    c = np.zeros((0, states, 3)) if centers is None or K == 0 else np.ascontiguousarray(centers, dtype=np.float64)
+    if c.shape != (K, states, 3):
+        raise ValueError(f"centers: expected [{K}][{states}][3], got {list(c.shape)}")
+    if K > capacity:
+        raise ValueError(f"{K} moving spheres, room for {capacity}")
+    return K, r, c
 
 
 # ---- distinct alternatives (include/gpmp2mi.h): the grouping rule in numpy terms and the shape checks of its wrappers

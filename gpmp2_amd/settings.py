@@ -52,6 +52,14 @@ class TrajOptimizerSetting:
         self.workspace_factors = []          # dicts(mode, link, first_state, last_state, sigma, des_pose 4x4)
         self.self_collision = None           # [n][4] = sphere A, sphere B, epsilon, sigma
         self.self_collision_states = None    # (first, last) support states, default all
+        self.moving_spheres = None           # dict(capacity, epsilon, sigma, states): set_moving_spheres
+
+    def set_moving_spheres(self, capacity, epsilon, sigma, states=None):
+        """Room for `capacity` moving spheres in the plan (include/gpmp2mi.h "moving obstacles") and the constants of
+        their factor on the support states `states` = (first, last), default all; the spheres themselves are data of
+        Plan.set_moving_spheres.  capacity 0: none."""
+        self.moving_spheres = dict(capacity=int(capacity), epsilon=float(epsilon), sigma=float(sigma),
+                                   states=None if states is None else (int(states[0]), int(states[1])))
 
     # extra factors (names follow the reference's factor classes)
     def add_goal_factor_arm(self, link, dest_point, sigma, state=None):

@@ -191,6 +191,7 @@ void gpmp2mi_settings_default(gpmp2mi_settings* s, int dof);
 #define GPMP2MI_WORKSPACE_POSE 2
 #define GPMP2MI_MAX_WORKSPACE_FACTORS 4
 #define GPMP2MI_MAX_SELF_COLLISION_PAIRS 16
+#define GPMP2MI_MAX_MOVING_SPHERES 64
 /* A workspace factor carried by a plan: GaussianPriorWorkspace{Position,Orientation,Pose}<Arm>
  * (kinematics/GaussianPriorWorkspacePosition.h:52-67, ...Orientation.h:52-69, ...Pose.h:53-70) or GoalFactorArm
  * (kinematics/GoalFactorArm.h:58-77 = POSITION on the last link) on the support states first_state..last_state,
@@ -229,6 +230,11 @@ typedef struct gpmp2mi_graph_opts {
                                     self_collision_first..last; <= GPMP2MI_MAX_SELF_COLLISION_PAIRS rows */
   int self_collision_first, self_collision_last;
   double self_collision[GPMP2MI_MAX_SELF_COLLISION_PAIRS][4];  /* sphere A, sphere B, epsilon, sigma */
+  /* ---- moving spheres ("moving obstacles" below): the capacity and the factor's constants; the spheres themselves are
+   * data of gpmp2mi_plan_set_moving_spheres.  Appended at the end of the struct; all default to 0 = none */
+  int max_moving_spheres;        /* capacity reserved at plan creation, <= GPMP2MI_MAX_MOVING_SPHERES; 0: none */
+  int moving_first, moving_last; /* inclusive range of support states that carry the factor */
+  double moving_epsilon, moving_sigma;
 } gpmp2mi_graph_opts;
 void gpmp2mi_graph_opts_default(gpmp2mi_graph_opts* o);
 
@@ -670,6 +676,87 @@ int gpmp2mi_plan_select_feasible_dev(gpmp2mi_plan* p, int inter_step, double req
                                      const gpmp2mi_motion_limits* limits, double required_pos_margin,
                                      double max_time_scale, int* best, int* n_eligible, double* time_scale_best,
                                      double* traj_best, double* dense_best, void* stream);
+
+/* ---- moving obstacles: time-indexed spheres as a plan factor and a check, on the device ---------------------------
+ * Every obstacle of "scoring" lives in one static signed-distance field.  A person or another robot crossing the
+ * workspace is a set of K spheres whose centres are indexed by the support time: radius [K], centers [K][N+1][3],
+ * sphere k at centers[k][i] at support state i.  One set per plan, shared by its B trajectories.  A plan created with
+ * gpmp2mi_graph_opts::max_moving_spheres > 0 reserves room for that many spheres (all device memory is taken at
+ * gpmp2mi_plan_create), carries the factor below on the support states moving_first..moving_last, and takes its data
+ * from gpmp2mi_plan_set_moving_spheres, which may be repeated every control cycle.
+ *
+ * Definitions, for robot sphere s (all S spheres, ids in the order of the robot description) and moving sphere k:
+ *  - total_eps(s, k) = (radius_s + radius_k) + epsilon, evaluated in that order in fp64.
+ *  - The factor, at support state i in [moving_first, moving_last]: dist = |c_s(q_i) - centers[k][i]|;
+ *    err = dist > total_eps ? 0 : total_eps - dist (the strictness of obstacle/SelfCollision.h:114-127); the Jacobian row
+ *    is -n^T J_s when active and zero otherwise, n = (c_s - o_k) / dist, J_s the sphereCenters Jacobian as
+ *    gpmp2mi_sphere_centers returns it (the Pose2 chart for the mobile kinds).  dist == 0: err = total_eps, a zero
+ *    row, no NaN.  Noise: isotropic moving_sigma.  In a plan the S K rows of a state are never stored: one kernel adds
+ *    sum w h h^T, sum w h r and sum w r^2 (w = 1 / sigma^2) to the record of the state's unary point, in pair order
+ *    (s, k) ascending, so a state's contribution is the same bits alone, in any batch and on any run.  Every call that
+ *    linearizes a plan carries the factor: optimize, the queue runs, plan_update, plan_linearize, plan_graph_error;
+ *    Gauss-Newton, LM and Dogleg; narrow, wide and dense blocks.  With K == 0 nothing is launched for it.
+ *  - The check: the checked states of "scoring" (Md = N (J+1) + 1).  At checked state i (J+1) + j sphere k is at
+ *    o_i + tau (o_{i+1} - o_i), tau = j / (J+1), evaluated in that form; support states use o_i itself.
+ *    clearance(m, s, k) = dist - total_eps; a pair whose dist is not finite is invalid: it enters no sum and no minimum,
+ *    and it is counted.  moving_support_cost [B] / moving_dense_cost [B]: the unwhitened hinge sums over the support /
+ *    all checked states.  min_moving_clearance [B]: the minimum over the valid (m, s, k), +inf if there is none (K = 0).
+ *    worst [B][3]: the (checked state, robot sphere, moving sphere) attaining it; on exact ties the lowest state, then
+ *    the lowest sphere, then the lowest moving sphere; (-1, -1, -1) if none.  invalid [B].  Any output may be NULL.
+ *  - Determinism as in "self-collision check": sums are taken in an order fixed by (N, J, S, K), without floating-point
+ *    atomics; a row scores the same bits alone, in any batch, through the trajectory form or the plan form.
+ *  - Selection: the rule of gpmp2mi_plan_select (of gpmp2mi_plan_select_checked when pairs != NULL) with one more
+ *    condition,
+ *      eligible(b) = <that rule> && moving_invalid[b] == 0 && min_moving_clearance[b] >= required_moving_clearance;
+ *    ranking and ties unchanged.  With K == 0 and required_moving_clearance = -inf it answers what the existing call does.
+ * Errors: GPMP2MI_ERR_INVALID (checked before any device work) for a NULL plan / robot / traj, K < 0, K above the
+ * capacity (the plan forms) or above GPMP2MI_MAX_MOVING_SPHERES (the others), a NULL radius / centers with K > 0, a NaN
+ * epsilon, the argument errors of "scoring"; the plan forms of the check also for a plan created without capacity, and
+ * with the preconditions of gpmp2mi_plan_score.  GPMP2MI_ERR_TIMEOUT for a poisoned plan.
+ * Memory: the workspace rules of "scoring"; the records (one 40-byte record per tile of "self-collision check") are kept
+ * with the plan, and by gpmp2mi_moving_score_traj_dev with the robot handle.
+ * Not here: gpmp2mi_multi_plan_* twins, C++ facade classes, the factor at GP-interpolated sub-steps (the dense check is
+ * what looks between support states), per-trajectory sphere sets, moving spheres in the risk / collision-probability
+ * calls, shapes other than spheres. */
+
+/* The plan's sphere set.  Valid at any time between solves; K = 0 clears the set; a fresh plan holds K = 0.  Host form:
+ * the data is copied before the call returns, and a non-finite centre or a negative / non-finite radius is refused.
+ * _dev: device pointers, the copies are enqueued on `stream`, the values are not inspected.  A refused call changes
+ * nothing. */
+int gpmp2mi_plan_set_moving_spheres(gpmp2mi_plan* p, int K, const double* radius /*[K]*/,
+                                    const double* centers /*[K][N+1][3]*/);
+int gpmp2mi_plan_set_moving_spheres_dev(gpmp2mi_plan* p, int K, const double* radius, const double* centers,
+                                        void* stream);
+/* The factor, batched over M evaluations with one centre set per evaluation: conf [M][D], centers [M][K][3] ->
+ * err [M][S][K] (unwhitened), H [M][S][K][D] (NULL ok). */
+int gpmp2mi_moving_sphere_factor(const gpmp2mi_robot* r, int K, const double* radius, double epsilon, int M,
+                                 const double* conf, const double* centers, double* err, double* H);
+/* The check for caller buffers; traj [B][total_step+1][2D], centers [K][total_step+1][3].  The device of the robot
+ * handle must be current. */
+int gpmp2mi_moving_score_traj(const gpmp2mi_robot* robot, int K, const double* radius, const double* centers,
+                              double epsilon, double delta_t, int inter_step, int B, int total_step, const double* traj,
+                              double* moving_support_cost, double* moving_dense_cost, double* min_moving_clearance,
+                              int* worst, int* invalid);
+int gpmp2mi_moving_score_traj_dev(const gpmp2mi_robot* robot, int K, const double* radius, const double* centers,
+                                  double epsilon, double delta_t, int inter_step, int B, int total_step,
+                                  const double* traj, double* moving_support_cost, double* moving_dense_cost,
+                                  double* min_moving_clearance, int* worst, int* invalid, void* stream);
+/* The plan's resident result against the plan's resident set, with its moving_epsilon and delta_t. */
+int gpmp2mi_plan_moving_score(gpmp2mi_plan* p, int inter_step, double* moving_support_cost, double* moving_dense_cost,
+                              double* min_moving_clearance, int* worst, int* invalid);
+int gpmp2mi_plan_moving_score_dev(gpmp2mi_plan* p, int inter_step, double* moving_support_cost,
+                                  double* moving_dense_cost, double* min_moving_clearance, int* worst, int* invalid,
+                                  void* stream);
+/* One enqueue: the existing score stages, the moving scores, then one finish that reads them all.  Outputs as
+ * gpmp2mi_plan_select. */
+int gpmp2mi_plan_select_moving(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                               const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                               double required_moving_clearance, int* best, int* n_eligible, double* traj_best,
+                               double* dense_best);
+int gpmp2mi_plan_select_moving_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                   const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                   double required_moving_clearance, int* best, int* n_eligible, double* traj_best,
+                                   double* dense_best, void* stream);
 
 /* ---- distinct alternatives: how many different solutions the restarts found, one row per mode, on the device ------
  * The calls of "scoring" answer with one row.  These calls say how many different trajectories a batch holds and hand
