@@ -104,4 +104,19 @@ if feasible["best"] >= 0:
     s = feasible["time_scale_best"]
     print(f"  time_scale {s:.3f}: run it over {max(s, 1.0) * total_time_sec:.2f} s instead of {total_time_sec:.2f} s "
           f"(velocities divided by {max(s, 1.0):.3f})")
+
+# ---- the static map changes.  The field is rewritten in place (include/gpmp2mi.h "live map"): `plan` and the replanner
+# above keep their memory and read the new map in their next call.  The desk scene becomes the base; this cycle's cloud, a
+# box where the hand passes half-way, is united with it, and the points on the robot's own arm are dropped.
+sdf.updateFromOccupancy(g.sdf3_zyx(np.asarray(dataset.map, dtype=np.float64)))
+hand = eng.sphere_centers(robot, 0.5 * (start_conf + end_conf))[0][0][-1]
+side = np.arange(-3, 4) * dataset.cell_size
+cloud = np.array([[hand[0] + dx, hand[1] + dy, hand[2] + dz] for dx in side for dy in side for dz in side])
+on_arm = eng.sphere_centers(robot, start_conf)[0][0]
+counts = sdf.updateFromPoints(np.concatenate([cloud, on_arm]), use_base=True, robot=arm, conf=start_conf, margin=0.02)
+plan.set_problem(*[np.repeat(v[None], B, axis=0) for v in (start_conf, zero, end_conf, zero)], inits)
+plan.optimize()
+again = plan.select_checked(9, pairs, required_clearance=0.0, require_in_range=True, required_self_clearance=0.0)
+print(f"map changed in place ({counts['kept']} points kept, {counts['self']} on the robot itself dropped): "
+      f"{again['n_eligible']} restarts clear of the new map, best = restart {again['best']}")
 plan.close()

@@ -218,6 +218,26 @@ def declare_moving(lib):
         getattr(lib, name).restype = i
 
 
+def declare_map(lib):
+    """argtypes of the live-map entry points (include/gpmp2mi.h "live map") and their stage timer; the `_dev` forms take
+    device addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_sdf_reserve_update": [vp],
+        "gpmp2mi_sdf_update": [vp, d, i],
+        "gpmp2mi_sdf_update_dev": [vp, vp, vp],
+        "gpmp2mi_sdf_update_from_occupancy": [vp, d, i],
+        "gpmp2mi_sdf_update_from_occupancy_dev": [vp, vp, vp],
+        "gpmp2mi_sdf_update_from_points": [vp, i, d, i, vp, d, f, ip],
+        "gpmp2mi_sdf_update_from_points_dev": [vp, i, vp, i, vp, vp, f, vp, vp],
+        "gpmp2mi_multi_plan_refresh_field": [vp],
+        "gpmp2mi_debug_sdf_update_timing": [vp, i, d],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def declare_group(lib):
     """include/gpmp2mi.h "distinct alternatives"; `weights` is a host array in every form"""
     vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double

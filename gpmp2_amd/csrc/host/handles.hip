@@ -108,12 +108,9 @@ int sdf_alloc(int dim, const double origin[3], double cell, int nx, int ny, int 
   h.cells = s->cells;
   return GPMP2MI_OK;
 }
-}  // namespace g2
-
-using namespace g2;
 
 // caller layout -> [nz][ny][nx]
-static const double* to_zyx(const double* vox, int layout, int nx, int ny, int nz, std::vector<double>& tmp) {
+const double* to_zyx(const double* vox, int layout, int nx, int ny, int nz, std::vector<double>& tmp) {
   if (layout != GPMP2MI_SDF_LAYOUT_GTSAM) return vox;
   tmp.resize((size_t)nx * ny * nz);
   for (int z = 0; z < nz; z++)
@@ -121,6 +118,9 @@ static const double* to_zyx(const double* vox, int layout, int nx, int ny, int n
       for (int x = 0; x < nx; x++) tmp[((size_t)z * ny + y) * nx + x] = vox[((size_t)z * nx + x) * ny + y];
   return tmp.data();
 }
+}  // namespace g2
+
+using namespace g2;
 
 extern "C" {
 

@@ -142,9 +142,20 @@ struct gpmp2mi_sdf {
   double* cells = nullptr;
   int device = -1;        // the device `plain` / `cells` live on (current device at sdf_alloc)
   bool replica = false;   // a multi plan's copy (sdf_replica)
+  // live map (map.hip; include/gpmp2mi.h "live map"): two int32 volumes, the byte mask of the base, [MAXS][3] sphere
+  // centres and four counters in one block on `device`, taken at the first update or by gpmp2mi_sdf_reserve_update and
+  // kept.  has_base: the mask holds the obstacle set of the last gpmp2mi_sdf_update_from_occupancy(_dev).
+  void* map_ws = nullptr;
+  bool has_base = false;
+  // gpmp2mi_debug_sdf_update_timing: five events around the four stages of an update, recorded while map_timing
+  hipEvent_t map_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool map_timing = false;
   ~gpmp2mi_sdf() {   // also runs when a create function fails half-way (unique_ptr)
     if (plain) (void)hipFree(plain);
     if (cells) (void)hipFree(cells);
+    if (map_ws) (void)hipFree(map_ws);
+    for (hipEvent_t e : map_ev)
+      if (e) (void)hipEventDestroy(e);
     if (replica) g2::g_sdf_replicas.fetch_sub(1);
   }
 };
@@ -169,6 +180,8 @@ struct gpmp2mi_self_pairs {
 namespace g2 {
 // geometry + device storage of a field handle; the caller fills s->plain ([nz][ny][nx]) and packs (handles.hip)
 int sdf_alloc(int dim, const double origin[3], double cell, int nx, int ny, int nz, std::unique_ptr<gpmp2mi_sdf>& s);
+// caller layout -> [nz][ny][nx] (handles.hip); `tmp` holds the reordered copy when one is needed
+const double* to_zyx(const double* vox, int layout, int nx, int ny, int nz, std::vector<double>& tmp);
 
 struct KernelTimer {
   // One HIP event per kernel boundary on the launch stream: begin(name) is recorded right before kernel `name`,

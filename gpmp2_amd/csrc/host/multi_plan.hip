@@ -60,6 +60,7 @@ struct gpmp2mi_multi_plan {
   int B = 0, D = 0, N = 0, T = 0;  // T = max_iter + 1 (error trace columns)
   std::vector<MultiShard> shards;
   std::vector<MultiReplica> replicas;
+  const gpmp2mi_sdf* src_sdf = nullptr;            // the caller's field handle: what refresh_field copies from
   std::vector<std::pair<int, hipEvent_t>> entry;   // get_result_dev: per gather device, recorded on the caller's stream
   bool problem_set = false, optimized = false, queue_ran = false;
   bool poisoned = false;           // a shard timed out: every later call returns GPMP2MI_ERR_TIMEOUT
@@ -242,6 +243,7 @@ int gpmp2mi_debug_multi_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sd
   m->D = robot->h.dof;
   m->N = s->total_step;
   m->T = s->max_iter + 1;
+  m->src_sdf = sdf;
   std::vector<int> row0, rows;
   split_rows(B, nshards, row0, rows);
   m->shards.resize(nshards);
@@ -287,6 +289,27 @@ int gpmp2mi_multi_plan_shards(const gpmp2mi_multi_plan* m, int* nshards, int* de
     if (row_begin) row_begin[k] = m->shards[k].row0;
   }
   if (row_begin) row_begin[n] = m->B;
+  return GPMP2MI_OK;
+}
+
+// Live map (map.hip): the voxels of the caller's handle again to every copy this multi plan owns, by the steps of
+// sdf_replica: a peer copy of `plain`, then the pack kernel on the copy's device.
+int gpmp2mi_multi_plan_refresh_field(gpmp2mi_multi_plan* m) {
+  G2_MULTI_LIVE(m);
+  DeviceGuard guard;
+  const gpmp2mi_sdf* src = m->src_sdf;
+  const size_t bytes = (size_t)src->h.nx * src->h.ny * src->h.nz * sizeof(double);
+  for (MultiReplica& r : m->replicas) {
+    if (!r.sdf) continue;
+    G2_HIP(hipSetDevice(r.device));
+    G2_HIP(hipMemcpyPeer(r.sdf->plain, r.device, src->plain, src->device, bytes));
+    G2_TRY(launch_sdf_pack(r.sdf->h, r.sdf->cells, nullptr));
+  }
+  for (MultiReplica& r : m->replicas) {
+    if (!r.sdf) continue;
+    G2_HIP(hipSetDevice(r.device));
+    G2_HIP(hipStreamSynchronize(nullptr));
+  }
   return GPMP2MI_OK;
 }
 

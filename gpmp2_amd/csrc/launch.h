@@ -7,8 +7,30 @@
 namespace g2 {
 
 // sdf_kernels.hip
+constexpr int EDT_INF = 0x3fffffff;   // "no cell of the target set" in the two int32 volumes of squared distances
 int launch_sdf_from_occupancy(int nx, int ny, int nz, const double* occ, double cell, int* wa, int* wb,
                               double* field, hipStream_t st);
+// the steps of launch_sdf_from_occupancy behind its seed: the three axis passes over two seeded volumes, and
+// field = (sqrt(wa) - sqrt(wb)) * cell.  edt_check_axes: the axis limits of the passes, without a launch.
+int edt_check_axes(int nx, int ny, int nz);
+int launch_edt_passes(int nx, int ny, int nz, int* wa, int* wb, hipStream_t st);
+int launch_edt_finish(size_t n, const int* wa, const int* wb, double cell, double* field, hipStream_t st);
+// map_kernels.hip (include/gpmp2mi.h "live map"): seeds that take the place of the occupancy seed
+// occ [n] -> the two volumes and the obstacle set as one byte per cell
+int launch_map_seed_occ(size_t n, const double* occ, int* wa, int* wb, unsigned char* mask, hipStream_t st);
+// mask [n] (null: every cell free) -> the two volumes
+int launch_map_seed(size_t n, const unsigned char* mask, int* wa, int* wb, hipStream_t st);
+// arguments of k_map_mark: M points classified and the kept ones stored into the two volumes
+struct MapMark {
+  int dim, nx, ny, nz, M, S;
+  double ox, oy, oz, cell, margin;
+  const double* pts;   // [M][dim]
+  const RobotDev* R;   // null: no self filter
+  const double* cen;   // [S][3] in the caller's sphere order (launch_sphere_centers, M = 1)
+  int *wa, *wb;
+  int* cnt;            // [4]: kept, non-finite, self, outside; zeroed by the caller
+};
+int launch_map_mark(const MapMark& a, hipStream_t st);
 // factor_kernels.hip
 int launch_sdf_pack(const SdfDev& s, double* cells, hipStream_t st);
 int launch_sdf_query(const SdfDev& s, int M, const double* pts, double* dist, double* grad, int* inr,

@@ -20,8 +20,6 @@
 
 namespace g2 {
 
-constexpr int EDT_INF = 0x3fffffff;
-
 // a = squared distance seed to the obstacle set (0 on obstacle cells), b = to the free set
 __global__ void k_edt_seed(size_t n, const double* __restrict__ occ, int* __restrict__ a, int* __restrict__ b) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -156,45 +154,76 @@ __global__ void k_edt_finish(size_t n, const int* __restrict__ a, const int* __r
   }
 }
 
-// occ, field: [nz][ny][nx] device pointers; wa, wb: int32 scratch of the same element count
-int launch_sdf_from_occupancy(int nx, int ny, int nz, const double* occ, double cell, int* wa, int* wb,
-                              double* field, hipStream_t st) {
-  const size_t n = (size_t)nx * ny * nz;
-  const int sweep = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
-  k_edt_seed<<<dim3(sweep), dim3(256), 0, st>>>(n, occ, wa, wb);
-  constexpr size_t kLdsBudget = 144 * 1024;
-  auto strided = [&](int len, size_t inner, size_t outer) -> int {
-    if (len < 2) return GPMP2MI_OK;
-    if (len < 32768 && (size_t)len * 32 * 2 * sizeof(int) <= kLdsBudget) {  // linear-time scan, 32 lines per block
-      k_edt_strided_scan<32><<<dim3((unsigned)((inner + 31) / 32), (unsigned)outer, 2), dim3(256),
-                               (size_t)len * 32 * 2 * sizeof(int), st>>>(len, inner, wa, wb);
-    } else if ((size_t)len * 64 * sizeof(int) <= kLdsBudget) {
-      k_edt_strided<64><<<dim3((unsigned)((inner + 63) / 64), (unsigned)outer, 2), dim3(256),
-                          ((size_t)len * 64 + 64) * sizeof(int), st>>>(len, inner, wa, wb);
-    } else if ((size_t)len * 8 * sizeof(int) <= kLdsBudget) {
-      k_edt_strided<8><<<dim3((unsigned)((inner + 7) / 8), (unsigned)outer, 2), dim3(256),
-                         ((size_t)len * 8 + 8) * sizeof(int), st>>>(len, inner, wa, wb);
-    } else {
-      set_error("occupancy grid axis too long for the LDS-staged distance transform (max 4608 cells)");
-      return GPMP2MI_ERR_UNSUPPORTED;
+constexpr size_t kLdsBudget = 144 * 1024;
+// the form the strided pass along an axis of `len` cells takes: 0 none (len < 2), 1 linear-time scan, 2 / 3 outward
+// search over 64 / 8 lines per block, -1 too long for LDS
+static int strided_form(int len) {
+  if (len < 2) return 0;
+  if (len < 32768 && (size_t)len * 32 * 2 * sizeof(int) <= kLdsBudget) return 1;
+  if ((size_t)len * 64 * sizeof(int) <= kLdsBudget) return 2;
+  if ((size_t)len * 8 * sizeof(int) <= kLdsBudget) return 3;
+  return -1;
+}
+
+int edt_check_axes(int nx, int ny, int nz) {
+  if (nx >= 2 && (size_t)nx * sizeof(int) > kLdsBudget) {
+    set_error("occupancy grid axis too long for the LDS-staged distance transform");
+    return GPMP2MI_ERR_UNSUPPORTED;
+  }
+  if (strided_form(ny) < 0 || strided_form(nz) < 0) {
+    set_error("occupancy grid axis too long for the LDS-staged distance transform (max 4608 cells)");
+    return GPMP2MI_ERR_UNSUPPORTED;
+  }
+  return GPMP2MI_OK;
+}
+
+// the three axis passes over two seeded int32 volumes: x, then the two strided axes
+int launch_edt_passes(int nx, int ny, int nz, int* wa, int* wb, hipStream_t st) {
+  G2_TRY(edt_check_axes(nx, ny, nz));
+  auto strided = [&](int len, size_t inner, size_t outer) {
+    switch (strided_form(len)) {
+      case 1:   // linear-time scan, 32 lines per block
+        k_edt_strided_scan<32><<<dim3((unsigned)((inner + 31) / 32), (unsigned)outer, 2), dim3(256),
+                                 (size_t)len * 32 * 2 * sizeof(int), st>>>(len, inner, wa, wb);
+        break;
+      case 2:
+        k_edt_strided<64><<<dim3((unsigned)((inner + 63) / 64), (unsigned)outer, 2), dim3(256),
+                            ((size_t)len * 64 + 64) * sizeof(int), st>>>(len, inner, wa, wb);
+        break;
+      case 3:
+        k_edt_strided<8><<<dim3((unsigned)((inner + 7) / 8), (unsigned)outer, 2), dim3(256),
+                           ((size_t)len * 8 + 8) * sizeof(int), st>>>(len, inner, wa, wb);
+        break;
+      default: break;
     }
-    return GPMP2MI_OK;
   };
   if (nx >= 2) {
-    if ((size_t)nx * sizeof(int) > kLdsBudget) {
-      set_error("occupancy grid axis too long for the LDS-staged distance transform");
-      return GPMP2MI_ERR_UNSUPPORTED;
-    }
     const size_t nrows = (size_t)ny * nz;
     const int rows = (int)std::max<size_t>(1, std::min<size_t>(nrows, 2048 / nx));
     k_edt_x<<<dim3((unsigned)((nrows + rows - 1) / rows), 1, 2), dim3(256), ((size_t)rows * nx + rows) * sizeof(int), st>>>(
         nx, nrows, rows, wa, wb);
   }
-  G2_TRY(strided(ny, (size_t)nx, (size_t)nz));
-  G2_TRY(strided(nz, (size_t)nx * ny, 1));
-  k_edt_finish<<<dim3(sweep), dim3(256), 0, st>>>(n, wa, wb, cell, field);
+  strided(ny, (size_t)nx, (size_t)nz);
+  strided(nz, (size_t)nx * ny, 1);
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
+}
+
+static int edt_sweep(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 256 * 16); }
+
+int launch_edt_finish(size_t n, const int* wa, const int* wb, double cell, double* field, hipStream_t st) {
+  k_edt_finish<<<dim3(edt_sweep(n)), dim3(256), 0, st>>>(n, wa, wb, cell, field);
+  G2_HIP(hipGetLastError());
+  return GPMP2MI_OK;
+}
+
+// occ, field: [nz][ny][nx] device pointers; wa, wb: int32 scratch of the same element count
+int launch_sdf_from_occupancy(int nx, int ny, int nz, const double* occ, double cell, int* wa, int* wb,
+                              double* field, hipStream_t st) {
+  const size_t n = (size_t)nx * ny * nz;
+  k_edt_seed<<<dim3(edt_sweep(n)), dim3(256), 0, st>>>(n, occ, wa, wb);
+  G2_TRY(launch_edt_passes(nx, ny, nz, wa, wb, st));
+  return launch_edt_finish(n, wa, wb, cell, field, st);
 }
 
 }  // namespace g2

@@ -45,6 +45,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_self(lib)
     _capi.declare_motion(lib)
     _capi.declare_moving(lib)
+    _capi.declare_map(lib)
     _capi.declare_group(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
@@ -276,7 +277,7 @@ class Engine:
         self._ck(self.lib.gpmp2mi_sdf_create(C.c_int(dim), dptr(org), C.c_double(cell_size), nx, ny, nz,
                                              dptr(data), C.c_int(layout), C.byref(out)))
         h = _Handle(out, self.lib.gpmp2mi_sdf_destroy)
-        h.dim = dim
+        h.dim, h.shape = dim, data.shape
         return h
 
     def sdf_field_from_occupancy(self, occ, cell_size):
@@ -298,7 +299,7 @@ class Engine:
         self._ck(self.lib.gpmp2mi_sdf_create_from_occupancy(C.c_int(dim), dptr(org), C.c_double(cell_size), nx, ny, nz,
                                                             dptr(occ), C.c_int(layout), C.byref(out)))
         h = _Handle(out, self.lib.gpmp2mi_sdf_destroy)
-        h.dim = dim
+        h.dim, h.shape = dim, occ.shape
         return h
 
     def sdf_read_vol(self, filename_pre):
@@ -746,6 +747,95 @@ class Engine:
                 _dev_arg("mode", mode, (B,), True), _dev_arg("leaders", leaders, (B,), True),
                 _dev_arg("sizes", sizes, (B,), True), _dev_arg("n_modes", n_modes, (1,), True)]
         self._ck(self.lib.gpmp2mi_group_traj_dev(dof, B, N, *args, C.c_void_p(stream or 0)))
+
+    # ---------------------------------------------------------------- live map (include/gpmp2mi.h "live map")
+    def _sdf_shape(self, sdf):
+        """The voxel shape of a field handle, [nz][ny][nx] or [ny][nx]: kept by the calls that made it from an array, asked
+        of the library once otherwise."""
+        if getattr(sdf, "shape", None) is None:
+            nx, ny, nz = C.c_int(), C.c_int(), C.c_int()
+            self._ck(self.lib.gpmp2mi_sdf_get_field(sdf.ptr, None, C.byref(nx), C.byref(ny), C.byref(nz), None, None, None))
+            sdf.shape = (nz.value, ny.value, nx.value)[3 - sdf.dim:]
+        return tuple(sdf.shape)
+
+    def _grid_arg(self, sdf, name, a, layout):
+        a, shape = f64(a), self._sdf_shape(sdf)
+        if layout not in (_capi.SDF_LAYOUT_ZYX, _capi.SDF_LAYOUT_GTSAM):
+            raise ValueError("unknown voxel layout")
+        if a.ndim != len(shape) or a.size != int(np.prod(shape)) or (layout == _capi.SDF_LAYOUT_ZYX and a.shape != shape):
+            raise ValueError(f"{name}: expected {list(shape)} (the handle's grid), got {list(a.shape)}")
+        return a
+
+    def _points_args(self, sdf, robot, conf, margin):
+        margin = float(margin)
+        if np.isnan(margin):
+            raise ValueError("margin must not be NaN")
+        if robot is not None and conf is None:
+            raise ValueError("the self filter needs the robot's configuration")
+        return margin
+
+    def sdf_reserve_update(self, sdf):
+        """Takes the update workspace of the handle now, so that the first `_dev` update does not allocate."""
+        self._ck(self.lib.gpmp2mi_sdf_reserve_update(sdf.ptr))
+
+    def sdf_update(self, sdf, data, layout=_capi.SDF_LAYOUT_ZYX):
+        """New voxels of the handle's own shape, in place; the handle then equals Engine.sdf of the same data."""
+        data = self._grid_arg(sdf, "data", data, layout)
+        self._ck(self.lib.gpmp2mi_sdf_update(sdf.ptr, dptr(data), C.c_int(layout)))
+
+    def sdf_update_dev(self, sdf, data, stream=None):
+        """The same from a device buffer in [nz][ny][nx] order (torch tensor or raw pointer), enqueued on `stream`."""
+        self._ck(self.lib.gpmp2mi_sdf_update_dev(sdf.ptr, _dev_arg("data", data, self._sdf_shape(sdf)),
+                                                 C.c_void_p(stream or 0)))
+
+    def sdf_update_from_occupancy(self, sdf, occ, layout=_capi.SDF_LAYOUT_ZYX):
+        """The handle's field from an occupancy grid of its own shape, in place (as Engine.sdf_from_occupancy); the
+        obstacle set becomes the handle's base."""
+        occ = self._grid_arg(sdf, "occ", occ, layout)
+        self._ck(self.lib.gpmp2mi_sdf_update_from_occupancy(sdf.ptr, dptr(occ), C.c_int(layout)))
+
+    def sdf_update_from_occupancy_dev(self, sdf, occ, stream=None):
+        self._ck(self.lib.gpmp2mi_sdf_update_from_occupancy_dev(sdf.ptr, _dev_arg("occ", occ, self._sdf_shape(sdf)),
+                                                                C.c_void_p(stream or 0)))
+
+    def sdf_update_from_points(self, sdf, points, use_base=True, robot=None, conf=None, margin=0.0):
+        """The handle's field from a point cloud [M][dim] (and the base when use_base), in place.  robot / conf: drop the
+        points inside the robot's body spheres grown by `margin`.  -> dict(kept, non_finite, self, outside)."""
+        margin = self._points_args(sdf, robot, conf, margin)
+        p = f64(points)
+        if p.size == 0:
+            p = p.reshape(0, sdf.dim)
+        if p.ndim != 2 or p.shape[1] != sdf.dim:
+            raise ValueError(f"points: expected [M][{sdf.dim}], got {list(p.shape)}")
+        q = None
+        if robot is not None:
+            q = f64(conf).reshape(-1)
+            if q.size != robot.dof:
+                raise ValueError(f"conf: expected [{robot.dof}], got {list(np.shape(conf))}")
+        stats = np.zeros(4, dtype=np.int32)
+        self._ck(self.lib.gpmp2mi_sdf_update_from_points(sdf.ptr, p.shape[0], dptr(p), int(bool(use_base)),
+                                                         None if robot is None else robot.ptr, dptr(q), margin,
+                                                         iptr(stats)))
+        return dict(zip(("kept", "non_finite", "self", "outside"), (int(x) for x in stats)))
+
+    def sdf_update_from_points_dev(self, sdf, M, points, use_base=True, robot=None, conf=None, margin=0.0, stats=None,
+                                   stream=None):
+        """The same from device buffers (torch tensors or raw pointers): points [M][dim], conf [dof], stats [4] int32 or
+        None; enqueued on `stream`, no host synchronisation."""
+        margin, M = self._points_args(sdf, robot, conf, margin), int(M)
+        if M < 0:
+            raise ValueError("M must be >= 0")
+        args = [_dev_arg("points", points, (M, sdf.dim)), int(bool(use_base)), None if robot is None else robot.ptr,
+                None if robot is None else _dev_arg("conf", conf, (robot.dof,)), margin,
+                _dev_arg("stats", stats, (4,), True)]
+        self._ck(self.lib.gpmp2mi_sdf_update_from_points_dev(sdf.ptr, M, *args, C.c_void_p(stream or 0)))
+
+    def sdf_update_timing(self, sdf, on=True, read=False):
+        """Stage timer of the updates (gpmp2mi_debug_sdf_update_timing): read = True returns the device times in ms of the
+        last recorded update as dict(seed_mark, passes, finish, pack)."""
+        ms = np.zeros(4) if read else None
+        self._ck(self.lib.gpmp2mi_debug_sdf_update_timing(sdf.ptr, int(bool(on)), dptr(ms)))
+        return None if ms is None else dict(zip(("seed_mark", "passes", "finish", "pack"), (float(x) for x in ms)))
 
     # ---------------------------------------------------------------- plans
     def plan(self, robot, sdf, setting, B, forms=None):
@@ -1476,6 +1566,11 @@ class MultiPlan:
             raise ValueError(f"expected {self.B} rows, got {B}")
         self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_set_problem(self.h.ptr, dptr(sc), dptr(sv), dptr(ec), dptr(ev),
                                                                  dptr(t)))
+
+    def refresh_field(self):
+        """After an update of the field handle this multi plan was made on (include/gpmp2mi.h "live map"): the new voxels
+        to every copy of the field the multi plan owns."""
+        self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_refresh_field(self.h.ptr))
 
     def optimize(self):
         self.eng._ck(self.eng.lib.gpmp2mi_multi_plan_optimize(self.h.ptr))

@@ -45,6 +45,23 @@ class _DeviceSdf:
             raise SDFQueryOutOfRange()
         return float(dist[0])
 
+    # Live map (include/gpmp2mi.h "live map"): both act on the live handle, so planners already made on this field
+    # see the new map in their next call; data_ is read back from the handle to stay in step.
+    def updateFromOccupancy(self, occupancy):
+        """The field again from an occupancy grid of its own shape (cells > 0.75 are obstacles); the grid becomes the
+        base that updateFromPoints adds a cloud to."""
+        _eng().sdf_update_from_occupancy(self.handle(), occupancy)
+        self.data_ = _eng().sdf_field(self.handle())["data"]
+
+    def updateFromPoints(self, points, use_base=True, robot=None, conf=None, margin=0.0):
+        """The field again from a point cloud [M][dim], united with the base when use_base.  robot (a robot model) and
+        conf: points inside the robot's body spheres grown by `margin` are dropped.  Returns the counts
+        dict(kept, non_finite, self, outside)."""
+        stats = _eng().sdf_update_from_points(self.handle(), points, use_base,
+                                              None if robot is None else _robot_handle(robot), conf, margin)
+        self.data_ = _eng().sdf_field(self.handle())["data"]
+        return stats
+
 
 class SignedDistanceField(_DeviceSdf):
     """gpmp2::SignedDistanceField (gpmp2/obstacle/SignedDistanceField.h:28-72): origin, cell size and

@@ -758,6 +758,65 @@ int gpmp2mi_plan_select_moving_dev(gpmp2mi_plan* p, int inter_step, double requi
                                    double required_moving_clearance, int* best, int* n_eligible, double* traj_best,
                                    double* dense_best, void* stream);
 
+/* ---- live map: a field handle updated in place from a field, an occupancy grid or a point cloud, on the device ------
+ * A plan binds one field handle for life.  These calls rewrite the handle's voxels where they are, so the static map can
+ * change between two solves without destroying the field and the plans on it.
+ *
+ * Definitions:
+ *  - Geometry is fixed.  An update never changes dim, nx, ny, nz, the origin, the cell size or the addresses of the
+ *    handle's device buffers.  Every plan created on the handle, and every call that takes the handle, sees the new
+ *    voxels in the calls that follow the update in stream order.  Host forms run on the default stream and synchronise
+ *    before they return; `_dev` forms enqueue on `stream` and return without a host synchronisation.  An update
+ *    concurrent with a call that reads the field is the caller's error: use the same stream, or events.
+ *  - gpmp2mi_sdf_update: the handle afterwards equals, bit for bit, one made by gpmp2mi_sdf_create with the same voxels,
+ *    the plain voxels and the packed cells alike.  It clears the base (below).
+ *  - gpmp2mi_sdf_update_from_occupancy: the handle afterwards equals one made by gpmp2mi_sdf_create_from_occupancy: cells
+ *    with occ > 0.75 are obstacles, an empty or full grid gives the constant 1000.  It records the obstacle set as the
+ *    handle's base, one byte per cell.  A handle that never took this call has no base; the constructors record none.
+ *  - Point-to-cell rule.  Per axis a < dim, u = (p_a - origin_a) / cell_size + 0.5, evaluated in fp64 in exactly that
+ *    form (a true division, not a multiplication by a reciprocal).  The point is in the grid iff u >= 0 && u < n_a on
+ *    every axis, compared in double before any conversion to an integer; its cell index on the axis is floor(u).
+ *  - Classification of a point; the first rule that matches applies:
+ *      1. non-finite: a coordinate (of the first dim) is NaN or infinite;
+ *      2. self: robot != NULL and, for some body sphere s, sqrt(dx^2 + dy^2 + dz^2) <= radius_s + margin, the centres
+ *         being those of gpmp2mi_sphere_centers(robot, conf) (the same kernel: the same bits); dim == 2 uses x, y only;
+ *      3. outside the grid;
+ *      4. kept.
+ *    stats = {kept, non-finite, self, outside}; the four counts sum to M.
+ *  - Occupied set and field.  O = (use_base ? base : empty) united with the cells of the kept points.  The field written
+ *    is, bit for bit, what the occupancy path gives for the indicator of O.  M == 0 is valid.  Nothing persists between
+ *    calls except the base: the cloud of the previous call is gone.  The result is a function of the set of points, not
+ *    of their order; no floating-point atomic is used.
+ * Errors, all checked before any device work (a refused call changes nothing): GPMP2MI_ERR_INVALID for a NULL handle, a
+ * NULL voxels / occ, NULL points with M > 0, M < 0, an unknown layout, a NaN margin, robot != NULL with a NULL conf,
+ * use_base on a handle without a base, a robot on another device than the field, a field whose device is not the current
+ * one; GPMP2MI_ERR_UNSUPPORTED for an axis too long for the distance transform (as the constructor); GPMP2MI_ERR_ALLOC
+ * and GPMP2MI_ERR_HIP as elsewhere.
+ * Memory: the workspace is two int32 volumes, the byte mask, [S][3] centres and four counters.  It is taken at the first
+ * update call on the handle, or by gpmp2mi_sdf_reserve_update, and kept until gpmp2mi_sdf_destroy.  A later `_dev` call
+ * neither allocates nor synchronises.  (The host forms stage their inputs in temporary device memory.)
+ * Multi plans: an update touches the caller's handle only.  gpmp2mi_multi_plan_refresh_field copies the source handle's
+ * voxels to every copy the multi plan owns (a peer copy of the plain voxels, packed there by the constructor's kernel, so
+ * the cells are bit-identical) and returns when all copies are done.  The source handle must still be alive, its update
+ * complete, and the multi plan idle; shards on the source's own device read the caller's handle and need no copy.  A poisoned multi plan returns GPMP2MI_ERR_TIMEOUT.  The caller's current device is the same on return
+ * as on entry.
+ * Not here: ray casting of free space, decay or accumulation of clouds, depth images as opposed to clouds, a field per
+ * trajectory, a change of geometry, updates of a sub-box of the grid. */
+int gpmp2mi_sdf_reserve_update(gpmp2mi_sdf* s);
+/* voxels in `layout`, [nz][ny][nx] cells as at gpmp2mi_sdf_create; _dev: a device pointer in GPMP2MI_SDF_LAYOUT_ZYX */
+int gpmp2mi_sdf_update(gpmp2mi_sdf* s, const double* voxels, int layout);
+int gpmp2mi_sdf_update_dev(gpmp2mi_sdf* s, const double* voxels_zyx, void* stream);
+int gpmp2mi_sdf_update_from_occupancy(gpmp2mi_sdf* s, const double* occ, int layout);
+int gpmp2mi_sdf_update_from_occupancy_dev(gpmp2mi_sdf* s, const double* occ_zyx, void* stream);
+/* points [M][dim]; conf [D] of `robot`; stats [4] or NULL.  _dev: points, conf and stats are device pointers. */
+int gpmp2mi_sdf_update_from_points(gpmp2mi_sdf* s, int M, const double* points /*[M][dim]*/, int use_base,
+                                   const gpmp2mi_robot* robot /*NULL: no self filter*/, const double* conf /*[D]*/,
+                                   double margin, int* stats /*[4] or NULL*/);
+int gpmp2mi_sdf_update_from_points_dev(gpmp2mi_sdf* s, int M, const double* points, int use_base,
+                                       const gpmp2mi_robot* robot, const double* conf, double margin, int* stats,
+                                       void* stream);
+int gpmp2mi_multi_plan_refresh_field(gpmp2mi_multi_plan* m);
+
 /* ---- distinct alternatives: how many different solutions the restarts found, one row per mode, on the device ------
  * The calls of "scoring" answer with one row.  These calls say how many different trajectories a batch holds and hand
  * over one representative of each, best first, without the trajectories leaving the device: the fallback when the

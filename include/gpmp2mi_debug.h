@@ -54,6 +54,12 @@ int gpmp2mi_debug_plan_seed_prior(gpmp2mi_plan* p, double* Hdiag, double* Hoff);
  * so a small budget lets a test cross chunk borders at small K. */
 int gpmp2mi_debug_sampled_chunk_bytes(size_t bytes);
 
+/* Diagnostic (scripts/map_throughput.py): stage times of the updates of "live map" (include/gpmp2mi.h).  With ms4 != NULL
+ * it first waits for the last update from occupancy / from points recorded on this handle and returns the device time
+ * of its stages in ms: {seed (and mark), the three axis passes, finish, pack}.  Then on = 1 makes the updates that follow
+ * record an event between their stages; on = 0 stops that. */
+int gpmp2mi_debug_sdf_update_timing(gpmp2mi_sdf* s, int on, double* ms4 /*[4] or NULL*/);
+
 /* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
 int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);
 /* Diagnostic: scalars of trajectory b's last LM / Dogleg trial step, out17 = {g.delta, |delta|^2, g.g, g^T H g,

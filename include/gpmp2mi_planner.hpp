@@ -200,6 +200,31 @@ class Pose2MobileArmModel {
   gpmp2mi_robot* h_ = nullptr;
 };
 
+/// counts of a point cloud update (include/gpmp2mi.h "live map"): the four classes sum to the number of points
+struct MapUpdateStats {
+  int kept = 0, non_finite = 0, self = 0, outside = 0;
+};
+
+namespace internal {
+/// gpmp2mi_sdf_update_from_points for the two field classes: points row-major [M][dim]
+inline MapUpdateStats UpdateFieldFromPoints(gpmp2mi_sdf* h, std::size_t dim, const Vector& points, bool use_base,
+                                            const gpmp2mi_robot* robot, const Vector* conf, double margin) {
+  if (points.size() % dim != 0) throw std::runtime_error("[updateFromPoints] points are not [M][dim]");
+  if (robot && (!conf || conf->size() != static_cast<std::size_t>(gpmp2mi_robot_dof(robot))))
+    throw std::runtime_error("[updateFromPoints] conf does not fit the robot's dof");
+  int st[4] = {0, 0, 0, 0};
+  check(gpmp2mi_sdf_update_from_points(h, static_cast<int>(points.size() / dim), points.data(), use_base ? 1 : 0, robot,
+                                       robot ? conf->data() : nullptr, margin, st),
+        "gpmp2mi_sdf_update_from_points");
+  MapUpdateStats s;
+  s.kept = st[0];
+  s.non_finite = st[1];
+  s.self = st[2];
+  s.outside = st[3];
+  return s;
+}
+}  // namespace internal
+
 /// 3-D signed distance field; data in the reference's own storage order: z slices of column-major
 /// (row = y, col = x) matrices, i.e. voxels[(z * cols + x) * rows + y]
 class SignedDistanceField {
@@ -211,6 +236,7 @@ class SignedDistanceField {
     check(gpmp2mi_sdf_create(3, origin.data(), cell_size, static_cast<int>(field_cols), static_cast<int>(field_rows),
                              static_cast<int>(field_z), column_major_slices.data(), GPMP2MI_SDF_LAYOUT_GTSAM, &h_),
           "gpmp2mi_sdf_create");
+    cells_ = column_major_slices.size();
   }
   SignedDistanceField(const SignedDistanceField&) = delete;
   SignedDistanceField& operator=(const SignedDistanceField&) = delete;
@@ -222,9 +248,28 @@ class SignedDistanceField {
     return in != 0;
   }
   const gpmp2mi_sdf* handle() const { return h_; }
+  /// Live map: the field again, in place, from an occupancy grid in the constructor's storage order (cells > 0.75 are
+  /// obstacles).  Optimizers already made on this field see the new map in their next call; the grid becomes the base.
+  void updateFromOccupancy(const Vector& column_major_slices) {
+    if (column_major_slices.size() != cells_)
+      throw std::runtime_error("[SignedDistanceField] occupancy size does not match the field dimensions");
+    check(gpmp2mi_sdf_update_from_occupancy(h_, column_major_slices.data(), GPMP2MI_SDF_LAYOUT_GTSAM),
+          "gpmp2mi_sdf_update_from_occupancy");
+  }
+  /// Live map: the field again from a point cloud, row-major [M][3], united with the base when use_base
+  MapUpdateStats updateFromPoints(const Vector& points, bool use_base = true) {
+    return internal::UpdateFieldFromPoints(h_, 3, points, use_base, nullptr, nullptr, 0.0);
+  }
+  /// ... without the points inside the body spheres of `robot` at `conf`, grown by `margin`
+  template <class ROBOT>
+  MapUpdateStats updateFromPoints(const Vector& points, bool use_base, const ROBOT& robot, const Vector& conf,
+                                  double margin = 0.0) {
+    return internal::UpdateFieldFromPoints(h_, 3, points, use_base, robot.handle(), &conf, margin);
+  }
 
  private:
   gpmp2mi_sdf* h_ = nullptr;
+  std::size_t cells_ = 0;
 };
 
 /// 2-D signed distance field, column-major (row = y, col = x) like the gtsam::Matrix it replaces
@@ -238,14 +283,31 @@ class PlanarSDF {
     check(gpmp2mi_sdf_create(2, o, cell_size, static_cast<int>(field_cols), static_cast<int>(field_rows), 1,
                              column_major.data(), GPMP2MI_SDF_LAYOUT_GTSAM, &h_),
           "gpmp2mi_sdf_create");
+    cells_ = column_major.size();
   }
   PlanarSDF(const PlanarSDF&) = delete;
   PlanarSDF& operator=(const PlanarSDF&) = delete;
   ~PlanarSDF() { gpmp2mi_sdf_destroy(h_); }
   const gpmp2mi_sdf* handle() const { return h_; }
+  /// Live map, as SignedDistanceField: occupancy column-major like the constructor's data; points row-major [M][2]
+  void updateFromOccupancy(const Vector& column_major) {
+    if (column_major.size() != cells_)
+      throw std::runtime_error("[PlanarSDF] occupancy size does not match the field dimensions");
+    check(gpmp2mi_sdf_update_from_occupancy(h_, column_major.data(), GPMP2MI_SDF_LAYOUT_GTSAM),
+          "gpmp2mi_sdf_update_from_occupancy");
+  }
+  MapUpdateStats updateFromPoints(const Vector& points, bool use_base = true) {
+    return internal::UpdateFieldFromPoints(h_, 2, points, use_base, nullptr, nullptr, 0.0);
+  }
+  template <class ROBOT>
+  MapUpdateStats updateFromPoints(const Vector& points, bool use_base, const ROBOT& robot, const Vector& conf,
+                                  double margin = 0.0) {
+    return internal::UpdateFieldFromPoints(h_, 2, points, use_base, robot.handle(), &conf, margin);
+  }
 
  private:
   gpmp2mi_sdf* h_ = nullptr;
+  std::size_t cells_ = 0;
 };
 
 /// general setting of all trajectory optimizers -- same public fields and setters as the reference
