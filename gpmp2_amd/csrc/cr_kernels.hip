@@ -125,11 +125,16 @@ __device__ __forceinline__ Tile coupling(const Tile& A, const Tile& B, int lane)
 //                two is eliminated at level 4 (the odd multiple of 4): rows 4q, cols 4q+4 for odd q, the transpose else
 // so that a level-4 task is: S - pend, two ready-made couplings, eliminate -- no tile product in front of it.
 constexpr int ASM_WAVES = 4;
+// ASM_OUT, the policy of the stores that end a group's work and are next read by the step / finish kernels (fac, tiles,
+// pend, coup; tiles.h StorePolicy): write-through for plans of up to ASM_WT_MAX_B trajectories, so that the end of the
+// kernel does not wait for their write-back.  Larger plans keep the memory system busy while the kernel runs and the
+// 8-byte write-through stores then cost more than the write-back they spare (DESIGN section 4 has the numbers).
+constexpr int ASM_WT_MAX_B = 256;
 // register budget of k_assemble: wavefronts per SIMD the kernel must leave room for (5 -> <= 96 VGPRs)
 #ifndef G2_ASM_MINW
 #define G2_ASM_MINW 5
 #endif
-template <int D, bool LIE>
+template <int D, bool LIE, StorePolicy ASM_OUT>
 __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assemble(const PlanParams* __restrict__ pp, PlanBuffers pb,
                                                               const double* __restrict__ traj, int bufsel,
                                                               double* __restrict__ tiles,
@@ -201,7 +206,7 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
         if (g + 4 * k == c && c < n) S.r[k] += lam;
     }
     if (!odd) {
-      if (!fuse2) tile_store_rows<n>(tiles + ((size_t)b * (N + 1) + i) * TILE_DBL, S, lane);
+      if (!fuse2) tile_store_rows<n, ASM_OUT>(tiles + ((size_t)b * (N + 1) + i) * TILE_DBL, S, lane);
       else if (wv == 0) tile_store(xs0, S, lane);   // folded and written back by wavefront 2
     } else {
       // level h = 1: odd blocks only couple to their (even) neighbours
@@ -210,9 +215,9 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
       const bool ok = tile_eliminate_cv<n>(S, Cl, Cr, V, lane);
       G2_ASTAMP(4);
       double* f = pb.fac + ((size_t)b * (N + 1) + i) * 3 * TILE_DBL;
-      tile_store_rows<n>(f, Cl, lane);
-      tile_store_rows<n>(f + TILE_DBL, Cr, lane);
-      tile_store_transposed<n>(f + 2 * TILE_DBL, V, lane);
+      tile_store_rows<n, ASM_OUT>(f, Cl, lane);
+      tile_store_rows<n, ASM_OUT>(f + TILE_DBL, Cr, lane);
+      tile_store_transposed<n, ASM_OUT>(f + 2 * TILE_DBL, V, lane);
       if (fuse2) {  // hand W_l, W_r to wavefront 2
         double* x = xch + (size_t)(wv >> 1) * 2 * TILE_DBL;
         tile_store(x, Cl, lane);
@@ -264,9 +269,9 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
     Tile V;
     const bool ok = tile_eliminate_cv<n>(S, C2l, C2r, V, lane);
     double* f = pb.fac + ((size_t)b * (N + 1) + i) * 3 * TILE_DBL;
-    tile_store_rows<n>(f, C2l, lane);
-    tile_store_rows<n>(f + TILE_DBL, C2r, lane);
-    tile_store_transposed<n>(f + 2 * TILE_DBL, V, lane);
+    tile_store_rows<n, ASM_OUT>(f, C2l, lane);
+    tile_store_rows<n, ASM_OUT>(f + TILE_DBL, C2r, lane);
+    tile_store_transposed<n, ASM_OUT>(f + 2 * TILE_DBL, V, lane);
     if (!ok && lane == 0) pb.notspd[b] = 1;
     const Tile A2 = tile_atb(C2l, C2l);                      // W_l(j)^T W_l(j): owed by block 4q
 #pragma unroll
@@ -277,7 +282,7 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
       for (int k = 0; k < 4; k++) R.r[k] += B2.r[k];
       if (has0) {   // fill-in between 4q and 4q + 4: rows of the one that level 4 eliminates
         const Tile K = (q & 1) ? coupling<n>(C2l, C2r, lane) : coupling<n>(C2r, C2l, lane);
-        tile_store_rows<n>(pb.coup + ((size_t)b * groups + q) * TILE_DBL, K, lane);
+        tile_store_rows<n, ASM_OUT>(pb.coup + ((size_t)b * groups + q) * TILE_DBL, K, lane);
       }
     }
     G2_ASTAMP(7);
@@ -287,9 +292,9 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   if (has0) {
 #pragma unroll
     for (int k = 0; k < 4; k++) Sp.r[k] -= A1.r[k];
-    tile_store_rows<n>(tiles + ((size_t)b * (N + 1) + v0 - 1) * TILE_DBL, Sp, lane);
+    tile_store_rows<n, ASM_OUT>(tiles + ((size_t)b * (N + 1) + v0 - 1) * TILE_DBL, Sp, lane);
   }
-  if (next) tile_store_rows<n>(pb.pend + ((size_t)b * groups + q) * TILE_DBL, R, lane);
+  if (next) tile_store_rows<n, ASM_OUT>(pb.pend + ((size_t)b * groups + q) * TILE_DBL, R, lane);
 }
 
 int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel,
@@ -300,8 +305,12 @@ int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* t
   const size_t shmem = ((ASM_WAVES + 1) * slotd + (slotd >= TILE_DBL ? 4 : 5) * TILE_DBL) * sizeof(double);
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    if (hp.lie) k_assemble<D, true><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
-    else k_assemble<D, false><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    constexpr StorePolicy WT = StorePolicy::WriteThrough, PL = StorePolicy::Plain;
+    const bool wt = hp.B <= ASM_WT_MAX_B;
+    if (hp.lie && wt) k_assemble<D, true, WT><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else if (hp.lie) k_assemble<D, true, PL><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else if (wt) k_assemble<D, false, WT><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else k_assemble<D, false, PL><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
   });
 }
 

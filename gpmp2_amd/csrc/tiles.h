@@ -191,9 +191,22 @@ __device__ __forceinline__ Tile tile_load(const double* p, int lane) {
   for (int k = 0; k < 4; k++) T.r[k] = p[k * 64 + lane];
   return T;
 }
+// Store policy of data handed from one kernel to the next.  Plain stores stay dirty in the L2 of the writing XCD until
+// the kernel ends, and the end of the kernel then waits for their write-back (the XCDs' L2s are not coherent with each
+// other for plain stores).  WriteThrough stores (device scope, `sc1`) leave the L2 as they are issued, so the write-back
+// is spread over the kernel's run.  The value stored is the same either way.  WriteThrough is meant for stores that end
+// a workgroup's work and are next read by ANOTHER kernel: the line is dropped from the writer's L2, so a re-read in the
+// same kernel pays the cross-XCD latency.
+enum class StorePolicy { Plain, WriteThrough };
+template <StorePolicy SP = StorePolicy::Plain>
+__device__ __forceinline__ void store_f64(double* p, double v) {
+  if constexpr (SP == StorePolicy::WriteThrough) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+template <StorePolicy SP = StorePolicy::Plain>
 __device__ __forceinline__ void tile_store(double* p, const Tile& T, int lane) {
 #pragma unroll
-  for (int k = 0; k < 4; k++) p[k * 64 + lane] = T.r[k];
+  for (int k = 0; k < 4; k++) store_f64<SP>(p + k * 64 + lane, T.r[k]);
 }
 // the same for tiles whose rows >= n are structurally zero (factor and diagonal tiles of the cyclic reduction): the
 // padding rows are neither written nor read, a load leaves zeros there
@@ -204,11 +217,11 @@ __device__ __forceinline__ Tile tile_load_rows(const double* p, int lane) {
   for (int k = 0; k < 4; k++) T.r[k] = ((lane >> 4) + 4 * k < n) ? p[k * 64 + lane] : 0.0;
   return T;
 }
-template <int n>
+template <int n, StorePolicy SP = StorePolicy::Plain>
 __device__ __forceinline__ void tile_store_rows(double* p, const Tile& T, int lane) {
 #pragma unroll
   for (int k = 0; k < 4; k++)
-    if ((lane >> 4) + 4 * k < n) p[k * 64 + lane] = T.r[k];
+    if ((lane >> 4) + 4 * k < n) store_f64<SP>(p + k * 64 + lane, T.r[k]);
 }
 __device__ __forceinline__ Tile tile_zero() {
   Tile T;
@@ -422,12 +435,12 @@ __device__ __forceinline__ Tile tile_load_transposed(const double* __restrict__ 
 // its plain coalesced tile loads.  (The first form of round 3 stored Vt and loaded it transposed: 16 cache lines per
 // load instruction in the latency-bound finish kernel, 6.8 -> 7.3 us.)  Rows c >= n of V and the columns >= n of its
 // rows are never written: they keep the zeros the plan's arena was created with.
-template <int n>
+template <int n, StorePolicy SP = StorePolicy::Plain>
 __device__ __forceinline__ void tile_store_transposed(double* __restrict__ p, const Tile& Vt, int lane) {
   const int c = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int k = 0; k < 4; k++)
-    if (c < n && g + 4 * k < n) p[c * 16 + g + 4 * k] = Vt.r[k];
+    if (c < n && g + 4 * k < n) store_f64<SP>(p + c * 16 + g + 4 * k, Vt.r[k]);
 }
 
 // =============================================================================== chain solve

@@ -26,6 +26,18 @@ def kernel_sources_digest(root=ROOT):
 
 
 
+def kernel_of(signature):
+    """`void g2::k<7, false, (g2::StorePolicy)1>(args...)` -> `k<7, false, (StorePolicy)1>`: the argument list opens at
+    the first parenthesis outside the template brackets"""
+    depth = 0
+    for k, ch in enumerate(signature):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            signature = signature[:k]
+            break
+    return signature.replace("void ", "").replace("g2::", "")
+
+
 def per_kernel(d, counter):
     acc = {}
     files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
@@ -35,7 +47,7 @@ def per_kernel(d, counter):
         for row in csv.DictReader(open(f)):
             if row.get("Counter_Name") != counter:
                 continue
-            name = row["Kernel_Name"].split("(")[0].replace("void ", "").replace("g2::", "")
+            name = kernel_of(row["Kernel_Name"])
             a = acc.setdefault(name, [0.0, set()])
             a[0] += float(row["Counter_Value"])
             a[1].add(row.get("Dispatch_Id", str(len(a[1]))))
