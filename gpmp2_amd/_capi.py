@@ -337,6 +337,40 @@ def declare_sampled(lib):
         getattr(lib, name).restype = i
 
 
+RNG_IK = 4
+IK_MAX_ITER = 1000
+IK_CONVERGED, IK_MAX_ITER_REACHED, IK_INVALID = 0, 1, 2
+WORKSPACE_POSITION, WORKSPACE_ORIENTATION, WORKSPACE_POSE = 0, 1, 2
+
+
+class IkOptsC(C.Structure):
+    """gpmp2mi_ik_opts (include/gpmp2mi.h "goal configurations"); pos_down / pos_up: host arrays [dof] or NULL"""
+    _fields_ = [("mode", C.c_int), ("link", C.c_int), ("pos_tol", C.c_double), ("rot_tol", C.c_double),
+                ("rot_weight", C.c_double), ("max_iter", C.c_int), ("lambda_initial", C.c_double),
+                ("lambda_factor", C.c_double), ("lambda_lower", C.c_double), ("lambda_upper", C.c_double),
+                ("pos_down", c_double_p), ("pos_up", c_double_p)]
+
+
+def declare_ik(lib):
+    """argtypes of the inverse-kinematics entry points (include/gpmp2mi.h "goal configurations"); the options, near and
+    weights are host data in every form, the `_dev` forms take device addresses for everything else."""
+    vp, i, d, ip, f, u64 = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double, C.c_uint64
+    op = C.POINTER(IkOptsC)
+    decl = {
+        "gpmp2mi_ik_solve": [vp, op, i, d, i, d, d, d, ip, ip],
+        "gpmp2mi_ik_solve_dev": [vp, op, i, vp, i, vp, vp, vp, vp, vp, vp],
+        "gpmp2mi_ik_solve_seeded": [vp, op, i, d, i, u64, i, d, d, ip, ip],
+        "gpmp2mi_ik_solve_seeded_dev": [vp, op, i, vp, i, u64, i, vp, vp, vp, vp, vp],
+        "gpmp2mi_ik_goals": [vp, op, vp, i, d, i, d, u64, i, f, i, d, d, f, i, d, ip, d, ip, ip, ip, ip, ip, d, ip, d, d],
+        "gpmp2mi_ik_goals_dev": [vp, op, vp, i, vp, i, vp, u64, i, f, i, d, d, f, i] + [vp] * 13,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_ik_opts_default.argtypes = [op]
+    lib.gpmp2mi_ik_opts_default.restype = None
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 array (None -> NULL)."""
     if a is None:

@@ -227,6 +227,41 @@ struct GroupCopy {
 };
 int launch_group_copy(const GroupCopy& a, hipStream_t st);
 
+// ik_kernels.hip (include/gpmp2mi.h "goal configurations")
+constexpr int IK_MAX_DOF = 7;   // k_ik is instantiated for fixed-base arms of 1..7 joints
+// arguments of k_ik: G * M problems, one lane each.  seeds == null: the seed rows are drawn (seed, first).
+struct IkArgs {
+  int G, M, mode, link, max_iter, first;
+  double pos_tol, rot_tol, rot_weight, lam0, lam_factor, lam_lo, lam_hi;
+  double down[IK_MAX_DOF], up[IK_MAX_DOF];   // -inf / +inf: no limit
+  uint64_t seed;
+  const double* des;     // [G][16]
+  const double* seeds;   // [G][M][D] or null
+  double *conf, *residual;
+  int *iters, *status;
+};
+int launch_ik(const RobotDev& h, const RobotDev* R, const IkArgs& a, hipStream_t st);
+// arguments of k_ik_rows (one lane per row: clearance of conf, eligibility, score, the row staged as a one-state
+// trajectory for k_traj_pairs) and k_ik_goal_copy (one workgroup per pose, reading what k_group_rule left)
+struct IkRows {
+  int G, M, has_near, require_in_range;
+  double required_clearance;
+  double near_conf[IK_MAX_DOF], w[IK_MAX_DOF];
+  const double* conf;    // [G][M][D]
+  const int* status;
+  double *clearance, *score, *stage;   // [G][M], [G][M], [G][M][2D]
+  int *oor, *eligible;
+};
+int launch_ik_rows(const RobotDev& h, const RobotDev* R, const SdfDev* s, const IkRows& a, hipStream_t st);
+struct IkGoalCopy {
+  int M, D, max_goals;
+  const double *conf, *score, *clearance;
+  const int *status, *leaders, *n_modes, *n_eligible;   // leaders [G][M], n_modes / n_eligible [G]
+  int *n_goals, *n_converged, *out_n_eligible, *goal_seed;
+  double *goal_conf, *goal_score, *goal_clearance;
+};
+int launch_ik_goal_copy(const IkGoalCopy& a, int G, hipStream_t st);
+
 // risk_kernels.hip
 // what one workgroup of k_risk leaves for k_risk_finish; k = s = INT_MAX: no pair of the tile was in range
 struct RiskRec {

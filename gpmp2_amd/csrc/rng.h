@@ -95,6 +95,14 @@ G2_PURE void normal_pair(uint64_t seed, uint32_t stream, uint32_t a, uint32_t b,
   rng_box_muller(rng_block(seed, stream, a, b, i, pair), zc, zs);
 }
 
+// The uniform of coordinate r (include/gpmp2mi.h "goal configurations"): x 2^-53 in [0, 1), x the hi53 word of r's
+// block for a cosine member and the lo53 word for a sine member -- the words Box-Muller reads, without the + 1.
+G2_PURE double uniform(uint64_t seed, uint32_t stream, uint32_t a, uint32_t b, uint32_t i, int r) {
+  const RngBlock k = rng_block(seed, stream, a, b, i, rng_pair_of(r));
+  const uint64_t hi53 = ((uint64_t)k.o[0] << 21) | (k.o[1] >> 11), lo53 = ((uint64_t)k.o[2] << 21) | (k.o[3] >> 11);
+  return (double)(rng_is_sine(r) ? lo53 : hi53) * (1.0 / 9007199254740992.0);
+}
+
 G2_PURE double normal(uint64_t seed, uint32_t stream, uint32_t a, uint32_t b, uint32_t i, int r) {
   double zc, zs;
   normal_pair(seed, stream, a, b, i, rng_pair_of(r), zc, zs);

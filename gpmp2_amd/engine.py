@@ -51,6 +51,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_risk(lib)
     _capi.declare_seed(lib)
     _capi.declare_sampled(lib)
+    _capi.declare_ik(lib)
     return lib
 
 
@@ -747,6 +748,152 @@ class Engine:
                 _dev_arg("mode", mode, (B,), True), _dev_arg("leaders", leaders, (B,), True),
                 _dev_arg("sizes", sizes, (B,), True), _dev_arg("n_modes", n_modes, (1,), True)]
         self._ck(self.lib.gpmp2mi_group_traj_dev(dof, B, N, *args, C.c_void_p(stream or 0)))
+
+    # ---------------------------------------------------------------- goal configurations (include/gpmp2mi.h)
+    def ik_opts(self, robot, mode=_capi.WORKSPACE_POSE, link=None, limits=None, **kw):
+        """gpmp2mi_ik_opts with the library's defaults: link defaults to the last one, limits = (down, up) or None, any
+        other field by keyword (pos_tol, rot_tol, rot_weight, max_iter, lambda_initial / _factor / _lower / _upper).
+        Returns (struct, keepalive)."""
+        o = _capi.IkOptsC()
+        self.lib.gpmp2mi_ik_opts_default(C.byref(o))
+        o.mode, o.link = int(mode), int(robot.L - 1 if link is None else link)
+        names = {n for n, _ in _capi.IkOptsC._fields_} - {"mode", "link", "pos_down", "pos_up"}
+        for k, v in kw.items():
+            if k not in names:
+                raise ValueError(f"unknown IK option {k}")
+            setattr(o, k, v)
+        keep = None
+        if limits is not None:
+            keep = [f64(x).reshape(-1) for x in limits]
+            if len(keep) != 2 or any(x.shape != (robot.dof,) for x in keep):
+                raise ValueError(f"limits: expected (down [{robot.dof}], up [{robot.dof}])")
+            o.pos_down, o.pos_up = dptr(keep[0]), dptr(keep[1])
+        return o, keep
+
+    @staticmethod
+    def _ik_poses(des_pose):
+        des = f64(des_pose)
+        if des.shape == (4, 4):
+            des = des.reshape(1, 4, 4)
+        if des.ndim != 3 or des.shape[1:] != (4, 4):
+            raise ValueError(f"des_pose: expected [G][4][4], got {list(des.shape)}")
+        return des
+
+    @staticmethod
+    def _ik_seeds(seeds, G, D):
+        s = f64(seeds)
+        if s.ndim == 2 and G == 1:
+            s = s.reshape(1, *s.shape)
+        if s.ndim != 3 or s.shape[0] != G or s.shape[2] != D:
+            raise ValueError(f"seeds: expected [{G}][M][{D}], got {list(s.shape)}")
+        return s
+
+    def ik_solve(self, robot, opts, des_pose, seeds=None, M=None, seed=0, first=0):
+        """des_pose [G][4][4]; seeds [G][M][D], or None: M rows per pose drawn from (seed, first) inside the limits ->
+        dict(conf [G][M][D], residual [G][M][2], iters [G][M], status [G][M])."""
+        o, keep = opts if isinstance(opts, tuple) else (opts, None)
+        des, D = self._ik_poses(des_pose), robot.dof
+        G = des.shape[0]
+        if seeds is not None:
+            s = self._ik_seeds(seeds, G, D)
+            M = s.shape[1]
+        elif M is None or int(M) < 0 or int(first) < 0:
+            raise ValueError("the seeded form needs M >= 0 and first >= 0")
+        M = int(M)
+        out = dict(conf=np.zeros((G, M, D)), residual=np.zeros((G, M, 2)), iters=np.zeros((G, M), dtype=np.int32),
+                   status=np.zeros((G, M), dtype=np.int32))
+        ptrs = (dptr(out["conf"]), dptr(out["residual"]), iptr(out["iters"]), iptr(out["status"]))
+        if seeds is not None:
+            self._ck(self.lib.gpmp2mi_ik_solve(robot.ptr, C.byref(o), G, dptr(des), M, dptr(s), *ptrs))
+        else:
+            self._ck(self.lib.gpmp2mi_ik_solve_seeded(robot.ptr, C.byref(o), G, dptr(des), M, int(seed), int(first), *ptrs))
+        return out
+
+    def ik_solve_dev(self, robot, opts, G, M, des_pose, seeds=None, seed=0, first=0, conf=None, residual=None, iters=None,
+                     status=None, stream=None):
+        """The same on device buffers (torch tensors or raw pointers), one enqueue: des_pose [G][16], seeds [G][M][D] or
+        None (drawn); outputs conf [G][M][D], residual [G][M][2], int32 iters / status [G][M], any may be None."""
+        o, keep = opts if isinstance(opts, tuple) else (opts, None)
+        G, M, D = int(G), int(M), robot.dof
+        outs = [_dev_arg("conf", conf, (G, M, D)), _dev_arg("residual", residual, (G, M, 2)),
+                _dev_arg("iters", iters, (G, M), True), _dev_arg("status", status, (G, M), True)]
+        des = _dev_arg("des_pose", des_pose, (G, 16))
+        if seeds is not None:
+            self._ck(self.lib.gpmp2mi_ik_solve_dev(robot.ptr, C.byref(o), G, des, M, _dev_arg("seeds", seeds, (G, M, D)),
+                                                   *outs, C.c_void_p(stream or 0)))
+        else:
+            self._ck(self.lib.gpmp2mi_ik_solve_seeded_dev(robot.ptr, C.byref(o), G, des, M, int(seed), int(first), *outs,
+                                                          C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def _ik_goal_args(D, M, near, weights, radius, max_goals):
+        if int(M) > scoring.MAX_GROUP_ROWS:
+            raise ValueError(f"at most {scoring.MAX_GROUP_ROWS} seed rows per pose can be grouped, got {M}")
+        if not 1 <= int(max_goals) <= scoring.MAX_ALTERNATIVES:
+            raise ValueError(f"max_goals must be in 1..{scoring.MAX_ALTERNATIVES}")
+        nr = None if near is None else f64(near).reshape(-1)
+        if nr is not None and (nr.shape != (D,) or not np.isfinite(nr).all()):
+            raise ValueError(f"near: expected {D} finite coordinates")
+        return nr, scoring.group_weights(weights, D), scoring.group_radius(radius), int(max_goals)
+
+    def ik_goals(self, robot, opts, des_pose, sdf=None, seeds=None, M=None, seed=0, first=0, radius=0.1, max_goals=8,
+                 required_clearance=0.0, require_in_range=False, near=None, weights=None):
+        """IK, the clearance of every answer, then one goal per distinct answer (the leader rule of scoring.group_rule per
+        pose) -> dict(conf, status, clearance, out_of_range, mode [G][M]..; n_goals, n_converged, n_eligible [G];
+        goal_conf [G][max_goals][D], goal_seed, goal_score, goal_clearance [G][max_goals]).  Slots beyond n_goals hold
+        goal_seed = -1 and NaN."""
+        o, keep = opts if isinstance(opts, tuple) else (opts, None)
+        des, D = self._ik_poses(des_pose), robot.dof
+        G = des.shape[0]
+        s = None
+        if seeds is not None:
+            s = self._ik_seeds(seeds, G, D)
+            M = s.shape[1]
+        elif M is None or int(M) < 0 or int(first) < 0:
+            raise ValueError("the seeded form needs M >= 0 and first >= 0")
+        M = int(M)
+        nr, w, radius, K = self._ik_goal_args(D, M, near, weights, radius, max_goals)
+        i32 = lambda *shape: np.zeros(shape, dtype=np.int32)   # noqa: E731
+        out = dict(conf=np.zeros((G, M, D)), status=i32(G, M), clearance=np.zeros((G, M)), out_of_range=i32(G, M),
+                   mode=i32(G, M), n_goals=i32(G), n_converged=i32(G), n_eligible=i32(G),
+                   goal_conf=np.full((G, K, D), np.nan), goal_seed=i32(G, K), goal_score=np.full((G, K), np.nan),
+                   goal_clearance=np.full((G, K), np.nan))
+        self._ck(self.lib.gpmp2mi_ik_goals(
+            robot.ptr, C.byref(o), None if sdf is None else sdf.ptr, G, dptr(des), M, dptr(s), int(seed), int(first),
+            float(required_clearance), int(bool(require_in_range)), dptr(nr), dptr(w), radius, K, dptr(out["conf"]),
+            iptr(out["status"]), dptr(out["clearance"]), iptr(out["out_of_range"]), iptr(out["mode"]),
+            iptr(out["n_goals"]), iptr(out["n_converged"]), iptr(out["n_eligible"]), dptr(out["goal_conf"]),
+            iptr(out["goal_seed"]), dptr(out["goal_score"]), dptr(out["goal_clearance"])))
+        return out
+
+    def ik_goals_dev(self, robot, opts, G, M, des_pose, sdf=None, seeds=None, seed=0, first=0, radius=0.1, max_goals=8,
+                     required_clearance=0.0, require_in_range=False, near=None, weights=None, conf=None, status=None,
+                     clearance=None, out_of_range=None, mode=None, n_goals=None, n_converged=None, n_eligible=None,
+                     goal_conf=None, goal_seed=None, goal_score=None, goal_clearance=None, stream=None):
+        """The same on device buffers; near and weights stay host arrays.  The workspace is allocated and freed inside the
+        call: one synchronising allocation per call."""
+        o, keep = opts if isinstance(opts, tuple) else (opts, None)
+        G, M, D = int(G), int(M), robot.dof
+        nr, w, radius, K = self._ik_goal_args(D, M, near, weights, radius, max_goals)
+        outs = [_dev_arg("conf", conf, (G, M, D)), _dev_arg("status", status, (G, M), True),
+                _dev_arg("clearance", clearance, (G, M)), _dev_arg("out_of_range", out_of_range, (G, M), True),
+                _dev_arg("mode", mode, (G, M), True), _dev_arg("n_goals", n_goals, (G,), True),
+                _dev_arg("n_converged", n_converged, (G,), True), _dev_arg("n_eligible", n_eligible, (G,), True),
+                _dev_arg("goal_conf", goal_conf, (G, K, D)), _dev_arg("goal_seed", goal_seed, (G, K), True),
+                _dev_arg("goal_score", goal_score, (G, K)), _dev_arg("goal_clearance", goal_clearance, (G, K))]
+        self._ck(self.lib.gpmp2mi_ik_goals_dev(
+            robot.ptr, C.byref(o), None if sdf is None else sdf.ptr, G, _dev_arg("des_pose", des_pose, (G, 16)), M,
+            _dev_arg("seeds", seeds, (G, M, D)), int(seed), int(first), float(required_clearance),
+            int(bool(require_in_range)), dptr(nr), dptr(w), radius, K, *outs, C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def goal_rows(goals, B, pose=0):
+        """[B][D] end configurations for Plan.set_problem: the goals of pose `pose` (a dict of ik_goals) cycled over the B
+        rows, row b taking goal b % min(n_goals, max_goals).  ValueError when the pose has no goal."""
+        n = min(int(goals["n_goals"][pose]), goals["goal_conf"].shape[1])
+        if n < 1:
+            raise ValueError("no goal configuration was found for this pose")
+        return np.ascontiguousarray(goals["goal_conf"][pose, np.arange(int(B)) % n])
 
     # ---------------------------------------------------------------- live map (include/gpmp2mi.h "live map")
     def _sdf_shape(self, sdf):

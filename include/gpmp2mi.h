@@ -1274,6 +1274,106 @@ int gpmp2mi_plan_sample_dense_seeded(gpmp2mi_plan* p, int inter_step, int K, uin
 int gpmp2mi_plan_sample_dense_seeded_dev(gpmp2mi_plan* p, int inter_step, int K, uint64_t seed, int row_first,
                                          int sample_first, int bridge, double* conf, int* ok, void* stream);
 
+/* ---- goal configurations: batched inverse kinematics from a workspace pose, on the device -----------------------------
+ * gpmp2mi_plan_set_problem wants end configurations; a manipulation task knows the pose of the hand.  These calls turn
+ * G poses into joint configurations by damped least squares from M seeds each, and (gpmp2mi_ik_goals) keep the distinct
+ * collision-free answers: the IK branches of a pose (elbow up / down, wrist flips, a redundant arm's null space) are
+ * the goals to spread restarts over, and gpmp2mi_plan_select_distinct chooses among what they lead to.
+ *
+ * Definitions.  One problem = one pose g (des_pose [G][16], row-major 4x4) and one seed row m (seeds [G][M][D]).
+ *  1. q = clamp(seed) into [pos_down, pos_up] (min(max(x, down), up) per coordinate; both NULL: no limits);
+ *     lambda = lambda_initial, it = 0.
+ *  2. (e, H) are the rows of gpmp2mi_workspace_prior_factor(mode, link, des_pose[g]) at q, by the arithmetic of that
+ *     entry point (the kernels share one copy of the log maps).  e^, H^ are e, H with the omega rows multiplied by
+ *     rot_weight: rows 0..2 for POSE, all rows for ORIENTATION, none for POSITION.  c = sum of e^_r^2, ascending r.
+ *  3. converged: POSITION |e| <= pos_tol; ORIENTATION |e| <= rot_tol; POSE |e[0:3]| <= rot_tol && |e[3:6]| <= pos_tol
+ *     (|.| = the root of the sum of squares in ascending order, unscaled rows).
+ *  4. A non-finite seed or e stops with GPMP2MI_IK_INVALID, conf = the clamped seed.  Otherwise, if converged, stop
+ *     with GPMP2MI_IK_CONVERGED.
+ *  5. While it < max_iter: A = H^ H^T + lambda I (r x r, r = 3 or 6: the dual form, whatever the dof); Cholesky of A,
+ *     y = A^-1 e^, dq = -H^T y, q' = clamp(q + dq); (e', c') at q'; it += 1.  A non-positive or NaN pivot, or a c'
+ *     that is not finite, counts as a rejection.  If c' < c: accept (q = q'), lambda = max(lambda / lambda_factor,
+ *     lambda_lower), and stop with CONVERGED if converged.  Else lambda = min(lambda * lambda_factor, lambda_upper).
+ *  6. Stop with GPMP2MI_IK_MAX_ITER_REACHED.
+ *  - Outputs per row: conf [G][M][D] the last accepted q (always inside the limits: the clamp is exact); residual
+ *    [G][M][2] = (|omega rows|, |translation rows|) of e there, unscaled, 0 for a part the mode does not have; iters
+ *    [G][M] = it; status [G][M].  Any output may be NULL.
+ *  - Seeded forms.  Coordinate d of seed row first + m of pose g is down[d] + u * (up[d] - down[d]), the difference,
+ *    the product and the sum each rounded once, where u = x * 2^-53 in [0, 1) and x is the hi53 (d & 4 clear) or lo53
+ *    (d & 4 set) word of the block that normal(seed, GPMP2MI_RNG_IK, g, first + m, 0, d) of "seeding" reads.  They
+ *    need finite limits.
+ *  - Goal stage (gpmp2mi_ik_goals): IK as above (seeds given, or drawn when seeds == NULL), then per row
+ *      clearance, out_of_range: min_clearance and the count of spheres outside the field of "scoring" for the single
+ *        configuration conf; +inf / 0 when sdf == NULL;
+ *      eligible = status == CONVERGED && (no field || (clearance >= required_clearance &&
+ *                                                       (!require_in_range || out_of_range == 0)));
+ *      score = sqrt(sum_d w_d (conf[d] - near[d])^2), or (double)m when near == NULL;
+ *      dist(m, m') = sqrt(sum_d w_d (conf_m[d] - conf_m'[d])^2),
+ *    both sums by the roundings of s_i in "distinct alternatives" (that section's pair kernel computes dist).  Then
+ *    the leader rule of "distinct alternatives" per pose, by that section's rule kernel, over (score, eligible, dist
+ *    <= radius).  Per pose: n_goals = number of modes (all of them, also beyond max_goals), n_converged, n_eligible;
+ *    goal_conf [G][max_goals][D], goal_seed [G][max_goals] (the leader's m), goal_score, goal_clearance
+ *    [G][max_goals] for the first min(n_goals, max_goals) leaders in leader order; beyond that goal_seed = -1 and the
+ *    doubles are untouched.  mode [G][M] as in "distinct alternatives".  No angle is wrapped in score or dist.
+ *  - Determinism: a row's IK outputs are a function of the robot, the options, its pose and its seed row alone:
+ *    bit-identical alone, at any position of any G x M, through the seeded or the given-seed form, through host or
+ *    _dev.  One lane per problem, no cross-lane arithmetic, no atomics.
+ * Errors, before any device work (a refused call writes nothing): GPMP2MI_ERR_INVALID for a NULL robot / opts /
+ * des_pose / seeds, G or M < 0 (0 is fine and does nothing), a tolerance, rot_weight or lambda that is <= 0 or NaN,
+ * lambda_lower > lambda_upper, max_iter outside 1..GPMP2MI_IK_MAX_ITER, an unknown mode, a link outside the robot's,
+ * one of pos_down / pos_up alone, down > up or a NaN limit, first < 0, infinite or no limits in a seeded form, a
+ * negative or NaN radius, a non-finite near, a negative or non-finite weight, a required_clearance that is NaN, max_goals
+ * outside 1..GPMP2MI_MAX_ALTERNATIVES, a field whose dimension does not fit.  GPMP2MI_ERR_UNSUPPORTED, the limit in
+ * the message, for a robot that is not a GPMP2MI_ROBOT_ARM of dof 1..7 (the Pose2 kinds need a retraction on the base)
+ * and, for gpmp2mi_ik_goals, M > GPMP2MI_MAX_GROUP_ROWS.
+ * Memory: opts, pos_down / pos_up, near and weights are HOST data in every form, read before the call returns.
+ * gpmp2mi_ik_solve*_dev allocate nothing and enqueue one kernel.  gpmp2mi_ik_goals_dev has no handle to keep a
+ * workspace with: as gpmp2mi_group_traj_dev it allocates one block (the staged configurations, the bit matrices, a
+ * few [G][M] arrays) and waits for `stream` before it frees it -- ONE synchronising allocation per call.  It enqueues
+ * the IK kernel, one row kernel, then per pose one launch of the pair kernel and one of the rule kernel (the rule
+ * kernel has no batched form), then one copy kernel.
+ * Not here: the Pose2 robot kinds and arms of more than 7 joints, angle wrapping in the distances, null-space
+ * objectives, self-collision in the eligibility, gpmp2mi_multi_plan_* twins. */
+#define GPMP2MI_IK_MAX_ITER 1000
+enum { GPMP2MI_IK_CONVERGED = 0, GPMP2MI_IK_MAX_ITER_REACHED = 1, GPMP2MI_IK_INVALID = 2 };
+enum { GPMP2MI_RNG_IK = 4 };
+typedef struct gpmp2mi_ik_opts {
+  int mode;                 /* GPMP2MI_WORKSPACE_POSITION / _ORIENTATION / _POSE */
+  int link;                 /* as gpmp2mi_workspace_factor::link */
+  double pos_tol, rot_tol;  /* > 0 */
+  double rot_weight;        /* > 0: the omega rows are multiplied by it (metres per radian) */
+  int max_iter;             /* 1..GPMP2MI_IK_MAX_ITER */
+  double lambda_initial, lambda_factor, lambda_lower, lambda_upper;
+  const double *pos_down, *pos_up;   /* HOST [dof]; both NULL = unlimited (then the seeded forms are refused) */
+} gpmp2mi_ik_opts;
+/* POSE, link = 0 (the caller fills in the last link), 1e-6, 1e-6, 1, 100, 1e-2, 4, 1e-9, 1e6, NULL, NULL; NULL: no-op */
+void gpmp2mi_ik_opts_default(gpmp2mi_ik_opts* o);
+/* des_pose [G][16], seeds [G][M][D] -> conf [G][M][D], residual [G][M][2], iters [G][M], status [G][M] */
+int gpmp2mi_ik_solve(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, int G, const double* des_pose, int M,
+                     const double* seeds, double* conf, double* residual, int* iters, int* status);
+int gpmp2mi_ik_solve_dev(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, int G, const double* des_pose, int M,
+                         const double* seeds, double* conf, double* residual, int* iters, int* status, void* stream);
+int gpmp2mi_ik_solve_seeded(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, int G, const double* des_pose, int M,
+                            uint64_t seed, int first, double* conf, double* residual, int* iters, int* status);
+int gpmp2mi_ik_solve_seeded_dev(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, int G, const double* des_pose, int M,
+                                uint64_t seed, int first, double* conf, double* residual, int* iters, int* status,
+                                void* stream);
+/* seeds [G][M][D] or NULL (then drawn from seed / first); sdf may be NULL; near [D], weights [D]: HOST or NULL.
+ * Per row: conf, status, clearance, out_of_range, mode [G][M](..[D]); per pose: n_goals, n_converged, n_eligible [G],
+ * goal_conf [G][max_goals][D], goal_seed / goal_score / goal_clearance [G][max_goals].  Any output may be NULL. */
+int gpmp2mi_ik_goals(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, const gpmp2mi_sdf* sdf, int G,
+                     const double* des_pose, int M, const double* seeds, uint64_t seed, int first,
+                     double required_clearance, int require_in_range, const double* near_conf, const double* weights,
+                     double radius, int max_goals, double* conf, int* status, double* clearance, int* out_of_range,
+                     int* mode, int* n_goals, int* n_converged, int* n_eligible, double* goal_conf, int* goal_seed,
+                     double* goal_score, double* goal_clearance);
+int gpmp2mi_ik_goals_dev(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, const gpmp2mi_sdf* sdf, int G,
+                         const double* des_pose, int M, const double* seeds, uint64_t seed, int first,
+                         double required_clearance, int require_in_range, const double* near_conf, const double* weights,
+                         double radius, int max_goals, double* conf, int* status, double* clearance, int* out_of_range,
+                         int* mode, int* n_goals, int* n_converged, int* n_eligible, double* goal_conf, int* goal_seed,
+                         double* goal_score, double* goal_clearance, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 const char* gpmp2mi_last_error(void);  /* thread-local message of the last failing call */
 int gpmp2mi_device_count(void);
