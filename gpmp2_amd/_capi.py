@@ -238,6 +238,43 @@ def declare_map(lib):
         getattr(lib, name).restype = i
 
 
+class EvidenceOpts(C.Structure):
+    """gpmp2mi_evidence_opts (include/gpmp2mi.h "sensor map")"""
+    _fields_ = [(n, C.c_int) for n in ("hit", "miss", "lo", "hi", "occupied_at", "use_base", "refresh")]
+
+
+class DepthCamera(C.Structure):
+    """gpmp2mi_depth_camera (include/gpmp2mi.h "sensor map")"""
+    _fields_ = ([("width", C.c_int), ("height", C.c_int)] +
+                [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "depth_min", "depth_max")] +
+                [("pose", C.c_double * 12)])
+
+
+def declare_sensor(lib):
+    """argtypes of the sensor-map entry points (include/gpmp2mi.h "sensor map") and their stage timer; the `_dev` forms
+    take device addresses; sensor_origin, the camera and the opts are host data in every form."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    op, cam = C.POINTER(EvidenceOpts), C.POINTER(DepthCamera)
+    decl = {
+        "gpmp2mi_sdf_reserve_evidence": [vp],
+        "gpmp2mi_sdf_integrate_points": [vp, i, d, d, vp, d, f, op, ip],
+        "gpmp2mi_sdf_integrate_points_dev": [vp, i, vp, d, vp, vp, f, op, vp, vp],
+        "gpmp2mi_sdf_integrate_depth": [vp, cam, C.POINTER(C.c_float), vp, d, f, op, ip],
+        "gpmp2mi_sdf_integrate_depth_dev": [vp, cam, vp, vp, vp, f, op, vp, vp],
+        "gpmp2mi_sdf_refresh_from_evidence": [vp, i, i],
+        "gpmp2mi_sdf_refresh_from_evidence_dev": [vp, i, i, vp],
+        "gpmp2mi_sdf_evidence_reset": [vp],
+        "gpmp2mi_sdf_evidence_reset_dev": [vp, vp],
+        "gpmp2mi_sdf_get_evidence": [vp, C.POINTER(C.c_int16)],
+        "gpmp2mi_debug_sdf_integrate_timing": [vp, i, d],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_evidence_opts_default.argtypes = [op]
+    lib.gpmp2mi_evidence_opts_default.restype = None
+
+
 def declare_group(lib):
     """include/gpmp2mi.h "distinct alternatives"; `weights` is a host array in every form"""
     vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double

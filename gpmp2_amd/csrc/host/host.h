@@ -150,11 +150,23 @@ struct gpmp2mi_sdf {
   // gpmp2mi_debug_sdf_update_timing: five events around the four stages of an update, recorded while map_timing
   hipEvent_t map_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   bool map_timing = false;
+  // sensor map (sensor.hip; include/gpmp2mi.h "sensor map"): the int16 evidence, the two byte volumes of marks and six
+  // counters in one block on `device`, taken at the first call of that section or by gpmp2mi_sdf_reserve_evidence and
+  // kept.  ray_ws: the records of one frame's rays ([M][3] cell coordinates, [M] classes), grown when a frame has more
+  // rays than any before.  sensor_ev: the events in front of the three sensor stages (the rest are map_ev's).
+  void* ev_ws = nullptr;
+  void* ray_ws = nullptr;
+  size_t ray_ws_bytes = 0;
+  hipEvent_t sensor_ev[3] = {nullptr, nullptr, nullptr};
   ~gpmp2mi_sdf() {   // also runs when a create function fails half-way (unique_ptr)
     if (plain) (void)hipFree(plain);
     if (cells) (void)hipFree(cells);
     if (map_ws) (void)hipFree(map_ws);
+    if (ev_ws) (void)hipFree(ev_ws);
+    if (ray_ws) (void)hipFree(ray_ws);
     for (hipEvent_t e : map_ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sensor_ev)
       if (e) (void)hipEventDestroy(e);
     if (replica) g2::g_sdf_replicas.fetch_sub(1);
   }
@@ -182,6 +194,23 @@ namespace g2 {
 int sdf_alloc(int dim, const double origin[3], double cell, int nx, int ny, int nz, std::unique_ptr<gpmp2mi_sdf>& s);
 // caller layout -> [nz][ny][nx] (handles.hip); `tmp` holds the reordered copy when one is needed
 const double* to_zyx(const double* vox, int layout, int nx, int ny, int nz, std::vector<double>& tmp);
+
+// map.hip, shared with sensor.hip.  The handle's update workspace for n cells:
+struct MapWs {
+  int *wa, *wb;          // [n] squared distance to the obstacle set / to the free set
+  unsigned char* mask;   // [n] the base: 1 on the obstacle cells of the last update from occupancy
+  double* cen;           // [MAXS][3] sphere centres of the self filter
+  int* cnt;              // [4] kept, non-finite, self, outside
+  size_t bytes;
+};
+MapWs map_ws_layout(char* base, size_t n);
+inline size_t cells_of(const gpmp2mi_sdf* s) { return (size_t)s->h.nx * s->h.ny * s->h.nz; }
+// what every update does once its arguments are accepted: a device, the handle's device current, the workspace
+int map_ready(gpmp2mi_sdf* s, bool transform);
+// the event in front of stage k while the handle's stage timer is on
+void mark_stage(gpmp2mi_sdf* s, int k, hipStream_t st);
+// the two seeded volumes -> plain -> cells on `st`
+int map_transform(gpmp2mi_sdf* s, const MapWs& w, hipStream_t st);
 
 struct KernelTimer {
   // One HIP event per kernel boundary on the launch stream: begin(name) is recorded right before kernel `name`,

@@ -9,16 +9,9 @@
 
 using namespace g2;
 
-namespace {
+// shared with the sensor map (sensor.hip), declared in host.h: the workspace, the stage marks and the transform
+namespace g2 {
 
-// the handle's update workspace for n cells
-struct MapWs {
-  int *wa, *wb;          // [n] squared distance to the obstacle set / to the free set
-  unsigned char* mask;   // [n] the base: 1 on the obstacle cells of the last update from occupancy
-  double* cen;           // [MAXS][3] sphere centres of the self filter
-  int* cnt;              // [4] kept, non-finite, self, outside
-  size_t bytes;
-};
 MapWs map_ws_layout(char* base, size_t n) {
   MapWs w{};
   size_t off = 0;
@@ -35,8 +28,6 @@ MapWs map_ws_layout(char* base, size_t n) {
   w.bytes = off;
   return w;
 }
-size_t cells_of(const gpmp2mi_sdf* s) { return (size_t)s->h.nx * s->h.ny * s->h.nz; }
-
 // what every update does once its arguments are accepted: a device, the handle's device current, the workspace
 int map_ready(gpmp2mi_sdf* s, bool transform) {
   G2_TRY(ensure_device());
@@ -48,7 +39,7 @@ int map_ready(gpmp2mi_sdf* s, bool transform) {
   return GPMP2MI_OK;
 }
 
-int check_layout(int layout) {
+static int check_layout(int layout) {
   G2_CHECK(layout == GPMP2MI_SDF_LAYOUT_ZYX || layout == GPMP2MI_SDF_LAYOUT_GTSAM, GPMP2MI_ERR_INVALID,
            "unknown voxel layout");
   return GPMP2MI_OK;
@@ -69,6 +60,10 @@ int map_transform(gpmp2mi_sdf* s, const MapWs& w, hipStream_t st) {
   mark_stage(s, 4, st);
   return GPMP2MI_OK;
 }
+
+}  // namespace g2
+
+namespace {
 
 int update_from_occupancy(gpmp2mi_sdf* s, const double* d_occ, hipStream_t st) {
   const MapWs w = map_ws_layout((char*)s->map_ws, cells_of(s));

@@ -31,6 +31,49 @@ struct MapMark {
   int* cnt;            // [4]: kept, non-finite, self, outside; zeroed by the caller
 };
 int launch_map_mark(const MapMark& a, hipStream_t st);
+// sensor_kernels.hip (include/gpmp2mi.h "sensor map"): the rays of a frame, their walk, and evidence -> seeds
+struct SensorGrid {
+  int dim, nx, ny, nz;   // nz == 1 for a planar grid
+  double ox, oy, oz, cell;
+};
+// arguments of k_sensor_rays: M rays classified; cell coordinates of the end points and classes to the ray records
+struct SensorRays {
+  SensorGrid g;
+  int M, S;
+  double o[3];              // the sensor origin in the world (the unused axis of a planar grid: 0)
+  double margin;
+  const double* pts;        // [M][dim], the points form
+  const float* depth;       // [height][width], the depth form (null: the points form)
+  int width;
+  double fx, fy, cx, cy, depth_min, depth_max, pose[12];
+  const RobotDev* R;        // null: no self filter
+  const double* cen;        // [S][3] in the caller's sphere order (launch_sphere_centers, M = 1)
+  double* rb;               // [M][3] cell coordinates of the end point
+  int* rcls;                // [M] class: hit, invalid, max_range, self, outside
+  int* cnt;                 // [5] in that order; zeroed by the caller
+};
+int launch_sensor_rays(const SensorRays& a, hipStream_t st);
+// arguments of k_sensor_walk: the rays of k_sensor_rays walked into the two byte volumes of marks
+struct SensorWalk {
+  SensorGrid g;
+  int M;
+  double o[3];
+  const double* rb;
+  const int* rcls;
+  unsigned char *miss, *hit;   // [n] each, all 0 between two calls
+};
+int launch_sensor_walk(const SensorWalk& a, hipStream_t st);
+// arguments of k_sensor_apply: marks -> evidence (marks cleared), the occupied cells counted, the two volumes seeded
+struct SensorApply {
+  size_t n;
+  int hit, miss, lo, hi, occupied_at;
+  short* E;                           // [n]
+  unsigned char *miss_marks, *hit_marks;
+  const unsigned char* mask;          // the base (null: none)
+  int *wa, *wb;                       // null: the evidence only
+  int* cnt;                           // one word, zeroed by the caller: cells with E' >= occupied_at
+};
+int launch_sensor_apply(const SensorApply& a, hipStream_t st);
 // factor_kernels.hip
 int launch_sdf_pack(const SdfDev& s, double* cells, hipStream_t st);
 int launch_sdf_query(const SdfDev& s, int M, const double* pts, double* dist, double* grad, int* inr,

@@ -46,6 +46,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_motion(lib)
     _capi.declare_moving(lib)
     _capi.declare_map(lib)
+    _capi.declare_sensor(lib)
     _capi.declare_group(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
@@ -983,6 +984,148 @@ class Engine:
         ms = np.zeros(4) if read else None
         self._ck(self.lib.gpmp2mi_debug_sdf_update_timing(sdf.ptr, int(bool(on)), dptr(ms)))
         return None if ms is None else dict(zip(("seed_mark", "passes", "finish", "pack"), (float(x) for x in ms)))
+
+    # ---------------------------------------------------------------- sensor map (include/gpmp2mi.h "sensor map")
+    EVIDENCE_DEFAULTS = dict(hit=2, miss=1, lo=-4, hi=8, occupied_at=1, use_base=False, refresh=True)
+    EVIDENCE_STATS = ("hit", "invalid", "max_range", "self", "outside", "occupied")
+
+    @classmethod
+    def _evidence_opts(cls, opts):
+        unknown = set(opts) - set(cls.EVIDENCE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown evidence options: {sorted(unknown)}")
+        o = _capi.EvidenceOpts()
+        for k, v in dict(cls.EVIDENCE_DEFAULTS, **opts).items():
+            setattr(o, k, int(v))
+        return o
+
+    @staticmethod
+    def _camera(camera):
+        """dict(width, height, fx, fy, cx, cy, depth_min, depth_max, pose [3][4] camera -> world) -> DepthCamera"""
+        pose = f64(camera["pose"])
+        if pose.size != 12:
+            raise ValueError(f"camera pose: expected [3][4], got {list(pose.shape)}")
+        cam = _capi.DepthCamera()
+        cam.width, cam.height = int(camera["width"]), int(camera["height"])
+        for k in ("fx", "fy", "cx", "cy", "depth_min", "depth_max"):
+            setattr(cam, k, float(camera[k]))
+        for k, v in enumerate(pose.reshape(12)):
+            cam.pose[k] = float(v)
+        return cam
+
+    def _sensor_origin(self, sdf, sensor_origin):
+        o = f64(sensor_origin).reshape(-1)
+        if o.size != sdf.dim:
+            raise ValueError(f"sensor_origin: expected [{sdf.dim}], got {list(np.shape(sensor_origin))}")
+        return o
+
+    def _conf_arg(self, robot, conf):
+        if robot is None:
+            return None
+        q = f64(conf).reshape(-1)
+        if q.size != robot.dof:
+            raise ValueError(f"conf: expected [{robot.dof}], got {list(np.shape(conf))}")
+        return q
+
+    def sdf_reserve_evidence(self, sdf):
+        """Takes the evidence workspace of the handle now, so that the first `_dev` integrate call does not allocate."""
+        self._ck(self.lib.gpmp2mi_sdf_reserve_evidence(sdf.ptr))
+
+    def sdf_integrate_points(self, sdf, points, sensor_origin, robot=None, conf=None, margin=0.0, **opts):
+        """One frame of rays from sensor_origin [dim] to points [M][dim] into the handle's evidence: +hit where a ray
+        ends, -miss where rays pass, clamped; then (refresh) the field again from the cells with evidence >= occupied_at.
+        opts: hit, miss, lo, hi, occupied_at, use_base, refresh (EVIDENCE_DEFAULTS).  robot / conf / margin: rays that
+        end inside the robot's body spheres carve and do not mark.
+        -> dict(hit, invalid, max_range, self, outside, occupied)."""
+        margin = self._points_args(sdf, robot, conf, margin)
+        p = f64(points)
+        if p.size == 0:
+            p = p.reshape(0, sdf.dim)
+        if p.ndim != 2 or p.shape[1] != sdf.dim:
+            raise ValueError(f"points: expected [M][{sdf.dim}], got {list(p.shape)}")
+        o, q, eo = self._sensor_origin(sdf, sensor_origin), self._conf_arg(robot, conf), self._evidence_opts(opts)
+        stats = np.zeros(6, dtype=np.int32)
+        self._ck(self.lib.gpmp2mi_sdf_integrate_points(sdf.ptr, p.shape[0], dptr(p), dptr(o),
+                                                       None if robot is None else robot.ptr, dptr(q), margin,
+                                                       C.byref(eo), iptr(stats)))
+        return dict(zip(self.EVIDENCE_STATS, (int(x) for x in stats)))
+
+    def sdf_integrate_points_dev(self, sdf, M, points, sensor_origin, robot=None, conf=None, margin=0.0, stats=None,
+                                 stream=None, **opts):
+        """The same from device buffers (torch tensors or raw pointers): points [M][dim], conf [dof], stats [6] int32 or
+        None; sensor_origin is a host array.  Enqueued on `stream`, no host synchronisation."""
+        margin, M = self._points_args(sdf, robot, conf, margin), int(M)
+        if M < 0:
+            raise ValueError("M must be >= 0")
+        o, eo = self._sensor_origin(sdf, sensor_origin), self._evidence_opts(opts)
+        self._ck(self.lib.gpmp2mi_sdf_integrate_points_dev(
+            sdf.ptr, M, _dev_arg("points", points, (M, sdf.dim)), dptr(o), None if robot is None else robot.ptr,
+            None if robot is None else _dev_arg("conf", conf, (robot.dof,)), margin, C.byref(eo),
+            _dev_arg("stats", stats, (6,), True), C.c_void_p(stream or 0)))
+
+    def sdf_integrate_depth(self, sdf, camera, depth, robot=None, conf=None, margin=0.0, **opts):
+        """One depth image [height][width] (float32 metres along the optical axis) of `camera` (a dict: width, height,
+        fx, fy, cx, cy, depth_min, depth_max, pose [3][4] camera -> world) into the evidence of a 3-D handle, as
+        sdf_integrate_points; pixels beyond depth_max carve up to depth_max and mark no end."""
+        margin = self._points_args(sdf, robot, conf, margin)
+        cam = self._camera(camera)
+        z = np.ascontiguousarray(depth, dtype=np.float32)
+        if sdf.dim != 3:
+            raise ValueError("the depth form needs a 3-D field")
+        if z.shape != (cam.height, cam.width):
+            raise ValueError(f"depth: expected [{cam.height}][{cam.width}], got {list(z.shape)}")
+        q, eo = self._conf_arg(robot, conf), self._evidence_opts(opts)
+        stats = np.zeros(6, dtype=np.int32)
+        self._ck(self.lib.gpmp2mi_sdf_integrate_depth(sdf.ptr, C.byref(cam), z.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      None if robot is None else robot.ptr, dptr(q), margin,
+                                                      C.byref(eo), iptr(stats)))
+        return dict(zip(self.EVIDENCE_STATS, (int(x) for x in stats)))
+
+    def sdf_integrate_depth_dev(self, sdf, camera, depth, robot=None, conf=None, margin=0.0, stats=None, stream=None,
+                                **opts):
+        """The same from device buffers: depth a contiguous float32 cuda tensor [height][width] or a raw pointer."""
+        margin = self._points_args(sdf, robot, conf, margin)
+        cam, eo = self._camera(camera), self._evidence_opts(opts)
+        if hasattr(depth, "data_ptr"):
+            if (str(depth.dtype) != "torch.float32" or not depth.is_contiguous() or depth.device.type != "cuda"
+                    or tuple(depth.shape) != (cam.height, cam.width)):
+                raise ValueError(f"depth: expected a contiguous torch.float32 cuda tensor of shape "
+                                 f"{[cam.height, cam.width]}, got {depth.dtype} {list(depth.shape)} on {depth.device}")
+            depth = depth.data_ptr()
+        self._ck(self.lib.gpmp2mi_sdf_integrate_depth_dev(
+            sdf.ptr, C.byref(cam), C.c_void_p(int(depth)), None if robot is None else robot.ptr,
+            None if robot is None else _dev_arg("conf", conf, (robot.dof,)), margin, C.byref(eo),
+            _dev_arg("stats", stats, (6,), True), C.c_void_p(stream or 0)))
+
+    def sdf_refresh_from_evidence(self, sdf, occupied_at=1, use_base=False, stream=None, dev=False):
+        """The field again from the evidence as it stands: the cells with evidence >= occupied_at, united with the base
+        when use_base.  dev = True: enqueued on `stream` without a host synchronisation."""
+        if dev:
+            self._ck(self.lib.gpmp2mi_sdf_refresh_from_evidence_dev(sdf.ptr, int(occupied_at), int(bool(use_base)),
+                                                                    C.c_void_p(stream or 0)))
+        else:
+            self._ck(self.lib.gpmp2mi_sdf_refresh_from_evidence(sdf.ptr, int(occupied_at), int(bool(use_base))))
+
+    def sdf_evidence_reset(self, sdf, stream=None, dev=False):
+        """Evidence 0 everywhere; the field stays as it is."""
+        if dev:
+            self._ck(self.lib.gpmp2mi_sdf_evidence_reset_dev(sdf.ptr, C.c_void_p(stream or 0)))
+        else:
+            self._ck(self.lib.gpmp2mi_sdf_evidence_reset(sdf.ptr))
+
+    def sdf_evidence(self, sdf):
+        """-> the handle's evidence, int16 [nz][ny][nx] or [ny][nx] (all 0 before the first integrate call)"""
+        E = np.zeros(self._sdf_shape(sdf), dtype=np.int16)
+        self._ck(self.lib.gpmp2mi_sdf_get_evidence(sdf.ptr, E.ctypes.data_as(C.POINTER(C.c_int16))))
+        return E
+
+    def sdf_integrate_timing(self, sdf, on=True, read=False):
+        """Stage timer of the integrate calls (gpmp2mi_debug_sdf_integrate_timing): read = True returns the device times
+        in ms of the last recorded call with refresh as dict(deproject, walk, apply_seed, passes, finish, pack)."""
+        ms = np.zeros(6) if read else None
+        self._ck(self.lib.gpmp2mi_debug_sdf_integrate_timing(sdf.ptr, int(bool(on)), dptr(ms)))
+        names = ("deproject", "walk", "apply_seed", "passes", "finish", "pack")
+        return None if ms is None else dict(zip(names, (float(x) for x in ms)))
 
     # ---------------------------------------------------------------- plans
     def plan(self, robot, sdf, setting, B, forms=None):

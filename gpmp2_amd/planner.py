@@ -62,6 +62,26 @@ class _DeviceSdf:
         self.data_ = _eng().sdf_field(self.handle())["data"]
         return stats
 
+    # Sensor map (include/gpmp2mi.h "sensor map"): evidence kept on the live handle from frame to frame
+    def integratePoints(self, points, sensor_origin, robot=None, conf=None, margin=0.0, **opts):
+        """One frame of rays from sensor_origin to points [M][dim]: the evidence rises where rays end and falls where they
+        pass, and the field is rebuilt from it (opts: hit, miss, lo, hi, occupied_at, use_base, refresh).  Returns the
+        counts dict(hit, invalid, max_range, self, outside, occupied)."""
+        stats = _eng().sdf_integrate_points(self.handle(), points, sensor_origin,
+                                            None if robot is None else _robot_handle(robot), conf, margin, **opts)
+        self.data_ = _eng().sdf_field(self.handle())["data"]
+        return stats
+
+    def refreshFromEvidence(self, occupied_at=1, use_base=False):
+        _eng().sdf_refresh_from_evidence(self.handle(), occupied_at, use_base)
+        self.data_ = _eng().sdf_field(self.handle())["data"]
+
+    def evidence(self):
+        return _eng().sdf_evidence(self.handle())
+
+    def resetEvidence(self):
+        _eng().sdf_evidence_reset(self.handle())
+
 
 class SignedDistanceField(_DeviceSdf):
     """gpmp2::SignedDistanceField (gpmp2/obstacle/SignedDistanceField.h:28-72): origin, cell size and
@@ -102,6 +122,14 @@ class SignedDistanceField(_DeviceSdf):
 
     def _upload(self):
         return _eng().sdf(self.origin_, self.cell_size_, self.data_)
+
+    def integrateDepth(self, camera, depth, robot=None, conf=None, margin=0.0, **opts):
+        """One depth image [height][width] (float32 metres) of `camera` (dict: width, height, fx, fy, cx, cy, depth_min,
+        depth_max, pose [3][4] camera -> world) into the evidence, as integratePoints."""
+        stats = _eng().sdf_integrate_depth(self.handle(), camera, depth,
+                                           None if robot is None else _robot_handle(robot), conf, margin, **opts)
+        self.data_ = _eng().sdf_field(self.handle())["data"]
+        return stats
 
 
 class PlanarSDF(_DeviceSdf):

@@ -800,8 +800,8 @@ int gpmp2mi_plan_select_moving_dev(gpmp2mi_plan* p, int inter_step, double requi
  * the cells are bit-identical) and returns when all copies are done.  The source handle must still be alive, its update
  * complete, and the multi plan idle; shards on the source's own device read the caller's handle and need no copy.  A poisoned multi plan returns GPMP2MI_ERR_TIMEOUT.  The caller's current device is the same on return
  * as on entry.
- * Not here: ray casting of free space, decay or accumulation of clouds, depth images as opposed to clouds, a field per
- * trajectory, a change of geometry, updates of a sub-box of the grid. */
+ * Not here: a field per trajectory, a change of geometry, updates of a sub-box of the grid.  Ray casting of free space,
+ * accumulation of clouds and depth images are in "sensor map" below; decay over time is in neither. */
 int gpmp2mi_sdf_reserve_update(gpmp2mi_sdf* s);
 /* voxels in `layout`, [nz][ny][nx] cells as at gpmp2mi_sdf_create; _dev: a device pointer in GPMP2MI_SDF_LAYOUT_ZYX */
 int gpmp2mi_sdf_update(gpmp2mi_sdf* s, const double* voxels, int layout);
@@ -816,6 +816,115 @@ int gpmp2mi_sdf_update_from_points_dev(gpmp2mi_sdf* s, int M, const double* poin
                                        const gpmp2mi_robot* robot, const double* conf, double margin, int* stats,
                                        void* stream);
 int gpmp2mi_multi_plan_refresh_field(gpmp2mi_multi_plan* m);
+
+/* ---- sensor map: evidence per cell kept on the field handle, free space carved by ray casting, from clouds or depth --
+ * The calls of "live map" build the field from the base and the cloud of one call: nothing is remembered and nothing is
+ * cleared.  These calls keep an integer evidence value per cell on the handle.  A frame raises it where rays end and
+ * lowers it where rays pass; the field is rebuilt from the cells whose evidence reaches a threshold, by the distance
+ * transform the handle already runs.  Geometry, streams, `_dev` forms and the meaning of "the handle afterwards equals"
+ * are those of "live map".
+ *
+ * Data on the handle: E, int16 [nz][ny][nx], all 0 when first allocated; two byte volumes of per-call marks; six
+ * counters; the records of one frame's rays.  They are taken at the first call of this section, or by
+ * gpmp2mi_sdf_reserve_evidence, together with the workspace of gpmp2mi_sdf_reserve_update, and kept until
+ * gpmp2mi_sdf_destroy.  A later `_dev` call neither allocates nor synchronises; the one exception is a frame with more
+ * rays than any frame before it on this handle, which grows the ray records (28 bytes a ray).
+ * gpmp2mi_sdf_reserve_update and the update calls of "live map" keep their memory and behaviour exactly; they neither
+ * read nor change E.
+ *
+ * Rules.  Every expression is evaluated in IEEE double exactly as written, each operation rounded once (no fused
+ * multiply-add); divisions are true divisions.  k runs over the axes x, y(, z) of the handle.
+ *  1. Deprojection (depth form).  Pixel column u, row v, z = (double)depth[v][u], P = cam->pose as [3][4]:
+ *       xc = (((double)u - cx) / fx) * z,  yc = (((double)v - cy) / fy) * z,
+ *       p_i = ((P[i][0]*xc + P[i][1]*yc) + P[i][2]*z) + P[i][3],  sensor origin o_i = P[i][3],  M = width * height.
+ *  2. Cell coordinates, the point-to-cell rule of "live map" per axis: a_k = (o_k - origin_k) / cell_size + 0.5 and
+ *     b_k = (p_k - origin_k) / cell_size + 0.5.  The end point is in the grid iff 0 <= b_k < n_k on every axis, compared
+ *     in double.
+ *  3. Class of a ray; the first rule that matches applies:
+ *       (1) invalid -- depth form: z is NaN, infinite, <= 0 or < depth_min; points form: a coordinate is not finite;
+ *           either form: |b_k - a_k| >= 1048576 on some axis (a difference that is not a number counts as such);
+ *       (2) max_range (depth form only): z > depth_max.  The point is recomputed with z = depth_max, and with it b; the
+ *           span rule of (1) is applied to the recomputed b as well;
+ *       (3) self: the self rule of "live map" on the end point, with the centres of gpmp2mi_sphere_centers(robot, conf)
+ *           and radius + margin;
+ *       (4) outside: the end point is not in the grid;
+ *       (5) hit.
+ *     Invalid rays do nothing.  Rays of classes 2-5 carve.  Only class 5 marks its end cell.
+ *  4. The walk.  c_k = floor(a_k), e_k = floor(b_k), left_k = |e_k - c_k|, step_k = sign(e_k - c_k).  For the axes with
+ *     left_k > 0: d_k = b_k - a_k, inv_k = 1.0 / |d_k|, first_k = (c_k + 1.0) - a_k when step_k > 0, else a_k - c_k.
+ *     The walk has sum_k left_k steps.  At each step, among the axes with j_k < left_k (j_k = 0 at the start), the one
+ *     with the smallest t_k = (first_k + (double)j_k) * inv_k is taken; ties go to the lowest axis index (x, then y, then
+ *     z; a comparison with a NaN t is false, so such an axis is taken last); then c_k += step_k and j_k += 1 on that
+ *     axis.  The products are recomputed from j_k, not accumulated, so the last cell is exactly e.  The cells of the
+ *     walk are the start cell and the cell after every step.  Every cell of the walk other than its last one that lies
+ *     in the grid gets this call's miss mark; the last cell of a class-5 ray gets this call's hit mark.  Cells outside
+ *     the grid are walked over, not written.  (The implementation skips a ray whose cells all lie beyond the grid on
+ *     one axis, and leaves a walk at a cell beyond the grid on an axis whose remaining motion is away from the grid or
+ *     none: neither changes the set of marked cells.)  A planar handle has no z axis.
+ *  5. Apply, per cell: E' = clamp(E + (hit mark ? hit : miss mark ? -miss : 0), lo, hi).  A hit wins over any number of
+ *     misses in the same call.  The marks are per call and are gone afterwards.  The result depends on the set of rays
+ *     only, not on their order: marks are plain stores of one value, no floating-point atomic and no ordered reduction
+ *     is used; integer atomics add up the counts only.
+ *  6. Field.  With opts->refresh, O = {E' >= occupied_at}, united with the base if use_base.  The handle is then, bit
+ *     for bit, what gpmp2mi_sdf_create_from_occupancy gives for the indicator of O (the constant 1000 for an empty or a
+ *     full O).  The base is never changed by these calls, and evidence cannot clear a base cell.  With refresh == 0 only
+ *     E changes; gpmp2mi_sdf_refresh_from_evidence is the rebuild alone, from E as it stands.
+ *  7. stats [6] (NULL ok): entries 0-4 are {hit, invalid, max_range, self, outside} and sum to M; entry 5 is the
+ *     number of cells with E' >= occupied_at.
+ *  8. Errors, all checked before any device work (a refused call changes nothing): GPMP2MI_ERR_INVALID for a NULL
+ *     handle, camera, opts or sensor_origin; M < 0; NULL points / depth with M > 0; a negative width or height, or more
+ *     than INT_MAX pixels; a non-finite sensor origin, pose or intrinsics; fx or fy == 0; a depth range that is not
+ *     0 <= depth_min < depth_max, both finite; opts outside the ranges given at the struct; occupied_at outside
+ *     -32768 .. 32767 for the rebuild alone; a NaN margin; robot != NULL with a NULL conf; use_base on a handle
+ *     without a base; a planar handle given to the depth form; and the device rules of "live map" (a robot on another
+ *     device than the field, a field whose device is not the current one).  GPMP2MI_ERR_UNSUPPORTED, GPMP2MI_ERR_ALLOC
+ *     and GPMP2MI_ERR_HIP as there.
+ * `sensor_origin`, `cam` and `opts` are HOST data in every form, read before the call returns.
+ * Not here: decay of evidence over time, depth as uint16, gpmp2mi_multi_plan_* twins beyond the existing
+ * gpmp2mi_multi_plan_refresh_field, updates of a sub-box of the grid. */
+typedef struct gpmp2mi_evidence_opts {
+  int hit, miss;        /* added to a cell where a ray ends / subtracted where rays pass; >= 0 (and <= 65535) */
+  int lo, hi;           /* E is clamped to [lo, hi]; -32768 <= lo <= 0 <= hi <= 32767 */
+  int occupied_at;      /* a cell is an obstacle iff E >= occupied_at; lo < occupied_at <= hi */
+  int use_base;         /* unite with the handle's base (as gpmp2mi_sdf_update_from_points) */
+  int refresh;          /* 1: rebuild the field after the evidence; 0: evidence only, field untouched */
+} gpmp2mi_evidence_opts;
+/* hit 2, miss 1, lo -4, hi 8, occupied_at 1, use_base 0, refresh 1 */
+void gpmp2mi_evidence_opts_default(gpmp2mi_evidence_opts* opts);
+
+typedef struct gpmp2mi_depth_camera {
+  int width, height;
+  double fx, fy, cx, cy;
+  double depth_min, depth_max;     /* metres along the optical axis; 0 <= depth_min < depth_max, finite */
+  double pose[12];                 /* camera -> world, row-major 3 x 4 [R | t] */
+} gpmp2mi_depth_camera;
+
+int gpmp2mi_sdf_reserve_evidence(gpmp2mi_sdf* s);
+/* rays from sensor_origin [dim] (host) to points [M][dim]; dim 2 or 3 as the handle.  conf [D] of `robot`; stats [6] or
+ * NULL.  _dev: points, conf and stats are device pointers. */
+int gpmp2mi_sdf_integrate_points(gpmp2mi_sdf* s, int M, const double* points /*[M][dim]*/,
+                                 const double* sensor_origin /*[dim]*/, const gpmp2mi_robot* robot /*NULL: no filter*/,
+                                 const double* conf /*[D]*/, double margin, const gpmp2mi_evidence_opts* opts,
+                                 int* stats /*[6] or NULL*/);
+int gpmp2mi_sdf_integrate_points_dev(gpmp2mi_sdf* s, int M, const double* points, const double* sensor_origin,
+                                     const gpmp2mi_robot* robot, const double* conf, double margin,
+                                     const gpmp2mi_evidence_opts* opts, int* stats, void* stream);
+/* depth [height][width] float32, metres along the optical axis; the handle must be 3-D.  _dev: depth, conf and stats are
+ * device pointers. */
+int gpmp2mi_sdf_integrate_depth(gpmp2mi_sdf* s, const gpmp2mi_depth_camera* cam, const float* depth,
+                                const gpmp2mi_robot* robot /*NULL: no filter*/, const double* conf /*[D]*/, double margin,
+                                const gpmp2mi_evidence_opts* opts, int* stats /*[6] or NULL*/);
+int gpmp2mi_sdf_integrate_depth_dev(gpmp2mi_sdf* s, const gpmp2mi_depth_camera* cam, const float* depth,
+                                    const gpmp2mi_robot* robot, const double* conf, double margin,
+                                    const gpmp2mi_evidence_opts* opts, int* stats, void* stream);
+/* the rebuild alone: O = {E >= occupied_at}, united with the base if use_base */
+int gpmp2mi_sdf_refresh_from_evidence(gpmp2mi_sdf* s, int occupied_at, int use_base);
+int gpmp2mi_sdf_refresh_from_evidence_dev(gpmp2mi_sdf* s, int occupied_at, int use_base, void* stream);
+/* E = 0 everywhere; the field is left as it is */
+int gpmp2mi_sdf_evidence_reset(gpmp2mi_sdf* s);
+int gpmp2mi_sdf_evidence_reset_dev(gpmp2mi_sdf* s, void* stream);
+/* E to a host array (all 0 for a handle that never took a call of this section); waits for the default stream */
+int gpmp2mi_sdf_get_evidence(const gpmp2mi_sdf* s, int16_t* E /*[nz][ny][nx]*/);
 
 /* ---- distinct alternatives: how many different solutions the restarts found, one row per mode, on the device ------
  * The calls of "scoring" answer with one row.  These calls say how many different trajectories a batch holds and hand

@@ -59,6 +59,10 @@ int gpmp2mi_debug_sampled_chunk_bytes(size_t bytes);
  * of its stages in ms: {seed (and mark), the three axis passes, finish, pack}.  Then on = 1 makes the updates that follow
  * record an event between their stages; on = 0 stops that. */
 int gpmp2mi_debug_sdf_update_timing(gpmp2mi_sdf* s, int on, double* ms4 /*[4] or NULL*/);
+/* Diagnostic (scripts/sensor_throughput.py): the same for the integrate calls of "sensor map" with opts->refresh set.
+ * ms6 = {deproject and classify, walk, apply and seed, the three axis passes, finish, pack}.  It switches the timer of
+ * gpmp2mi_debug_sdf_update_timing with it: the last four stages are recorded by the same events. */
+int gpmp2mi_debug_sdf_integrate_timing(gpmp2mi_sdf* s, int on, double* ms6 /*[6] or NULL*/);
 
 /* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
 int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);

@@ -225,6 +225,50 @@ inline MapUpdateStats UpdateFieldFromPoints(gpmp2mi_sdf* h, std::size_t dim, con
 }
 }  // namespace internal
 
+/// counts of an integrate call (include/gpmp2mi.h "sensor map"): the five classes sum to the number of rays; `occupied`
+/// is the number of cells whose evidence reaches occupied_at afterwards
+struct EvidenceStats {
+  int hit = 0, invalid = 0, max_range = 0, self = 0, outside = 0, occupied = 0;
+};
+/// gpmp2mi_evidence_opts with its defaults: hit 2, miss 1, lo -4, hi 8, occupied_at 1, use_base 0, refresh 1
+struct EvidenceOptions : gpmp2mi_evidence_opts {
+  EvidenceOptions() { gpmp2mi_evidence_opts_default(this); }
+};
+/// camera -> world pose, intrinsics and depth range of a depth image
+using DepthCamera = gpmp2mi_depth_camera;
+
+namespace internal {
+inline EvidenceStats EvidenceStatsOf(const int (&st)[6]) {
+  EvidenceStats s;
+  s.hit = st[0];
+  s.invalid = st[1];
+  s.max_range = st[2];
+  s.self = st[3];
+  s.outside = st[4];
+  s.occupied = st[5];
+  return s;
+}
+/// gpmp2mi_sdf_integrate_points for the two field classes: points row-major [M][dim], sensor_origin [dim]
+inline EvidenceStats IntegratePoints(gpmp2mi_sdf* h, std::size_t dim, const Vector& points, const Vector& sensor_origin,
+                                     const gpmp2mi_evidence_opts& opts, const gpmp2mi_robot* robot, const Vector* conf,
+                                     double margin) {
+  if (points.size() % dim != 0) throw std::runtime_error("[integratePoints] points are not [M][dim]");
+  if (sensor_origin.size() != dim) throw std::runtime_error("[integratePoints] sensor_origin is not [dim]");
+  if (robot && (!conf || conf->size() != static_cast<std::size_t>(gpmp2mi_robot_dof(robot))))
+    throw std::runtime_error("[integratePoints] conf does not fit the robot's dof");
+  int st[6] = {0, 0, 0, 0, 0, 0};
+  check(gpmp2mi_sdf_integrate_points(h, static_cast<int>(points.size() / dim), points.data(), sensor_origin.data(), robot,
+                                     robot ? conf->data() : nullptr, margin, &opts, st),
+        "gpmp2mi_sdf_integrate_points");
+  return EvidenceStatsOf(st);
+}
+inline std::vector<int16_t> Evidence(const gpmp2mi_sdf* h, std::size_t cells) {
+  std::vector<int16_t> e(cells);
+  check(gpmp2mi_sdf_get_evidence(h, e.data()), "gpmp2mi_sdf_get_evidence");
+  return e;
+}
+}  // namespace internal
+
 /// 3-D signed distance field; data in the reference's own storage order: z slices of column-major
 /// (row = y, col = x) matrices, i.e. voxels[(z * cols + x) * rows + y]
 class SignedDistanceField {
@@ -266,8 +310,50 @@ class SignedDistanceField {
                                   double margin = 0.0) {
     return internal::UpdateFieldFromPoints(h_, 3, points, use_base, robot.handle(), &conf, margin);
   }
+  /// Sensor map: one frame of rays from sensor_origin [3] to points (row-major [M][3]) into the evidence kept on this
+  /// field -- +hit where a ray ends, -miss where rays pass -- and, with opts.refresh, the field again from the cells
+  /// whose evidence reaches opts.occupied_at.  Optimizers already made on this field see the new map in their next call.
+  EvidenceStats integratePoints(const Vector& points, const Vector& sensor_origin,
+                                const EvidenceOptions& opts = EvidenceOptions()) {
+    return internal::IntegratePoints(h_, 3, points, sensor_origin, opts, nullptr, nullptr, 0.0);
+  }
+  /// ... rays that end inside the body spheres of `robot` at `conf`, grown by `margin`, carve and do not mark
+  template <class ROBOT>
+  EvidenceStats integratePoints(const Vector& points, const Vector& sensor_origin, const EvidenceOptions& opts,
+                                const ROBOT& robot, const Vector& conf, double margin = 0.0) {
+    return internal::IntegratePoints(h_, 3, points, sensor_origin, opts, robot.handle(), &conf, margin);
+  }
+  /// Sensor map: one depth image, row-major [height][width] float metres along the optical axis
+  EvidenceStats integrateDepth(const DepthCamera& cam, const std::vector<float>& depth,
+                               const EvidenceOptions& opts = EvidenceOptions()) {
+    return integrateDepthImpl(cam, depth, opts, nullptr, nullptr, 0.0);
+  }
+  template <class ROBOT>
+  EvidenceStats integrateDepth(const DepthCamera& cam, const std::vector<float>& depth, const EvidenceOptions& opts,
+                               const ROBOT& robot, const Vector& conf, double margin = 0.0) {
+    if (conf.size() != static_cast<std::size_t>(gpmp2mi_robot_dof(robot.handle())))
+      throw std::runtime_error("[integrateDepth] conf does not fit the robot's dof");
+    return integrateDepthImpl(cam, depth, opts, robot.handle(), conf.data(), margin);
+  }
+  /// the field again from the evidence as it stands
+  void refreshFromEvidence(int occupied_at = 1, bool use_base = false) {
+    check(gpmp2mi_sdf_refresh_from_evidence(h_, occupied_at, use_base ? 1 : 0), "gpmp2mi_sdf_refresh_from_evidence");
+  }
+  /// the evidence, [z][y][x]
+  std::vector<int16_t> evidence() const { return internal::Evidence(h_, cells_); }
+  void resetEvidence() { check(gpmp2mi_sdf_evidence_reset(h_), "gpmp2mi_sdf_evidence_reset"); }
 
  private:
+  EvidenceStats integrateDepthImpl(const DepthCamera& cam, const std::vector<float>& depth, const EvidenceOptions& opts,
+                                   const gpmp2mi_robot* robot, const double* conf, double margin) {
+    if (cam.width < 0 || cam.height < 0 ||
+        depth.size() != static_cast<std::size_t>(cam.width) * static_cast<std::size_t>(cam.height))
+      throw std::runtime_error("[integrateDepth] depth is not [height][width]");
+    int st[6] = {0, 0, 0, 0, 0, 0};
+    check(gpmp2mi_sdf_integrate_depth(h_, &cam, depth.data(), robot, conf, margin, &opts, st),
+          "gpmp2mi_sdf_integrate_depth");
+    return internal::EvidenceStatsOf(st);
+  }
   gpmp2mi_sdf* h_ = nullptr;
   std::size_t cells_ = 0;
 };
@@ -304,6 +390,22 @@ class PlanarSDF {
                                   double margin = 0.0) {
     return internal::UpdateFieldFromPoints(h_, 2, points, use_base, robot.handle(), &conf, margin);
   }
+  /// Sensor map, as SignedDistanceField: points row-major [M][2], sensor_origin [2]
+  EvidenceStats integratePoints(const Vector& points, const Vector& sensor_origin,
+                                const EvidenceOptions& opts = EvidenceOptions()) {
+    return internal::IntegratePoints(h_, 2, points, sensor_origin, opts, nullptr, nullptr, 0.0);
+  }
+  template <class ROBOT>
+  EvidenceStats integratePoints(const Vector& points, const Vector& sensor_origin, const EvidenceOptions& opts,
+                                const ROBOT& robot, const Vector& conf, double margin = 0.0) {
+    return internal::IntegratePoints(h_, 2, points, sensor_origin, opts, robot.handle(), &conf, margin);
+  }
+  void refreshFromEvidence(int occupied_at = 1, bool use_base = false) {
+    check(gpmp2mi_sdf_refresh_from_evidence(h_, occupied_at, use_base ? 1 : 0), "gpmp2mi_sdf_refresh_from_evidence");
+  }
+  /// the evidence, [y][x]
+  std::vector<int16_t> evidence() const { return internal::Evidence(h_, cells_); }
+  void resetEvidence() { check(gpmp2mi_sdf_evidence_reset(h_), "gpmp2mi_sdf_evidence_reset"); }
 
  private:
   gpmp2mi_sdf* h_ = nullptr;
