@@ -66,6 +66,7 @@ class GraphOpts(C.Structure):
                 ("workspace", WorkspaceFactor * MAX_WORKSPACE_FACTORS),
                 ("n_self_collision", C.c_int), ("self_collision_first", C.c_int), ("self_collision_last", C.c_int),
                 ("self_collision", (C.c_double * 4) * MAX_SELF_COLLISION_PAIRS),
+                ("workspace_path", C.c_int), ("workspace_path_mode", C.c_int), ("workspace_path_link", C.c_int),
                 ("max_moving_spheres", C.c_int), ("moving_first", C.c_int), ("moving_last", C.c_int),
                 ("moving_epsilon", C.c_double), ("moving_sigma", C.c_double)]
 
@@ -273,6 +274,26 @@ def declare_sensor(lib):
         getattr(lib, name).restype = i
     lib.gpmp2mi_evidence_opts_default.argtypes = [op]
     lib.gpmp2mi_evidence_opts_default.restype = None
+
+
+def declare_path(lib):
+    """argtypes of the workspace-path entry points (include/gpmp2mi.h "workspace path"); the `_dev` forms take device
+    addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_plan_set_workspace_path": [vp, d, d],
+        "gpmp2mi_plan_set_workspace_path_dev": [vp, vp, vp, vp],
+        "gpmp2mi_workspace_path_factor": [vp, i, i, i, d, d, d, d],
+        "gpmp2mi_path_score_traj": [vp, i, i, d, d, f, i, i, i, d, d, d, ip, d, d, ip],
+        "gpmp2mi_path_score_traj_dev": [vp, i, i, vp, vp, f, i, i, i] + [vp] * 8,
+        "gpmp2mi_plan_path_score": [vp, i, d, d, ip, d, d, ip],
+        "gpmp2mi_plan_path_score_dev": [vp, i] + [vp] * 7,
+        "gpmp2mi_plan_select_path": [vp, i, f, i, f, f, ip, ip, d, d],
+        "gpmp2mi_plan_select_path_dev": [vp, i, f, i, f, f] + [vp] * 5,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
 
 
 def declare_group(lib):
@@ -525,4 +546,9 @@ def make_settings(setting):
         rng_ = mv.get("states") or (0, setting.total_step)
         o.moving_first, o.moving_last = int(rng_[0]), int(rng_[1])
         o.moving_epsilon, o.moving_sigma = float(mv["epsilon"]), float(mv["sigma"])
+    wp = getattr(setting, "workspace_path", None)
+    if wp is not None:
+        if int(wp["mode"]) not in (WORKSPACE_POSITION, WORKSPACE_ORIENTATION, WORKSPACE_POSE):
+            raise ValueError("workspace path: unknown mode")
+        o.workspace_path, o.workspace_path_mode, o.workspace_path_link = 1, int(wp["mode"]), int(wp["link"])
     return s, o, keep

@@ -127,7 +127,11 @@ struct gpmp2mi_robot {
   // the records of gpmp2mi_moving_score_traj(_dev) calls on this handle (moving.hip), under the same guard and rule
   mutable void* moving_ws = nullptr;
   mutable size_t moving_ws_bytes = 0;
+  // the records of gpmp2mi_path_score_traj(_dev) calls on this handle (path.hip), under the same guard and rule
+  mutable void* path_ws = nullptr;
+  mutable size_t path_ws_bytes = 0;
   ~gpmp2mi_robot() {
+    if (path_ws) (void)hipFree(path_ws);
     if (d) (void)hipFree(d);
     if (score_ws) (void)hipFree(score_ws);
     if (motion_ws) (void)hipFree(motion_ws);
@@ -372,6 +376,11 @@ struct gpmp2mi_plan {
   // select_moving call and kept.  (The sphere set itself is part of `ex`, taken at creation.)
   void* moving_ws = nullptr;
   size_t moving_ws_bytes = 0;
+  // workspace path (path.hip): the records of k_path_deviation, the per-row scores of the obstacle stage that
+  // select_path's rule reads and the staging of the host-pointer forms, taken at the first path_score / select_path
+  // call and kept.  (The path itself is part of `ex`, taken at creation.)
+  void* path_ws = nullptr;
+  size_t path_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }

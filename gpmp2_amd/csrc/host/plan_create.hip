@@ -6,6 +6,7 @@
 
 #include "host.h"
 #include "../cr_schedule.h"
+#include "../dispatch.h"
 
 namespace g2 {
 // Host-mapped pass-flag arrays are recycled across plans: pinning and unpinning host memory costs more than the
@@ -100,6 +101,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (group_ws) (void)hipFree(group_ws);
   if (motion_ws) (void)hipFree(motion_ws);
   if (moving_ws) (void)hipFree(moving_ws);
+  if (path_ws) (void)hipFree(path_ws);
   sampled_fac.release();
   flags_release(qflags);
 }
@@ -329,6 +331,17 @@ static int check_extras(const RobotDev& h, const gpmp2mi_graph_opts& o, int N, P
   // the robot's radii in the caller's sphere order: read by the self-collision rows and the moving-sphere factor
   if (ex.n_sc > 0 || ex.mv_cap > 0)
     for (int sidx = 0; sidx < h.nr_spheres; sidx++) hx.radius[h.sph_orig[sidx]] = h.sph_r[sidx];
+  G2_CHECK(o.workspace_path == 0 || o.workspace_path == 1, GPMP2MI_ERR_INVALID, "workspace_path must be 0 or 1");
+  if (o.workspace_path) {
+    G2_CHECK(o.workspace_path_mode >= GPMP2MI_WORKSPACE_POSITION && o.workspace_path_mode <= GPMP2MI_WORKSPACE_POSE,
+             GPMP2MI_ERR_INVALID, "workspace path: unknown mode");
+    G2_CHECK(o.workspace_path_link >= 0 && o.workspace_path_link < h.nr_links, GPMP2MI_ERR_INVALID,
+             "workspace path: link out of range");
+    G2_DISPATCH_ROBOT_H(h, (void)0);   // a (kind, dof) the chain kernels are not instantiated for: GPMP2MI_ERR_UNSUPPORTED
+    ex.wp_cap = 1;
+    ex.wp_mode = o.workspace_path_mode;
+    ex.wp_link = o.workspace_path_link;
+  }
   return GPMP2MI_OK;
 }
 
@@ -399,6 +412,12 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
     }
     G2_TRY(plan_alloc(p, &ex.mv_radius, (size_t)ex.mv_cap));
     G2_TRY(plan_alloc(p, &ex.mv_centers, (size_t)ex.mv_cap * (P.N + 1) * 3));
+  }
+  if (ex.wp_cap > 0) {   // the path and the list of its constrained states; no poses, Jacobians or rows
+    G2_TRY(plan_alloc(p, &ex.wp_des, (size_t)(P.N + 1) * 16));
+    G2_TRY(plan_alloc(p, &ex.wp_sigma, (size_t)P.N + 1));
+    G2_TRY(plan_alloc(p, &ex.wp_list, (size_t)P.N + 1));
+    G2_TRY(plan_alloc(p, &ex.wp_count, 1));
   }
   G2_TRY(plan_alloc(p, &pb.n_active, p->n_active_len));
   G2_TRY(plan_alloc(p, &pb.stamps, (size_t)B * 128));   // rows 0..B-1: kernel phases, rows B..2B-1: one CR task per level
@@ -485,7 +504,7 @@ int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf
   if (s->Qc) std::copy(s->Qc, s->Qc + (size_t)D * D, p->Qc.begin());
   ExtrasHost hx;
   G2_TRY(check_extras(robot->h, o, p->hp.N, p->ex, hx));
-  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0;
+  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0 || p->ex.wp_cap > 0;
   p->h_xp_n.assign(B, 0);
   p->goal_removed.assign(B, 0);
   G2_TRY(alloc_buffers(p.get(), hx));

@@ -10,7 +10,8 @@ using namespace g2;
 // linearize `traj` into record buffer `bufsel` of every (active) trajectory: the fused obstacle / GP-prior kernel,
 // then -- only for plans that carry extra factors -- the workspace / self-collision factor kernels on the support
 // states and their accumulation into the unary records, and the moving-sphere factor of a non-empty resident set
-// (moving_kernels.hip), which adds its terms to the same records without storing rows
+// (moving_kernels.hip) and the workspace-path factor of a resident path (path_kernels.hip), which add their terms to
+// the same records without storing rows
 // dst / pass: fused finish (launch_linearize); the extra-factor kernels then run on the NEW states in dst
 int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st, double* dst,
                        int pass, bool trial) {
@@ -33,7 +34,9 @@ int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const in
     G2_TRY(launch_self_collision(ex.n_sc, S, D, M, ex.sc_data, ex.radius, ex.cen, ex.Jc, ex.sc_err, ex.sc_H, st));
   // the two accumulations follow each other on the stream: they never touch a record concurrently
   if (ex.n_ws > 0 || ex.n_sc > 0) G2_TRY(launch_extra_accumulate(P, p->pb, ex, L, S, bufsel, active, st));
-  return launch_moving_accumulate(P, p->pb, ex, S, bufsel, active, st);   // nothing for an empty set
+  G2_TRY(launch_moving_accumulate(P, p->pb, ex, S, bufsel, active, st));   // nothing for an empty set
+  // the workspace path (path_kernels.hip): nothing without a constrained state
+  return launch_path_accumulate(h, p->robot->d, P, p->pb, ex, traj, bufsel, active, st);
 }
 
 // Active-trajectory count of a finished pass.  The closing kernel of every pass publishes it to a pinned,

@@ -224,8 +224,39 @@ int launch_moving_clearance(const RobotDev& h, const RobotDev* R, int K, const d
                             hipStream_t st);
 int launch_moving_finish(const MovingFinish& a, hipStream_t st);
 
+// path_kernels.hip (include/gpmp2mi.h "workspace path"; the in-plan factor's launcher is in plan.h)
+// the factor on M evaluations, one target per evaluation: conf [M][D], des [M][16] -> err [M][rows], H [M][rows][D] or
+// null (rows = 6 for the POSE mode, else 3)
+int launch_path_factor(const RobotDev& h, const RobotDev* R, int mode, int link, int M, const double* conf,
+                       const double* des, double* err, double* H, hipStream_t st);
+// sigma [N+1] -> the states with a finite sigma, ascending, and their count
+int launch_path_list(int N, const double* sigma, int* list, int* count, hipStream_t st);
+// what one workgroup of k_path_deviation (64 checked states) leaves for k_path_finish; kp / kr = INT_MAX: no state of
+// the tile was checked for that deviation
+struct PathRec {
+  double support, dense, pos, rot;
+  int kp, kr, inv, pad;
+};
+// arguments of k_path_finish; every output may be null.  `sel` carries the selection (sel.select) and the shape of the
+// trajectories; the rule reads the per-row scores the obstacle stage left, as MovingFinish does.
+struct PathFinish {
+  ScoreFinish sel;
+  const PathRec* recs;   // [B][nblk]
+  int nblk;
+  double *max_pos, *max_rot, *support, *dense;
+  int *worst, *invalid;   // [B][2], [B]
+  const double* clearance;
+  const int* oor;
+  double allowed_pos, allowed_rot;
+};
+int path_blocks(int Md);   // records per row
+// des [N+1][16], sigma [N+1]
+int launch_path_deviation(const RobotDev& h, const RobotDev* R, int mode, int link, const double* des, const double* sigma,
+                          double dt, int inter, int B, int N, const double* traj, PathRec* recs, hipStream_t st);
+int launch_path_finish(const PathFinish& a, hipStream_t st);
+
 // group_kernels.hip (include/gpmp2mi.h "distinct alternatives")
-constexpr int GROUP_TILE = 64;          // k_traj_pairs: one workgroup per 64 x 64 tile of pairs
+constexpr int GROUP_TILE = 64;         // k_traj_pairs: one workgroup per 64 x 64 tile of pairs
 constexpr int GROUP_CHUNK_ELEMS = 32;   // configuration doubles of a row staged through LDS at a time
 // support states per LDS chunk: whole states only, so that s_i closes inside a chunk
 constexpr int group_chunk_states(int D) { return D >= GROUP_CHUNK_ELEMS ? 1 : GROUP_CHUNK_ELEMS / D; }

@@ -1,5 +1,6 @@
 // lie_log.h -- the SO(3) / SE(3) log maps and their derivatives, one copy for the workspace priors (k_workspace_prior,
-// factor_kernels.hip) and the inverse kinematics built on them (k_ik, ik_kernels.hip).
+// factor_kernels.hip), the inverse kinematics built on them (k_ik, ik_kernels.hip) and the workspace path
+// (path_kernels.hip), whose check also needs the SO(3) exponential.
 #pragma once
 #include "device_math.h"
 
@@ -52,6 +53,20 @@ __device__ __forceinline__ void rot3_logmap_derivative(const double* w, double* 
   mat3_mul(W, W, WW);
   const double k = 1.0 / (theta * theta) - (1.0 + cos(theta)) / (2.0 * theta * sin(theta));
   for (int i = 0; i < 9; i++) H[i] += 0.5 * W[i] + k * WW[i];
+}
+// SO3::Expmap by Rodrigues' formula, R row-major; theta^2 at or below the threshold of rot3_logmap_derivative takes
+// the first-order branch I + [w]x.  Used by the workspace-path check (path_kernels.hip) between two targets.
+__device__ __forceinline__ void rot3_expmap(const double* w, double* R) {
+  const double theta2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double W[9];
+  skew3(w, W);
+  for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + W[i];
+  if (theta2 <= 2.220446049250313e-16) return;
+  const double theta = sqrt(theta2);
+  double WW[9];
+  mat3_mul(W, W, WW);
+  const double a = sin(theta) / theta, b = (1.0 - cos(theta)) / theta2;
+  for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + (a * W[i] + b * WW[i]);
 }
 __device__ __forceinline__ void pose3_logmap(const double* R, const double* T, double* xi) {
   double w[3];

@@ -73,6 +73,15 @@ struct PlanExtras {
   double mv_eps, mv_w;   // epsilon, 1 / sigma^2
   double* mv_radius;     // [mv_cap]
   double* mv_centers;    // [mv_cap][N+1][3], the first mv_K spheres in use
+  // workspace path (include/gpmp2mi.h "workspace path"): the capacity, the factor's constants and the resident path.
+  // wp_n is a host value: the entries of wp_list a launch looks at, one wavefront each per trajectory -- the number of
+  // constrained states after the host setter, N + 1 after the _dev setter (the count is then known to the device
+  // only), 0 for no path (path_kernels.hip)
+  int wp_cap, wp_mode, wp_link, wp_n;
+  double* wp_des;        // [N+1][16]
+  double* wp_sigma;      // [N+1], +inf: the state carries no factor
+  int* wp_list;          // [N+1] the constrained states, ascending
+  int* wp_count;         // [1] how many
 };
 
 // Per-plan device buffers.
@@ -191,6 +200,10 @@ int launch_extra_accumulate(const PlanParams& hp, const PlanBuffers& pb, const P
 // set (ex.mv_K > 0), straight into the unary records
 int launch_moving_accumulate(const PlanParams& hp, const PlanBuffers& pb, const PlanExtras& ex, int S, int bufsel,
                              const int* active, hipStream_t st);
+// path_kernels.hip: the workspace-path factor of the constrained states of the resident path (ex.wp_n > 0), from the
+// states in `traj` straight into the unary records
+int launch_path_accumulate(const RobotDev& h, const RobotDev* R, const PlanParams& hp, const PlanBuffers& pb,
+                           const PlanExtras& ex, const double* traj, int bufsel, const int* active, hipStream_t st);
 int launch_set_mode(const PlanBuffers& pb, int opt_type, int fixed_iters, hipStream_t st);
 int launch_error_parts(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel, const int* active,
                        hipStream_t st);

@@ -45,6 +45,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_self(lib)
     _capi.declare_motion(lib)
     _capi.declare_moving(lib)
+    _capi.declare_path(lib)
     _capi.declare_map(lib)
     _capi.declare_sensor(lib)
     _capi.declare_group(lib)
@@ -123,6 +124,11 @@ def _self_ptrs(o):
 def _moving_ptrs(o):
     return (dptr(o["moving_support_cost"]), dptr(o["moving_dense_cost"]), dptr(o["min_moving_clearance"]),
             iptr(o["worst"]), iptr(o["invalid"]))
+
+
+def _path_ptrs(o):
+    return (dptr(o["max_pos_dev"]), dptr(o["max_rot_dev"]), iptr(o["worst"]), dptr(o["support_cost"]),
+            dptr(o["dense_cost"]), iptr(o["invalid"]))
 
 
 def _motion_ptrs(o):
@@ -680,6 +686,33 @@ class Engine:
         o = scoring.score_outputs(B, out, scoring.MOVING_NAMES)
         self._ck(self.lib.gpmp2mi_moving_score_traj(robot.ptr, K, dptr(r), dptr(c), float(epsilon), float(delta_t),
                                                     inter_step, B, N, dptr(t), *_moving_ptrs(o)))
+        return o
+
+    # ---------------------------------------------------------------- workspace path (include/gpmp2mi.h)
+    def workspace_path_factor(self, robot, mode, link, conf, des, jac=True):
+        """The workspace-path factor with one target per evaluation (include/gpmp2mi.h "workspace path"): conf [M][D],
+        des [M][4][4] -> err [M][rows], H [M][rows][D] (rows = 6 for mode 2, else 3)"""
+        q = f64(conf).reshape(-1, robot.dof)
+        M, rows = q.shape[0], 6 if int(mode) == 2 else 3
+        d = f64(des).reshape(M, 16)
+        err, H = np.zeros((M, rows)), (np.zeros((M, rows, robot.dof)) if jac else None)
+        self._ck(self.lib.gpmp2mi_workspace_path_factor(robot.ptr, int(mode), int(link), M, dptr(q), dptr(d), dptr(err),
+                                                        dptr(H)))
+        return err, H
+
+    def path_score_traj(self, robot, mode, link, des, sigma, delta_t, inter_step, traj, out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) against the path des [N+1][4][4], sigma [N+1] (or a scalar) -> dict(
+        max_pos_dev [B], max_rot_dev [B], worst [B][2], support_cost [B], dense_cost [B], invalid [B]) of the
+        inter_step-up-sampled trajectories."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        d, s = scoring.path_arrays(des, sigma, N + 1)
+        o = scoring.path_outputs(B, out)
+        self._ck(self.lib.gpmp2mi_path_score_traj(robot.ptr, int(mode), int(link), dptr(d), dptr(s), float(delta_t),
+                                                  inter_step, B, N, dptr(t), *_path_ptrs(o)))
         return o
 
     # ---------------------------------------------------------------- distinct alternatives (include/gpmp2mi.h)
@@ -1558,6 +1591,68 @@ class Plan:
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
             None if pairs is None else pairs.ptr, float(required_self_clearance), float(required_moving_clearance),
             *args, C.c_void_p(stream or 0)))
+
+    # ---- one target pose per support state (include/gpmp2mi.h "workspace path")
+    def set_workspace_path(self, des, sigma=None):
+        """The plan's path: des [N+1][4][4], sigma [N+1] (or a scalar; +inf: the state carries no factor); des None
+        clears it.  May be repeated between solves; the plan must have been created with room for a path
+        (TrajOptimizerSetting.set_workspace_path)."""
+        if des is None:
+            self.eng._ck(self.eng.lib.gpmp2mi_plan_set_workspace_path(self.h.ptr, None, None))
+            return
+        d, s = scoring.path_arrays(des, sigma, self.N + 1)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_workspace_path(self.h.ptr, dptr(d), dptr(s)))
+
+    def set_workspace_path_dev(self, des, sigma, stream=None):
+        """The same from device buffers (torch tensors or raw pointers); the copies are enqueued on `stream`."""
+        args = [_dev_arg("des", des, (self.N + 1, 4, 4)), _dev_arg("sigma", sigma, (self.N + 1,))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_workspace_path_dev(self.h.ptr, *args, C.c_void_p(stream or 0)))
+
+    def path_score(self, inter_step, out=None):
+        """dict(max_pos_dev, max_rot_dev, worst [B][2], support_cost, dense_cost, invalid) of the plan's result against
+        its resident path, B rows."""
+        inter_step = _score_args(inter_step)
+        o = scoring.path_outputs(self.B, out)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_path_score(self.h.ptr, inter_step, *_path_ptrs(o)))
+        return o
+
+    def path_score_dev(self, inter_step, max_pos_dev=None, max_rot_dev=None, worst=None, support_cost=None,
+                       dense_cost=None, invalid=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        B = self.B
+        args = [_dev_arg("max_pos_dev", max_pos_dev, (B,)), _dev_arg("max_rot_dev", max_rot_dev, (B,)),
+                _dev_arg("worst", worst, (B, 2), True), _dev_arg("support_cost", support_cost, (B,)),
+                _dev_arg("dense_cost", dense_cost, (B,)), _dev_arg("invalid", invalid, (B,), True)]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_path_score_dev(self.h.ptr, _score_args(inter_step), *args,
+                                                              C.c_void_p(stream or 0)))
+
+    def select_path(self, inter_step, max_pos_dev_allowed=np.inf, max_rot_dev_allowed=np.inf, required_clearance=0.0,
+                    require_in_range=False):
+        """select() with the rule that also asks for no invalid checked state and deviations from the plan's path
+        within the two allowances: dict(best, n_eligible, traj_best, dense_best); best = -1: the two trajectories
+        are None."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D))
+        best, n = C.c_int(-1), C.c_int(0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_path(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)), float(max_pos_dev_allowed),
+            float(max_rot_dev_allowed), C.byref(best), C.byref(n), dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_path_dev(self, inter_step, max_pos_dev_allowed=np.inf, max_rot_dev_allowed=np.inf, required_clearance=0.0,
+                        require_in_range=False, best=None, n_eligible=None, traj_best=None, dense_best=None, stream=None):
+        """The same with device outputs, as select_dev.  One enqueue on `stream`, no host synchronisation once the
+        plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_path_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)), float(max_pos_dev_allowed),
+            float(max_rot_dev_allowed), *args, C.c_void_p(stream or 0)))
 
     # ---- one representative per mode of the resident result (include/gpmp2mi.h "distinct alternatives")
     def _distinct_args(self, inter_step, radius, weights, metric, max_alt):

@@ -232,6 +232,106 @@ def moving_set(radius, centers, states, capacity=MAX_MOVING_SPHERES):
     return K, r, c
 
 
+# ---- workspace path (include/gpmp2mi.h "workspace path"): the output names, the extended rule, a straight-line path
+PATH_NAMES = ("max_pos_dev", "max_rot_dev", "worst", "support_cost", "dense_cost", "invalid")
+
+
+def path_outputs(B, out=None):
+    """The six per-row outputs of a path score call: fresh arrays, or the caller's (a dict with any of PATH_NAMES),
+    checked for dtype, contiguity and shape."""
+    want = dict(zip(PATH_NAMES, (((B,), np.float64), ((B,), np.float64), ((B, 2), np.int32), ((B,), np.float64),
+                                 ((B,), np.float64), ((B,), np.int32))))
+    res = {}
+    out = out or {}
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"unknown path outputs: {sorted(unknown)}")
+    for name, (shape, dt) in want.items():
+        x = out.get(name)
+        if x is None:
+            x = np.zeros(shape, dtype=dt)
+        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
+            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
+                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
+        res[name] = x
+    return res
+
+
+def path_arrays(des, sigma, states):
+    """A path as contiguous float64 (des [states][4][4], sigma [states]); a scalar sigma is repeated.  ValueError for
+    another shape."""
+    d = np.ascontiguousarray(des, dtype=np.float64)
+    if d.shape == (states, 16):
+        d = d.reshape(states, 4, 4)
+    if d.shape != (states, 4, 4):
+        raise ValueError(f"des: expected [{states}][4][4], got {list(d.shape)}")
+    if sigma is None:
+        raise ValueError("sigma: a path needs one sigma per state (or a scalar)")
+    s =np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (states,)) if np.ndim(sigma) == 0
+                             else sigma, dtype=np.float64)
+    if s.shape != (states,):
+        raise ValueError(f"sigma: expected [{states}], got {list(s.shape)}")
+    return d, s
+
+
+def path_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+              max_pos_dev=None, max_rot_dev=None, path_invalid=None, max_pos_dev_allowed=np.inf,
+              max_rot_dev_allowed=np.inf):
+    """(best, n_eligible) by the rule of select_rule with one more condition: no invalid checked state,
+    max_pos_dev <= max_pos_dev_allowed and max_rot_dev <= max_rot_dev_allowed (each None: not asked)."""
+    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
+    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range)
+    if path_invalid is not None:
+        ok &= np.asarray(path_invalid).reshape(-1) == 0
+    with np.errstate(invalid="ignore"):
+        if max_pos_dev is not None:
+            ok &= np.asarray(max_pos_dev, dtype=np.float64).reshape(-1) <= max_pos_dev_allowed
+        if max_rot_dev is not None:
+            ok &= np.asarray(max_rot_dev, dtype=np.float64).reshape(-1) <= max_rot_dev_allowed
+    rows = np.flatnonzero(ok)
+    if rows.size == 0:
+        return -1, 0
+    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+
+
+def _rot_log(R):
+    """SO(3) logarithm of a rotation matrix, angle in [0, pi)"""
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = np.linalg.norm(v)
+    th = np.arctan2(s, 0.5 * (np.trace(R) - 1.0))
+    return v if s < 1e-12 else v * (th / s)
+
+
+def _rot_exp(w):
+    th = np.linalg.norm(w)
+    W = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th * th <= 2.220446049250313e-16:
+        return np.eye(3) + W
+    return np.eye(3) + (np.sin(th) / th) * W + ((1.0 - np.cos(th)) / (th * th)) * (W @ W)
+
+
+def line_path(pose_a, pose_b, N, s=None):
+    """des [N+1][4][4]: positions on the straight line from pose_a to pose_b, orientations on the geodesic between
+    them, at the N + 1 support states.  The end poses are pose_a and pose_b themselves.  s [N+1]: where on the line
+    each support state is, from s[0] = 0 to s[N] = 1 (default i / N, constant speed; a motion that starts and ends at
+    rest wants an eased profile such as 3 u^2 - 2 u^3 of u = i / N)."""
+    A, Bm = np.asarray(pose_a, dtype=np.float64).reshape(4, 4), np.asarray(pose_b, dtype=np.float64).reshape(4, 4)
+    if int(N) < 1:
+        raise ValueError("N must be >= 1")
+    s = np.arange(int(N) + 1) / float(N) if s is None else np.asarray(s, dtype=np.float64).reshape(-1)
+    if s.shape != (int(N) + 1,) or s[0] != 0.0 or s[-1] != 1.0:
+        raise ValueError(f"s: expected [{int(N) + 1}] from 0 to 1")
+    w = _rot_log(A[:3, :3].T @ Bm[:3, :3])
+    des = np.zeros((int(N) + 1, 4, 4))
+    for i in range(int(N) + 1):
+        tau = s[i]
+        des[i, :3, :3] = A[:3, :3] @ _rot_exp(tau * w)
+        des[i, :3, 3] = A[:3, 3] + tau * (Bm[:3, 3] - A[:3, 3])
+        des[i, 3, 3] = 1.0
+    des[0], des[int(N)] = A, Bm
+    return des
+
+
 # ---- distinct alternatives (include/gpmp2mi.h): the grouping rule in numpy terms and the shape checks of its wrappers
 DIST_MAX_STATE, DIST_RMS = 0, 1
 MAX_GROUP_ROWS = 8192       # GPMP2MI_MAX_GROUP_ROWS

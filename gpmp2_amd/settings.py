@@ -53,6 +53,7 @@ class TrajOptimizerSetting:
         self.self_collision = None           # [n][4] = sphere A, sphere B, epsilon, sigma
         self.self_collision_states = None    # (first, last) support states, default all
         self.moving_spheres = None           # dict(capacity, epsilon, sigma, states): set_moving_spheres
+        self.workspace_path = None           # dict(mode, link): set_workspace_path
 
     def set_moving_spheres(self, capacity, epsilon, sigma, states=None):
         """Room for `capacity` moving spheres in the plan (include/gpmp2mi.h "moving obstacles") and the constants of
@@ -60,6 +61,12 @@ class TrajOptimizerSetting:
         Plan.set_moving_spheres.  capacity 0: none."""
         self.moving_spheres = dict(capacity=int(capacity), epsilon=float(epsilon), sigma=float(sigma),
                                    states=None if states is None else (int(states[0]), int(states[1])))
+
+    def set_workspace_path(self, mode, link):
+        """Room for a workspace path in the plan (include/gpmp2mi.h "workspace path"): one target pose and one sigma
+        per support state for `link`, in `mode` (0 position, 1 orientation, 2 pose, as add_workspace_prior); the path
+        itself is data of Plan.set_workspace_path."""
+        self.workspace_path = dict(mode=int(mode), link=int(link))
 
     # extra factors (names follow the reference's factor classes)
     def add_goal_factor_arm(self, link, dest_point, sigma, state=None):

@@ -230,6 +230,12 @@ typedef struct gpmp2mi_graph_opts {
                                     self_collision_first..last; <= GPMP2MI_MAX_SELF_COLLISION_PAIRS rows */
   int self_collision_first, self_collision_last;
   double self_collision[GPMP2MI_MAX_SELF_COLLISION_PAIRS][4];  /* sphere A, sphere B, epsilon, sigma */
+  /* ---- workspace path ("workspace path" below): room for one target pose and one sigma per support state; the path
+   * itself is data of gpmp2mi_plan_set_workspace_path.  All default to 0 = none.  (They stand ahead of the moving-sphere
+   * block, which stays the struct's tail; fill the struct by field name.) */
+  int workspace_path;            /* 1: reserve the path at plan creation; 0: none */
+  int workspace_path_mode;       /* GPMP2MI_WORKSPACE_POSITION / _ORIENTATION / _POSE */
+  int workspace_path_link;       /* link index of the FK model */
   /* ---- moving spheres ("moving obstacles" below): the capacity and the factor's constants; the spheres themselves are
    * data of gpmp2mi_plan_set_moving_spheres.  Appended at the end of the struct; all default to 0 = none */
   int max_moving_spheres;        /* capacity reserved at plan creation, <= GPMP2MI_MAX_MOVING_SPHERES; 0: none */
@@ -757,6 +763,93 @@ int gpmp2mi_plan_select_moving_dev(gpmp2mi_plan* p, int inter_step, double requi
                                    const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
                                    double required_moving_clearance, int* best, int* n_eligible, double* traj_best,
                                    double* dense_best, void* stream);
+
+/* ---- workspace path: time-indexed end-effector targets as a plan factor and a check, on the device ----------------
+ * The workspace factors of gpmp2mi_graph_opts hold one constant des_pose over a range of states.  A workspace path is
+ * one target pose and one sigma per support state: des [N+1][16] (row-major 4x4) and sigma [N+1], for one link and one
+ * mode, shared by the plan's B trajectories and replaceable between solves.  A plan created with
+ * gpmp2mi_graph_opts::workspace_path = 1 takes the memory of the path at gpmp2mi_plan_create (2 (N+1) words of list,
+ * 17 (N+1) doubles; no link poses, pose Jacobians or rows), carries the factor below on the constrained states and
+ * takes its data from gpmp2mi_plan_set_workspace_path, which may be repeated every control cycle.
+ *
+ * Definitions:
+ *  - State i is constrained if sigma[i] is finite (and > 0); sigma[i] = +inf: the state carries no factor, it is
+ *    skipped and its record is not touched.
+ *  - The factor, at constrained state i: the rows of gpmp2mi_workspace_prior_factor(robot, workspace_path_mode,
+ *    workspace_path_link, des[i], q_i) (GaussianPriorWorkspace{Position,Orientation,Pose}; 3 rows, 6 for the POSE mode),
+ *    isotropic noise sigma[i].  In a plan the rows are never stored: one kernel (one wavefront per trajectory and
+ *    constrained state) adds sum w h h^T, sum w h r and sum w r^2 (w = 1 / sigma_i^2, rows ascending) to the record of
+ *    the state's unary point, after the moving-sphere factor on the same stream.  A state's contribution is a function
+ *    of (D, mode, link) and its own data: the same bits alone, in any batch and on any run; no floating-point atomics.
+ *    Every call that linearizes a plan carries it: optimize, the queue runs, plan_update, plan_linearize,
+ *    plan_graph_error; Gauss-Newton, LM and Dogleg; trial points; narrow, wide and dense blocks.  With no constrained
+ *    state nothing is launched for it.
+ *  - Robot kinds: every kind gpmp2mi_workspace_prior_factor answers for, which is every kind of gpmp2mi_robot_kind in
+ *    the instantiated (kind, dof) table, with its chart (the Pose2 chart for the mobile kinds).  A robot outside the
+ *    table is refused at plan creation with GPMP2MI_ERR_UNSUPPORTED.
+ *  - The check: the checked states of "scoring" (Md = N (J+1) + 1).  At checked state i (J+1) + j, tau = j / (J+1), the
+ *    target position is t_i + tau (t_{i+1} - t_i), evaluated in that form, the target rotation
+ *    R_i Exp(tau Log(R_i^T R_{i+1})) (Log: SO3::Logmap as the factor uses it; Exp: Rodrigues' formula, and for
+ *    theta^2 <= 2.22e-16 the first-order I + [w]x), sigma = sigma_i + tau (sigma_{i+1} - sigma_i); support states use
+ *    des[i] and sigma[i] themselves.  A support state is checked if sigma_i is finite, a sub-step if both ends are.
+ *    pos_dev = |t(q) - t_target|, rot_dev = |Log(R_target^T R(q))| in radians; only the deviations the mode constrains
+ *    are computed, the other output is 0.  r is the factor's residual against the target of the checked state (for the
+ *    POSE mode the Pose3 logarithm, 6 numbers).  Outputs, any of which may be NULL: max_pos_dev [B], max_rot_dev [B]
+ *    (0 if nothing is checked); worst [B][2]: the checked states attaining them, the lowest state on exact ties, -1 if
+ *    nothing is checked (or the mode does not constrain that deviation); support_cost [B] / dense_cost [B]: the sum of
+ *    |r|^2 / sigma^2 over the support / all checked states; invalid [B]: the checked states with a non-finite
+ *    deviation, which enter no sum and no maximum.  Sums are taken in an order fixed by (N, J), without atomics: a row
+ *    scores the same bits alone, in any batch, through the trajectory form or the plan form.
+ *  - Selection: the rule of gpmp2mi_plan_select with one more condition,
+ *      eligible(b) = <that rule> && invalid[b] == 0 && max_pos_dev[b] <= max_pos_dev_allowed
+ *                    && max_rot_dev[b] <= max_rot_dev_allowed;
+ *    ranking and ties unchanged.  With no path and +inf allowances it answers what gpmp2mi_plan_select answers.
+ * Errors: GPMP2MI_ERR_INVALID (checked before any device work) for a NULL plan / robot / traj / conf, a plan created
+ * without workspace_path (the plan forms), an unknown mode or a link out of range (at plan creation and in the
+ * robot-handle forms), a NULL sigma with a path, the argument errors of "scoring"; the plan forms of the check also with
+ * the preconditions of gpmp2mi_plan_score.  GPMP2MI_ERR_TIMEOUT for a poisoned plan.
+ * Memory: the workspace rules of "scoring"; the records (one 48-byte record per 64 checked states) are kept with the
+ * plan, and by gpmp2mi_path_score_traj_dev with the robot handle.
+ * Not here: gpmp2mi_multi_plan_* twins, C++ facade classes, the factor at GP-interpolated sub-steps (the dense check is
+ * what looks between support states), a path per trajectory, anisotropic noise, the path condition combined with the
+ * self / moving / motion selections, any change to the <= 4 workspace factors of gpmp2mi_graph_opts or their kernels. */
+
+/* The plan's path.  Valid at any time between solves; des == NULL clears it; a fresh plan holds none.  Queue runs and
+ * plan_update use the resident path.  Host form: the data is copied before the call returns; refused are a non-finite
+ * pose entry, a rotation block with max |R^T R - I| > 1e-6, a sigma that is <= 0 or NaN and, for the ORIENTATION and
+ * POSE modes, two consecutive constrained targets whose relative angle exceeds pi - 1e-3 (the check's interpolation is
+ * undefined there).  _dev: device pointers, the copies and the list of constrained states are enqueued on `stream`, the
+ * values are not inspected.  A refused call changes nothing. */
+int gpmp2mi_plan_set_workspace_path(gpmp2mi_plan* p, const double* des /*[N+1][16]*/, const double* sigma /*[N+1]*/);
+int gpmp2mi_plan_set_workspace_path_dev(gpmp2mi_plan* p, const double* des, const double* sigma, void* stream);
+/* The factor, batched over M evaluations with one target per evaluation, by the device functions of the plan's kernel
+ * (not by forward kinematics plus gpmp2mi_workspace_prior_factor's kernel): conf [M][D], des [M][16] -> err [M][rows]
+ * (unwhitened), H [M][rows][D] (NULL ok); rows = 6 for GPMP2MI_WORKSPACE_POSE, else 3. */
+int gpmp2mi_workspace_path_factor(const gpmp2mi_robot* r, int mode, int link, int M, const double* conf,
+                                  const double* des, double* err, double* H);
+/* The check for caller buffers; traj [B][total_step+1][2D], des [total_step+1][16], sigma [total_step+1].  The device
+ * of the robot handle must be current. */
+int gpmp2mi_path_score_traj(const gpmp2mi_robot* robot, int mode, int link, const double* des, const double* sigma,
+                            double delta_t, int inter_step, int B, int total_step, const double* traj,
+                            double* max_pos_dev, double* max_rot_dev, int* worst, double* support_cost,
+                            double* dense_cost, int* invalid);
+int gpmp2mi_path_score_traj_dev(const gpmp2mi_robot* robot, int mode, int link, const double* des, const double* sigma,
+                                double delta_t, int inter_step, int B, int total_step, const double* traj,
+                                double* max_pos_dev, double* max_rot_dev, int* worst, double* support_cost,
+                                double* dense_cost, int* invalid, void* stream);
+/* The plan's resident result against the plan's resident path (no path: nothing is checked). */
+int gpmp2mi_plan_path_score(gpmp2mi_plan* p, int inter_step, double* max_pos_dev, double* max_rot_dev, int* worst,
+                            double* support_cost, double* dense_cost, int* invalid);
+int gpmp2mi_plan_path_score_dev(gpmp2mi_plan* p, int inter_step, double* max_pos_dev, double* max_rot_dev, int* worst,
+                                double* support_cost, double* dense_cost, int* invalid, void* stream);
+/* One enqueue: the obstacle score stage, the deviations, then one finish that reads both.  Outputs as
+ * gpmp2mi_plan_select. */
+int gpmp2mi_plan_select_path(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                             double max_pos_dev_allowed, double max_rot_dev_allowed, int* best, int* n_eligible,
+                             double* traj_best, double* dense_best);
+int gpmp2mi_plan_select_path_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                 double max_pos_dev_allowed, double max_rot_dev_allowed, int* best, int* n_eligible,
+                                 double* traj_best, double* dense_best, void* stream);
 
 /* ---- live map: a field handle updated in place from a field, an occupancy grid or a point cloud, on the device ------
  * A plan binds one field handle for life.  These calls rewrite the handle's voxels where they are, so the static map can
