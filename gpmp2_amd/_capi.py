@@ -276,6 +276,42 @@ def declare_sensor(lib):
     lib.gpmp2mi_evidence_opts_default.restype = None
 
 
+SCENE_BOX, SCENE_SPHERE, SCENE_CYLINDER, SCENE_MESH = 0, 1, 2, 3
+MAX_SCENE_OBJECTS = 256
+MAX_SCENE_TRIANGLES = 1 << 20
+
+
+class SceneObject(C.Structure):
+    """gpmp2mi_scene_object (include/gpmp2mi.h "scene")"""
+    _fields_ = [("kind", C.c_int), ("size", C.c_double * 3), ("inflate", C.c_double),
+                ("n_vertices", C.c_int), ("vertices", c_double_p), ("n_triangles", C.c_int), ("triangles", c_int_p),
+                ("pose", C.c_double * 12), ("enabled", C.c_int)]
+
+
+def declare_scene(lib):
+    """argtypes of the scene entry points (include/gpmp2mi.h "scene") and their stage timer; the `_dev` forms take device
+    addresses; objects, poses, enabled flags and the grid origin are host data in every form."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    ob, bp = C.POINTER(SceneObject), C.POINTER(C.c_ubyte)
+    decl = {
+        "gpmp2mi_scene_create": [i, ob, C.POINTER(vp)],
+        "gpmp2mi_scene_count": [vp],
+        "gpmp2mi_scene_set_poses": [vp, i, i, d],
+        "gpmp2mi_scene_set_enabled": [vp, i, i, ip],
+        "gpmp2mi_scene_reserve": [vp, i, i, i],
+        "gpmp2mi_scene_rasterize": [vp, i, d, f, i, i, i, bp, ip],
+        "gpmp2mi_scene_rasterize_dev": [vp, i, d, f, i, i, i, vp, vp, vp],
+        "gpmp2mi_sdf_update_from_scene": [vp, vp, i, i, i, ip],
+        "gpmp2mi_sdf_update_from_scene_dev": [vp, vp, i, i, i, vp, vp],
+        "gpmp2mi_debug_scene_timing": [vp, i, d],
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_scene_destroy.argtypes = [vp]
+    lib.gpmp2mi_scene_destroy.restype = None
+
+
 def declare_path(lib):
     """argtypes of the workspace-path entry points (include/gpmp2mi.h "workspace path"); the `_dev` forms take device
     addresses."""

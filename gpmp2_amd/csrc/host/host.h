@@ -193,6 +193,36 @@ struct gpmp2mi_self_pairs {
   }
 };
 
+// A scene (scene.hip; include/gpmp2mi.h "scene"): the objects on the host as they were given (poses and enabled flags
+// change in place), the meshes' vertices and triangles on the device, and the workspace of a rasterisation.
+struct gpmp2mi_scene {
+  struct Object {
+    int kind = 0, enabled = 0;
+    double s[3] = {0.0, 0.0, 0.0};   // size + inflate of a primitive
+    double pose[12] = {};
+    int V = 0, T = 0;
+    size_t vert_off = 0, tri_off = 0, q_off = 0;   // bytes into `geo` (meshes)
+  };
+  std::vector<Object> obj;
+  int device = -1;
+  char* geo = nullptr;        // every mesh's vertices [V][3] fp64, triangles [T][3] and fixed-point vertices [V][3] int32
+  int* counts = nullptr;      // [K] cells of the call in flight, behind them [K] out-of-range flags
+  // crossing bits of one mesh, [nz][ny][nx rounded up to 32], all 0 between two meshes; taken at the first call for a
+  // grid (or by gpmp2mi_scene_reserve) and grown when a later grid needs more
+  mutable void* bits = nullptr;
+  mutable size_t bits_bytes = 0;
+  // gpmp2mi_debug_scene_timing: events in front of the primitives, between them and the meshes, and behind the meshes
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  bool timing = false;
+  ~gpmp2mi_scene() {
+    if (geo) (void)hipFree(geo);
+    if (counts) (void)hipFree(counts);
+    if (bits) (void)hipFree(bits);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 namespace g2 {
 // geometry + device storage of a field handle; the caller fills s->plain ([nz][ny][nx]) and packs (handles.hip)
 int sdf_alloc(int dim, const double origin[3], double cell, int nx, int ny, int nz, std::unique_ptr<gpmp2mi_sdf>& s);
@@ -215,6 +245,9 @@ int map_ready(gpmp2mi_sdf* s, bool transform);
 void mark_stage(gpmp2mi_sdf* s, int k, hipStream_t st);
 // the two seeded volumes -> plain -> cells on `st`
 int map_transform(gpmp2mi_sdf* s, const MapWs& w, hipStream_t st);
+// sensor.hip, for scene.hip: the two volumes seeded from {E >= occupied_at}, united with the base if use_base, on `st`.
+// E, the marks and the base stay as they are; the handle must have its evidence (s->ev_ws) and its update workspace.
+int evidence_seed(gpmp2mi_sdf* s, int occupied_at, int use_base, hipStream_t st);
 
 struct KernelTimer {
   // One HIP event per kernel boundary on the launch stream: begin(name) is recorded right before kernel `name`,

@@ -119,20 +119,26 @@ void mark_sensor(gpmp2mi_sdf* s, int k, hipStream_t st) {
   if (s->map_timing && s->sensor_ev[0]) (void)hipEventRecord(s->sensor_ev[k], st);
 }
 
-// marks -> evidence, the occupied count, and (refresh) the seeds and the transform
-int apply_and_refresh(gpmp2mi_sdf* s, const EvWs& e, int hit, int miss, int lo, int hi, int occupied_at, int use_base,
-                      bool refresh, hipStream_t st) {
-  const MapWs w = map_ws_layout((char*)s->map_ws, cells_of(s));
+// marks -> evidence, the occupied count, and (seed) the two seeded volumes
+int apply_and_seed(gpmp2mi_sdf* s, const EvWs& e, const MapWs& w, int hit, int miss, int lo, int hi, int occupied_at,
+                   int use_base, bool seed, hipStream_t st) {
   SensorApply a{};
   a.n = cells_of(s);
   a.hit = hit; a.miss = miss; a.lo = lo; a.hi = hi; a.occupied_at = occupied_at;
   a.E = e.E;
   a.miss_marks = e.miss; a.hit_marks = e.hit;
   a.mask = use_base ? w.mask : nullptr;
-  a.wa = refresh ? w.wa : nullptr;
-  a.wb = refresh ? w.wb : nullptr;
+  a.wa = seed ? w.wa : nullptr;
+  a.wb = seed ? w.wb : nullptr;
   a.cnt = e.cnt + 5;
-  G2_TRY(launch_sensor_apply(a, st));
+  return launch_sensor_apply(a, st);
+}
+
+// the same, and (refresh) the transform behind the seeds
+int apply_and_refresh(gpmp2mi_sdf* s, const EvWs& e, int hit, int miss, int lo, int hi, int occupied_at, int use_base,
+                      bool refresh, hipStream_t st) {
+  const MapWs w = map_ws_layout((char*)s->map_ws, cells_of(s));
+  G2_TRY(apply_and_seed(s, e, w, hit, miss, lo, hi, occupied_at, use_base, refresh, st));
   return refresh ? map_transform(s, w, st) : GPMP2MI_OK;
 }
 
@@ -205,6 +211,17 @@ int refresh_from_evidence(gpmp2mi_sdf* s, int occupied_at, int use_base, hipStre
 }
 
 }  // namespace
+
+namespace g2 {
+// for scene.hip: the seeds of {E >= occupied_at} (and the base) without the transform.  No marks are set between two
+// calls, so E stays as it is; only the count of occupied cells (stats entry 5 of a later call is zeroed first) moves.
+int evidence_seed(gpmp2mi_sdf* s, int occupied_at, int use_base, hipStream_t st) {
+  const EvWs e = ev_ws_layout((char*)s->ev_ws, cells_of(s));
+  const MapWs w = map_ws_layout((char*)s->map_ws, cells_of(s));
+  G2_HIP(hipMemsetAsync(e.cnt + 5, 0, sizeof(int), st));
+  return apply_and_seed(s, e, w, 0, 0, -32768, 32767, occupied_at, use_base, true, st);
+}
+}  // namespace g2
 
 extern "C" {
 

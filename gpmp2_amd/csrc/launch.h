@@ -74,6 +74,41 @@ struct SensorApply {
   int* cnt;                           // one word, zeroed by the caller: cells with E' >= occupied_at
 };
 int launch_sensor_apply(const SensorApply& a, hipStream_t st);
+// scene_kernels.hip (include/gpmp2mi.h "scene"): known geometry rasterised into the two seeded volumes or a byte mask.
+// A hit stores (0, EDT_INF) into its cell of wa / wb when `mask` is null, else 1 into its byte of `mask`.
+constexpr int SCENE_BOX = 0, SCENE_SPHERE = 1, SCENE_CYLINDER = 2, SCENE_MESH = 3;
+constexpr int SCENE_PRIM_BATCH = 8;   // primitives of one launch: their records travel as kernel arguments
+struct ScenePrim {
+  int kind, obj;        // obj: the entry of `cells` the hits are counted in
+  int lo[3], n[3];      // the cell box the lanes run over, inside the grid
+  double R[9], t[3];    // object -> world, as given
+  double s[3];          // size + inflate
+};
+struct ScenePrims {
+  SensorGrid g;
+  int count;
+  ScenePrim p[SCENE_PRIM_BATCH];
+  int *wa, *wb;
+  unsigned char* mask;
+  int* cells;           // [K], zeroed by the caller
+};
+int launch_scene_prims(const ScenePrims& a, hipStream_t st);
+// one mesh: k_scene_quantize, k_scene_cross, k_scene_fill on `st`
+struct SceneMesh {
+  SensorGrid g;
+  int obj, V, T;
+  const double* verts;  // [V][3], object frame
+  const int* tris;      // [T][3]
+  int* q;               // [V][3] fixed-point grid coordinates of this call
+  double pose[12];
+  int* flag;            // one word, zeroed by the caller: a vertex is out of range
+  unsigned* bits;       // [nz][ny][W] crossing bits, all 0 between two meshes
+  int W;                // words per row: nx rounded up to 32 bits
+  int *wa, *wb;
+  unsigned char* mask;
+  int* cells;           // [K]
+};
+int launch_scene_mesh(const SceneMesh& a, hipStream_t st);
 // factor_kernels.hip
 int launch_sdf_pack(const SdfDev& s, double* cells, hipStream_t st);
 int launch_sdf_query(const SdfDev& s, int M, const double* pts, double* dist, double* grad, int* inr,

@@ -48,6 +48,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_path(lib)
     _capi.declare_map(lib)
     _capi.declare_sensor(lib)
+    _capi.declare_scene(lib)
     _capi.declare_group(lib)
     _capi.declare_posterior(lib)
     _capi.declare_risk(lib)
@@ -1159,6 +1160,56 @@ class Engine:
         self._ck(self.lib.gpmp2mi_debug_sdf_integrate_timing(sdf.ptr, int(bool(on)), dptr(ms)))
         names = ("deproject", "walk", "apply_seed", "passes", "finish", "pack")
         return None if ms is None else dict(zip(names, (float(x) for x in ms)))
+
+    # ---------------------------------------------------------------- scene (include/gpmp2mi.h "scene")
+    def scene(self, objects):
+        """A scene handle of Box / Sphere / Cylinder / Mesh objects (gpmp2_amd.scene) on the current device."""
+        from . import scene as _scene
+        return _scene.Scene(objects, self)
+
+    def sdf_update_from_scene(self, sdf, scene, use_base=False, use_evidence=False, occupied_at=1):
+        """The handle's field from the scene's enabled objects, united with the base (use_base) and with the cells whose
+        evidence is >= occupied_at (use_evidence), in place.  -> cells [K] int32: the count of each object alone
+        (0 disabled, -1 a mesh out of range)."""
+        cells = np.zeros(scene.K, dtype=np.int32)
+        self._ck(self.lib.gpmp2mi_sdf_update_from_scene(sdf.ptr, scene.ptr, int(bool(use_base)), int(bool(use_evidence)),
+                                                        int(occupied_at), iptr(cells)))
+        return cells
+
+    def sdf_update_from_scene_dev(self, sdf, scene, use_base=False, use_evidence=False, occupied_at=1, cells=None,
+                                  stream=None):
+        """The same enqueued on `stream` without a host synchronisation; cells: a device buffer [K] int32 or None."""
+        self._ck(self.lib.gpmp2mi_sdf_update_from_scene_dev(sdf.ptr, scene.ptr, int(bool(use_base)),
+                                                            int(bool(use_evidence)), int(occupied_at),
+                                                            _dev_arg("cells", cells, (scene.K,), True),
+                                                            C.c_void_p(stream or 0)))
+
+    def scene_rasterize_dev(self, scene, origin, cell_size, shape, mask, cells=None, stream=None):
+        """The scene alone into a device byte mask of `shape` ([nz][ny][nx] or [ny][nx]; a contiguous torch.uint8 cuda
+        tensor or a raw pointer) on `stream`; cells: a device buffer [K] int32 or None."""
+        shape = tuple(int(x) for x in shape)
+        dim = len(shape)
+        origin = f64(origin).reshape(-1)
+        if dim not in (2, 3) or origin.size != dim:
+            raise ValueError(f"a shape of 2 or 3 sizes and an origin of as many numbers, got {shape}, {origin.size}")
+        if hasattr(mask, "data_ptr"):
+            if (str(mask.dtype) != "torch.uint8" or not mask.is_contiguous() or mask.device.type != "cuda"
+                    or tuple(mask.shape) != shape):
+                raise ValueError(f"mask: expected a contiguous torch.uint8 cuda tensor of shape {list(shape)}, got "
+                                 f"{mask.dtype} {list(mask.shape)} on {mask.device}")
+            mask = mask.data_ptr()
+        nz, ny, nx = ((1,) + shape) if dim == 2 else shape
+        org = f64(list(origin) + [0.0] * (3 - dim))
+        self._ck(self.lib.gpmp2mi_scene_rasterize_dev(scene.ptr, dim, dptr(org), float(cell_size), nx, ny, nz,
+                                                      C.c_void_p(int(mask)), _dev_arg("cells", cells, (scene.K,), True),
+                                                      C.c_void_p(stream or 0)))
+
+    def scene_timing(self, scene, on=True, read=False):
+        """Stage timer of the rasterisation (gpmp2mi_debug_scene_timing): read = True returns the device times in ms of
+        the last recorded call as dict(primitives, meshes)."""
+        ms = np.zeros(2) if read else None
+        self._ck(self.lib.gpmp2mi_debug_scene_timing(scene.ptr, int(bool(on)), dptr(ms)))
+        return None if ms is None else dict(zip(("primitives", "meshes"), (float(x) for x in ms)))
 
     # ---------------------------------------------------------------- plans
     def plan(self, robot, sdf, setting, B, forms=None):

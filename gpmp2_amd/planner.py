@@ -82,6 +82,20 @@ class _DeviceSdf:
     def resetEvidence(self):
         _eng().sdf_evidence_reset(self.handle())
 
+    # Scene (include/gpmp2mi.h "scene"): known geometry -- boxes, spheres, cylinders, closed meshes (gpmp2_amd.scene)
+    def update_from_scene(self, scene, use_base=False, use_evidence=False, occupied_at=1):
+        """The field again from the enabled objects of `scene` (a gpmp2_amd.scene.Scene, or a list of objects), united
+        with the base when use_base and with the cells whose evidence is >= occupied_at when use_evidence.  Returns the
+        cells [K] each object occupies alone (0 disabled, -1 a mesh out of range)."""
+        from .scene import Scene
+        if not isinstance(scene, Scene):
+            scene = Scene(scene, _eng())
+        cells = _eng().sdf_update_from_scene(self.handle(), scene, use_base, use_evidence, occupied_at)
+        self.data_ = _eng().sdf_field(self.handle())["data"]
+        return cells
+
+    updateFromScene = update_from_scene
+
 
 class SignedDistanceField(_DeviceSdf):
     """gpmp2::SignedDistanceField (gpmp2/obstacle/SignedDistanceField.h:28-72): origin, cell size and

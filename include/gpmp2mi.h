@@ -1019,6 +1019,106 @@ int gpmp2mi_sdf_evidence_reset_dev(gpmp2mi_sdf* s, void* stream);
 /* E to a host array (all 0 for a handle that never took a call of this section); waits for the default stream */
 int gpmp2mi_sdf_get_evidence(const gpmp2mi_sdf* s, int16_t* E /*[nz][ny][nx]*/);
 
+/* ---- scene: boxes, spheres, cylinders and closed meshes into the field, on the device -------------------------------
+ * "live map" takes an occupancy grid or a cloud, "sensor map" takes evidence.  These calls take known geometry: a table
+ * as a box, a post as a cylinder, a fixture from CAD as a closed triangle mesh, each with a pose that may change from
+ * call to call.  The objects are one more source of the occupied set O; the field is rebuilt from O by the distance
+ * transform the handle already runs.  Geometry, streams, `_dev` forms and the meaning of "the handle afterwards equals"
+ * are those of "live map".
+ *
+ * A scene handle holds 1 .. GPMP2MI_MAX_SCENE_OBJECTS objects.  Mesh vertices and triangles are copied to the device of
+ * gpmp2mi_scene_create (the current one); poses and enabled flags stay on the host and are HOST data in every form, read
+ * before the call returns.  The handle also owns the workspace of a rasterisation: the fixed-point vertices, one count and
+ * one flag per object, and a bit volume of nx rounded up to 32 bits per row (j, k).  The bit volume is taken at the first
+ * call for a grid, or by gpmp2mi_scene_reserve, and grows when a later grid needs more; a `_dev` call whose grid the
+ * handle already holds neither allocates nor synchronises.  The workspace belongs to one call at a time: calls with the
+ * same scene must be in stream order.  Neither the base nor E of the field handle is changed by these calls, and the
+ * existing update calls keep their behaviour and their memory exactly.
+ *
+ * Rules.  Every floating-point expression is evaluated in IEEE double exactly as written, each operation rounded once
+ * (no fused multiply-add); divisions are true divisions.  pose = [R | t], row-major 3 x 4, object -> world.
+ *  1. Cell centres.  Cell (i, j, k) has the centre c = (origin_x + i*cell, origin_y + j*cell, origin_z + k*cell): the
+ *     point-to-cell rule of "live map" read backwards.  On a planar handle nz = 1, c_z = 0 and origin_z counts as 0;
+ *     every kind works there through the same formulas (the scene is cut by the plane z = 0).
+ *  2. Primitives.  d = c - t, local coordinates l_m = (R[0][m]*d_0 + R[1][m]*d_1) + R[2][m]*d_2, s_n = size[n] + inflate.
+ *       box:      occupied iff |l_0| <= s_0 and |l_1| <= s_1 and |l_2| <= s_2;
+ *       sphere:   occupied iff sqrt((d_0^2 + d_1^2) + d_2^2) <= s_0;
+ *       cylinder: occupied iff sqrt(l_0^2 + l_1^2) <= s_0 and |l_2| <= s_1.
+ *     R is used as given (it is not made orthonormal).  Only cell CENTRES are tested: an object that contains no centre
+ *     marks nothing, however large a part of a cell it covers.  An inflate of cell * sqrt(3) / 2 (half a cell's diagonal)
+ *     guarantees that every cell the object touches is marked.  Sizes a kind does not use are not read.
+ *  3. Meshes: solid fill by crossing parity along x, in exact integers.  It holds for any closed mesh, any winding and
+ *     any triangle order; a point exactly on a vertex or an edge is resolved by a fixed symbolic shift, not by luck.
+ *       (1) world vertex   w_m = ((R[m][0]*v_0 + R[m][1]*v_1) + R[m][2]*v_2) + t_m;
+ *       (2) grid           g_m = (w_m - origin_m) / cell_size;
+ *       (3) fixed point    q_m = (int64) rint(g_m * 1024.0), ties to even;
+ *       (4) whole-mesh guard: if any vertex of the mesh has a non-finite g or |g_m * 1024| > 2^29, the WHOLE mesh marks
+ *           nothing and its `cells` entry is -1.  Differences then fit in 32 bits, and every product below is exact;
+ *       (5) per triangle with fixed-point vertices P0, P1, P2:
+ *           a = (P1.y - P0.y)(P2.z - P0.z) - (P1.z - P0.z)(P2.y - P0.y); a == 0: the triangle is skipped; a < 0: P1 and
+ *           P2 are swapped and a is negated;
+ *       (6) per column (j, k) of the grid, Y = 1024 j, Z = 1024 k, and per edge (A, B) of ((P1,P2), (P2,P0), (P0,P1)):
+ *           d = B - A, e = d.y (Z - A.z) - d.z (Y - A.y).  The edge passes iff e > 0, or e == 0 and (d.y > 0 or (d.y == 0
+ *           and d.z > 0)).  The column crosses the triangle iff all three edges pass; then e0 + e1 + e2 = a;
+ *       (7) crossing abscissa: X_n = (double)P_n.x / 1024.0,
+ *           x = (((double)e0*X0 + (double)e1*X1) + (double)e2*X2) / (double)a, first = ceil(x), compared in double;
+ *       (8) the crossing flips every cell i >= first of row (j, k): the whole row if first <= 0, nothing if first >= nx;
+ *       (9) after all triangles of THIS mesh a cell is occupied by the mesh iff it was flipped an odd number of times.
+ *     Parity is per mesh: two overlapping meshes unite, they do not cancel.
+ *  4. cells [K] (NULL ok): the number of grid cells occupied by object o alone; 0 for a disabled object, -1 for a mesh
+ *     that is out of range.  Integer atomics add the counts and flip the crossing bits; marks are plain stores of one
+ *     value; no result depends on an order.
+ *  5. Scene set and field.  The scene set is the union over the enabled objects.  gpmp2mi_sdf_update_from_scene builds
+ *     O = scene set, united with the base if use_base and with {E >= occupied_at} if use_evidence; the handle is then,
+ *     bit for bit, what gpmp2mi_sdf_create_from_occupancy gives for the indicator of O (the constant 1000 for an empty or
+ *     a full O).  Nothing of the scene persists on the field handle: the next update of any kind starts without it.
+ *  6. Errors, all checked before any device work (a refused call changes nothing).  GPMP2MI_ERR_INVALID: a NULL argument
+ *     (cells may be NULL); K outside 1 .. 256; an unknown kind; a non-finite pose, size or inflate; a negative size or
+ *     inflate; a mesh with inflate != 0, with V < 4 or T < 4, with NULL vertices or triangles,
+ *     with an index outside 0 .. V-1 or with a triangle that repeats an index; a mesh that is not closed: some undirected
+ *     edge, taken as a pair of vertex indices, occurs in an odd number of triangles; first / count outside the scene;
+ *     a grid with dim not 2 or 3, a size < 1, nz != 1 on a planar grid, a cell size that is not finite and > 0 or a
+ *     non-finite origin; use_base on a handle without a base; use_evidence on a handle without evidence (no call of
+ *     "sensor map" or gpmp2mi_sdf_reserve_evidence yet); occupied_at outside -32768 .. 32767; a scene on another device
+ *     than the field, or on one that is not the current device.  GPMP2MI_ERR_UNSUPPORTED: more than 2^20 triangles in a
+ *     mesh; an axis too long for the distance transform.  GPMP2MI_ERR_ALLOC and GPMP2MI_ERR_HIP as elsewhere.
+ * Not here: open meshes and surface (shell) voxelisation, mesh inflation, objects attached to a robot link (take the link
+ * pose from gpmp2mi_forward_kinematics and call gpmp2mi_scene_set_poses), updates of a sub-box of the grid,
+ * gpmp2mi_multi_plan_* twins beyond gpmp2mi_multi_plan_refresh_field, capsules and cones. */
+enum { GPMP2MI_SCENE_BOX = 0, GPMP2MI_SCENE_SPHERE = 1, GPMP2MI_SCENE_CYLINDER = 2, GPMP2MI_SCENE_MESH = 3 };
+#define GPMP2MI_MAX_SCENE_OBJECTS 256
+#define GPMP2MI_MAX_SCENE_TRIANGLES 1048576   /* per mesh */
+typedef struct gpmp2mi_scene_object {
+  int kind;
+  double size[3];        /* box: half extents x,y,z; sphere: radius,-,-; cylinder: radius, half height (local z),- */
+  double inflate;        /* >= 0, added to every size of a primitive; must be 0 for a mesh */
+  int n_vertices;  const double* vertices;   /* mesh: [V][3], object frame (host) */
+  int n_triangles; const int* triangles;     /* mesh: [T][3] vertex indices (host) */
+  double pose[12];       /* object -> world, row-major 3 x 4 [R | t] */
+  int enabled;
+} gpmp2mi_scene_object;
+typedef struct gpmp2mi_scene gpmp2mi_scene;
+
+int  gpmp2mi_scene_create(int K, const gpmp2mi_scene_object* objs, gpmp2mi_scene** out);   /* on the current device */
+void gpmp2mi_scene_destroy(gpmp2mi_scene* sc);                                            /* NULL: no-op */
+int  gpmp2mi_scene_count(const gpmp2mi_scene* sc);                                        /* -1 for NULL */
+int  gpmp2mi_scene_set_poses(gpmp2mi_scene* sc, int first, int count, const double* poses /*[count][12], host*/);
+int  gpmp2mi_scene_set_enabled(gpmp2mi_scene* sc, int first, int count, const int* enabled /*[count], host*/);
+/* takes the bit volume for a grid of this size now, so that the first `_dev` call on it does not allocate */
+int  gpmp2mi_scene_reserve(gpmp2mi_scene* sc, int nx, int ny, int nz);
+/* the occupied set of the scene alone on a grid, one byte per cell [nz][ny][nx] (1 occupied, 0 free); cells [K] or NULL.
+ * _dev: mask and cells are device pointers. */
+int gpmp2mi_scene_rasterize(const gpmp2mi_scene* sc, int dim, const double origin[3], double cell_size, int nx, int ny,
+                            int nz, unsigned char* mask, int* cells);
+int gpmp2mi_scene_rasterize_dev(const gpmp2mi_scene* sc, int dim, const double origin[3], double cell_size, int nx,
+                                int ny, int nz, unsigned char* mask, int* cells, void* stream);
+/* O = scene  U (use_base ? base : {})  U (use_evidence ? {E >= occupied_at} : {}); the field rebuilt in place.
+ * _dev: cells is a device pointer. */
+int gpmp2mi_sdf_update_from_scene(gpmp2mi_sdf* s, const gpmp2mi_scene* sc, int use_base, int use_evidence,
+                                  int occupied_at, int* cells /*[K] or NULL*/);
+int gpmp2mi_sdf_update_from_scene_dev(gpmp2mi_sdf* s, const gpmp2mi_scene* sc, int use_base, int use_evidence,
+                                      int occupied_at, int* cells, void* stream);
+
 /* ---- distinct alternatives: how many different solutions the restarts found, one row per mode, on the device ------
  * The calls of "scoring" answer with one row.  These calls say how many different trajectories a batch holds and hand
  * over one representative of each, best first, without the trajectories leaving the device: the fallback when the

@@ -63,6 +63,10 @@ int gpmp2mi_debug_sdf_update_timing(gpmp2mi_sdf* s, int on, double* ms4 /*[4] or
  * ms6 = {deproject and classify, walk, apply and seed, the three axis passes, finish, pack}.  It switches the timer of
  * gpmp2mi_debug_sdf_update_timing with it: the last four stages are recorded by the same events. */
 int gpmp2mi_debug_sdf_integrate_timing(gpmp2mi_sdf* s, int on, double* ms6 /*[6] or NULL*/);
+/* Diagnostic (scripts/scene_throughput.py): the rasterisation of a scene (include/gpmp2mi.h "scene"), which in a
+ * gpmp2mi_sdf_update_from_scene is part of the first stage of gpmp2mi_debug_sdf_update_timing.  ms2 = {the primitives,
+ * the meshes: quantize, cross and fill of each} of the last call recorded on this scene handle. */
+int gpmp2mi_debug_scene_timing(gpmp2mi_scene* sc, int on, double* ms2 /*[2] or NULL*/);
 
 /* Diagnostic builds (-DG2_STAMPS) only: 64 raw s_memtime stamps of trajectory b's last solve step. */
 int gpmp2mi_plan_debug_stamps(gpmp2mi_plan* p, int b, unsigned long long* out64);

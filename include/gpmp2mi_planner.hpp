@@ -269,6 +269,109 @@ inline std::vector<int16_t> Evidence(const gpmp2mi_sdf* h, std::size_t cells) {
 }
 }  // namespace internal
 
+/// Scene (include/gpmp2mi.h "scene"): boxes, spheres, cylinders and closed triangle meshes with poses (row-major 3 x 4
+/// [R | t], object -> world).  Objects are added first; the handle is made by the first use (or by build()), after which
+/// only poses and enabled flags change.  Only cell centres are tested: give a thin object an inflate of
+/// cell * sqrt(3) / 2 to be sure that every cell it touches is marked.
+class Scene {
+ public:
+  using Pose = std::array<double, 12>;
+  static Pose identity() { return Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; }
+  static Pose translation(double x, double y, double z) { return Pose{1, 0, 0, x, 0, 1, 0, y, 0, 0, 1, z}; }
+  Scene() = default;
+  Scene(const Scene&) = delete;
+  Scene& operator=(const Scene&) = delete;
+  ~Scene() { gpmp2mi_scene_destroy(h_); }
+  /// each returns the index of the new object
+  std::size_t addBox(const std::array<double, 3>& half_extents, const Pose& pose, double inflate = 0.0) {
+    return add(GPMP2MI_SCENE_BOX, half_extents, inflate, pose, nullptr, nullptr);
+  }
+  std::size_t addSphere(double radius, const std::array<double, 3>& center, double inflate = 0.0) {
+    return add(GPMP2MI_SCENE_SPHERE, {radius, 0.0, 0.0}, inflate, translation(center[0], center[1], center[2]), nullptr,
+               nullptr);
+  }
+  /// axis along the object's z
+  std::size_t addCylinder(double radius, double half_height, const Pose& pose, double inflate = 0.0) {
+    return add(GPMP2MI_SCENE_CYLINDER, {radius, half_height, 0.0}, inflate, pose, nullptr, nullptr);
+  }
+  /// a closed mesh: vertices row-major [V][3] in the object frame, triangles [T][3] vertex indices, any winding
+  std::size_t addMesh(const Vector& vertices, const std::vector<int>& triangles, const Pose& pose) {
+    if (vertices.size() % 3 != 0 || triangles.size() % 3 != 0)
+      throw std::runtime_error("[Scene] vertices are not [V][3] or triangles are not [T][3]");
+    return add(GPMP2MI_SCENE_MESH, {0.0, 0.0, 0.0}, 0.0, pose, &vertices, &triangles);
+  }
+  std::size_t size() const { return objs_.size(); }
+  void setPose(std::size_t index, const Pose& pose) {
+    if (index >= objs_.size()) throw std::runtime_error("[Scene] no such object");
+    for (int k = 0; k < 12; k++) objs_[index].pose[k] = pose[k];
+    if (h_) check(gpmp2mi_scene_set_poses(h_, static_cast<int>(index), 1, pose.data()), "gpmp2mi_scene_set_poses");
+  }
+  void setEnabled(std::size_t index, bool enabled) {
+    if (index >= objs_.size()) throw std::runtime_error("[Scene] no such object");
+    const int e = enabled ? 1 : 0;
+    objs_[index].enabled = e;
+    if (h_) check(gpmp2mi_scene_set_enabled(h_, static_cast<int>(index), 1, &e), "gpmp2mi_scene_set_enabled");
+  }
+  /// makes the handle (on the current device) from the objects added so far; no object can be added afterwards
+  void build() {
+    if (h_) return;
+    for (std::size_t k = 0; k < objs_.size(); k++)
+      if (objs_[k].kind == GPMP2MI_SCENE_MESH) {
+        objs_[k].vertices = verts_[k].data();
+        objs_[k].triangles = tris_[k].data();
+      }
+    check(gpmp2mi_scene_create(static_cast<int>(objs_.size()), objs_.data(), &h_), "gpmp2mi_scene_create");
+  }
+  const gpmp2mi_scene* handle() {
+    build();
+    return h_;
+  }
+  /// the occupied set of the scene alone, one byte per cell [nz][ny][nx]; cells: the count of each object alone
+  std::vector<unsigned char> rasterize(const std::array<double, 3>& origin, double cell_size, std::size_t nx,
+                                       std::size_t ny, std::size_t nz, std::vector<int>* cells = nullptr) {
+    std::vector<unsigned char> mask(nx * ny * nz);
+    if (cells) cells->assign(objs_.size(), 0);
+    check(gpmp2mi_scene_rasterize(handle(), 3, origin.data(), cell_size, static_cast<int>(nx), static_cast<int>(ny),
+                                  static_cast<int>(nz), mask.data(), cells ? cells->data() : nullptr),
+          "gpmp2mi_scene_rasterize");
+    return mask;
+  }
+
+ private:
+  std::size_t add(int kind, const std::array<double, 3>& size, double inflate, const Pose& pose, const Vector* vertices,
+                  const std::vector<int>* triangles) {
+    if (h_) throw std::runtime_error("[Scene] the scene is built: objects can no longer be added");
+    gpmp2mi_scene_object o{};
+    o.kind = kind;
+    for (int k = 0; k < 3; k++) o.size[k] = size[k];
+    o.inflate = inflate;
+    for (int k = 0; k < 12; k++) o.pose[k] = pose[k];
+    o.enabled = 1;
+    verts_.push_back(vertices ? *vertices : Vector());
+    tris_.push_back(triangles ? *triangles : std::vector<int>());
+    o.n_vertices = static_cast<int>(verts_.back().size() / 3);
+    o.n_triangles = static_cast<int>(tris_.back().size() / 3);
+    objs_.push_back(o);
+    return objs_.size() - 1;
+  }
+  std::vector<gpmp2mi_scene_object> objs_;
+  std::vector<Vector> verts_;
+  std::vector<std::vector<int>> tris_;
+  gpmp2mi_scene* h_ = nullptr;
+};
+
+namespace internal {
+/// gpmp2mi_sdf_update_from_scene for the two field classes: the cells each object occupies alone
+inline std::vector<int> UpdateFieldFromScene(gpmp2mi_sdf* h, Scene& scene, bool use_base, bool use_evidence,
+                                             int occupied_at) {
+  std::vector<int> cells(scene.size(), 0);
+  check(gpmp2mi_sdf_update_from_scene(h, scene.handle(), use_base ? 1 : 0, use_evidence ? 1 : 0, occupied_at,
+                                      cells.data()),
+        "gpmp2mi_sdf_update_from_scene");
+  return cells;
+}
+}  // namespace internal
+
 /// 3-D signed distance field; data in the reference's own storage order: z slices of column-major
 /// (row = y, col = x) matrices, i.e. voxels[(z * cols + x) * rows + y]
 class SignedDistanceField {
@@ -342,6 +445,11 @@ class SignedDistanceField {
   /// the evidence, [z][y][x]
   std::vector<int16_t> evidence() const { return internal::Evidence(h_, cells_); }
   void resetEvidence() { check(gpmp2mi_sdf_evidence_reset(h_), "gpmp2mi_sdf_evidence_reset"); }
+  /// Scene: the field again from the enabled objects of `scene`, united with the base (use_base) and with the cells whose
+  /// evidence reaches occupied_at (use_evidence).  Returns the cells each object occupies alone (-1: mesh out of range).
+  std::vector<int> updateFromScene(Scene& scene, bool use_base = false, bool use_evidence = false, int occupied_at = 1) {
+    return internal::UpdateFieldFromScene(h_, scene, use_base, use_evidence, occupied_at);
+  }
 
  private:
   EvidenceStats integrateDepthImpl(const DepthCamera& cam, const std::vector<float>& depth, const EvidenceOptions& opts,
@@ -406,6 +514,11 @@ class PlanarSDF {
   /// the evidence, [y][x]
   std::vector<int16_t> evidence() const { return internal::Evidence(h_, cells_); }
   void resetEvidence() { check(gpmp2mi_sdf_evidence_reset(h_), "gpmp2mi_sdf_evidence_reset"); }
+  /// Scene: the field again from the enabled objects of `scene`, united with the base (use_base) and with the cells whose
+  /// evidence reaches occupied_at (use_evidence).  Returns the cells each object occupies alone (-1: mesh out of range).
+  std::vector<int> updateFromScene(Scene& scene, bool use_base = false, bool use_evidence = false, int occupied_at = 1) {
+    return internal::UpdateFieldFromScene(h_, scene, use_base, use_evidence, occupied_at);
+  }
 
  private:
   gpmp2mi_sdf* h_ = nullptr;
