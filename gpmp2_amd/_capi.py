@@ -199,6 +199,26 @@ def declare_motion(lib):
     lib.gpmp2mi_motion_limits_default.restype = None
 
 
+def declare_retime(lib):
+    """argtypes of the re-timing entry points (include/gpmp2mi.h "re-timing"); `limits` and `acc` are host data in every
+    form, the `_dev` forms take device addresses for everything else."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    lp = C.POINTER(MotionLimitsC)
+    decl = {
+        "gpmp2mi_retime_path": [i, i, i, d, d, d, d, d, f, f, f, f, d, d, d, d, ip, d],
+        "gpmp2mi_retime_path_dev": [i, i, i, vp, vp, vp, vp, d, f, f, f, f] + [vp] * 8,
+        "gpmp2mi_retime_traj": [vp, lp, f, i, i, i, d, f, f, f, d, d, d, d, ip, d, d],
+        "gpmp2mi_retime_traj_dev": [vp, lp, f, i, i, i, vp, f, f, f] + [vp] * 8,
+        "gpmp2mi_plan_retime": [vp, lp, i, f, f, f, d, d, d, d, ip, d, d],
+        "gpmp2mi_plan_retime_dev": [vp, lp, i, f, f, f] + [vp] * 8,
+        "gpmp2mi_plan_select_retimed": [vp, i, f, i, vp, f, lp, f, f, f, f, f, ip, ip, d, d, d, d],
+        "gpmp2mi_plan_select_retimed_dev": [vp, i, f, i, vp, f, lp, f, f, f, f, f] + [vp] * 7,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def declare_moving(lib):
     """argtypes of the moving-obstacle entry points (include/gpmp2mi.h "moving obstacles"); the `_dev` forms take device
     addresses."""

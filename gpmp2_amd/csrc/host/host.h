@@ -130,7 +130,11 @@ struct gpmp2mi_robot {
   // the records of gpmp2mi_path_score_traj(_dev) calls on this handle (path.hip), under the same guard and rule
   mutable void* path_ws = nullptr;
   mutable size_t path_ws_bytes = 0;
+  // the workspace of gpmp2mi_retime_traj(_dev) calls on this handle (retime.hip), under the same guard and rule
+  mutable void* retime_ws = nullptr;
+  mutable size_t retime_ws_bytes = 0;
   ~gpmp2mi_robot() {
+    if (retime_ws) (void)hipFree(retime_ws);
     if (path_ws) (void)hipFree(path_ws);
     if (d) (void)hipFree(d);
     if (score_ws) (void)hipFree(score_ws);
@@ -414,6 +418,11 @@ struct gpmp2mi_plan {
   // call and kept.  (The path itself is part of `ex`, taken at creation.)
   void* path_ws = nullptr;
   size_t path_ws_bytes = 0;
+  // re-timing (retime.hip): ps, the caps and the sets of k_retime, the profile, the per-row scores of the existing stages
+  // that select_retimed's rule reads and the staging of the host-pointer forms, taken at the first retime /
+  // select_retimed call and kept
+  void* retime_ws = nullptr;
+  size_t retime_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -533,6 +542,10 @@ int plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, con
                     bool host, hipStream_t st);
 // the argument rules the score calls share (inter_step, B, total_step, delta_t, the launch limits)
 int check_score_args(int inter, int B, int total_step, double delta_t);
+// motion_score.hip, shared with retime.hip: the rules of a gpmp2mi_motion_limits that need no robot handle (the struct
+// itself and its scalar), and its arrays [dof] as the kernels read them (+-inf where there is no limit)
+int check_limits_head(const gpmp2mi_motion_limits* l);
+int read_limits(const gpmp2mi_motion_limits* l, int dof, MotionLimitsDev* out);
 // B comparisons on the host: the rule of gpmp2mi_select_best
 void select_rule_host(int B, const double* ferr, const int* status, const double* clearance, const int* oor,
                       double required_clearance, int require_in_range, int* best, int* n_eligible);

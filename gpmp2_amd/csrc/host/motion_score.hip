@@ -9,12 +9,10 @@
 
 using namespace g2;
 
-namespace {
-
 constexpr double INF = std::numeric_limits<double>::infinity();
 
 // what needs no robot handle: the struct itself and its scalar
-int check_limits_head(const gpmp2mi_motion_limits* l) {
+int g2::check_limits_head(const gpmp2mi_motion_limits* l) {
   G2_CHECK(l, GPMP2MI_ERR_INVALID, "null motion limits");
   G2_CHECK((l->pos_down == nullptr) == (l->pos_up == nullptr), GPMP2MI_ERR_INVALID,
            "pos_down and pos_up are given together or not at all");
@@ -23,7 +21,7 @@ int check_limits_head(const gpmp2mi_motion_limits* l) {
 }
 
 // the arrays, [dof]: read here, before the call returns
-int read_limits(const gpmp2mi_motion_limits* l, int dof, MotionLimitsDev* out) {
+int g2::read_limits(const gpmp2mi_motion_limits* l, int dof, MotionLimitsDev* out) {
   G2_CHECK(dof >= 1 && dof <= GPMP2MI_MAX_DOF, GPMP2MI_ERR_INVALID, "dof outside 1..GPMP2MI_MAX_DOF");
   for (int d = 0; d < GPMP2MI_MAX_DOF; d++) {
     out->down[d] = -INF;
@@ -48,6 +46,8 @@ int read_limits(const gpmp2mi_motion_limits* l, int dof, MotionLimitsDev* out) {
   }
   return GPMP2MI_OK;
 }
+
+namespace {
 
 struct MotionOut {
   double *pos_margin = nullptr, *vel_ratio = nullptr, *acc_ratio = nullptr, *point_speed = nullptr, *time_scale = nullptr;

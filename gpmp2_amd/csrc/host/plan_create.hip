@@ -102,6 +102,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
   if (motion_ws) (void)hipFree(motion_ws);
   if (moving_ws) (void)hipFree(moving_ws);
   if (path_ws) (void)hipFree(path_ws);
+  if (retime_ws) (void)hipFree(retime_ws);
   sampled_fac.release();
   flags_release(qflags);
 }

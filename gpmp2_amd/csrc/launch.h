@@ -233,6 +233,37 @@ int launch_motion(const RobotDev& h, const RobotDev* R, const MotionLimitsDev& l
                   const double* traj, MotionRec* recs, hipStream_t st);
 int launch_motion_finish(const MotionFinish& a, hipStream_t st);
 
+// retime_kernels.hip (include/gpmp2mi.h "re-timing")
+// ps [B][Md]: the largest sphere speed of every checked state (NaN where one is not finite); fixed-base kinds only
+int launch_retime_caps(const RobotDev& h, const RobotDev* R, double dt, int inter, int B, int N, const double* traj,
+                       double* ps, hipStream_t st);
+// arguments of k_retime.  The trajectory form reads traj / ps and the limits vel / point_speed; the path form reads the
+// caller's qd / ql / qr [B][Md][D] and cap [B][Md].  acc / vel: +inf where there is no limit.  X [B][Md] and K [B][Md][2]
+// are workspace; sdot, u and stamps [B][Md] are never null (sdot carries x on the way); the other outputs may be.
+struct RetimeArgs {
+  int B, Md, D, N, inter;
+  double dt, h, max_rate, rate_start, rate_end, point_speed;
+  double acc[GPMP2MI_MAX_DOF], vel[GPMP2MI_MAX_DOF];
+  const double *traj, *ps;
+  const double *qd, *ql, *qr, *cap;
+  double *X, *K;
+  double *sdot, *u, *stamps, *duration, *achieved, *dense;
+  int* status;
+};
+int launch_retime(const RetimeArgs& a, bool traj, hipStream_t st);
+// arguments of k_retime_finish (one workgroup): `sel` carries the selection and the shape of the trajectories; the rule
+// reads the per-row scores the existing stages left, as MotionFinish does, and what k_retime left.
+struct RetimeFinish {
+  ScoreFinish sel;
+  const double *clearance, *self_clearance, *pos_margin;
+  const int *oor, *self_invalid, *motion_invalid;
+  const int* rstatus;
+  const double *duration, *sdot, *stamps;   // [B], [B][Md], [B][Md]
+  double required_self_clearance, required_pos_margin, max_duration;
+  double *duration_best, *stamps_best;
+};
+int launch_retime_finish(const RetimeFinish& a, hipStream_t st);
+
 // moving_kernels.hip (include/gpmp2mi.h "moving obstacles"; the in-plan factor's launcher is in plan.h)
 // the factor on M evaluations: cen / Jc from launch_sphere_centers, robot_radius [S] in the caller's sphere order,
 // centers [M][K][3] -> err [M][S][K], H [M][S][K][D] or null

@@ -44,6 +44,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_score(lib)
     _capi.declare_self(lib)
     _capi.declare_motion(lib)
+    _capi.declare_retime(lib)
     _capi.declare_moving(lib)
     _capi.declare_path(lib)
     _capi.declare_map(lib)
@@ -135,6 +136,11 @@ def _path_ptrs(o):
 def _motion_ptrs(o):
     return (dptr(o["pos_margin"]), dptr(o["vel_ratio"]), dptr(o["acc_ratio"]), dptr(o["point_speed"]),
             dptr(o["time_scale"]), iptr(o["worst"]), iptr(o["invalid"]))
+
+
+def _retime_ptrs(o):
+    return (dptr(o["sdot"]), dptr(o["u"]), dptr(o["stamps"]), dptr(o["duration"]), iptr(o["status"]),
+            dptr(o["achieved"])) + ((dptr(o["dense_retimed"]),) if "dense_retimed" in o else ())
 
 
 class MotionLimits:
@@ -671,6 +677,44 @@ class Engine:
         lim = _limits_arg(limits, robot.dof)
         self._ck(self.lib.gpmp2mi_motion_score_traj(robot.ptr, lim, float(delta_t), inter_step, B, N, dptr(t),
                                                     *_motion_ptrs(o)))
+        return o
+
+    # ---------------------------------------------------------------- re-timing (include/gpmp2mi.h)
+    def retime_path(self, qd, qdd_left, qdd_right, cap, acc, h, max_rate=1.0, rate_start=None, rate_end=None, out=None):
+        """The bare rule on any joint-space path: qd, qdd_left, qdd_right [B][Md][D] (or one [Md][D]), cap [B][Md] (a
+        bound on sdot^2, inf: none), acc [D] or None -> dict(sdot, u, stamps [B][Md], duration [B], status [B],
+        achieved [B][4])."""
+        q = np.ascontiguousarray(qd, dtype=np.float64)
+        q = q[None] if q.ndim == 2 else q
+        if q.ndim != 3 or q.shape[1] < 2:
+            raise ValueError(f"qd: expected [B][Md][D] with Md >= 2, got {list(np.shape(qd))}")
+        B, Md, D = q.shape
+        ql, qr = (np.ascontiguousarray(x, dtype=np.float64).reshape(q.shape) for x in (qdd_left, qdd_right))
+        c = np.ascontiguousarray(cap, dtype=np.float64).reshape(B, Md)
+        a = None if acc is None else scoring.motion_limits(D, acc=acc)[3]
+        if not (np.isfinite(float(h)) and float(h) > 0):
+            raise ValueError("h must be finite and > 0")
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        o = scoring.retime_outputs(B, Md, None, out)
+        self._ck(self.lib.gpmp2mi_retime_path(B, Md, D, dptr(q), dptr(ql), dptr(qr), dptr(c), dptr(a), float(h), *rates,
+                                              *_retime_ptrs(o)))
+        return o
+
+    def retime_traj(self, robot, limits, delta_t, inter_step, traj, max_rate=1.0, rate_start=None, rate_end=None,
+                    out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) -> dict(sdot, u, stamps [B][Md], duration [B], status [B], achieved
+        [B][4], dense_retimed [B][Md][2D]): the fastest speed profile along the unchanged path under the rate limits of
+        `limits` (a MotionLimits; None: max_rate alone).  rate_start / rate_end: a forced rate, None = free."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        o = scoring.retime_outputs(B, scoring.checked_states(N, inter_step), robot.dof, out)
+        lim = _limits_arg(limits, robot.dof)
+        self._ck(self.lib.gpmp2mi_retime_traj(robot.ptr, lim, float(delta_t), inter_step, B, N, dptr(t), *rates,
+                                              *_retime_ptrs(o)))
         return o
 
     # ---------------------------------------------------------------- moving obstacles (include/gpmp2mi.h)
@@ -1578,6 +1622,70 @@ class Plan:
         self.eng._ck(self.eng.lib.gpmp2mi_plan_select_feasible_dev(
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
             None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts,
+            *args, C.c_void_p(stream or 0)))
+
+    # ---- how fast can the robot run it (include/gpmp2mi.h "re-timing")
+    def retime(self, limits, inter_step, max_rate=1.0, rate_start=None, rate_end=None, out=None):
+        """dict(sdot, u, stamps, duration, status, achieved, dense_retimed) of the plan's result, B rows."""
+        inter_step = _score_args(inter_step)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        o = scoring.retime_outputs(self.B, scoring.checked_states(self.N, inter_step), self.D, out)
+        lim = _limits_arg(limits, self.D)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_retime(self.h.ptr, lim, inter_step, *rates, *_retime_ptrs(o)))
+        return o
+
+    def retime_dev(self, limits, inter_step, max_rate=1.0, rate_start=None, rate_end=None, sdot=None, u=None,
+                   stamps=None, duration=None, status=None, achieved=None, dense_retimed=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        inter_step = _score_args(inter_step)
+        B, Md = self.B, scoring.checked_states(self.N, inter_step)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        args = [_dev_arg("sdot", sdot, (B, Md)), _dev_arg("u", u, (B, Md)), _dev_arg("stamps", stamps, (B, Md)),
+                _dev_arg("duration", duration, (B,)), _dev_arg("status", status, (B,), True),
+                _dev_arg("achieved", achieved, (B, 4)), _dev_arg("dense_retimed", dense_retimed, (B, Md, 2 * self.D))]
+        lim = _limits_arg(limits, self.D)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_retime_dev(self.h.ptr, lim, inter_step, *rates, *args,
+                                                          C.c_void_p(stream or 0)))
+
+    def select_retimed(self, inter_step, limits, required_pos_margin=0.0, max_duration=np.inf, max_rate=1.0,
+                       rate_start=None, rate_end=None, required_clearance=0.0, require_in_range=False, pairs=None,
+                       required_self_clearance=0.0):
+        """select_feasible() with the duration of the re-timed row in place of time_scale: the row must re-time OK within
+        max_duration.  dict(best, n_eligible, duration_best, stamps_best, traj_best, dense_best); best = -1: the last
+        four are None.  dense_best carries the re-timed velocities (as dense_retimed of retime())."""
+        inter_step = _score_args(inter_step)
+        rpm, md = scoring.retimed_thresholds(required_pos_margin, max_duration)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        lim = _limits_arg(limits, self.D)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db, sb = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D)), np.zeros(Md)
+        best, n, dur = C.c_int(-1), C.c_int(0), C.c_double(0.0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_retimed(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, *rates, md,
+            C.byref(best), C.byref(n), C.cast(C.byref(dur), _capi.c_double_p), dptr(sb), dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, duration_best=dur.value if hit else None,
+                    stamps_best=sb if hit else None, traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_retimed_dev(self, inter_step, limits, required_pos_margin=0.0, max_duration=np.inf, max_rate=1.0,
+                           rate_start=None, rate_end=None, required_clearance=0.0, require_in_range=False, pairs=None,
+                           required_self_clearance=0.0, best=None, n_eligible=None, duration_best=None,
+                           stamps_best=None, traj_best=None, dense_best=None, stream=None):
+        """The same with device outputs, as select_feasible_dev, plus duration_best float64 [1] and stamps_best [Md].
+        One enqueue on `stream`, no host synchronisation once the plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        rpm, md = scoring.retimed_thresholds(required_pos_margin, max_duration)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        lim = _limits_arg(limits, self.D)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("duration_best", duration_best, (1,)), _dev_arg("stamps_best", stamps_best, (Md,)),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_retimed_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, *rates, md,
             *args, C.c_void_p(stream or 0)))
 
     # ---- spheres that move with the support time (include/gpmp2mi.h "moving obstacles")

@@ -195,6 +195,77 @@ def feasible_thresholds(required_pos_margin, max_time_scale):
     return required_pos_margin, max_time_scale
 
 
+# ---- re-timing (include/gpmp2mi.h "re-timing"): the status values, the outputs, the rates and the rule of its selection
+RETIME_OK, RETIME_BOUNDARY, RETIME_EMPTY, RETIME_INVALID = range(4)
+RETIME_NAMES = ("sdot", "u", "stamps", "duration", "status", "achieved", "dense_retimed")
+
+
+def retime_outputs(B, Md, D=None, out=None):
+    """The per-row outputs of a re-timing call: fresh arrays, or the caller's (checked as score_outputs does).
+    D = None: the path form, which has no dense_retimed."""
+    f, i = np.float64, np.int32
+    want = dict(sdot=((B, Md), f), u=((B, Md), f), stamps=((B, Md), f), duration=((B,), f), status=((B,), i),
+                achieved=((B, 4), f))
+    if D is not None:
+        want["dense_retimed"] = ((B, Md, 2 * D), f)
+    res = {}
+    out = out or {}
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"unknown retime outputs: {sorted(unknown)}")
+    for name, (shape, dt) in want.items():
+        x = out.get(name)
+        if x is None:
+            x = np.zeros(shape, dtype=dt)
+        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
+            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
+                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
+        res[name] = x
+    return res
+
+
+def retime_rates(max_rate=1.0, rate_start=None, rate_end=None):
+    """(max_rate, rate_start, rate_end) as the C side takes them: None = a free end = -1; ValueError for a NaN, a
+    max_rate that is not finite and > 0, or a negative forced rate."""
+    max_rate = float(max_rate)
+    if not (np.isfinite(max_rate) and max_rate > 0):
+        raise ValueError("max_rate must be finite and > 0")
+    ends = []
+    for name, r in (("rate_start", rate_start), ("rate_end", rate_end)):
+        if r is not None and not float(r) >= 0:
+            raise ValueError(f"{name} must be >= 0 (None: free)")
+        ends.append(-1.0 if r is None else float(r))
+    return max_rate, ends[0], ends[1]
+
+
+def retimed_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+                 min_self_clearance=None, invalid=None, required_self_clearance=0.0, pos_margin=None,
+                 motion_invalid=None, required_pos_margin=0.0, retime_status=None, duration=None, max_duration=np.inf):
+    """(best, n_eligible) by feasible_rule without its time_scale test, and then status == RETIME_OK and
+    duration <= max_duration."""
+    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
+    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+                  invalid, required_self_clearance)
+    if motion_invalid is not None:
+        ok &= np.asarray(motion_invalid).reshape(-1) == 0
+    with np.errstate(invalid="ignore"):
+        if pos_margin is not None:
+            ok &= np.asarray(pos_margin, dtype=np.float64).reshape(-1) >= required_pos_margin
+        ok &= np.asarray(retime_status).reshape(-1) == RETIME_OK
+        ok &= np.asarray(duration, dtype=np.float64).reshape(-1) <= max_duration
+    rows = np.flatnonzero(ok)
+    if rows.size == 0:
+        return -1, 0
+    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+
+
+def retimed_thresholds(required_pos_margin, max_duration):
+    required_pos_margin, max_duration = float(required_pos_margin), float(max_duration)
+    if np.isnan(required_pos_margin) or np.isnan(max_duration):
+        raise ValueError("required_pos_margin / max_duration must not be NaN")
+    return required_pos_margin, max_duration
+
+
 # ---- moving obstacles (include/gpmp2mi.h "moving obstacles"): the output names, the extended rule, the sphere set
 MOVING_NAMES = ("moving_support_cost", "moving_dense_cost", "min_moving_clearance", "worst", "invalid")
 MAX_MOVING_SPHERES = 64     # GPMP2MI_MAX_MOVING_SPHERES

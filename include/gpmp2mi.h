@@ -643,7 +643,8 @@ int gpmp2mi_plan_select_checked_dev(gpmp2mi_plan* p, int inter_step, double requ
  * delta_t, have the preconditions of gpmp2mi_plan_score and leave the optimizer's state untouched.
  * Not here: gpmp2mi_multi_plan_* twins, a motion term inside gpmp2mi_plan_select_distinct, the acceleration of the Pose2
  * coordinates (the acceleration of the tangent-space interpolation is not built), exact continuous-time velocity maxima
- * between checked states, jerk limits, per-interval re-timing (time_scale is one uniform factor per row). */
+ * between checked states, jerk limits.  time_scale is one uniform factor per row; the per-state speed profile is
+ * "re-timing" below. */
 typedef struct gpmp2mi_motion_limits {
   const double* pos_down;   /* [dof] or NULL (then pos_up is NULL too) */
   const double* pos_up;
@@ -682,6 +683,113 @@ int gpmp2mi_plan_select_feasible_dev(gpmp2mi_plan* p, int inter_step, double req
                                      const gpmp2mi_motion_limits* limits, double required_pos_margin,
                                      double max_time_scale, int* best, int* n_eligible, double* time_scale_best,
                                      double* traj_best, double* dense_best, void* stream);
+
+/* ---- re-timing: a speed profile along the unchanged path, per checked state, on the device -------------------------
+ * time_scale of "motion limits" is one uniform factor per row: one sharp corner slows the whole trajectory.  These calls
+ * keep the path and give every checked state k of "scoring" (Md = N (J+1) + 1 states, spacing h = delta_t / (J+1)) a rate
+ * sdot_k = ds/dt' of planned time s against executed time t', such that the duration is as short as the rate limits of
+ * gpmp2mi_motion_limits allow (vel, acc, point_speed; the position limits do not depend on time and are not read).  The
+ * method is time-optimal path parameterisation by reachability (the TOPP-RA scheme), specialised to box limits so that
+ * every step is a minimum or maximum of quotients: no LP solver, no epsilon, and no floating-point sum but the stamps.
+ * Every operation is rounded once in the order written (csrc/retime_rule.h states the rule for host and device).
+ *
+ * The rule, for one row, with x_k = sdot_k^2, u_k constant over stage k = 0 .. Md-2 and x_{k+1} = x_k + 2 h u_k:
+ *  - Path derivatives: q'_k is the velocity half of checked state k.  q'' inside interval i is linear between a_i,0 and
+ *    a_i,1 of "motion limits": at sub-state j of J+1 it is a_i,0 + (a_i,1 - a_i,0) * (j / (J+1)), the two ends exact.  At a
+ *    checked state this gives a right value q''_{k+} and a left value q''_{k-}; they differ only at support states.
+ *  - Cap: X_k = min(max_rate^2, min_d (vel[d] / |q'_k[d]|)^2, (point_speed / ps_k)^2), ps_k the largest sphere speed at
+ *    state k (the per-state quantity whose row maximum is point_speed of "motion limits").  A zero denominator or an
+ *    infinite limit contributes no cap.  max_rate is finite and > 0; with max_rate = 1 the robot never runs faster than
+ *    planned.
+ *  - Rows of stage k: for every joint d with a finite acc[d] two two-sided rows |a x_k + b u_k| <= acc[d]: at the start
+ *    of the stage a = q''_{k+}[d], b = q'_k[d]; at its end a = q''_{(k+1)-}[d], b = q'_{k+1}[d] + 2 h q''_{(k+1)-}[d] (the
+ *    acceleration at state k+1 seen from the left, written in (x_k, u_k)).  A row with b == 0 caps x_k at acc[d] / |a| and
+ *    bounds no u; every other row gives the bounds -acc/|b| - (a/b) x <= u <= acc/|b| - (a/b) x.  The next set
+ *    K_{k+1} = [lo, hi] gives lo/2h - x/2h <= u <= hi/2h - x/2h.
+ *  - Backward pass: K_{Md-1} = [0, X_{Md-1}], or [rate_end^2, rate_end^2] when rate_end >= 0.  For k = Md-2 .. 0, K_k is
+ *    the set of x in [0, X_k] for which some u meets all bounds: every (lower i, upper j) pair is one inequality
+ *    alpha x <= beta with alpha = r_i - r_j, beta = pu_j - pl_i; alpha > 0 lowers the upper end to beta / alpha,
+ *    alpha < 0 raises the lower end, alpha == 0 with beta < 0 makes the stage empty.
+ *  - Forward pass: x_0 = hi(K_0), or rate_start^2 when rate_start >= 0.  u = the smallest upper bound pu_j + r_j x_k;
+ *    x_{k+1} = x_k + 2 h u clamped into K_{k+1}; the reported u_k = (x_{k+1} - x_k) / 2h (u[Md-1] = 0).  The greedy
+ *    profile is pointwise maximal over all feasible ones.
+ *  - Time: stamps[0] = 0, stamps[k+1] = stamps[k] + 2 h / (sdot_k + sdot_{k+1}), summed in index order;
+ *    duration = stamps[Md-1].
+ *  - status [B]: GPMP2MI_RETIME_OK; _BOUNDARY: a forced rate lies outside its set (rate_start^2 outside K_0, rate_end^2
+ *    above X_{Md-1}); _EMPTY: a stage set is empty, or a denominator of the time is zero; _INVALID: a non-finite q', q''
+ *    or ps (path form: a cap that is NaN or < 0).  A row that is not OK has duration = +inf and NaN in sdot, u, stamps
+ *    and achieved (and in the velocity half of dense_retimed).
+ *  - achieved [B][4], the largest ratios after re-timing: |q'_k[d]| sdot_k / vel[d]; the accelerations
+ *    |a x_k + b u_k| / acc[d] of the rows at both ends of every stage; the accelerations at the stage midpoints (x and q''
+ *    at their means, q' of the cubic there); ps_k sdot_k / point_speed.  The first, second and fourth are <= 1 up to
+ *    rounding.  The third shows what the discretisation leaves between checked states: O(h^2), not bounded here.  The
+ *    path form has one cap: its [0] is sdot_k / sqrt(cap_k) over the finite caps, its [3] is 0.
+ *  - Determinism: a row's outputs are a function of the row, the robot, the limits, delta_t, J and the three rates
+ *    alone: bit-identical alone, in any batch, through the trajectory form or the plan form.
+ *  - Selection (gpmp2mi_plan_select_retimed): the rule of gpmp2mi_plan_select_feasible without its time_scale test,
+ *      eligible(b) = <that rule> && status[b] == GPMP2MI_RETIME_OK && duration[b] <= max_duration;
+ *    the ranking stays final_error, the lowest row on ties.  Outputs as select_feasible, plus duration_best and
+ *    stamps_best [Md] (untouched when no row is chosen).  dense_best carries the RE-TIMED velocities here: the velocity
+ *    half of state k is multiplied by sdot_k of the chosen row, as in dense_retimed.
+ * Re-timing changes WHEN the robot is where: the moving-obstacle and workspace-path checks of a row, which index their
+ * spheres and targets by planned time, are not valid for the re-timed row.
+ * Errors, before any device work: the argument errors of "motion limits"; GPMP2MI_ERR_INVALID for a NaN rate or
+ * max_duration, max_rate <= 0 or not finite, (path form) a NULL array, Md < 2, dof outside 1..GPMP2MI_MAX_DOF, h <= 0 or
+ * an acc entry that is NaN or <= 0; GPMP2MI_ERR_UNSUPPORTED, with the reason in the message, for the Pose2 kinds (the
+ * acceleration of the tangent-space interpolation is not built).  A refused call writes nothing.
+ * Memory: the workspace rules of "scoring".  Seven doubles per checked state of every row (ps, X, K, and sdot / u / stamps
+ * where the caller gives no array), with the robot handle for gpmp2mi_retime_traj_dev (under the stream-order rule of
+ * gpmp2mi_score_traj_dev), with the plan for the plan forms, taken at the first call and grown on demand.
+ * gpmp2mi_retime_path_dev has no handle: the caller gives `workspace`, 3 * B * Md doubles on the device, and none of its
+ * sdot / u / stamps may be NULL.  Any other output may be NULL.  The `_dev` forms enqueue and return.
+ * Not here: gpmp2mi_multi_plan_* twins, jerk limits, the Pose2 kinds, a guard for quotients that overflow (a row whose
+ * |b| is below acc / 1.8e308, such as a denormal velocity, is outside the rule's range). */
+enum {
+  GPMP2MI_RETIME_OK = 0,
+  GPMP2MI_RETIME_BOUNDARY = 1,
+  GPMP2MI_RETIME_EMPTY = 2,
+  GPMP2MI_RETIME_INVALID = 3
+};
+/* The bare rule on any joint-space path: qd, qdd_left, qdd_right [B][Md][D] (qdd_left of state 0 and qdd_right of state
+ * Md-1 are not read), cap [B][Md] (a bound on x = sdot^2, +inf: none), acc HOST [D] or NULL, rate_start / rate_end < 0:
+ * free.  sdot, u, stamps [B][Md], duration, status [B], achieved [B][4]. */
+int gpmp2mi_retime_path(int B, int Md, int dof, const double* qd, const double* qdd_left, const double* qdd_right,
+                        const double* cap, const double* acc, double h, double max_rate, double rate_start,
+                        double rate_end, double* sdot, double* u, double* stamps, double* duration, int* status,
+                        double* achieved);
+int gpmp2mi_retime_path_dev(int B, int Md, int dof, const double* qd, const double* qdd_left, const double* qdd_right,
+                            const double* cap, const double* acc, double h, double max_rate, double rate_start,
+                            double rate_end, double* sdot, double* u, double* stamps, double* duration, int* status,
+                            double* achieved, double* workspace, void* stream);
+/* caller buffers; traj [B][total_step+1][2D]; dense_retimed [B][Md][2D]: the configurations as interpolated, the
+ * velocities multiplied by sdot_k.  The device of the robot handle must be current. */
+int gpmp2mi_retime_traj(const gpmp2mi_robot* robot, const gpmp2mi_motion_limits* limits, double delta_t, int inter_step,
+                        int B, int total_step, const double* traj, double max_rate, double rate_start, double rate_end,
+                        double* sdot, double* u, double* stamps, double* duration, int* status, double* achieved,
+                        double* dense_retimed);
+int gpmp2mi_retime_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_motion_limits* limits, double delta_t,
+                            int inter_step, int B, int total_step, const double* traj, double max_rate,
+                            double rate_start, double rate_end, double* sdot, double* u, double* stamps,
+                            double* duration, int* status, double* achieved, double* dense_retimed, void* stream);
+/* The plan's resident result; preconditions and errors as gpmp2mi_plan_score. */
+int gpmp2mi_plan_retime(gpmp2mi_plan* p, const gpmp2mi_motion_limits* limits, int inter_step, double max_rate,
+                        double rate_start, double rate_end, double* sdot, double* u, double* stamps, double* duration,
+                        int* status, double* achieved, double* dense_retimed);
+int gpmp2mi_plan_retime_dev(gpmp2mi_plan* p, const gpmp2mi_motion_limits* limits, int inter_step, double max_rate,
+                            double rate_start, double rate_end, double* sdot, double* u, double* stamps,
+                            double* duration, int* status, double* achieved, double* dense_retimed, void* stream);
+/* gpmp2mi_plan_select_feasible with the duration of the re-timed row in place of time_scale, one enqueue. */
+int gpmp2mi_plan_select_retimed(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                const gpmp2mi_motion_limits* limits, double required_pos_margin, double max_rate,
+                                double rate_start, double rate_end, double max_duration, int* best, int* n_eligible,
+                                double* duration_best, double* stamps_best, double* traj_best, double* dense_best);
+int gpmp2mi_plan_select_retimed_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                    const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                    const gpmp2mi_motion_limits* limits, double required_pos_margin, double max_rate,
+                                    double rate_start, double rate_end, double max_duration, int* best,
+                                    int* n_eligible, double* duration_best, double* stamps_best, double* traj_best,
+                                    double* dense_best, void* stream);
 
 /* ---- moving obstacles: time-indexed spheres as a plan factor and a check, on the device ---------------------------
  * Every obstacle of "scoring" lives in one static signed-distance field.  A person or another robot crossing the

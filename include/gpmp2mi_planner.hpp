@@ -995,6 +995,65 @@ inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int
   return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
 }
 
+/// The speed profile of a trajectory along its unchanged path (include/gpmp2mi.h "re-timing"): at every checked state k
+/// the rate sdot[k] of planned against executed time, the path acceleration u[k] of the stage behind it and the new time
+/// stamp stamps[k], such that the duration is as short as the rate limits (vel, acc, point_speed of MotionLimits; the
+/// joint ranges are not read) and max_rate allow.  status is GPMP2MI_RETIME_OK or says why there is no profile (then
+/// duration is +infinity and the arrays hold NaN).  achieved: the largest velocity, stage-end acceleration, stage-midpoint
+/// acceleration and point-speed ratios after re-timing.  dense holds the checked states with their velocities multiplied
+/// by sdot.  The moving-obstacle and workspace-path checks of a trajectory index by planned time: they do not hold for
+/// the re-timed one.
+struct RetimedTrajectory {
+  Vector sdot, u, stamps;
+  double duration = 0.0, achieved[4] = {0.0, 0.0, 0.0, 0.0};
+  int status = GPMP2MI_RETIME_INVALID;
+  Trajectory dense;   // total_step * (inter_step + 1) intervals
+};
+/// ROBOT: a fixed-base robot model (the Pose2 kinds throw).  rate_start / rate_end: a forced rate at the first / last
+/// state (0: at rest), negative: free.  With max_rate = 1 the robot never runs faster than planned.
+template <class ROBOT>
+inline RetimedTrajectory RetimeTrajectory(const ROBOT& robot, const MotionLimits& limits, const Trajectory& result,
+                                          const TrajOptimizerSetting& setting, std::size_t inter_step, double max_rate = 1.0,
+                                          double rate_start = -1.0, double rate_end = -1.0) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[RetimeTrajectory] result does not match dof / total_step");
+  const gpmp2mi_motion_limits l = limits.c(robot.dof());
+  RetimedTrajectory rt;
+  rt.dense = Trajectory(result.dof, result.total_step * (inter_step + 1));
+  const std::size_t Md = rt.dense.total_step + 1;
+  rt.sdot.assign(Md, 0.0);
+  rt.u.assign(Md, 0.0);
+  rt.stamps.assign(Md, 0.0);
+  check(gpmp2mi_retime_traj(robot.handle(), &l, setting.total_time / static_cast<double>(setting.total_step),
+                            static_cast<int>(inter_step), 1, static_cast<int>(result.total_step), result.data.data(), max_rate,
+                            rate_start, rate_end, rt.sdot.data(), rt.u.data(), rt.stamps.data(), &rt.duration, &rt.status,
+                            rt.achieved, rt.dense.data.data()),
+        "gpmp2mi_retime_traj");
+  return rt;
+}
+/// The SelectBestTrajectory above with the duration of the re-timed result in place of time_scale: besides the rule of
+/// the obstacle scores, no motion quantity may be non-finite, pos_margin must reach required_pos_margin, and the result
+/// must re-time (GPMP2MI_RETIME_OK) within max_duration.  Host code.
+inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int>& status,
+                                const std::vector<TrajectoryScore>& scores,
+                                const std::vector<TrajectoryMotionScore>& motion_scores,
+                                const std::vector<RetimedTrajectory>& retimed, double required_pos_margin, double max_duration,
+                                double required_clearance = 0.0, bool require_in_range = false,
+                                std::size_t* n_eligible = nullptr) {
+  if (motion_scores.size() != scores.size() || retimed.size() != scores.size())
+    throw std::runtime_error("[SelectBestTrajectory] scores, motion_scores and retimed differ in length");
+  if (required_pos_margin != required_pos_margin || max_duration != max_duration)
+    throw std::runtime_error("[SelectBestTrajectory] required_pos_margin / max_duration is NaN");
+  std::vector<TrajectoryScore> both(scores);
+  for (std::size_t b = 0; b < both.size(); b++) {
+    const TrajectoryMotionScore& m = motion_scores[b];
+    const bool ok = m.invalid == 0 && m.pos_margin >= required_pos_margin && retimed[b].status == GPMP2MI_RETIME_OK &&
+                    retimed[b].duration <= max_duration;
+    if (!ok) both[b].min_clearance = std::nan("");   // a NaN clearance is never eligible
+  }
+  return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
+}
+
 namespace internal {
 inline Trajectory interpolateTraj(const Trajectory& opt_values, const Vector& Qc, double delta_t, std::size_t inter_step,
                                   std::size_t start_index, std::size_t end_index, bool lie) {
