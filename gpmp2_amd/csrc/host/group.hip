@@ -47,44 +47,6 @@ PairArgs pair_args(int dof, int B, int N, const double* traj, const double* w, i
   return a;
 }
 
-// Layout of a plan's grouping workspace for (B, N, D, inter, max_alt): the bit matrix, the per-row scores the rule
-// reads, what the rule leaves, then the staging of the host-pointer form
-struct PlanGroupWs {
-  unsigned long long* bits;
-  double *clearance, *self_clearance;
-  int *oor, *self_invalid, *mode, *leaders, *sizes;
-  int* pick;   // n_modes, n_eligible
-  int *alt, *alt_size;
-  double *alt_error, *traj_alt, *dense_alt;
-  size_t bytes;
-};
-PlanGroupWs plan_ws_layout(char* base, int B, int N, int D, int inter, int max_alt) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanGroupWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
-  w.bits = (unsigned long long*)take((size_t)B * group_words(B) * sizeof(unsigned long long));
-  w.clearance = (double*)take(B * sizeof(double));
-  w.self_clearance = (double*)take(B * sizeof(double));
-  w.oor = (int*)take(B * sizeof(int));
-  w.self_invalid = (int*)take(B * sizeof(int));
-  w.mode = (int*)take(B * sizeof(int));
-  w.leaders = (int*)take(B * sizeof(int));
-  w.sizes = (int*)take(B * sizeof(int));
-  w.pick = (int*)take(2 * sizeof(int));
-  w.alt = (int*)take(GPMP2MI_MAX_ALTERNATIVES * sizeof(int));
-  w.alt_size = (int*)take(GPMP2MI_MAX_ALTERNATIVES * sizeof(int));
-  w.alt_error = (double*)take(GPMP2MI_MAX_ALTERNATIVES * sizeof(double));
-  w.traj_alt = (double*)take((size_t)max_alt * (N + 1) * 2 * D * sizeof(double));
-  w.dense_alt = (double*)take((size_t)max_alt * Md * 2 * D * sizeof(double));
-  w.bytes = off;
-  return w;
-}
-
 struct DistinctArgs {
   int inter, require_in_range, metric, max_alt;
   double required_clearance, required_self_clearance, radius;
@@ -108,21 +70,14 @@ int plan_select_distinct(gpmp2mi_plan* p, const DistinctArgs& a, bool host, hipS
   G2_TRY(check_score_args(a.inter, P.B, P.N, P.delta_t));
   G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
   G2_TRY(check_rows(P.B));
-  G2_TRY(ws_reserve(&p->group_ws, &p->group_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, a.inter, a.max_alt).bytes));
-  const PlanGroupWs w = plan_ws_layout((char*)p->group_ws, P.B, P.N, P.D, a.inter, a.max_alt);
   const int Md = P.N * (a.inter + 1) + 1;
-  // eligibility: the scores of the existing paths, into the workspace.  The self check goes first: it is the one that
-  // can still refuse (a table made for another robot), and then nothing has been enqueued.
-  if (a.pairs) {
-    ScoreOut so;
-    so.clearance = w.self_clearance;
-    so.oor = w.self_invalid;
-    G2_TRY(plan_self_score(p, a.pairs, a.inter, so, nullptr, false, st));
-  }
-  ScoreOut o;
-  o.clearance = w.clearance;
-  o.oor = w.oor;
-  G2_TRY(plan_score(p, a.inter, o, nullptr, false, st));
+  const auto layout = [&](void* base) {
+    return carve_group((char*)base, shape_of(p, a.inter), group_words(P.B), GPMP2MI_MAX_ALTERNATIVES, a.max_alt);
+  };
+  GroupWs w;
+  G2_TRY(carve_into(p->ws[p->WS_GROUP], layout, &w));
+  PriorRows got;   // eligibility: the scores of the existing stages, into the workspace
+  G2_TRY(enqueue_prior_stages(p, a.pairs, a.inter, w.prior, st, &got));
   G2_TRY(launch_traj_pairs(pair_args(P.D, P.B, P.N, p->pb.result, a.weights, a.metric, a.radius, nullptr, w.bits), st));
   GroupRule r{};
   r.B = P.B;
@@ -134,10 +89,10 @@ int plan_select_distinct(gpmp2mi_plan* p, const DistinctArgs& a, bool host, hipS
   r.bits = w.bits;
   r.score = p->pb.final_err;
   r.status = p->pb.status;
-  r.clearance = w.clearance;
-  r.oor = w.oor;
-  r.self_clearance = a.pairs ? w.self_clearance : nullptr;
-  r.self_invalid = a.pairs ? w.self_invalid : nullptr;
+  r.clearance = got.clearance;
+  r.oor = got.oor;
+  r.self_clearance = got.self_clearance;
+  r.self_invalid = got.self_invalid;
   r.mode = host ? w.mode : a.mode;
   r.leaders = w.leaders;
   r.sizes = w.sizes;
@@ -167,10 +122,7 @@ int plan_select_distinct(gpmp2mi_plan* p, const DistinctArgs& a, bool host, hipS
   c.out_n_eligible = host ? nullptr : a.n_eligible;
   G2_TRY(launch_group_copy(c, st));
   if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst && bytes) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
+  const auto back = [&](void* dst, const void* src, size_t bytes) { return copy_back(dst, src, bytes, st); };
   int pick[2] = {0, 0};
   G2_TRY(back(pick, w.pick, sizeof(pick)));
   G2_TRY(back(a.alt, w.alt, a.max_alt * sizeof(int)));

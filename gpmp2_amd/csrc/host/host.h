@@ -12,6 +12,7 @@
 #include "../../../include/gpmp2mi_debug.h"
 #include "../launch.h"
 #include "../plan.h"
+#include "staging.h"
 
 namespace g2 {
 // The thread_local last-error string is private to handles.hip: set_error (common.h) writes it, this reads it.
@@ -62,18 +63,34 @@ int fetch_all(const Bufs&... bufs) {
   return rc;
 }
 
-// A device workspace that only grows (the scoring and posterior workspaces of a plan, the score records of a robot
-// handle).  hipFree waits for the device, so whatever still reads the old block is done before it goes; a call whose
-// shape the block already holds neither allocates nor synchronises.
-constexpr size_t WS_ALIGN = 256;
-inline size_t ws_round(size_t bytes) { return (bytes + WS_ALIGN - 1) / WS_ALIGN * WS_ALIGN; }
-inline int ws_reserve(void** ws, size_t* have, size_t need) {
-  if (need <= *have) return GPMP2MI_OK;
-  if (*ws) (void)hipFree(*ws);
-  *ws = nullptr;
-  *have = 0;
-  G2_TRY(dev_malloc(ws, need));
-  *have = need;
+// A device workspace that only grows, owned by its handle (the stage workspaces of a plan, the records of a robot
+// handle; laid out by staging.h).  hipFree waits for the device, so whatever still reads the old block is done before it
+// goes; a call whose shape the block already holds neither allocates nor synchronises.
+struct Workspace {
+  void* p = nullptr;
+  size_t bytes = 0;
+  Workspace() = default;
+  Workspace(const Workspace&) = delete;
+  int reserve(size_t need) {
+    if (need <= bytes) return GPMP2MI_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    G2_TRY(dev_malloc(&p, need));
+    bytes = need;
+    return GPMP2MI_OK;
+  }
+  void leak() { p = nullptr; bytes = 0; }   // a hung kernel may still write the block: it goes with a poisoned plan
+  ~Workspace() { if (p) (void)hipFree(p); }
+};
+// Carves `ws` by `layout` (base -> a staging.h layout with its .bytes) into *w.  A call whose shape the block already
+// holds carves once; otherwise the block grows first and is carved again (the first carving gave the size alone).
+template <class W, class L>
+int carve_into(Workspace& ws, L&& layout, W* w) {
+  *w = layout(ws.p);
+  if (w->bytes <= ws.bytes) return GPMP2MI_OK;
+  G2_TRY(ws.reserve(w->bytes));
+  *w = layout(ws.p);
   return GPMP2MI_OK;
 }
 
@@ -117,29 +134,19 @@ struct gpmp2mi_robot {
   // score_mu guards the pointer against host threads that share the handle; the records themselves belong to one
   // call at a time, so such calls must be in stream order (include/gpmp2mi.h "scoring", Memory).
   mutable std::mutex score_mu;
-  mutable void* score_ws = nullptr;
-  mutable size_t score_ws_bytes = 0;
+  mutable g2::Workspace score_ws;
   // the bridge factors of gpmp2mi_sampled_clearance_traj(_dev) calls on this handle, under the same guard and rule
   mutable g2::SampledFac sampled_fac;
   // the records of gpmp2mi_motion_score_traj(_dev) calls on this handle (motion_score.hip), under the same guard and rule
-  mutable void* motion_ws = nullptr;
-  mutable size_t motion_ws_bytes = 0;
+  mutable g2::Workspace motion_ws;
   // the records of gpmp2mi_moving_score_traj(_dev) calls on this handle (moving.hip), under the same guard and rule
-  mutable void* moving_ws = nullptr;
-  mutable size_t moving_ws_bytes = 0;
+  mutable g2::Workspace moving_ws;
   // the records of gpmp2mi_path_score_traj(_dev) calls on this handle (path.hip), under the same guard and rule
-  mutable void* path_ws = nullptr;
-  mutable size_t path_ws_bytes = 0;
+  mutable g2::Workspace path_ws;
   // the workspace of gpmp2mi_retime_traj(_dev) calls on this handle (retime.hip), under the same guard and rule
-  mutable void* retime_ws = nullptr;
-  mutable size_t retime_ws_bytes = 0;
+  mutable g2::Workspace retime_ws;
   ~gpmp2mi_robot() {
-    if (retime_ws) (void)hipFree(retime_ws);
-    if (path_ws) (void)hipFree(path_ws);
     if (d) (void)hipFree(d);
-    if (score_ws) (void)hipFree(score_ws);
-    if (motion_ws) (void)hipFree(motion_ws);
-    if (moving_ws) (void)hipFree(moving_ws);
     sampled_fac.release();
     if (replica) g2::g_robot_replicas.fetch_sub(1);
   }
@@ -163,15 +170,13 @@ struct gpmp2mi_sdf {
   // kept.  ray_ws: the records of one frame's rays ([M][3] cell coordinates, [M] classes), grown when a frame has more
   // rays than any before.  sensor_ev: the events in front of the three sensor stages (the rest are map_ev's).
   void* ev_ws = nullptr;
-  void* ray_ws = nullptr;
-  size_t ray_ws_bytes = 0;
+  g2::Workspace ray_ws;
   hipEvent_t sensor_ev[3] = {nullptr, nullptr, nullptr};
   ~gpmp2mi_sdf() {   // also runs when a create function fails half-way (unique_ptr)
     if (plain) (void)hipFree(plain);
     if (cells) (void)hipFree(cells);
     if (map_ws) (void)hipFree(map_ws);
     if (ev_ws) (void)hipFree(ev_ws);
-    if (ray_ws) (void)hipFree(ray_ws);
     for (hipEvent_t e : map_ev)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sensor_ev)
@@ -189,11 +194,9 @@ struct gpmp2mi_self_pairs {
   g2::SelfPair* d = nullptr;  // [P]
   // records of gpmp2mi_self_score_traj(_dev) calls with this table, by the rules of gpmp2mi_robot::score_ws
   mutable std::mutex mu;
-  mutable void* ws = nullptr;
-  mutable size_t ws_bytes = 0;
+  mutable g2::Workspace ws;
   ~gpmp2mi_self_pairs() {
     if (d) (void)hipFree(d);
-    if (ws) (void)hipFree(ws);
   }
 };
 
@@ -213,15 +216,13 @@ struct gpmp2mi_scene {
   int* counts = nullptr;      // [K] cells of the call in flight, behind them [K] out-of-range flags
   // crossing bits of one mesh, [nz][ny][nx rounded up to 32], all 0 between two meshes; taken at the first call for a
   // grid (or by gpmp2mi_scene_reserve) and grown when a later grid needs more
-  mutable void* bits = nullptr;
-  mutable size_t bits_bytes = 0;
+  mutable g2::Workspace bits;
   // gpmp2mi_debug_scene_timing: events in front of the primitives, between them and the meshes, and behind the meshes
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   bool timing = false;
   ~gpmp2mi_scene() {
     if (geo) (void)hipFree(geo);
     if (counts) (void)hipFree(counts);
-    if (bits) (void)hipFree(bits);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -364,65 +365,33 @@ struct gpmp2mi_plan {
   bool poisoned = false;
   // queue runs (plan_queue_impl): device workspace of the per-slot words and the pass-indexed scratch of the step
   // kernels, grown on demand; host-mapped per-pass counts; the statistics of the last run
-  void* qws = nullptr;
-  size_t qws_bytes = 0;
   g2::FlagBuf qflags;
   gpmp2mi_queue_stats qstats{};
   bool queue_ran = false;
-  // scoring (score.hip): the records of k_score and the staging of the host-pointer forms, taken at the first score
-  // call for an inter_step and kept (grown when a later call needs more)
-  void* score_ws = nullptr;
-  size_t score_ws_bytes = 0;
-  // posterior (posterior.hip): the exported normal equations and the factor scratch of k_posterior, taken at the first
-  // marginals / sample call and kept
-  void* post_ws = nullptr;
-  size_t post_ws_bytes = 0;
-  // seeding (seed.hip): H_seed of the plan's linear prior graph on the host (built at the first seeded call or read-out),
-  // and on the device with its factors (uploaded and factored at the first seeded call, then kept)
+  // The workspaces of the stages, one each (calls of different stages may be in flight at once), taken at a stage's first
+  // call and kept, grown when a later call needs more.  An array, so that a poisoned plan leaks every one of them.
+  //   QUEUE    the per-slot words and the pass-indexed scratch of the step kernels of a queue run
+  //   SCORE    the records of k_score and the staging of the host-pointer forms (CheckWs: staging.h)
+  //   POST     the exported normal equations and the factor scratch of k_posterior
+  //   SEED     H_seed on the device with its factors (uploaded and factored at the first seeded call)
+  //   RISK     the band of Sigma, ok and the records of k_risk
+  //   SAMPLED  a chunk of delta, its records, the carried counts and ok
+  //   SELF     CheckWs with the records of k_self_clearance and those of k_score for select_checked
+  //   GROUP    the bit matrix of k_traj_pairs, the per-row scores the rule reads, what k_group_rule leaves, the staging
+  //   MOTION, MOVING, PATH   CheckWs with the stage's records and the per-row scores of the earlier stages its rule reads
+  //   RETIME   ps, the caps and the sets of k_retime, the profile, the scores of the earlier stages, the staging
+  enum Ws { WS_QUEUE, WS_SCORE, WS_POST, WS_SEED, WS_RISK, WS_SAMPLED, WS_SELF, WS_GROUP, WS_MOTION, WS_MOVING, WS_PATH,
+            WS_RETIME, WS_COUNT };
+  g2::Workspace ws[WS_COUNT];
+  // seeding (seed.hip): H_seed of the plan's linear prior graph on the host (built at the first seeded call or read-out)
   std::vector<double> seed_Hd, seed_Ho;
-  void* seed_ws = nullptr;
-  size_t seed_ws_bytes = 0;
   bool seed_ready = false;
-  // posterior on the executed timeline (risk.hip): the band of Sigma, ok and the records of k_risk, taken at the first
-  // marginals_dense / risk call and kept (grown when a later inter_step needs more records); Qc of the setting, on the
-  // host from creation and on the device from that first call
-  void* risk_ws = nullptr;
-  size_t risk_ws_bytes = 0;
+  // posterior on the executed timeline (risk.hip): Qc of the setting, on the host from creation and on the device from
+  // the first marginals_dense / risk call
   std::vector<double> Qc;
   double* risk_qc = nullptr;
-  // sampled clearance (sampled.hip): a chunk of delta, its records, the carried counts and ok, taken at the first
-  // collision_probability / sample_dense_seeded call and kept; the bridge factors of the last (inter_step) asked for
-  void* sampled_ws = nullptr;
-  size_t sampled_ws_bytes = 0;
+  // sampled clearance (sampled.hip): the bridge factors of the last (inter_step)s asked for
   g2::SampledFac sampled_fac;
-  // self-collision check (self_score.hip): the records of k_self_clearance, those of k_score for select_checked and
-  // the staging of the host-pointer forms, taken at the first self_score / select_checked call and kept
-  void* self_ws = nullptr;
-  size_t self_ws_bytes = 0;
-  // distinct alternatives (group.hip): the bit matrix of k_traj_pairs, the per-row scores the rule reads, what
-  // k_group_rule leaves and the staging of the host-pointer form, taken at the first select_distinct call and kept
-  void* group_ws = nullptr;
-  size_t group_ws_bytes = 0;
-  // motion limits (motion_score.hip): the records of k_motion, the per-row scores of the existing stages that
-  // select_feasible's rule reads and the staging of the host-pointer forms, taken at the first motion_score /
-  // select_feasible call and kept
-  void* motion_ws = nullptr;
-  size_t motion_ws_bytes = 0;
-  // moving obstacles (moving.hip): the records of k_moving_clearance, the per-row scores of the existing stages that
-  // select_moving's rule reads and the staging of the host-pointer forms, taken at the first moving_score /
-  // select_moving call and kept.  (The sphere set itself is part of `ex`, taken at creation.)
-  void* moving_ws = nullptr;
-  size_t moving_ws_bytes = 0;
-  // workspace path (path.hip): the records of k_path_deviation, the per-row scores of the obstacle stage that
-  // select_path's rule reads and the staging of the host-pointer forms, taken at the first path_score / select_path
-  // call and kept.  (The path itself is part of `ex`, taken at creation.)
-  void* path_ws = nullptr;
-  size_t path_ws_bytes = 0;
-  // re-timing (retime.hip): ps, the caps and the sets of k_retime, the profile, the per-row scores of the existing stages
-  // that select_retimed's rule reads and the staging of the host-pointer forms, taken at the first retime /
-  // select_retimed call and kept
-  void* retime_ws = nullptr;
-  size_t retime_ws_bytes = 0;
   size_t tsz() const { return (size_t)hp.B * (hp.N + 1) * hp.n; }
   void mark_dirty(hipStream_t st) {
     if (!st) { null_stream_dirty = true; return; }
@@ -517,11 +486,7 @@ int plan_seed_check(gpmp2mi_plan* p, int M, int first, double scale);
 int plan_seed_restarts(gpmp2mi_plan* p, int M, uint64_t seed, int first, double scale, int keep_first, const double* sc,
                        const double* ec, const double* mean, double* init, hipStream_t st);
 
-// score.hip: the per-row outputs of a score call and the selection of a select call (any pointer may be null)
-struct ScoreOut {
-  double *support = nullptr, *dense = nullptr, *clearance = nullptr;
-  int *worst = nullptr, *oor = nullptr;
-};
+// score.hip: the selection of a select call (any pointer may be null); the per-row outputs are staging.h's ScoreOut
 struct ScoreSel {
   double required_clearance = 0.0;
   int require_in_range = 0;
@@ -542,6 +507,45 @@ int plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, con
                     bool host, hipStream_t st);
 // the argument rules the score calls share (inter_step, B, total_step, delta_t, the launch limits)
 int check_score_args(int inter, int B, int total_step, double delta_t);
+
+// check_common.hip: the driver the check stages share.  A plan form goes: its own argument checks, check_plan_ready,
+// its workspace (carve_into by a staging.h layout), plan_shape and, for a selection, point_selection and
+// enqueue_prior_stages, mark_dirty, its launches, and for a host form finish_host.
+// What every plan form checks once its own arguments are accepted: live, optimized, check_score_args, the dof.
+int check_plan_ready(gpmp2mi_plan* p, int inter);
+// B, N, D, lie, inter, Md, dt and traj of a finish kernel on the plan's resident result
+void plan_shape(ScoreFinish& g, const gpmp2mi_plan* p, int inter);
+// the same shape for a staging.h layout
+inline Shape shape_of(const gpmp2mi_plan* p, int inter) {
+  const PlanParams& P = p->hp;
+  return Shape{(size_t)P.B, (size_t)P.N, (size_t)P.D, (size_t)P.N * (inter + 1) + 1};
+}
+// What a stage's selection adds to ScoreSel's outputs (motion limits: time_scale_best; re-timing: duration_best and
+// stamps_best): one double about the chosen row, carried in the pick, and one more array of that row.
+struct SelExtra {
+  double* value = nullptr;
+  double* row = nullptr;
+  size_t row_bytes = 0;
+};
+// The selection of `g`: the rule's inputs, and its outputs pointed at the caller's arrays (device form) or at the
+// workspace (host form; only what the caller asked for).  x: the caller's extra outputs, or null for a stage without;
+// returns where the stage's kernel writes them.
+SelExtra point_selection(ScoreFinish& g, const gpmp2mi_plan* p, const ScoreSel& sel, const SelExtra* x, bool host,
+                         const PickRows& w);
+// Enqueues plan_self_score (pairs != null) and plan_score for the plan's rows into `w` on `st`; *got: the rows written
+// (the self pair null without a table)
+int enqueue_prior_stages(gpmp2mi_plan* p, const gpmp2mi_self_pairs* pairs, int inter, const PriorRows& w, hipStream_t st,
+                         PriorRows* got);
+// the one read-back: an asynchronous copy to a host array on `st`; a null array or no bytes is left alone
+int copy_back(void* dst, const void* src, size_t bytes, hipStream_t st);
+// Closes a host form: the staged rows back, the pick in one copy, a synchronisation, the caller's scalars; if a row was
+// chosen and its arrays are asked for, those and a second synchronisation; the stream clean.
+int finish_host(gpmp2mi_plan* p, int inter, const RowOut* rows, int n_rows, const ScoreSel* sel, const SelExtra* x,
+                const PickRows& w, hipStream_t st);
+// What a caller-buffer `_dev` form does once its arguments are accepted and B > 0: a device, the handle(s) on the current
+// one, the lock that guards the handle's records (t != null: the pair table's, else the robot's) and room for them
+int records_ready(const gpmp2mi_robot* r, const gpmp2mi_self_pairs* t, Workspace& ws, size_t bytes,
+                  std::unique_lock<std::mutex>& lk);
 // motion_score.hip, shared with retime.hip: the rules of a gpmp2mi_motion_limits that need no robot handle (the struct
 // itself and its scalar), and its arrays [dof] as the kernels read them (+-inf where there is no limit)
 int check_limits_head(const gpmp2mi_motion_limits* l);

@@ -170,19 +170,14 @@ int ik_goals_dev(const gpmp2mi_robot* r, const gpmp2mi_ik_opts* o, int G, const 
   const int D = r->h.dof, W = group_words(M);
   const size_t P = (size_t)G * M;
   // the workspace: what the caller did not give room for, and what only the stages among themselves read
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += ws_round(bytes);
-    return at;
-  };
-  const size_t o_conf = take(g.conf ? 0 : P * D * sizeof(double)), o_clr = take(g.clearance ? 0 : P * sizeof(double)),
-               o_score = take(P * sizeof(double)), o_stage = take(P * 2 * D * sizeof(double)),
-               o_bits = take(P * W * sizeof(unsigned long long)), o_status = take(g.status ? 0 : P * sizeof(int)),
-               o_el = take(P * sizeof(int)), o_lead = take(P * sizeof(int)), o_nm = take((size_t)G * sizeof(int)),
-               o_ne = take((size_t)G * sizeof(int));
+  Carver take{nullptr};   // a null base: the offsets, until the size is known and the block allocated
+  const size_t o_conf = (size_t)take(g.conf ? 0 : P * D * sizeof(double)), o_clr = (size_t)take(g.clearance ? 0 : P * sizeof(double)),
+               o_score = (size_t)take(P * sizeof(double)), o_stage = (size_t)take(P * 2 * D * sizeof(double)),
+               o_bits = (size_t)take(P * W * sizeof(unsigned long long)), o_status = (size_t)take(g.status ? 0 : P * sizeof(int)),
+               o_el = (size_t)take(P * sizeof(int)), o_lead = (size_t)take(P * sizeof(int)), o_nm = (size_t)take((size_t)G * sizeof(int)),
+               o_ne = (size_t)take((size_t)G * sizeof(int));
   DevBuf<char> ws;
-  G2_TRY(ws.alloc(off));
+  G2_TRY(ws.alloc(take.off));
   struct Wait {   // also on an error path: nothing may still use the workspace when it goes
     hipStream_t st;
     ~Wait() { (void)hipStreamSynchronize(st); }

@@ -14,18 +14,13 @@ namespace g2 {
 
 MapWs map_ws_layout(char* base, size_t n) {
   MapWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
+  Carver take{base};
   w.wa = (int*)take(n * sizeof(int));
   w.wb = (int*)take(n * sizeof(int));
   w.mask = (unsigned char*)take(n);
   w.cen = (double*)take((size_t)MAXS * 3 * sizeof(double));
   w.cnt = (int*)take(4 * sizeof(int));
-  w.bytes = off;
+  w.bytes = take.off;
   return w;
 }
 // what every update does once its arguments are accepted: a device, the handle's device current, the workspace

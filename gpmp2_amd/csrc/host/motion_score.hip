@@ -49,16 +49,10 @@ int g2::read_limits(const gpmp2mi_motion_limits* l, int dof, MotionLimitsDev* ou
 
 namespace {
 
-struct MotionOut {
-  double *pos_margin = nullptr, *vel_ratio = nullptr, *acc_ratio = nullptr, *point_speed = nullptr, *time_scale = nullptr;
-  int *worst = nullptr, *invalid = nullptr;
-};
-struct MotionSel {
-  double required_clearance = 0.0, required_self_clearance = 0.0, required_pos_margin = 0.0, max_time_scale = 0.0;
-  int require_in_range = 0;
+struct MotionSel : ScoreSel {
+  double required_self_clearance = 0.0, required_pos_margin = 0.0, max_time_scale = 0.0;
   const gpmp2mi_self_pairs* pairs = nullptr;
-  int *best = nullptr, *n_eligible = nullptr;
-  double *time_scale_best = nullptr, *traj_best = nullptr, *dense_best = nullptr;
+  double* time_scale_best = nullptr;
 };
 
 void set_outputs(MotionFinish& f, const MotionOut& o) {
@@ -71,50 +65,6 @@ void set_outputs(MotionFinish& f, const MotionOut& o) {
   f.invalid = o.invalid;
 }
 
-// Layout of a plan's motion workspace for (B, N, D, inter): the records, the per-row scores of the existing stages,
-// then the staging of the host-pointer forms
-struct PlanMotionWs {
-  MotionRec* recs;
-  double *clearance, *self_clearance;
-  int *oor, *self_invalid;
-  MotionOut out;
-  char* pick;   // best, n_eligible, then (8-byte aligned) the chosen row's final_error and time_scale: one 24-byte copy
-  double *traj_best, *dense_best;
-  size_t bytes;
-};
-PlanMotionWs plan_ws_layout(char* base, int B, int N, int D, int inter) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanMotionWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
-  w.recs = (MotionRec*)take((size_t)B * score_blocks((int)Md) * sizeof(MotionRec));
-  w.clearance = (double*)take(B * sizeof(double));
-  w.self_clearance = (double*)take(B * sizeof(double));
-  w.oor = (int*)take(B * sizeof(int));
-  w.self_invalid = (int*)take(B * sizeof(int));
-  w.out.pos_margin = (double*)take(B * sizeof(double));
-  w.out.vel_ratio = (double*)take(B * sizeof(double));
-  w.out.acc_ratio = (double*)take(B * sizeof(double));
-  w.out.point_speed = (double*)take(B * sizeof(double));
-  w.out.time_scale = (double*)take(B * sizeof(double));
-  w.out.worst = (int*)take((size_t)8 * B * sizeof(int));
-  w.out.invalid = (int*)take(B * sizeof(int));
-  w.pick = take(2 * sizeof(int) + 2 * sizeof(double));
-  w.traj_best = (double*)take((size_t)(N + 1) * 2 * D * sizeof(double));
-  w.dense_best = (double*)take(Md * 2 * D * sizeof(double));
-  w.bytes = off;
-  return w;
-}
-
-struct Pick {
-  int best, n;
-  double err, time_scale;
-};
-
 // Scores the plan's resident result on `st`; sel != null: the existing stages for the same rows first, then the
 // extended rule and the copy of the chosen row.  host / out / sel as plan_score (score.hip).
 int plan_motion(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter, const MotionOut& out, const MotionSel* sel,
@@ -124,108 +74,41 @@ int plan_motion(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter, cons
   if (sel)
     G2_CHECK(!std::isnan(sel->required_pos_margin) && !std::isnan(sel->max_time_scale), GPMP2MI_ERR_INVALID,
              "required_pos_margin / max_time_scale is NaN");
-  G2_PLAN_LIVE(p);   // before anything is enqueued
-  G2_CHECK(p->optimized, GPMP2MI_ERR_INVALID, "plan has not been optimized");
+  G2_TRY(check_plan_ready(p, inter));
   const PlanParams& P = p->hp;
-  G2_TRY(check_score_args(inter, P.B, P.N, P.delta_t));
-  G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
   MotionLimitsDev lim;
   G2_TRY(read_limits(l, P.D, &lim));
-  G2_TRY(ws_reserve(&p->motion_ws, &p->motion_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, inter).bytes));
-  const PlanMotionWs w = plan_ws_layout((char*)p->motion_ws, P.B, P.N, P.D, inter);
-  const size_t Md = (size_t)P.N * (inter + 1) + 1;
-  Pick* pick = (Pick*)w.pick;
+  const int Md = P.N * (inter + 1) + 1;
+  const size_t rec_bytes = (size_t)P.B * score_blocks(Md) * sizeof(MotionRec);
+  RowOut rows[MOTION_ROWS];
+  rows_of(out, rows);
+  const auto layout = [&](void* base) { return carve_motion((char*)base, rec_bytes, rows, shape_of(p, inter)); };
+  CheckWs w;
+  G2_TRY(carve_into(p->ws[p->WS_MOTION], layout, &w));
   MotionFinish f{};
-  MotionOut o;   // the host form computes only what the caller asked for
-  if (host) {
-    o.pos_margin = out.pos_margin ? w.out.pos_margin : nullptr;
-    o.vel_ratio = out.vel_ratio ? w.out.vel_ratio : nullptr;
-    o.acc_ratio = out.acc_ratio ? w.out.acc_ratio : nullptr;
-    o.point_speed = out.point_speed ? w.out.point_speed : nullptr;
-    o.time_scale = out.time_scale ? w.out.time_scale : nullptr;
-    o.worst = out.worst ? w.out.worst : nullptr;
-    o.invalid = out.invalid ? w.out.invalid : nullptr;
-  } else {
-    o = out;
-  }
-  set_outputs(f, o);
-  f.recs = w.recs;
-  f.nblk = score_blocks((int)Md);
+  set_outputs(f, motion_out(rows, host));
+  f.recs = (MotionRec*)w.recs;
+  f.nblk = score_blocks(Md);
   f.limit_point_speed = l->point_speed;
-  ScoreFinish& g = f.sel;
-  g.B = P.B;
-  g.N = P.N;
-  g.D = P.D;
-  g.lie = p->robot->h.kind >= GPMP2MI_ROBOT_POSE2_MOBILE_BASE;
-  g.inter = inter;
-  g.Md = (int)Md;
-  g.dt = P.delta_t;
-  g.traj = p->pb.result;
+  plan_shape(f.sel, p, inter);
+  SelExtra x;
   if (sel) {
-    g.select = 1;
-    g.required_clearance = sel->required_clearance;
-    g.require_in_range = sel->require_in_range;
+    x.value = sel->time_scale_best;
+    f.time_scale_best = point_selection(f.sel, p, *sel, &x, host, w.sel).value;
     f.required_self_clearance = sel->required_self_clearance;
     f.required_pos_margin = sel->required_pos_margin;
     f.max_time_scale = sel->max_time_scale;
-    g.ferr = p->pb.final_err;
-    g.status = p->pb.status;
-    // the kernel reads `best` back for time_scale_best: a device form without one gets the workspace's
-    g.best = (host || !sel->best) ? &pick->best : sel->best;
-    g.n_eligible = host ? &pick->n : sel->n_eligible;
-    g.best_err = host ? &pick->err : nullptr;
-    f.time_scale_best = host ? &pick->time_scale : sel->time_scale_best;
-    g.traj_best = host ? (sel->traj_best ? w.traj_best : nullptr) : sel->traj_best;
-    g.dense_best = host ? (sel->dense_best ? w.dense_best : nullptr) : sel->dense_best;
-    // the per-row scores of the existing stages, into the workspace.  The self check goes first: it is the one that
-    // can still refuse (a table made for another robot), and a refused call enqueues nothing.
-    if (sel->pairs) {
-      ScoreOut so;
-      so.clearance = w.self_clearance;
-      so.oor = w.self_invalid;
-      G2_TRY(plan_self_score(p, sel->pairs, inter, so, nullptr, false, st));
-      f.self_clearance = w.self_clearance;
-      f.self_invalid = w.self_invalid;
-    }
-    ScoreOut so;
-    so.clearance = w.clearance;
-    so.oor = w.oor;
-    G2_TRY(plan_score(p, inter, so, nullptr, false, st));
-    f.clearance = w.clearance;
-    f.oor = w.oor;
+    PriorRows got;
+    G2_TRY(enqueue_prior_stages(p, sel->pairs, inter, w.prior, st, &got));
+    f.clearance = got.clearance;
+    f.oor = got.oor;
+    f.self_clearance = got.self_clearance;
+    f.self_invalid = got.self_invalid;
   }
   p->mark_dirty(st);
-  G2_TRY(launch_motion(p->robot->h, p->robot->d, lim, P.delta_t, inter, P.B, P.N, p->pb.result, w.recs, st));
+  G2_TRY(launch_motion(p->robot->h, p->robot->d, lim, P.delta_t, inter, P.B, P.N, p->pb.result, (MotionRec*)w.recs, st));
   G2_TRY(launch_motion_finish(f, st));
-  if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
-  G2_TRY(back(out.pos_margin, w.out.pos_margin, P.B * sizeof(double)));
-  G2_TRY(back(out.vel_ratio, w.out.vel_ratio, P.B * sizeof(double)));
-  G2_TRY(back(out.acc_ratio, w.out.acc_ratio, P.B * sizeof(double)));
-  G2_TRY(back(out.point_speed, w.out.point_speed, P.B * sizeof(double)));
-  G2_TRY(back(out.time_scale, w.out.time_scale, P.B * sizeof(double)));
-  G2_TRY(back(out.worst, w.out.worst, (size_t)8 * P.B * sizeof(int)));
-  G2_TRY(back(out.invalid, w.out.invalid, P.B * sizeof(int)));
-  Pick got{-1, 0, 0.0, 0.0};
-  if (sel) G2_TRY(back(&got, w.pick, sizeof(got)));
-  G2_HIP(hipStreamSynchronize(st));
-  if (sel) {
-    if (sel->best) *sel->best = got.best;
-    if (sel->n_eligible) *sel->n_eligible = got.n;
-    if (got.best >= 0) {   // nothing chosen: the outputs about the chosen row stay as they are
-      if (sel->time_scale_best) *sel->time_scale_best = got.time_scale;
-      if (sel->traj_best || sel->dense_best) {
-        G2_TRY(back(sel->traj_best, w.traj_best, (size_t)(P.N + 1) * 2 * P.D * sizeof(double)));
-        G2_TRY(back(sel->dense_best, w.dense_best, Md * 2 * P.D * sizeof(double)));
-        G2_HIP(hipStreamSynchronize(st));
-      }
-    }
-  }
-  p->mark_clean(st);
-  return GPMP2MI_OK;
+  return host ? finish_host(p, inter, rows, MOTION_ROWS, sel, &x, w.sel, st) : GPMP2MI_OK;
 }
 
 int check_traj_call(const gpmp2mi_robot* r, const gpmp2mi_motion_limits* l, double delta_t, int inter, int B,
@@ -233,6 +116,25 @@ int check_traj_call(const gpmp2mi_robot* r, const gpmp2mi_motion_limits* l, doub
   G2_CHECK(r && traj, GPMP2MI_ERR_INVALID, "null argument");
   G2_TRY(check_limits_head(l));
   return check_score_args(inter, B, total_step, delta_t);
+}
+
+MotionOut make_out(double* pos_margin, double* vel_ratio, double* acc_ratio, double* point_speed, double* time_scale,
+                   int* worst, int* invalid) {
+  MotionOut o;
+  o.pos_margin = pos_margin; o.vel_ratio = vel_ratio; o.acc_ratio = acc_ratio; o.point_speed = point_speed;
+  o.time_scale = time_scale; o.worst = worst; o.invalid = invalid;
+  return o;
+}
+MotionSel make_sel(double required_clearance, int require_in_range, const gpmp2mi_self_pairs* pairs,
+                   double required_self_clearance, double required_pos_margin, double max_time_scale, int* best,
+                   int* n_eligible, double* time_scale_best, double* traj_best, double* dense_best) {
+  MotionSel sel;
+  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
+  sel.pairs = pairs; sel.required_self_clearance = required_self_clearance;
+  sel.required_pos_margin = required_pos_margin; sel.max_time_scale = max_time_scale;
+  sel.best = best; sel.n_eligible = n_eligible; sel.time_scale_best = time_scale_best;
+  sel.traj_best = traj_best; sel.dense_best = dense_best;
+  return sel;
 }
 
 }  // namespace
@@ -253,24 +155,17 @@ int gpmp2mi_motion_score_traj_dev(const gpmp2mi_robot* r, const gpmp2mi_motion_l
   MotionLimitsDev lim;
   G2_TRY(read_limits(l, r->h.dof, &lim));
   if (B == 0) return GPMP2MI_OK;
-  G2_TRY(ensure_device());
-  int cur = -1;
-  G2_HIP(hipGetDevice(&cur));
-  G2_CHECK(cur == r->device, GPMP2MI_ERR_INVALID, "the robot handle lives on another device than the current one");
   const int Md = total_step * (inter_step + 1) + 1;
   const int nblk = score_blocks(Md);
-  std::lock_guard<std::mutex> lk(r->score_mu);
-  G2_TRY(ws_reserve(&r->motion_ws, &r->motion_ws_bytes, (size_t)B * nblk * sizeof(MotionRec)));
+  std::unique_lock<std::mutex> lk;
+  G2_TRY(records_ready(r, nullptr, r->motion_ws, (size_t)B * nblk * sizeof(MotionRec), lk));
   MotionFinish f{};
   f.sel.B = B;
-  f.recs = (MotionRec*)r->motion_ws;
+  f.recs = (MotionRec*)r->motion_ws.p;
   f.nblk = nblk;
   f.limit_point_speed = l->point_speed;
-  MotionOut o;
-  o.pos_margin = pos_margin; o.vel_ratio = vel_ratio; o.acc_ratio = acc_ratio; o.point_speed = point_speed;
-  o.time_scale = time_scale; o.worst = worst; o.invalid = invalid;
-  set_outputs(f, o);
-  G2_TRY(launch_motion(r->h, r->d, lim, delta_t, inter_step, B, total_step, traj, (MotionRec*)r->motion_ws,
+  set_outputs(f, make_out(pos_margin, vel_ratio, acc_ratio, point_speed, time_scale, worst, invalid));
+  G2_TRY(launch_motion(r->h, r->d, lim, delta_t, inter_step, B, total_step, traj, (MotionRec*)r->motion_ws.p,
                        (hipStream_t)stream));
   return launch_motion_finish(f, (hipStream_t)stream);
 }
@@ -301,18 +196,14 @@ int gpmp2mi_motion_score_traj(const gpmp2mi_robot* r, const gpmp2mi_motion_limit
 int gpmp2mi_plan_motion_score(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter_step, double* pos_margin,
                               double* vel_ratio, double* acc_ratio, double* point_speed, double* time_scale, int* worst,
                               int* invalid) {
-  MotionOut o;
-  o.pos_margin = pos_margin; o.vel_ratio = vel_ratio; o.acc_ratio = acc_ratio; o.point_speed = point_speed;
-  o.time_scale = time_scale; o.worst = worst; o.invalid = invalid;
-  return plan_motion(p, l, inter_step, o, nullptr, true, nullptr);
+  return plan_motion(p, l, inter_step, make_out(pos_margin, vel_ratio, acc_ratio, point_speed, time_scale, worst, invalid),
+                     nullptr, true, nullptr);
 }
 int gpmp2mi_plan_motion_score_dev(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter_step, double* pos_margin,
                                   double* vel_ratio, double* acc_ratio, double* point_speed, double* time_scale,
                                   int* worst, int* invalid, void* stream) {
-  MotionOut o;
-  o.pos_margin = pos_margin; o.vel_ratio = vel_ratio; o.acc_ratio = acc_ratio; o.point_speed = point_speed;
-  o.time_scale = time_scale; o.worst = worst; o.invalid = invalid;
-  return plan_motion(p, l, inter_step, o, nullptr, false, (hipStream_t)stream);
+  return plan_motion(p, l, inter_step, make_out(pos_margin, vel_ratio, acc_ratio, point_speed, time_scale, worst, invalid),
+                     nullptr, false, (hipStream_t)stream);
 }
 
 int gpmp2mi_plan_select_feasible(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
@@ -320,12 +211,8 @@ int gpmp2mi_plan_select_feasible(gpmp2mi_plan* p, int inter_step, double require
                                  const gpmp2mi_motion_limits* l, double required_pos_margin, double max_time_scale,
                                  int* best, int* n_eligible, double* time_scale_best, double* traj_best,
                                  double* dense_best) {
-  MotionSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.pairs = pairs; sel.required_self_clearance = required_self_clearance;
-  sel.required_pos_margin = required_pos_margin; sel.max_time_scale = max_time_scale;
-  sel.best = best; sel.n_eligible = n_eligible; sel.time_scale_best = time_scale_best;
-  sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const MotionSel sel = make_sel(required_clearance, require_in_range, pairs, required_self_clearance, required_pos_margin,
+                                 max_time_scale, best, n_eligible, time_scale_best, traj_best, dense_best);
   return plan_motion(p, l, inter_step, MotionOut{}, &sel, true, nullptr);
 }
 int gpmp2mi_plan_select_feasible_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
@@ -333,12 +220,8 @@ int gpmp2mi_plan_select_feasible_dev(gpmp2mi_plan* p, int inter_step, double req
                                      const gpmp2mi_motion_limits* l, double required_pos_margin, double max_time_scale,
                                      int* best, int* n_eligible, double* time_scale_best, double* traj_best,
                                      double* dense_best, void* stream) {
-  MotionSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.pairs = pairs; sel.required_self_clearance = required_self_clearance;
-  sel.required_pos_margin = required_pos_margin; sel.max_time_scale = max_time_scale;
-  sel.best = best; sel.n_eligible = n_eligible; sel.time_scale_best = time_scale_best;
-  sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const MotionSel sel = make_sel(required_clearance, require_in_range, pairs, required_self_clearance, required_pos_margin,
+                                 max_time_scale, best, n_eligible, time_scale_best, traj_best, dense_best);
   return plan_motion(p, l, inter_step, MotionOut{}, &sel, false, (hipStream_t)stream);
 }
 

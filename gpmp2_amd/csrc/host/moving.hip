@@ -11,14 +11,17 @@ using namespace g2;
 
 namespace {
 
-// the rules of check_score_args, then the launch limits of this stage (the tile of the self check, Md S K pairs per row)
-int check_moving_args(const gpmp2mi_robot* r, int K, int inter, int B, int total_step, double delta_t) {
-  G2_TRY(check_score_args(inter, B, total_step, delta_t));
+// behind the rules of check_score_args: the launch limits of this stage (the tile of the self check, Md S K pairs per row)
+int check_moving_limits(const gpmp2mi_robot* r, int K, int inter, int B, int total_step) {
   const int S = r->h.nr_spheres;
   const long long Md = (long long)total_step * (inter + 1) + 1;
   G2_CHECK((long long)self_blocks((int)Md, S) * std::max(B, 1) < (1ll << 31) && Md * std::max(S * K, 1) < (1ll << 31),
            GPMP2MI_ERR_INVALID, "too many checked (state, sphere, moving sphere)s for one launch");
   return GPMP2MI_OK;
+}
+int check_moving_args(const gpmp2mi_robot* r, int K, int inter, int B, int total_step, double delta_t) {
+  G2_TRY(check_score_args(inter, B, total_step, delta_t));
+  return check_moving_limits(r, K, inter, B, total_step);
 }
 
 int check_set_args(int K, int cap, const double* radius, const double* centers) {
@@ -58,137 +61,50 @@ struct MovingSel : ScoreSel {
   const gpmp2mi_self_pairs* pairs = nullptr;
 };
 
-// Layout of a plan's moving workspace for (B, N, D, S, inter): the records, the per-row scores of the existing stages,
-// then the staging of the host-pointer forms
-struct PlanMovingWs {
-  ScoreRec* recs;
-  double *clearance, *self_clearance;
-  int *oor, *self_invalid;
-  ScoreOut out;   // worst: [B][3]
-  int* pick;      // best, n_eligible, then (8-byte aligned) the chosen row's final_error: one 16-byte copy
-  double *traj_best, *dense_best;
-  size_t bytes;
-};
-PlanMovingWs plan_ws_layout(char* base, int B, int N, int D, int S, int inter) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanMovingWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
-  w.recs = (ScoreRec*)take((size_t)B * self_blocks((int)Md, S) * sizeof(ScoreRec));
-  w.clearance = (double*)take(B * sizeof(double));
-  w.self_clearance = (double*)take(B * sizeof(double));
-  w.oor = (int*)take(B * sizeof(int));
-  w.self_invalid = (int*)take(B * sizeof(int));
-  w.out.support = (double*)take(B * sizeof(double));
-  w.out.dense = (double*)take(B * sizeof(double));
-  w.out.clearance = (double*)take(B * sizeof(double));
-  w.out.worst = (int*)take((size_t)3 * B * sizeof(int));
-  w.out.oor = (int*)take(B * sizeof(int));
-  w.pick = (int*)take(2 * sizeof(int) + sizeof(double));
-  w.traj_best = (double*)take((size_t)(N + 1) * 2 * D * sizeof(double));
-  w.dense_best = (double*)take(Md * 2 * D * sizeof(double));
-  w.bytes = off;
-  return w;
-}
-
 // Scores the plan's resident result against its resident set on `st`; sel != null: the existing stages for the same
 // rows first, then the extended rule and the copy of the chosen row.  host / out / sel as plan_score (score.hip);
-// out.oor: invalid.
+// out.oor: invalid, out.worst: [B][3].
 int plan_moving(gpmp2mi_plan* p, int inter, const ScoreOut& out, const MovingSel* sel, bool host, hipStream_t st) {
   G2_CHECK(p, GPMP2MI_ERR_INVALID, "null plan");
   G2_CHECK(p->ex.mv_cap > 0, GPMP2MI_ERR_INVALID, "the plan was created without room for moving spheres");
-  G2_PLAN_LIVE(p);   // before anything is enqueued
-  G2_CHECK(p->optimized, GPMP2MI_ERR_INVALID, "plan has not been optimized");
+  G2_TRY(check_plan_ready(p, inter));
   const PlanParams& P = p->hp;
   const PlanExtras& ex = p->ex;
-  G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
-  G2_TRY(check_moving_args(p->robot, ex.mv_K, inter, P.B, P.N, P.delta_t));
-  const int S = p->robot->h.nr_spheres;
-  G2_TRY(ws_reserve(&p->moving_ws, &p->moving_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, S, inter).bytes));
-  const PlanMovingWs w = plan_ws_layout((char*)p->moving_ws, P.B, P.N, P.D, S, inter);
-  const size_t Md = (size_t)P.N * (inter + 1) + 1;
+  G2_TRY(check_moving_limits(p->robot, ex.mv_K, inter, P.B, P.N));
+  const int S = p->robot->h.nr_spheres, Md = P.N * (inter + 1) + 1;
+  const size_t rec_bytes = (size_t)P.B * self_blocks(Md, S) * sizeof(ScoreRec);
+  RowOut rows[SCORE_ROWS];
+  rows_of(out, MOVING_WORST, rows);
+  const auto layout = [&](void* base) { return carve_moving((char*)base, rec_bytes, rows, shape_of(p, inter)); };
+  CheckWs w;
+  G2_TRY(carve_into(p->ws[p->WS_MOVING], layout, &w));
   MovingFinish f{};
-  const ScoreOut& o = host ? w.out : out;
-  // the host form computes only what the caller asked for
-  f.support = (!host || out.support) ? o.support : nullptr;
-  f.dense = (!host || out.dense) ? o.dense : nullptr;
-  f.min_clearance = (!host || out.clearance) ? o.clearance : nullptr;
-  f.worst = (!host || out.worst) ? o.worst : nullptr;
-  f.invalid = (!host || out.oor) ? o.oor : nullptr;
-  f.recs = w.recs;
-  f.nblk = self_blocks((int)Md, S);
+  const ScoreOut o = score_out(rows, host);
+  f.support = o.support;
+  f.dense = o.dense;
+  f.min_clearance = o.clearance;
+  f.worst = o.worst;
+  f.invalid = o.oor;
+  f.recs = (ScoreRec*)w.recs;
+  f.nblk = self_blocks(Md, S);
   f.K = ex.mv_K;
-  ScoreFinish& g = f.sel;
-  g.B = P.B;
-  g.N = P.N;
-  g.D = P.D;
-  g.lie = p->robot->h.kind >= GPMP2MI_ROBOT_POSE2_MOBILE_BASE;
-  g.inter = inter;
-  g.Md = (int)Md;
-  g.dt = P.delta_t;
-  g.traj = p->pb.result;
+  plan_shape(f.sel, p, inter);
   if (sel) {
-    g.select = 1;
-    g.required_clearance = sel->required_clearance;
-    g.require_in_range = sel->require_in_range;
+    point_selection(f.sel, p, *sel, nullptr, host, w.sel);
     f.required_self_clearance = sel->required_self_clearance;
     f.required_moving_clearance = sel->required_moving_clearance;
-    g.ferr = p->pb.final_err;
-    g.status = p->pb.status;
-    g.best = host ? w.pick : sel->best;
-    g.n_eligible = host ? w.pick + 1 : sel->n_eligible;
-    g.best_err = host ? (double*)(w.pick + 2) : nullptr;
-    g.traj_best = host ? (sel->traj_best ? w.traj_best : nullptr) : sel->traj_best;
-    g.dense_best = host ? (sel->dense_best ? w.dense_best : nullptr) : sel->dense_best;
-    // the per-row scores of the existing stages, into the workspace.  The self check goes first: it is the one that
-    // can still refuse (a table made for another robot), and a refused call enqueues nothing.
-    if (sel->pairs) {
-      ScoreOut so;
-      so.clearance = w.self_clearance;
-      so.oor = w.self_invalid;
-      G2_TRY(plan_self_score(p, sel->pairs, inter, so, nullptr, false, st));
-      f.self_clearance = w.self_clearance;
-      f.self_invalid = w.self_invalid;
-    }
-    ScoreOut so;
-    so.clearance = w.clearance;
-    so.oor = w.oor;
-    G2_TRY(plan_score(p, inter, so, nullptr, false, st));
-    f.clearance = w.clearance;
-    f.oor = w.oor;
+    PriorRows got;
+    G2_TRY(enqueue_prior_stages(p, sel->pairs, inter, w.prior, st, &got));
+    f.clearance = got.clearance;
+    f.oor = got.oor;
+    f.self_clearance = got.self_clearance;
+    f.self_invalid = got.self_invalid;
   }
   p->mark_dirty(st);
   G2_TRY(launch_moving_clearance(p->robot->h, p->robot->d, ex.mv_K, ex.mv_radius, ex.mv_centers, ex.mv_eps, P.delta_t, inter,
-                                 P.B, P.N, p->pb.result, w.recs, st));
+                                 P.B, P.N, p->pb.result, (ScoreRec*)w.recs, st));
   G2_TRY(launch_moving_finish(f, st));
-  if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
-  G2_TRY(back(out.support, w.out.support, P.B * sizeof(double)));
-  G2_TRY(back(out.dense, w.out.dense, P.B * sizeof(double)));
-  G2_TRY(back(out.clearance, w.out.clearance, P.B * sizeof(double)));
-  G2_TRY(back(out.worst, w.out.worst, (size_t)3 * P.B * sizeof(int)));
-  G2_TRY(back(out.oor, w.out.oor, P.B * sizeof(int)));
-  struct { int best, n; double err; } pick{-1, 0, 0.0};
-  if (sel) G2_TRY(back(&pick, w.pick, sizeof(pick)));
-  G2_HIP(hipStreamSynchronize(st));
-  if (sel) {
-    if (sel->best) *sel->best = pick.best;
-    if (sel->n_eligible) *sel->n_eligible = pick.n;
-    if (pick.best >= 0 && (sel->traj_best || sel->dense_best)) {   // nothing chosen: the trajectory outputs stay as they are
-      G2_TRY(back(sel->traj_best, w.traj_best, (size_t)(P.N + 1) * 2 * P.D * sizeof(double)));
-      G2_TRY(back(sel->dense_best, w.dense_best, Md * 2 * P.D * sizeof(double)));
-      G2_HIP(hipStreamSynchronize(st));
-    }
-  }
-  p->mark_clean(st);
-  return GPMP2MI_OK;
+  return host ? finish_host(p, inter, rows, SCORE_ROWS, sel, nullptr, w.sel, st) : GPMP2MI_OK;
 }
 
 int check_traj_call(const gpmp2mi_robot* r, int K, const double* radius, const double* centers, double epsilon,
@@ -199,11 +115,6 @@ int check_traj_call(const gpmp2mi_robot* r, int K, const double* radius, const d
   return check_moving_args(r, K, inter, B, total_step, delta_t);
 }
 
-ScoreOut make_out(double* support, double* dense, double* clearance, int* worst, int* invalid) {
-  ScoreOut o;
-  o.support = support; o.dense = dense; o.clearance = clearance; o.worst = worst; o.oor = invalid;
-  return o;
-}
 MovingSel make_sel(double required_clearance, int require_in_range, const gpmp2mi_self_pairs* pairs,
                    double required_self_clearance, double required_moving_clearance, int* best, int* n_eligible,
                    double* traj_best, double* dense_best) {
@@ -256,17 +167,13 @@ int gpmp2mi_moving_score_traj_dev(const gpmp2mi_robot* r, int K, const double* r
                                   double* min_moving_clearance, int* worst, int* invalid, void* stream) {
   G2_TRY(check_traj_call(r, K, radius, centers, epsilon, delta_t, inter_step, B, total_step, traj));
   if (B == 0) return GPMP2MI_OK;
-  G2_TRY(ensure_device());
-  int cur = -1;
-  G2_HIP(hipGetDevice(&cur));
-  G2_CHECK(cur == r->device, GPMP2MI_ERR_INVALID, "the robot handle lives on another device than the current one");
   const int Md = total_step * (inter_step + 1) + 1;
   const int nblk = self_blocks(Md, r->h.nr_spheres);
-  std::lock_guard<std::mutex> lk(r->score_mu);
-  G2_TRY(ws_reserve(&r->moving_ws, &r->moving_ws_bytes, (size_t)B * nblk * sizeof(ScoreRec)));
+  std::unique_lock<std::mutex> lk;
+  G2_TRY(records_ready(r, nullptr, r->moving_ws, (size_t)B * nblk * sizeof(ScoreRec), lk));
   MovingFinish f{};
   f.sel.B = B;
-  f.recs = (ScoreRec*)r->moving_ws;
+  f.recs = (ScoreRec*)r->moving_ws.p;
   f.nblk = nblk;
   f.K = K;
   f.support = moving_support_cost;
@@ -275,7 +182,7 @@ int gpmp2mi_moving_score_traj_dev(const gpmp2mi_robot* r, int K, const double* r
   f.worst = worst;
   f.invalid = invalid;
   G2_TRY(launch_moving_clearance(r->h, r->d, K, radius, centers, epsilon, delta_t, inter_step, B, total_step, traj,
-                                 (ScoreRec*)r->moving_ws, (hipStream_t)stream));
+                                 (ScoreRec*)r->moving_ws.p, (hipStream_t)stream));
   return launch_moving_finish(f, (hipStream_t)stream);
 }
 

@@ -86,135 +86,51 @@ int set_path(gpmp2mi_plan* p, const double* des, const double* sigma, bool host,
   return GPMP2MI_OK;
 }
 
-struct PathOut {
-  double *max_pos = nullptr, *max_rot = nullptr;
-  int* worst = nullptr;
-  double *support = nullptr, *dense = nullptr;
-  int* invalid = nullptr;
-};
 struct PathSel : ScoreSel {
   double allowed_pos = 0.0, allowed_rot = 0.0;
 };
-
-// Layout of a plan's path workspace for (B, N, D, inter): the records, the per-row scores of the obstacle stage, then
-// the staging of the host-pointer forms
-struct PlanPathWs {
-  PathRec* recs;
-  double* clearance;
-  int* oor;
-  PathOut out;
-  int* pick;      // best, n_eligible, then (8-byte aligned) the chosen row's final_error: one 16-byte copy
-  double *traj_best, *dense_best;
-  size_t bytes;
-};
-PlanPathWs plan_ws_layout(char* base, int B, int N, int D, int inter) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanPathWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
-  w.recs = (PathRec*)take((size_t)B * path_blocks((int)Md) * sizeof(PathRec));
-  w.clearance = (double*)take(B * sizeof(double));
-  w.oor = (int*)take(B * sizeof(int));
-  w.out.max_pos = (double*)take(B * sizeof(double));
-  w.out.max_rot = (double*)take(B * sizeof(double));
-  w.out.worst = (int*)take((size_t)2 * B * sizeof(int));
-  w.out.support = (double*)take(B * sizeof(double));
-  w.out.dense = (double*)take(B * sizeof(double));
-  w.out.invalid = (int*)take(B * sizeof(int));
-  w.pick = (int*)take(2 * sizeof(int) + sizeof(double));
-  w.traj_best = (double*)take((size_t)(N + 1) * 2 * D * sizeof(double));
-  w.dense_best = (double*)take(Md * 2 * D * sizeof(double));
-  w.bytes = off;
-  return w;
-}
 
 // Scores the plan's resident result against its resident path on `st`; sel != null: the obstacle stage for the same
 // rows first, then the extended rule and the copy of the chosen row.  host / out / sel as plan_score (score.hip).
 int plan_path(gpmp2mi_plan* p, int inter, const PathOut& out, const PathSel* sel, bool host, hipStream_t st) {
   G2_CHECK(p, GPMP2MI_ERR_INVALID, "null plan");
   G2_CHECK(p->ex.wp_cap > 0, GPMP2MI_ERR_INVALID, "the plan was created without workspace_path");
-  G2_PLAN_LIVE(p);   // before anything is enqueued
-  G2_CHECK(p->optimized, GPMP2MI_ERR_INVALID, "plan has not been optimized");
+  G2_TRY(check_plan_ready(p, inter));
   const PlanParams& P = p->hp;
   const PlanExtras& ex = p->ex;
-  G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
-  G2_TRY(check_score_args(inter, P.B, P.N, P.delta_t));
-  G2_TRY(ws_reserve(&p->path_ws, &p->path_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, inter).bytes));
-  const PlanPathWs w = plan_ws_layout((char*)p->path_ws, P.B, P.N, P.D, inter);
-  const size_t Md = (size_t)P.N * (inter + 1) + 1;
+  const int Md = P.N * (inter + 1) + 1;
+  const size_t rec_bytes = (size_t)P.B * path_blocks(Md) * sizeof(PathRec);
+  RowOut rows[PATH_ROWS];
+  rows_of(out, rows);
+  const auto layout = [&](void* base) { return carve_path((char*)base, rec_bytes, rows, shape_of(p, inter)); };
+  CheckWs w;
+  G2_TRY(carve_into(p->ws[p->WS_PATH], layout, &w));
   PathFinish f{};
-  const PathOut& o = host ? w.out : out;
-  // the host form computes only what the caller asked for
-  f.max_pos = (!host || out.max_pos) ? o.max_pos : nullptr;
-  f.max_rot = (!host || out.max_rot) ? o.max_rot : nullptr;
-  f.worst = (!host || out.worst) ? o.worst : nullptr;
-  f.support = (!host || out.support) ? o.support : nullptr;
-  f.dense = (!host || out.dense) ? o.dense : nullptr;
-  f.invalid = (!host || out.invalid) ? o.invalid : nullptr;
-  f.recs = w.recs;
-  f.nblk = path_blocks((int)Md);
-  ScoreFinish& g = f.sel;
-  g.B = P.B;
-  g.N = P.N;
-  g.D = P.D;
-  g.lie = p->robot->h.kind >= GPMP2MI_ROBOT_POSE2_MOBILE_BASE;
-  g.inter = inter;
-  g.Md = (int)Md;
-  g.dt = P.delta_t;
-  g.traj = p->pb.result;
+  const PathOut o = path_out(rows, host);
+  f.max_pos = o.max_pos;
+  f.max_rot = o.max_rot;
+  f.worst = o.worst;
+  f.support = o.support;
+  f.dense = o.dense;
+  f.invalid = o.invalid;
+  f.recs = (PathRec*)w.recs;
+  f.nblk = path_blocks(Md);
+  plan_shape(f.sel, p, inter);
   if (sel) {
-    g.select = 1;
-    g.required_clearance = sel->required_clearance;
-    g.require_in_range = sel->require_in_range;
+    point_selection(f.sel, p, *sel, nullptr, host, w.sel);
     f.allowed_pos = sel->allowed_pos;
     f.allowed_rot = sel->allowed_rot;
-    g.ferr = p->pb.final_err;
-    g.status = p->pb.status;
-    g.best = host ? w.pick : sel->best;
-    g.n_eligible = host ? w.pick + 1 : sel->n_eligible;
-    g.best_err = host ? (double*)(w.pick + 2) : nullptr;
-    g.traj_best = host ? (sel->traj_best ? w.traj_best : nullptr) : sel->traj_best;
-    g.dense_best = host ? (sel->dense_best ? w.dense_best : nullptr) : sel->dense_best;
-    ScoreOut so;   // the per-row scores of the obstacle stage, into the workspace
-    so.clearance = w.clearance;
-    so.oor = w.oor;
-    G2_TRY(plan_score(p, inter, so, nullptr, false, st));
-    f.clearance = w.clearance;
-    f.oor = w.oor;
+    PriorRows got;   // the obstacle stage alone: this rule asks for no self clearance
+    G2_TRY(enqueue_prior_stages(p, nullptr, inter, w.prior, st, &got));
+    f.clearance = got.clearance;
+    f.oor = got.oor;
   }
   p->mark_dirty(st);
   G2_TRY(launch_path_deviation(p->robot->h, p->robot->d, ex.wp_mode, ex.wp_link, ex.wp_des,
-                               ex.wp_n > 0 ? ex.wp_sigma : nullptr, P.delta_t, inter, P.B, P.N, p->pb.result, w.recs, st));
+                               ex.wp_n > 0 ? ex.wp_sigma : nullptr, P.delta_t, inter, P.B, P.N, p->pb.result,
+                               (PathRec*)w.recs, st));
   G2_TRY(launch_path_finish(f, st));
-  if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
-  G2_TRY(back(out.max_pos, w.out.max_pos, P.B * sizeof(double)));
-  G2_TRY(back(out.max_rot, w.out.max_rot, P.B * sizeof(double)));
-  G2_TRY(back(out.worst, w.out.worst, (size_t)2 * P.B * sizeof(int)));
-  G2_TRY(back(out.support, w.out.support, P.B * sizeof(double)));
-  G2_TRY(back(out.dense, w.out.dense, P.B * sizeof(double)));
-  G2_TRY(back(out.invalid, w.out.invalid, P.B * sizeof(int)));
-  struct { int best, n; double err; } pick{-1, 0, 0.0};
-  if (sel) G2_TRY(back(&pick, w.pick, sizeof(pick)));
-  G2_HIP(hipStreamSynchronize(st));
-  if (sel) {
-    if (sel->best) *sel->best = pick.best;
-    if (sel->n_eligible) *sel->n_eligible = pick.n;
-    if (pick.best >= 0 && (sel->traj_best || sel->dense_best)) {   // nothing chosen: the trajectory outputs stay as they are
-      G2_TRY(back(sel->traj_best, w.traj_best, (size_t)(P.N + 1) * 2 * P.D * sizeof(double)));
-      G2_TRY(back(sel->dense_best, w.dense_best, Md * 2 * P.D * sizeof(double)));
-      G2_HIP(hipStreamSynchronize(st));
-    }
-  }
-  p->mark_clean(st);
-  return GPMP2MI_OK;
+  return host ? finish_host(p, inter, rows, PATH_ROWS, sel, nullptr, w.sel, st) : GPMP2MI_OK;
 }
 
 int check_traj_call(const gpmp2mi_robot* r, int mode, int link, const double* des, const double* sigma, double delta_t,
@@ -271,17 +187,13 @@ int gpmp2mi_path_score_traj_dev(const gpmp2mi_robot* r, int mode, int link, cons
                                 double* dense_cost, int* invalid, void* stream) {
   G2_TRY(check_traj_call(r, mode, link, des, sigma, delta_t, inter_step, B, total_step, traj));
   if (B == 0) return GPMP2MI_OK;
-  G2_TRY(ensure_device());
-  int cur = -1;
-  G2_HIP(hipGetDevice(&cur));
-  G2_CHECK(cur == r->device, GPMP2MI_ERR_INVALID, "the robot handle lives on another device than the current one");
   const int Md = total_step * (inter_step + 1) + 1;
   const int nblk = path_blocks(Md);
-  std::lock_guard<std::mutex> lk(r->score_mu);
-  G2_TRY(ws_reserve(&r->path_ws, &r->path_ws_bytes, (size_t)B * nblk * sizeof(PathRec)));
+  std::unique_lock<std::mutex> lk;
+  G2_TRY(records_ready(r, nullptr, r->path_ws, (size_t)B * nblk * sizeof(PathRec), lk));
   PathFinish f{};
   f.sel.B = B;
-  f.recs = (PathRec*)r->path_ws;
+  f.recs = (PathRec*)r->path_ws.p;
   f.nblk = nblk;
   f.max_pos = max_pos_dev;
   f.max_rot = max_rot_dev;
@@ -290,7 +202,7 @@ int gpmp2mi_path_score_traj_dev(const gpmp2mi_robot* r, int mode, int link, cons
   f.dense = dense_cost;
   f.invalid = invalid;
   G2_TRY(launch_path_deviation(r->h, r->d, mode, link, des, sigma, delta_t, inter_step, B, total_step, traj,
-                               (PathRec*)r->path_ws, (hipStream_t)stream));
+                               (PathRec*)r->path_ws.p, (hipStream_t)stream));
   return launch_path_finish(f, (hipStream_t)stream);
 }
 

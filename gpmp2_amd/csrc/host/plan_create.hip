@@ -81,6 +81,7 @@ using namespace g2;
 gpmp2mi_plan::~gpmp2mi_plan() {
   if (poisoned) {
     g_leaked_plans.fetch_add(1);
+    for (Workspace& w : ws) w.leak();   // the members are destroyed behind this body: hipFree would wait for the kernel
     return;
   }
   drain();
@@ -90,19 +91,7 @@ gpmp2mi_plan::~gpmp2mi_plan() {
     else (void)hipFree(allocs[k]);
   }
   flags_release(flagbuf);
-  if (qws) (void)hipFree(qws);
-  if (score_ws) (void)hipFree(score_ws);
-  if (post_ws) (void)hipFree(post_ws);
-  if (seed_ws) (void)hipFree(seed_ws);
-  if (risk_ws) (void)hipFree(risk_ws);
   if (risk_qc) (void)hipFree(risk_qc);
-  if (sampled_ws) (void)hipFree(sampled_ws);
-  if (self_ws) (void)hipFree(self_ws);
-  if (group_ws) (void)hipFree(group_ws);
-  if (motion_ws) (void)hipFree(motion_ws);
-  if (moving_ws) (void)hipFree(moving_ws);
-  if (path_ws) (void)hipFree(path_ws);
-  if (retime_ws) (void)hipFree(retime_ws);
   sampled_fac.release();
   flags_release(qflags);
 }

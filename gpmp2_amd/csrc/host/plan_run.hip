@@ -287,19 +287,13 @@ static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* pas
   // host_flags [cap] (device memory: the host reads k_queue_scan's counts instead)
   const size_t ints = 5 * (size_t)B + 1 + 3 * (size_t)cap;
   const size_t bytes = sizeof(long long) + ints * sizeof(int);
-  if (bytes > p->qws_bytes) {
-    if (p->qws) G2_HIP(hipFree(p->qws));
-    p->qws = nullptr;
-    p->qws_bytes = 0;
-    G2_TRY(dev_malloc(&p->qws, bytes));
-    p->qws_bytes = bytes;
-  }
+  G2_TRY(p->ws[p->WS_QUEUE].reserve(bytes));
   if (p->qflags.cap < cap) {
     flags_release(p->qflags);
     p->qflags = FlagBuf{};
     G2_TRY(flags_acquire(cap, &p->qflags));
   }
-  q.busy = (long long*)p->qws;
+  q.busy = (long long*)p->ws[p->WS_QUEUE].p;
   int* w = (int*)(q.busy + 1);
   q.job = w;
   q.next = w + B;
@@ -479,7 +473,7 @@ int g2::plan_optimize_queue(gpmp2mi_plan* p, QueueRun io, bool host, hipStream_t
   G2_TRY(guarded_run(p, st, host ? &stage : nullptr, [&] { return plan_queue_impl(p, st, q, &passes); }));
   p->qstats.passes = passes;
   p->qstats.slot_passes = (long)P.B * passes;
-  G2_HIP(hipMemcpy(&p->qstats.busy_slot_passes, p->qws, sizeof(long long), hipMemcpyDeviceToHost));
+  G2_HIP(hipMemcpy(&p->qstats.busy_slot_passes, p->ws[p->WS_QUEUE].p, sizeof(long long), hipMemcpyDeviceToHost));
   p->queue_ran = true;
   if (host) {
     G2_TRY(stage.download(io, 0, st));   // (the same on a failure here)

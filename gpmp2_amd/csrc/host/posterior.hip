@@ -77,8 +77,8 @@ int plan_posterior_dev(gpmp2mi_plan* p, const double* traj, int K, const double*
                        double* delta, int* ok, hipStream_t st) {
   const PlanParams& P = p->hp;
   if (!traj) traj = p->optimized ? p->pb.result : p->pb.init;
-  G2_TRY(ws_reserve(&p->post_ws, &p->post_ws_bytes, post_ws_layout(nullptr, P).bytes));
-  const PlanPostWs w = post_ws_layout((char*)p->post_ws, P);
+  G2_TRY(p->ws[p->WS_POST].reserve(post_ws_layout(nullptr, P).bytes));
+  const PlanPostWs w = post_ws_layout((char*)p->ws[p->WS_POST].p, P);
   p->mark_dirty(st);
   // into the spare record buffer (the one that does not hold the linearization at `cur`), as gpmp2mi_plan_linearize
   G2_TRY(plan_linearize(p, traj, 1, nullptr, st));
@@ -110,7 +110,7 @@ int plan_posterior_host(gpmp2mi_plan* p, const double* traj, int K, const double
 
 int g2::plan_posterior_factor(gpmp2mi_plan* p, int* ok, const double** fac, hipStream_t st) {
   G2_TRY(plan_posterior_dev(p, nullptr, 0, nullptr, nullptr, nullptr, nullptr, ok, st));
-  *fac = post_ws_layout((char*)p->post_ws, p->hp).fac;
+  *fac = post_ws_layout((char*)p->ws[p->WS_POST].p, p->hp).fac;
   return GPMP2MI_OK;
 }
 

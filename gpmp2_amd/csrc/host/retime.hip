@@ -30,39 +30,11 @@ int check_kind(const gpmp2mi_robot* r) {
   return GPMP2MI_OK;
 }
 
-struct RetimeOut {
-  double *sdot = nullptr, *u = nullptr, *stamps = nullptr, *duration = nullptr, *achieved = nullptr, *dense = nullptr;
-  int* status = nullptr;
-};
-
-// what k_retime_caps and k_retime need for (B, Md), whoever keeps it: ps and X [B][Md], K [B][Md][2], then the profile
-struct CoreWs {
-  double *ps, *X, *K, *sdot, *u, *stamps;
-};
-template <class Take>
-CoreWs core_layout(Take&& take, int B, size_t Md) {
-  CoreWs w;
-  w.ps = (double*)take(B * Md * sizeof(double));
-  w.X = (double*)take(B * Md * sizeof(double));
-  w.K = (double*)take(2 * B * Md * sizeof(double));
-  w.sdot = (double*)take(B * Md * sizeof(double));
-  w.u = (double*)take(B * Md * sizeof(double));
-  w.stamps = (double*)take(B * Md * sizeof(double));
-  return w;
-}
-struct Carver {
-  char* base;
-  size_t off = 0;
-  char* operator()(size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  }
-};
-
-// k_retime_caps, then k_retime over `traj`; o: device pointers, a null sdot / u / stamps takes the workspace's
+// k_retime_caps, then k_retime over `traj`; o: device pointers, a null sdot / u / stamps takes the workspace's (the
+// first rows of `rows`, carved with `w`)
 int enqueue_retime(const gpmp2mi_robot* r, const MotionLimitsDev& lim, double point_speed, double dt, int inter, int B,
-                   int N, const double* traj, const Rates& rt, const CoreWs& w, const RetimeOut& o, hipStream_t st) {
+                   int N, const double* traj, const Rates& rt, const RetimeCore& w, const RowOut* rows, const RetimeOut& o,
+                   hipStream_t st) {
   RetimeArgs a{};
   a.B = B;
   a.N = N;
@@ -83,9 +55,9 @@ int enqueue_retime(const gpmp2mi_robot* r, const MotionLimitsDev& lim, double po
   a.ps = w.ps;
   a.X = w.X;
   a.K = w.K;
-  a.sdot = o.sdot ? o.sdot : w.sdot;
-  a.u = o.u ? o.u : w.u;
-  a.stamps = o.stamps ? o.stamps : w.stamps;
+  a.sdot = o.sdot ? o.sdot : (double*)rows[0].staged;
+  a.u = o.u ? o.u : (double*)rows[1].staged;
+  a.stamps = o.stamps ? o.stamps : (double*)rows[2].staged;
   a.duration = o.duration;
   a.achieved = o.achieved;
   a.dense = o.dense;
@@ -94,52 +66,10 @@ int enqueue_retime(const gpmp2mi_robot* r, const MotionLimitsDev& lim, double po
   return launch_retime(a, true, st);
 }
 
-struct RetimeSel {
-  double required_clearance = 0.0, required_self_clearance = 0.0, required_pos_margin = 0.0, max_duration = 0.0;
-  int require_in_range = 0;
+struct RetimeSel : ScoreSel {
+  double required_self_clearance = 0.0, required_pos_margin = 0.0, max_duration = 0.0;
   const gpmp2mi_self_pairs* pairs = nullptr;
-  int *best = nullptr, *n_eligible = nullptr;
-  double *duration_best = nullptr, *stamps_best = nullptr, *traj_best = nullptr, *dense_best = nullptr;
-};
-
-// Layout of a plan's re-timing workspace for (B, N, D, inter): the core, the per-row results, the per-row scores of the
-// existing stages, then the staging of the host-pointer forms
-struct PlanRetimeWs {
-  CoreWs core;
-  double *duration, *achieved, *dense;
-  int* status;
-  double *clearance, *self_clearance, *pos_margin;
-  int *oor, *self_invalid, *motion_invalid;
-  char* pick;   // best, n_eligible, then the chosen row's final_error and duration: one 24-byte copy
-  double *traj_best, *dense_best, *stamps_best;
-  size_t bytes;
-};
-PlanRetimeWs plan_ws_layout(char* base, int B, int N, int D, int inter) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanRetimeWs w{};
-  Carver take{base};
-  w.core = core_layout(take, B, Md);
-  w.duration = (double*)take(B * sizeof(double));
-  w.achieved = (double*)take((size_t)4 * B * sizeof(double));
-  w.dense = (double*)take(B * Md * 2 * D * sizeof(double));
-  w.status = (int*)take(B * sizeof(int));
-  w.clearance = (double*)take(B * sizeof(double));
-  w.self_clearance = (double*)take(B * sizeof(double));
-  w.pos_margin = (double*)take(B * sizeof(double));
-  w.oor = (int*)take(B * sizeof(int));
-  w.self_invalid = (int*)take(B * sizeof(int));
-  w.motion_invalid = (int*)take(B * sizeof(int));
-  w.pick = take(2 * sizeof(int) + 2 * sizeof(double));
-  w.traj_best = (double*)take((size_t)(N + 1) * 2 * D * sizeof(double));
-  w.dense_best = (double*)take(Md * 2 * D * sizeof(double));
-  w.stamps_best = (double*)take(Md * sizeof(double));
-  w.bytes = take.off;
-  return w;
-}
-
-struct Pick {
-  int best, n;
-  double err, duration;
+  double *duration_best = nullptr, *stamps_best = nullptr;
 };
 
 // Re-times the plan's resident result on `st`; sel != null: the existing stages for the same rows first, then the rule
@@ -152,117 +82,53 @@ int plan_retime(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter, cons
   if (sel)
     G2_CHECK(!std::isnan(sel->required_pos_margin) && !std::isnan(sel->max_duration), GPMP2MI_ERR_INVALID,
              "required_pos_margin / max_duration is NaN");
-  G2_PLAN_LIVE(p);   // before anything is enqueued
-  G2_CHECK(p->optimized, GPMP2MI_ERR_INVALID, "plan has not been optimized");
+  G2_TRY(check_plan_ready(p, inter));
   const PlanParams& P = p->hp;
-  G2_TRY(check_score_args(inter, P.B, P.N, P.delta_t));
-  G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
   G2_TRY(check_kind(p->robot));
   MotionLimitsDev lim;
   G2_TRY(read_limits(l, P.D, &lim));
-  G2_TRY(ws_reserve(&p->retime_ws, &p->retime_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, inter).bytes));
-  const PlanRetimeWs w = plan_ws_layout((char*)p->retime_ws, P.B, P.N, P.D, inter);
   const size_t Md = (size_t)P.N * (inter + 1) + 1;
-  Pick* pick = (Pick*)w.pick;
-  RetimeOut o;
-  if (sel) {   // the rule reads the workspace's
-    o.duration = w.duration;
-    o.status = w.status;
-  } else if (host) {   // the host form computes only what the caller asked for
-    o.duration = out.duration ? w.duration : nullptr;
-    o.achieved = out.achieved ? w.achieved : nullptr;
-    o.dense = out.dense ? w.dense : nullptr;
-    o.status = out.status ? w.status : nullptr;
-  } else {
-    o = out;
-  }
+  RowOut rows[RETIME_ROWS];
+  rows_of(out, Md, P.D, rows);
+  const auto layout = [&](void* base) { return carve_retime((char*)base, rows, shape_of(p, inter)); };
+  RetimeWs w;
+  G2_TRY(carve_into(p->ws[p->WS_RETIME], layout, &w));
+  RetimeOut o = sel ? RetimeOut{} : retime_out(rows, host);
   RetimeFinish f{};
-  if (sel) {
-    ScoreFinish& g = f.sel;
-    g.B = P.B;
-    g.N = P.N;
-    g.D = P.D;
-    g.lie = 0;
-    g.inter = inter;
-    g.Md = (int)Md;
-    g.dt = P.delta_t;
-    g.traj = p->pb.result;
-    g.select = 1;
-    g.required_clearance = sel->required_clearance;
-    g.require_in_range = sel->require_in_range;
-    g.ferr = p->pb.final_err;
-    g.status = p->pb.status;
-    // the kernel reads `best` back for the chosen row's outputs: a device form without one gets the workspace's
-    g.best = (host || !sel->best) ? &pick->best : sel->best;
-    g.n_eligible = host ? &pick->n : sel->n_eligible;
-    g.best_err = host ? &pick->err : nullptr;
-    g.traj_best = host ? (sel->traj_best ? w.traj_best : nullptr) : sel->traj_best;
-    g.dense_best = host ? (sel->dense_best ? w.dense_best : nullptr) : sel->dense_best;
-    f.duration_best = host ? &pick->duration : sel->duration_best;
-    f.stamps_best = host ? (sel->stamps_best ? w.stamps_best : nullptr) : sel->stamps_best;
+  SelExtra x;
+  if (sel) {   // a selection has no per-row outputs of its own: the rule reads the workspace's duration and status
+    o.duration = (double*)rows[3].staged;
+    o.status = (int*)rows[6].staged;
+    plan_shape(f.sel, p, inter);
+    f.sel.lie = 0;   // the Pose2 kinds were refused above
+    x.value = sel->duration_best;
+    x.row = sel->stamps_best;
+    x.row_bytes = Md * sizeof(double);
+    const SelExtra k = point_selection(f.sel, p, *sel, &x, host, w.sel);
+    f.duration_best = k.value;
+    f.stamps_best = k.row;
     f.required_self_clearance = sel->required_self_clearance;
     f.required_pos_margin = sel->required_pos_margin;
     f.max_duration = sel->max_duration;
-    f.rstatus = w.status;
-    f.duration = w.duration;
-    f.sdot = w.core.sdot;
-    f.stamps = w.core.stamps;
-    // the per-row scores of the existing stages, into the workspace.  The self check goes first: it is the one that
-    // can still refuse (a table made for another robot), and a refused call enqueues nothing.
-    if (sel->pairs) {
-      ScoreOut so;
-      so.clearance = w.self_clearance;
-      so.oor = w.self_invalid;
-      G2_TRY(plan_self_score(p, sel->pairs, inter, so, nullptr, false, st));
-      f.self_clearance = w.self_clearance;
-      f.self_invalid = w.self_invalid;
-    }
-    ScoreOut so;
-    so.clearance = w.clearance;
-    so.oor = w.oor;
-    G2_TRY(plan_score(p, inter, so, nullptr, false, st));
-    f.clearance = w.clearance;
-    f.oor = w.oor;
-    G2_TRY(gpmp2mi_plan_motion_score_dev(p, l, inter, w.pos_margin, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                         w.motion_invalid, st));
-    f.pos_margin = w.pos_margin;
-    f.motion_invalid = w.motion_invalid;
+    f.rstatus = o.status;
+    f.duration = o.duration;
+    f.sdot = (double*)rows[0].staged;
+    f.stamps = (double*)rows[2].staged;
+    PriorRows got;
+    G2_TRY(enqueue_prior_stages(p, sel->pairs, inter, w.prior, st, &got));
+    f.clearance = got.clearance;
+    f.oor = got.oor;
+    f.self_clearance = got.self_clearance;
+    f.self_invalid = got.self_invalid;
+    G2_TRY(gpmp2mi_plan_motion_score_dev(p, l, inter, w.prior.pos_margin, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         w.prior.motion_invalid, st));
+    f.pos_margin = w.prior.pos_margin;
+    f.motion_invalid = w.prior.motion_invalid;
   }
   p->mark_dirty(st);
-  G2_TRY(enqueue_retime(p->robot, lim, l->point_speed, P.delta_t, inter, P.B, P.N, p->pb.result, rt, w.core, o, st));
+  G2_TRY(enqueue_retime(p->robot, lim, l->point_speed, P.delta_t, inter, P.B, P.N, p->pb.result, rt, w.core, rows, o, st));
   if (sel) G2_TRY(launch_retime_finish(f, st));
-  if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
-  if (!sel) {
-    G2_TRY(back(out.sdot, w.core.sdot, P.B * Md * sizeof(double)));
-    G2_TRY(back(out.u, w.core.u, P.B * Md * sizeof(double)));
-    G2_TRY(back(out.stamps, w.core.stamps, P.B * Md * sizeof(double)));
-    G2_TRY(back(out.duration, w.duration, P.B * sizeof(double)));
-    G2_TRY(back(out.status, w.status, P.B * sizeof(int)));
-    G2_TRY(back(out.achieved, w.achieved, (size_t)4 * P.B * sizeof(double)));
-    G2_TRY(back(out.dense, w.dense, P.B * Md * 2 * P.D * sizeof(double)));
-  }
-  Pick got{-1, 0, 0.0, 0.0};
-  if (sel) G2_TRY(back(&got, w.pick, sizeof(got)));
-  G2_HIP(hipStreamSynchronize(st));
-  if (sel) {
-    if (sel->best) *sel->best = got.best;
-    if (sel->n_eligible) *sel->n_eligible = got.n;
-    if (got.best >= 0) {   // nothing chosen: the outputs about the chosen row stay as they are
-      if (sel->duration_best) *sel->duration_best = got.duration;
-      if (sel->traj_best || sel->dense_best || sel->stamps_best) {
-        G2_TRY(back(sel->traj_best, w.traj_best, (size_t)(P.N + 1) * 2 * P.D * sizeof(double)));
-        G2_TRY(back(sel->dense_best, w.dense_best, Md * 2 * P.D * sizeof(double)));
-        G2_TRY(back(sel->stamps_best, w.stamps_best, Md * sizeof(double)));
-        G2_HIP(hipStreamSynchronize(st));
-      }
-    }
-  }
-  p->mark_clean(st);
-  return GPMP2MI_OK;
+  return host ? finish_host(p, inter, rows, RETIME_ROWS, sel, &x, w.sel, st) : GPMP2MI_OK;
 }
 
 int check_traj_call(const gpmp2mi_robot* r, const gpmp2mi_motion_limits* l, double delta_t, int inter, int B,
@@ -291,6 +157,25 @@ int check_path_call(int B, int Md, int dof, const double* qd, const double* ql, 
       acc_out[d] = acc[d];
     }
   return GPMP2MI_OK;
+}
+
+RetimeOut make_out(double* sdot, double* u, double* stamps, double* duration, int* status, double* achieved,
+                   double* dense) {
+  RetimeOut o;
+  o.sdot = sdot; o.u = u; o.stamps = stamps; o.duration = duration; o.status = status; o.achieved = achieved;
+  o.dense = dense;
+  return o;
+}
+RetimeSel make_sel(double required_clearance, int require_in_range, const gpmp2mi_self_pairs* pairs,
+                   double required_self_clearance, double required_pos_margin, double max_duration, int* best,
+                   int* n_eligible, double* duration_best, double* stamps_best, double* traj_best, double* dense_best) {
+  RetimeSel sel;
+  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
+  sel.pairs = pairs; sel.required_self_clearance = required_self_clearance;
+  sel.required_pos_margin = required_pos_margin; sel.max_duration = max_duration;
+  sel.best = best; sel.n_eligible = n_eligible; sel.duration_best = duration_best; sel.stamps_best = stamps_best;
+  sel.traj_best = traj_best; sel.dense_best = dense_best;
+  return sel;
 }
 
 }  // namespace
@@ -369,21 +254,18 @@ int gpmp2mi_retime_traj_dev(const gpmp2mi_robot* r, const gpmp2mi_motion_limits*
   MotionLimitsDev lim;
   G2_TRY(read_limits(l, r->h.dof, &lim));
   if (B == 0) return GPMP2MI_OK;
-  G2_TRY(ensure_device());
-  int cur = -1;
-  G2_HIP(hipGetDevice(&cur));
-  G2_CHECK(cur == r->device, GPMP2MI_ERR_INVALID, "the robot handle lives on another device than the current one");
   const size_t Md = (size_t)total_step * (inter_step + 1) + 1;
-  std::lock_guard<std::mutex> lk(r->score_mu);
+  const RetimeOut o = make_out(sdot, u, stamps, duration, status, achieved, dense_retimed);
+  RowOut rows[RETIME_ROWS];
+  rows_of(o, Md, r->h.dof, rows);
   Carver need{nullptr};
-  (void)core_layout(need, B, Md);
-  G2_TRY(ws_reserve(&r->retime_ws, &r->retime_ws_bytes, need.off));
-  Carver take{(char*)r->retime_ws};
-  const CoreWs w = core_layout(take, B, Md);
-  RetimeOut o;
-  o.sdot = sdot; o.u = u; o.stamps = stamps; o.duration = duration; o.status = status; o.achieved = achieved;
-  o.dense = dense_retimed;
-  return enqueue_retime(r, lim, l->point_speed, delta_t, inter_step, B, total_step, traj, rt, w, o, (hipStream_t)stream);
+  (void)carve_retime_core(need, rows, B, Md);
+  std::unique_lock<std::mutex> lk;
+  G2_TRY(records_ready(r, nullptr, r->retime_ws, need.off, lk));
+  Carver take{(char*)r->retime_ws.p};
+  const RetimeCore w = carve_retime_core(take, rows, B, Md);
+  return enqueue_retime(r, lim, l->point_speed, delta_t, inter_step, B, total_step, traj, rt, w, rows, o,
+                        (hipStream_t)stream);
 }
 
 int gpmp2mi_retime_traj(const gpmp2mi_robot* r, const gpmp2mi_motion_limits* l, double delta_t, int inter_step, int B,
@@ -414,18 +296,15 @@ int gpmp2mi_retime_traj(const gpmp2mi_robot* r, const gpmp2mi_motion_limits* l, 
 int gpmp2mi_plan_retime(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter_step, double max_rate,
                         double rate_start, double rate_end, double* sdot, double* u, double* stamps, double* duration,
                         int* status, double* achieved, double* dense_retimed) {
-  RetimeOut o;
-  o.sdot = sdot; o.u = u; o.stamps = stamps; o.duration = duration; o.status = status; o.achieved = achieved;
-  o.dense = dense_retimed;
-  return plan_retime(p, l, inter_step, Rates{max_rate, rate_start, rate_end}, o, nullptr, true, nullptr);
+  return plan_retime(p, l, inter_step, Rates{max_rate, rate_start, rate_end},
+                     make_out(sdot, u, stamps, duration, status, achieved, dense_retimed), nullptr, true, nullptr);
 }
 int gpmp2mi_plan_retime_dev(gpmp2mi_plan* p, const gpmp2mi_motion_limits* l, int inter_step, double max_rate,
                             double rate_start, double rate_end, double* sdot, double* u, double* stamps,
                             double* duration, int* status, double* achieved, double* dense_retimed, void* stream) {
-  RetimeOut o;
-  o.sdot = sdot; o.u = u; o.stamps = stamps; o.duration = duration; o.status = status; o.achieved = achieved;
-  o.dense = dense_retimed;
-  return plan_retime(p, l, inter_step, Rates{max_rate, rate_start, rate_end}, o, nullptr, false, (hipStream_t)stream);
+  return plan_retime(p, l, inter_step, Rates{max_rate, rate_start, rate_end},
+                     make_out(sdot, u, stamps, duration, status, achieved, dense_retimed), nullptr, false,
+                     (hipStream_t)stream);
 }
 
 int gpmp2mi_plan_select_retimed(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
@@ -433,12 +312,8 @@ int gpmp2mi_plan_select_retimed(gpmp2mi_plan* p, int inter_step, double required
                                 const gpmp2mi_motion_limits* l, double required_pos_margin, double max_rate,
                                 double rate_start, double rate_end, double max_duration, int* best, int* n_eligible,
                                 double* duration_best, double* stamps_best, double* traj_best, double* dense_best) {
-  RetimeSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.pairs = pairs; sel.required_self_clearance = required_self_clearance;
-  sel.required_pos_margin = required_pos_margin; sel.max_duration = max_duration;
-  sel.best = best; sel.n_eligible = n_eligible; sel.duration_best = duration_best; sel.stamps_best = stamps_best;
-  sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const RetimeSel sel = make_sel(required_clearance, require_in_range, pairs, required_self_clearance, required_pos_margin,
+                                 max_duration, best, n_eligible, duration_best, stamps_best, traj_best, dense_best);
   return plan_retime(p, l, inter_step, Rates{max_rate, rate_start, rate_end}, RetimeOut{}, &sel, true, nullptr);
 }
 int gpmp2mi_plan_select_retimed_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
@@ -447,12 +322,8 @@ int gpmp2mi_plan_select_retimed_dev(gpmp2mi_plan* p, int inter_step, double requ
                                     double rate_start, double rate_end, double max_duration, int* best,
                                     int* n_eligible, double* duration_best, double* stamps_best, double* traj_best,
                                     double* dense_best, void* stream) {
-  RetimeSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.pairs = pairs; sel.required_self_clearance = required_self_clearance;
-  sel.required_pos_margin = required_pos_margin; sel.max_duration = max_duration;
-  sel.best = best; sel.n_eligible = n_eligible; sel.duration_best = duration_best; sel.stamps_best = stamps_best;
-  sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const RetimeSel sel = make_sel(required_clearance, require_in_range, pairs, required_self_clearance, required_pos_margin,
+                                 max_duration, best, n_eligible, duration_best, stamps_best, traj_best, dense_best);
   return plan_retime(p, l, inter_step, Rates{max_rate, rate_start, rate_end}, RetimeOut{}, &sel, false,
                      (hipStream_t)stream);
 }

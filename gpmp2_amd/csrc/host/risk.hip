@@ -66,17 +66,12 @@ struct PlanRiskWs {
 PlanRiskWs risk_ws_layout(char* base, const PlanParams& P, int inter) {
   const size_t nn = (size_t)P.n * P.n, Md = (size_t)P.N * (inter + 1) + 1;
   PlanRiskWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = base + off;
-    off += ws_round(bytes);
-    return q;
-  };
+  Carver take{base};
   w.Sd = (double*)take((size_t)P.B * (P.N + 1) * nn * sizeof(double));
   w.So = (double*)take((size_t)P.B * P.N * nn * sizeof(double));
   w.ok = (int*)take(P.B * sizeof(int));
   w.recs = (RiskRec*)take((size_t)P.B * score_blocks((int)Md) * sizeof(RiskRec));
-  w.bytes = off;
+  w.bytes = take.off;
   return w;
 }
 
@@ -100,8 +95,8 @@ int plan_band(gpmp2mi_plan* p, int inter, PlanRiskWs* w, int* ok_out, hipStream_
     G2_TRY(dev_malloc((void**)&p->risk_qc, p->Qc.size() * sizeof(double)));
     G2_HIP(hipMemcpy(p->risk_qc, p->Qc.data(), p->Qc.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  G2_TRY(ws_reserve(&p->risk_ws, &p->risk_ws_bytes, risk_ws_layout(nullptr, P, inter).bytes));
-  *w = risk_ws_layout((char*)p->risk_ws, P, inter);
+  G2_TRY(p->ws[p->WS_RISK].reserve(risk_ws_layout(nullptr, P, inter).bytes));
+  *w = risk_ws_layout((char*)p->ws[p->WS_RISK].p, P, inter);
   G2_TRY(plan_posterior_band(p, w->Sd, w->So, w->ok, st));   // marks `st` dirty
   if (ok_out) G2_HIP(hipMemcpyAsync(ok_out, w->ok, P.B * sizeof(int), hipMemcpyDeviceToDevice, st));
   return GPMP2MI_OK;
@@ -171,11 +166,11 @@ int gpmp2mi_risk_traj_dev(const gpmp2mi_robot* r, const gpmp2mi_sdf* s, const do
   const size_t Md = (size_t)total_step * (inter_step + 1) + 1;
   // the records share the robot handle's workspace with gpmp2mi_score_traj_dev, under its rule: calls in stream order
   std::lock_guard<std::mutex> lk(r->score_mu);
-  G2_TRY(ws_reserve(&r->score_ws, &r->score_ws_bytes, (size_t)B * score_blocks((int)Md) * sizeof(RiskRec)));
+  G2_TRY(r->score_ws.reserve((size_t)B * score_blocks((int)Md) * sizeof(RiskRec)));
   RiskOut o;
   o.robust = robust_clearance; o.worst = worst; o.sigma_worst = sigma_worst; o.oor = out_of_range; o.sigma = sigma;
   return enqueue_risk(r, s, Qc, delta_t, inter_step, B, total_step, traj, Sdiag, Soff, ok, kappa, o,
-                      (RiskRec*)r->score_ws, (hipStream_t)stream);
+                      (RiskRec*)r->score_ws.p, (hipStream_t)stream);
 }
 
 int gpmp2mi_risk_traj(const gpmp2mi_robot* r, const gpmp2mi_sdf* s, const double* Qc, double delta_t, int inter_step,

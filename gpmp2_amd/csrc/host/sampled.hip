@@ -203,17 +203,12 @@ struct PlanSampledWs {
 PlanSampledWs sampled_ws_layout(char* base, const PlanParams& P, int inter, size_t chunk) {
   const size_t Md = (size_t)P.N * (inter + 1) + 1;
   PlanSampledWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = base + off;
-    off += ws_round(bytes);
-    return q;
-  };
+  Carver take{base};
   w.delta = (double*)take((size_t)P.B * chunk * (P.N + 1) * P.n * sizeof(double));
   w.recs = (SampledRec*)take((size_t)P.B * chunk * score_blocks((int)Md) * sizeof(SampledRec));
   w.acc = (int*)take((size_t)2 * P.B * sizeof(int));
   w.ok = (int*)take(P.B * sizeof(int));
-  w.bytes = off;
+  w.bytes = take.off;
   return w;
 }
 
@@ -250,8 +245,8 @@ int plan_sampled_dev(gpmp2mi_plan* p, int inter, int K, uint64_t seed, int row_f
   const double* bf = nullptr;
   G2_TRY(ensure_factors(p->sampled_fac, p->Qc.data(), P.D, P.delta_t, inter, st, &bf));
   const size_t chunk = chunk_samples(P, K);
-  G2_TRY(ws_reserve(&p->sampled_ws, &p->sampled_ws_bytes, sampled_ws_layout(nullptr, P, inter, chunk).bytes));
-  const PlanSampledWs w = sampled_ws_layout((char*)p->sampled_ws, P, inter, chunk);
+  G2_TRY(p->ws[p->WS_SAMPLED].reserve(sampled_ws_layout(nullptr, P, inter, chunk).bytes));
+  const PlanSampledWs w = sampled_ws_layout((char*)p->ws[p->WS_SAMPLED].p, P, inter, chunk);
   const double* fac = nullptr;
   G2_TRY(plan_posterior_factor(p, w.ok, &fac, st));   // marks `st` dirty
   if (ok_out) G2_HIP(hipMemcpyAsync(ok_out, w.ok, P.B * sizeof(int), hipMemcpyDeviceToDevice, st));
@@ -327,14 +322,14 @@ int gpmp2mi_sampled_clearance_traj_dev(const gpmp2mi_robot* r, const gpmp2mi_sdf
   const double* bf = nullptr;
   G2_TRY(ensure_factors(r->sampled_fac, Qc, r->h.dof, delta_t, inter_step, st, &bf));
   const size_t rec_bytes = ws_round((size_t)B * K * score_blocks(Md) * sizeof(SampledRec));
-  G2_TRY(ws_reserve(&r->score_ws, &r->score_ws_bytes, rec_bytes + (size_t)2 * B * sizeof(int)));
+  G2_TRY(r->score_ws.reserve(rec_bytes + (size_t)2 * B * sizeof(int)));
   SampledOut o;
   o.hits = hits; o.probability = probability; o.clearance = clearance; o.worst = worst;
   o.state_clearance = state_clearance; o.state_hits = state_hits; o.oor = oor_samples; o.conf = conf;
   if (state_hits) G2_HIP(hipMemsetAsync(state_hits, 0, (size_t)B * Md * sizeof(int), st));
   const SampledArgs a = sampled_args(delta_t, inter_step, B, total_step, K, seed, row_first, sample_first, bridge,
                                      required_clearance, traj, ok, bf, o);
-  return enqueue_chunk(r, s, a, 0, K, delta, (SampledRec*)r->score_ws, (int*)((char*)r->score_ws + rec_bytes), o, st);
+  return enqueue_chunk(r, s, a, 0, K, delta, (SampledRec*)r->score_ws.p, (int*)((char*)r->score_ws.p + rec_bytes), o, st);
 }
 
 int gpmp2mi_sampled_clearance_traj(const gpmp2mi_robot* r, const gpmp2mi_sdf* s, const double* Qc, double delta_t,

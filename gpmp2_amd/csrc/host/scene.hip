@@ -94,9 +94,9 @@ int scene_ready(const gpmp2mi_scene* sc, int nx, int ny, int nz) {
   G2_HIP(hipGetDevice(&cur));
   G2_CHECK(cur == sc->device, GPMP2MI_ERR_INVALID, "the scene handle lives on another device than the current one");
   const size_t need = bits_bytes_for(nx, ny, nz);
-  if (need > sc->bits_bytes) {
-    G2_TRY(ws_reserve(&sc->bits, &sc->bits_bytes, need));
-    G2_HIP(hipMemsetAsync(sc->bits, 0, need, nullptr));
+  if (need > sc->bits.bytes) {
+    G2_TRY(sc->bits.reserve(need));
+    G2_HIP(hipMemsetAsync(sc->bits.p, 0, need, nullptr));
     G2_HIP(hipStreamSynchronize(nullptr));   // the first `_dev` call may come on any stream
   }
   return GPMP2MI_OK;
@@ -178,7 +178,7 @@ int raster(const gpmp2mi_scene* sc, const SensorGrid& g, int* wa, int* wb, unsig
     m.q = (int*)(sc->geo + o.q_off);
     std::memcpy(m.pose, o.pose, sizeof(m.pose));
     m.flag = sc->counts + K + k;
-    m.bits = (unsigned*)sc->bits;
+    m.bits = (unsigned*)sc->bits.p;
     m.W = (g.nx + 31) / 32;
     m.wa = wa; m.wb = wb; m.mask = mask;
     m.cells = sc->counts;

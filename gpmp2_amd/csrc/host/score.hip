@@ -55,98 +55,40 @@ void g2::select_rule_host(int B, const double* ferr, const int* status, const do
   if (n_eligible) *n_eligible = n;
 }
 
-// Layout of a plan's scoring workspace for (B, N, D, inter): the records, then the staging of the host-pointer forms
-namespace {
-struct PlanScoreWs {
-  ScoreRec* recs;
-  ScoreOut out;
-  int* pick;   // best, n_eligible, then (8-byte aligned) the chosen row's final_error: one 16-byte copy
-  double *traj_best, *dense_best;
-  size_t bytes;
-};
-PlanScoreWs plan_ws_layout(char* base, int B, int N, int D, int inter) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanScoreWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
-  w.recs = (ScoreRec*)take((size_t)B * score_blocks((int)Md) * sizeof(ScoreRec));
-  w.out.support = (double*)take(B * sizeof(double));
-  w.out.dense = (double*)take(B * sizeof(double));
-  w.out.clearance = (double*)take(B * sizeof(double));
-  w.out.worst = (int*)take(2 * B * sizeof(int));
-  w.out.oor = (int*)take(B * sizeof(int));
-  w.pick = (int*)take(2 * sizeof(int) + sizeof(double));
-  w.traj_best = (double*)take((size_t)(N + 1) * 2 * D * sizeof(double));
-  w.dense_best = (double*)take(Md * 2 * D * sizeof(double));
-  w.bytes = off;
-  return w;
-}
-}  // namespace
-
+// The simplest client of the shared driver (check_common.hip): one record set, no earlier stage, no extra output
 int g2::plan_score(gpmp2mi_plan* p, int inter, const ScoreOut& out, const ScoreSel* sel, bool host, hipStream_t st) {
   G2_CHECK(p, GPMP2MI_ERR_INVALID, "null plan");
-  G2_PLAN_LIVE(p);   // before anything is enqueued
-  G2_CHECK(p->optimized, GPMP2MI_ERR_INVALID, "plan has not been optimized");
+  G2_TRY(check_plan_ready(p, inter));
   const PlanParams& P = p->hp;
-  G2_TRY(check_score_args(inter, P.B, P.N, P.delta_t));
-  G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
-  G2_TRY(ws_reserve(&p->score_ws, &p->score_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, inter).bytes));
-  const PlanScoreWs w = plan_ws_layout((char*)p->score_ws, P.B, P.N, P.D, inter);
-  const size_t Md = (size_t)P.N * (inter + 1) + 1;
+  const int Md = P.N * (inter + 1) + 1;
+  const size_t rec_bytes = (size_t)P.B * score_blocks(Md) * sizeof(ScoreRec);
+  RowOut rows[SCORE_ROWS];
+  rows_of(out, SCORE_WORST, rows);
+  const auto layout = [&](void* base) { return carve_score((char*)base, rec_bytes, rows, shape_of(p, inter)); };
+  CheckWs w;
+  G2_TRY(carve_into(p->ws[p->WS_SCORE], layout, &w));
   ScoreFinish f{};
-  const ScoreOut& o = host ? w.out : out;
-  // the host form computes only what the caller asked for
-  f.support = (!host || out.support) ? o.support : nullptr;
-  f.dense = (!host || out.dense) ? o.dense : nullptr;
-  f.clearance = (!host || out.clearance) ? o.clearance : nullptr;
-  f.worst = (!host || out.worst) ? o.worst : nullptr;
-  f.oor = (!host || out.oor) ? o.oor : nullptr;
-  if (sel) {
-    f.select = 1;
-    f.required_clearance = sel->required_clearance;
-    f.require_in_range = sel->require_in_range;
-    f.ferr = p->pb.final_err;
-    f.status = p->pb.status;
-    f.best = host ? w.pick : sel->best;
-    f.n_eligible = host ? w.pick + 1 : sel->n_eligible;
-    f.best_err = host ? (double*)(w.pick + 2) : nullptr;
-    f.traj_best = host ? (sel->traj_best ? w.traj_best : nullptr) : sel->traj_best;
-    f.dense_best = host ? (sel->dense_best ? w.dense_best : nullptr) : sel->dense_best;
-  }
+  const ScoreOut o = score_out(rows, host);
+  f.support = o.support;
+  f.dense = o.dense;
+  f.clearance = o.clearance;
+  f.worst = o.worst;
+  f.oor = o.oor;
+  if (sel) point_selection(f, p, *sel, nullptr, host, w.sel);
   p->mark_dirty(st);
-  G2_TRY(enqueue_score(p->robot, p->sdf, P.delta_t, inter, P.B, P.N, p->pb.result, w.recs, f, st));
-  if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
-  G2_TRY(back(out.support, w.out.support, P.B * sizeof(double)));
-  G2_TRY(back(out.dense, w.out.dense, P.B * sizeof(double)));
-  G2_TRY(back(out.clearance, w.out.clearance, P.B * sizeof(double)));
-  G2_TRY(back(out.worst, w.out.worst, 2 * P.B * sizeof(int)));
-  G2_TRY(back(out.oor, w.out.oor, P.B * sizeof(int)));
-  struct { int best, n; double err; } pick{-1, 0, 0.0};
-  if (sel) G2_TRY(back(&pick, w.pick, sizeof(pick)));
-  G2_HIP(hipStreamSynchronize(st));
-  if (sel) {
-    if (sel->best) *sel->best = pick.best;
-    if (sel->n_eligible) *sel->n_eligible = pick.n;
-    if (pick.best >= 0) {
-      if (sel->best_error) *sel->best_error = pick.err;
-      if (sel->traj_best || sel->dense_best) {   // nothing chosen: the trajectory outputs stay as they are
-        G2_TRY(back(sel->traj_best, w.traj_best, (size_t)(P.N + 1) * 2 * P.D * sizeof(double)));
-        G2_TRY(back(sel->dense_best, w.dense_best, Md * 2 * P.D * sizeof(double)));
-        G2_HIP(hipStreamSynchronize(st));
-      }
-    }
-  }
-  p->mark_clean(st);
-  return GPMP2MI_OK;
+  G2_TRY(enqueue_score(p->robot, p->sdf, P.delta_t, inter, P.B, P.N, p->pb.result, (ScoreRec*)w.recs, f, st));
+  return host ? finish_host(p, inter, rows, SCORE_ROWS, sel, nullptr, w.sel, st) : GPMP2MI_OK;
 }
+
+namespace {
+ScoreSel make_sel(double required_clearance, int require_in_range, int* best, int* n_eligible, double* traj_best,
+                  double* dense_best) {
+  ScoreSel sel;
+  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
+  sel.best = best; sel.n_eligible = n_eligible; sel.traj_best = traj_best; sel.dense_best = dense_best;
+  return sel;
+}
+}  // namespace
 
 extern "C" {
 
@@ -156,20 +98,16 @@ int gpmp2mi_score_traj_dev(const gpmp2mi_robot* r, const gpmp2mi_sdf* s, double 
   G2_CHECK(r && s && traj, GPMP2MI_ERR_INVALID, "null argument");
   G2_TRY(check_score_args(inter_step, B, total_step, delta_t));
   if (B == 0) return GPMP2MI_OK;
-  G2_TRY(ensure_device());
-  int cur = -1;
-  G2_HIP(hipGetDevice(&cur));
-  G2_CHECK(cur == r->device, GPMP2MI_ERR_INVALID, "the robot handle lives on another device than the current one");
   const size_t Md = (size_t)total_step * (inter_step + 1) + 1;
-  std::lock_guard<std::mutex> lk(r->score_mu);
-  G2_TRY(ws_reserve(&r->score_ws, &r->score_ws_bytes, (size_t)B * score_blocks((int)Md) * sizeof(ScoreRec)));
+  std::unique_lock<std::mutex> lk;
+  G2_TRY(records_ready(r, nullptr, r->score_ws, (size_t)B * score_blocks((int)Md) * sizeof(ScoreRec), lk));
   ScoreFinish f{};
   f.support = support_cost;
   f.dense = dense_cost;
   f.clearance = min_clearance;
   f.worst = worst;
   f.oor = out_of_range;
-  return enqueue_score(r, s, delta_t, inter_step, B, total_step, traj, (ScoreRec*)r->score_ws, f, (hipStream_t)stream);
+  return enqueue_score(r, s, delta_t, inter_step, B, total_step, traj, (ScoreRec*)r->score_ws.p, f, (hipStream_t)stream);
 }
 
 int gpmp2mi_score_traj(const gpmp2mi_robot* r, const gpmp2mi_sdf* s, double delta_t, int inter_step, int B,
@@ -225,29 +163,23 @@ int gpmp2mi_select_best_dev(int B, const double* final_error, const int* status,
 
 int gpmp2mi_plan_score(gpmp2mi_plan* p, int inter_step, double* support_cost, double* dense_cost,
                        double* min_clearance, int* worst, int* out_of_range) {
-  ScoreOut o;
-  o.support = support_cost; o.dense = dense_cost; o.clearance = min_clearance; o.worst = worst; o.oor = out_of_range;
-  return plan_score(p, inter_step, o, nullptr, true, nullptr);
+  return plan_score(p, inter_step, make_out(support_cost, dense_cost, min_clearance, worst, out_of_range), nullptr, true,
+                    nullptr);
 }
 int gpmp2mi_plan_score_dev(gpmp2mi_plan* p, int inter_step, double* support_cost, double* dense_cost,
                            double* min_clearance, int* worst, int* out_of_range, void* stream) {
-  ScoreOut o;
-  o.support = support_cost; o.dense = dense_cost; o.clearance = min_clearance; o.worst = worst; o.oor = out_of_range;
-  return plan_score(p, inter_step, o, nullptr, false, (hipStream_t)stream);
+  return plan_score(p, inter_step, make_out(support_cost, dense_cost, min_clearance, worst, out_of_range), nullptr, false,
+                    (hipStream_t)stream);
 }
 
 int gpmp2mi_plan_select(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range, int* best,
                         int* n_eligible, double* traj_best, double* dense_best) {
-  ScoreSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.best = best; sel.n_eligible = n_eligible; sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const ScoreSel sel = make_sel(required_clearance, require_in_range, best, n_eligible, traj_best, dense_best);
   return plan_score(p, inter_step, ScoreOut{}, &sel, true, nullptr);
 }
 int gpmp2mi_plan_select_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range, int* best,
                             int* n_eligible, double* traj_best, double* dense_best, void* stream) {
-  ScoreSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.best = best; sel.n_eligible = n_eligible; sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const ScoreSel sel = make_sel(required_clearance, require_in_range, best, n_eligible, traj_best, dense_best);
   return plan_score(p, inter_step, ScoreOut{}, &sel, false, (hipStream_t)stream);
 }
 

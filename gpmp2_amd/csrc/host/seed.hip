@@ -25,17 +25,12 @@ struct SeedWs {
 SeedWs seed_ws_layout(char* base, const PlanParams& P) {
   const size_t nb = (size_t)P.N + 1, nn = (size_t)P.n * P.n;
   SeedWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = base + off;
-    off += ws_round(bytes);
-    return q;
-  };
+  Carver take{base};
   w.Hd = (double*)take(nb * nn * sizeof(double));
   w.Ho = (double*)take((size_t)P.N * nn * sizeof(double));
   w.fac = (double*)take(nb * 512 * sizeof(double));
   w.ok = (int*)take(sizeof(int));
-  w.bytes = off;
+  w.bytes = take.off;
   return w;
 }
 
@@ -88,8 +83,8 @@ int ensure_seed_prior(gpmp2mi_plan* p, hipStream_t st) {
   if (p->seed_ready) return GPMP2MI_OK;
   const PlanParams& P = p->hp;
   ensure_seed_host(p);
-  G2_TRY(ws_reserve(&p->seed_ws, &p->seed_ws_bytes, seed_ws_layout(nullptr, P).bytes));
-  const SeedWs w = seed_ws_layout((char*)p->seed_ws, P);
+  G2_TRY(p->ws[p->WS_SEED].reserve(seed_ws_layout(nullptr, P).bytes));
+  const SeedWs w = seed_ws_layout((char*)p->ws[p->WS_SEED].p, P);
   G2_HIP(hipMemcpyAsync(w.Hd, p->seed_Hd.data(), p->seed_Hd.size() * sizeof(double), hipMemcpyHostToDevice, st));
   G2_HIP(hipMemcpyAsync(w.Ho, p->seed_Ho.data(), p->seed_Ho.size() * sizeof(double), hipMemcpyHostToDevice, st));
   const PosteriorArgs a{P.N + 1, 0, w.Hd, w.Ho, nullptr, nullptr, nullptr, nullptr, w.ok, w.fac};
@@ -163,7 +158,7 @@ int g2::plan_seed_restarts(gpmp2mi_plan* p, int M, uint64_t seed, int first, dou
   a.nblk = P.N + 1;
   a.count = M;
   a.a_first = first;
-  a.fac = seed_ws_layout((char*)p->seed_ws, P).fac;
+  a.fac = seed_ws_layout((char*)p->ws[p->WS_SEED].p, P).fac;
   a.out = init;
   a.scale = scale;
   a.keep_first = keep_first ? 1 : 0;

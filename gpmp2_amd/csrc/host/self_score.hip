@@ -10,15 +10,19 @@ using namespace g2;
 
 namespace {
 
-// the rules of check_score_args, then the launch limits of this stage (a smaller tile, a count of Md * P per row)
-int check_self_args(const gpmp2mi_robot* r, const gpmp2mi_self_pairs* t, int inter, int B, int total_step, double delta_t) {
-  G2_TRY(check_score_args(inter, B, total_step, delta_t));
+// behind the rules of check_score_args: the table's robot and the launch limits of this stage (a smaller tile, a count
+// of Md * P per row)
+int check_self_table(const gpmp2mi_robot* r, const gpmp2mi_self_pairs* t, int inter, int B, int total_step) {
   G2_CHECK(t->S == r->h.nr_spheres && t->dof == r->h.dof && t->kind == r->h.kind, GPMP2MI_ERR_INVALID,
            "the pair table was made for another robot (sphere count / dof / kind)");
   const long long Md = (long long)total_step * (inter + 1) + 1;
   G2_CHECK((long long)self_blocks((int)Md, t->S) * std::max(B, 1) < (1ll << 31) && Md * std::max(t->P, 1) < (1ll << 31),
            GPMP2MI_ERR_INVALID, "too many checked (state, pair)s for one launch");
   return GPMP2MI_OK;
+}
+int check_self_args(const gpmp2mi_robot* r, const gpmp2mi_self_pairs* t, int inter, int B, int total_step, double delta_t) {
+  G2_TRY(check_score_args(inter, B, total_step, delta_t));
+  return check_self_table(r, t, inter, B, total_step);
 }
 
 // parent of every link in the tree Kin::walk_links (device_math.h) walks, -1 for the root
@@ -41,117 +45,58 @@ int tree_distance(const std::vector<int>& par, int a, int b) {
   return n;
 }
 
-// Layout of a plan's self-check workspace for (B, N, D, S, inter): the two record sets, then the staging of the
-// host-pointer forms
-struct PlanSelfWs {
-  ScoreRec *recs, *obs_recs;
-  ScoreOut out;
-  int* pick;   // best, n_eligible, then (8-byte aligned) the chosen row's final_error: one 16-byte copy
-  double *traj_best, *dense_best;
-  size_t bytes;
-};
-PlanSelfWs plan_ws_layout(char* base, int B, int N, int D, int S, int inter) {
-  const size_t Md = (size_t)N * (inter + 1) + 1;
-  PlanSelfWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
-  w.recs = (ScoreRec*)take((size_t)B * self_blocks((int)Md, S) * sizeof(ScoreRec));
-  w.obs_recs = (ScoreRec*)take((size_t)B * score_blocks((int)Md) * sizeof(ScoreRec));
-  w.out.support = (double*)take(B * sizeof(double));
-  w.out.dense = (double*)take(B * sizeof(double));
-  w.out.clearance = (double*)take(B * sizeof(double));
-  w.out.worst = (int*)take(2 * B * sizeof(int));
-  w.out.oor = (int*)take(B * sizeof(int));
-  w.pick = (int*)take(2 * sizeof(int) + sizeof(double));
-  w.traj_best = (double*)take((size_t)(N + 1) * 2 * D * sizeof(double));
-  w.dense_best = (double*)take(Md * 2 * D * sizeof(double));
-  w.bytes = off;
-  return w;
+SelfSel make_sel(double required_clearance, int require_in_range, double required_self_clearance, int* best,
+                 int* n_eligible, double* traj_best, double* dense_best) {
+  SelfSel sel;
+  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
+  sel.required_self_clearance = required_self_clearance;
+  sel.best = best; sel.n_eligible = n_eligible; sel.traj_best = traj_best; sel.dense_best = dense_best;
+  return sel;
 }
 
 }  // namespace
 
-// Scores the plan's resident result against `t` on `st`; sel != null: k_score for the same rows first, then the rule
-// with both clearances and the copy of the chosen row.  host / out / sel as plan_score (score.hip); out.oor: invalid.
+// Scores the plan's resident result against `t` on `st`; sel != null: k_score for the same rows first (its records are
+// the second set of the workspace), then the rule with both clearances and the copy of the chosen row.  host / out / sel
+// as plan_score (score.hip); out.oor: invalid.
 int g2::plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter, const ScoreOut& out, const SelfSel* sel,
                     bool host, hipStream_t st) {
   G2_CHECK(p && t, GPMP2MI_ERR_INVALID, "null argument");
-  G2_PLAN_LIVE(p);   // before anything is enqueued
-  G2_CHECK(p->optimized, GPMP2MI_ERR_INVALID, "plan has not been optimized");
+  G2_TRY(check_plan_ready(p, inter));
   const PlanParams& P = p->hp;
-  G2_CHECK(p->robot->h.dof == P.D, GPMP2MI_ERR_INVALID, "robot dof does not fit the plan");
-  G2_TRY(check_self_args(p->robot, t, inter, P.B, P.N, P.delta_t));
+  G2_TRY(check_self_table(p->robot, t, inter, P.B, P.N));
   G2_CHECK(t->P == 0 || t->device == p->device, GPMP2MI_ERR_INVALID, "the pair table lives on another device than the plan");
-  const int S = p->robot->h.nr_spheres;
-  G2_TRY(ws_reserve(&p->self_ws, &p->self_ws_bytes, plan_ws_layout(nullptr, P.B, P.N, P.D, S, inter).bytes));
-  const PlanSelfWs w = plan_ws_layout((char*)p->self_ws, P.B, P.N, P.D, S, inter);
-  const size_t Md = (size_t)P.N * (inter + 1) + 1;
+  const int S = p->robot->h.nr_spheres, Md = P.N * (inter + 1) + 1;
+  const size_t rec_bytes = (size_t)P.B * self_blocks(Md, S) * sizeof(ScoreRec);
+  const size_t obs_bytes = (size_t)P.B * score_blocks(Md) * sizeof(ScoreRec);
+  RowOut rows[SCORE_ROWS];
+  rows_of(out, SELF_WORST, rows);
+  const auto layout = [&](void* base) { return carve_self((char*)base, rec_bytes, obs_bytes, rows, shape_of(p, inter)); };
+  CheckWs w;
+  G2_TRY(carve_into(p->ws[p->WS_SELF], layout, &w));
   SelfFinish f{};
-  const ScoreOut& o = host ? w.out : out;
-  // the host form computes only what the caller asked for
-  f.support = (!host || out.support) ? o.support : nullptr;
-  f.dense = (!host || out.dense) ? o.dense : nullptr;
-  f.clearance = (!host || out.clearance) ? o.clearance : nullptr;
-  f.worst = (!host || out.worst) ? o.worst : nullptr;
-  f.invalid = (!host || out.oor) ? o.oor : nullptr;
-  f.recs = w.recs;
-  f.nblk = self_blocks((int)Md, S);
-  ScoreFinish& g = f.sel;
-  g.B = P.B;
-  g.N = P.N;
-  g.D = P.D;
-  g.lie = p->robot->h.kind >= GPMP2MI_ROBOT_POSE2_MOBILE_BASE;
-  g.inter = inter;
-  g.Md = (int)Md;
-  g.dt = P.delta_t;
-  g.traj = p->pb.result;
+  const ScoreOut o = score_out(rows, host);
+  f.support = o.support;
+  f.dense = o.dense;
+  f.clearance = o.clearance;
+  f.worst = o.worst;
+  f.invalid = o.oor;
+  f.recs = (ScoreRec*)w.recs;
+  f.nblk = self_blocks(Md, S);
+  plan_shape(f.sel, p, inter);
   if (sel) {
-    g.select = 1;
-    g.recs = w.obs_recs;
-    g.nblk = score_blocks((int)Md);
-    g.required_clearance = sel->required_clearance;
-    g.require_in_range = sel->require_in_range;
+    point_selection(f.sel, p, *sel, nullptr, host, w.sel);
+    f.sel.recs = (ScoreRec*)w.recs2;
+    f.sel.nblk = score_blocks(Md);
     f.required_self_clearance = sel->required_self_clearance;
-    g.ferr = p->pb.final_err;
-    g.status = p->pb.status;
-    g.best = host ? w.pick : sel->best;
-    g.n_eligible = host ? w.pick + 1 : sel->n_eligible;
-    g.best_err = host ? (double*)(w.pick + 2) : nullptr;
-    g.traj_best = host ? (sel->traj_best ? w.traj_best : nullptr) : sel->traj_best;
-    g.dense_best = host ? (sel->dense_best ? w.dense_best : nullptr) : sel->dense_best;
   }
   p->mark_dirty(st);
-  if (sel) G2_TRY(launch_score(p->robot->h, p->robot->d, p->sdf->h, P.delta_t, inter, P.B, P.N, p->pb.result, w.obs_recs, st));
-  G2_TRY(launch_self_clearance(p->robot->h, p->robot->d, t->d, t->P, P.delta_t, inter, P.B, P.N, p->pb.result, w.recs, st));
+  if (sel)
+    G2_TRY(launch_score(p->robot->h, p->robot->d, p->sdf->h, P.delta_t, inter, P.B, P.N, p->pb.result, (ScoreRec*)w.recs2, st));
+  G2_TRY(launch_self_clearance(p->robot->h, p->robot->d, t->d, t->P, P.delta_t, inter, P.B, P.N, p->pb.result,
+                               (ScoreRec*)w.recs, st));
   G2_TRY(launch_self_finish(f, st));
-  if (!host) return GPMP2MI_OK;
-  auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (dst) G2_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return GPMP2MI_OK;
-  };
-  G2_TRY(back(out.support, w.out.support, P.B * sizeof(double)));
-  G2_TRY(back(out.dense, w.out.dense, P.B * sizeof(double)));
-  G2_TRY(back(out.clearance, w.out.clearance, P.B * sizeof(double)));
-  G2_TRY(back(out.worst, w.out.worst, 2 * P.B * sizeof(int)));
-  G2_TRY(back(out.oor, w.out.oor, P.B * sizeof(int)));
-  struct { int best, n; double err; } pick{-1, 0, 0.0};
-  if (sel) G2_TRY(back(&pick, w.pick, sizeof(pick)));
-  G2_HIP(hipStreamSynchronize(st));
-  if (sel) {
-    if (sel->best) *sel->best = pick.best;
-    if (sel->n_eligible) *sel->n_eligible = pick.n;
-    if (pick.best >= 0 && (sel->traj_best || sel->dense_best)) {   // nothing chosen: the trajectory outputs stay as they are
-      G2_TRY(back(sel->traj_best, w.traj_best, (size_t)(P.N + 1) * 2 * P.D * sizeof(double)));
-      G2_TRY(back(sel->dense_best, w.dense_best, Md * 2 * P.D * sizeof(double)));
-      G2_HIP(hipStreamSynchronize(st));
-    }
-  }
-  p->mark_clean(st);
-  return GPMP2MI_OK;
+  return host ? finish_host(p, inter, rows, SCORE_ROWS, sel, nullptr, w.sel, st) : GPMP2MI_OK;
 }
 
 namespace {
@@ -266,25 +211,20 @@ int gpmp2mi_self_score_traj_dev(const gpmp2mi_robot* r, const gpmp2mi_self_pairs
   G2_CHECK(r && t && traj, GPMP2MI_ERR_INVALID, "null argument");
   G2_TRY(check_self_args(r, t, inter_step, B, total_step, delta_t));
   if (B == 0) return GPMP2MI_OK;
-  G2_TRY(ensure_device());
-  int cur = -1;
-  G2_HIP(hipGetDevice(&cur));
-  G2_CHECK(cur == r->device && (t->P == 0 || cur == t->device), GPMP2MI_ERR_INVALID,
-           "the robot handle or the pair table lives on another device than the current one");
   const int Md = total_step * (inter_step + 1) + 1;
   const int nblk = self_blocks(Md, t->S);
-  std::lock_guard<std::mutex> lk(t->mu);
-  G2_TRY(ws_reserve(&t->ws, &t->ws_bytes, (size_t)B * nblk * sizeof(ScoreRec)));
+  std::unique_lock<std::mutex> lk;
+  G2_TRY(records_ready(r, t, t->ws, (size_t)B * nblk * sizeof(ScoreRec), lk));
   SelfFinish f{};
   f.sel.B = B;
-  f.recs = (ScoreRec*)t->ws;
+  f.recs = (ScoreRec*)t->ws.p;
   f.nblk = nblk;
   f.support = self_support_cost;
   f.dense = self_dense_cost;
   f.clearance = min_self_clearance;
   f.worst = worst;
   f.invalid = invalid;
-  G2_TRY(launch_self_clearance(r->h, r->d, t->d, t->P, delta_t, inter_step, B, total_step, traj, (ScoreRec*)t->ws,
+  G2_TRY(launch_self_clearance(r->h, r->d, t->d, t->P, delta_t, inter_step, B, total_step, traj, (ScoreRec*)t->ws.p,
                                (hipStream_t)stream));
   return launch_self_finish(f, (hipStream_t)stream);
 }
@@ -310,34 +250,28 @@ int gpmp2mi_self_score_traj(const gpmp2mi_robot* r, const gpmp2mi_self_pairs* t,
 
 int gpmp2mi_plan_self_score(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter_step, double* self_support_cost,
                             double* self_dense_cost, double* min_self_clearance, int* worst, int* invalid) {
-  ScoreOut o;
-  o.support = self_support_cost; o.dense = self_dense_cost; o.clearance = min_self_clearance; o.worst = worst; o.oor = invalid;
-  return plan_self_score(p, t, inter_step, o, nullptr, true, nullptr);
+  return plan_self_score(p, t, inter_step, make_out(self_support_cost, self_dense_cost, min_self_clearance, worst, invalid),
+                         nullptr, true, nullptr);
 }
 int gpmp2mi_plan_self_score_dev(gpmp2mi_plan* p, const gpmp2mi_self_pairs* t, int inter_step, double* self_support_cost,
                                 double* self_dense_cost, double* min_self_clearance, int* worst, int* invalid,
                                 void* stream) {
-  ScoreOut o;
-  o.support = self_support_cost; o.dense = self_dense_cost; o.clearance = min_self_clearance; o.worst = worst; o.oor = invalid;
-  return plan_self_score(p, t, inter_step, o, nullptr, false, (hipStream_t)stream);
+  return plan_self_score(p, t, inter_step, make_out(self_support_cost, self_dense_cost, min_self_clearance, worst, invalid),
+                         nullptr, false, (hipStream_t)stream);
 }
 
 int gpmp2mi_plan_select_checked(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
                                 const gpmp2mi_self_pairs* t, double required_self_clearance, int* best, int* n_eligible,
                                 double* traj_best, double* dense_best) {
-  SelfSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.required_self_clearance = required_self_clearance;
-  sel.best = best; sel.n_eligible = n_eligible; sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const SelfSel sel = make_sel(required_clearance, require_in_range, required_self_clearance, best, n_eligible, traj_best,
+                               dense_best);
   return plan_self_score(p, t, inter_step, ScoreOut{}, &sel, true, nullptr);
 }
 int gpmp2mi_plan_select_checked_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
                                     const gpmp2mi_self_pairs* t, double required_self_clearance, int* best,
                                     int* n_eligible, double* traj_best, double* dense_best, void* stream) {
-  SelfSel sel;
-  sel.required_clearance = required_clearance; sel.require_in_range = require_in_range;
-  sel.required_self_clearance = required_self_clearance;
-  sel.best = best; sel.n_eligible = n_eligible; sel.traj_best = traj_best; sel.dense_best = dense_best;
+  const SelfSel sel = make_sel(required_clearance, require_in_range, required_self_clearance, best, n_eligible, traj_best,
+                               dense_best);
   return plan_self_score(p, t, inter_step, ScoreOut{}, &sel, false, (hipStream_t)stream);
 }
 

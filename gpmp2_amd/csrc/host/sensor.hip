@@ -21,20 +21,15 @@ struct EvWs {
 };
 EvWs ev_ws_layout(char* base, size_t n) {
   EvWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += ws_round(bytes);
-    return p;
-  };
+  Carver take{base};
   w.E = (short*)take(n * sizeof(short));
   w.miss = (unsigned char*)take(n);
   w.hit = (unsigned char*)take(n);
   w.cnt = (int*)take(6 * sizeof(int));
-  w.bytes = off;
+  w.bytes = take.off;
   return w;
 }
-size_t ray_ws_bytes(int M) { return ws_round((size_t)M * 3 * sizeof(double)) + ws_round((size_t)M * sizeof(int)); }
+size_t ray_bytes(int M) { return ws_round((size_t)M * 3 * sizeof(double)) + ws_round((size_t)M * sizeof(int)); }
 
 // once the arguments are accepted: the live map's workspace (the rebuild runs in it), the evidence all 0, M ray records
 int evidence_ready(gpmp2mi_sdf* s, int M) {
@@ -45,7 +40,7 @@ int evidence_ready(gpmp2mi_sdf* s, int M) {
     G2_HIP(hipMemsetAsync(s->ev_ws, 0, bytes, nullptr));
     G2_HIP(hipStreamSynchronize(nullptr));   // the first `_dev` call may come on any stream
   }
-  if (M > 0) G2_TRY(ws_reserve(&s->ray_ws, &s->ray_ws_bytes, ray_ws_bytes(M)));
+  if (M > 0) G2_TRY(s->ray_ws.reserve(ray_bytes(M)));
   return GPMP2MI_OK;
 }
 
@@ -149,8 +144,8 @@ int integrate(gpmp2mi_sdf* s, int M, const double* d_points, const float* d_dept
   const size_t n = cells_of(s);
   const EvWs e = ev_ws_layout((char*)s->ev_ws, n);
   const MapWs w = map_ws_layout((char*)s->map_ws, n);
-  double* rb = (double*)s->ray_ws;
-  int* rcls = (int*)((char*)s->ray_ws + ws_round((size_t)M * 3 * sizeof(double)));
+  double* rb = (double*)s->ray_ws.p;
+  int* rcls = (int*)((char*)s->ray_ws.p + ws_round((size_t)M * 3 * sizeof(double)));
   mark_stage(s, 0, st);
   mark_sensor(s, 0, st);
   G2_HIP(hipMemsetAsync(e.cnt, 0, 6 * sizeof(int), st));
