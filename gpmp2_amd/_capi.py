@@ -47,6 +47,8 @@ class Settings(C.Structure):
 
 MAX_WORKSPACE_FACTORS, MAX_SELF_COLLISION_PAIRS = 4, 16
 MAX_MOVING_SPHERES = 64
+HEADER_MAX_SPHERES = 96   # GPMP2MI_MAX_SPHERES
+MAX_PLAN_SELF_PAIRS = HEADER_MAX_SPHERES * (HEADER_MAX_SPHERES - 1) // 2   # GPMP2MI_MAX_PLAN_SELF_PAIRS
 WORKSPACE_POSITION, WORKSPACE_ORIENTATION, WORKSPACE_POSE = 0, 1, 2
 
 
@@ -67,6 +69,7 @@ class GraphOpts(C.Structure):
                 ("n_self_collision", C.c_int), ("self_collision_first", C.c_int), ("self_collision_last", C.c_int),
                 ("self_collision", (C.c_double * 4) * MAX_SELF_COLLISION_PAIRS),
                 ("workspace_path", C.c_int), ("workspace_path_mode", C.c_int), ("workspace_path_link", C.c_int),
+                ("max_self_pairs", C.c_int), ("self_pairs_first", C.c_int), ("self_pairs_last", C.c_int),
                 ("max_moving_spheres", C.c_int), ("moving_first", C.c_int), ("moving_last", C.c_int),
                 ("moving_epsilon", C.c_double), ("moving_sigma", C.c_double)]
 
@@ -235,6 +238,14 @@ def declare_moving(lib):
         "gpmp2mi_plan_select_moving_dev": [vp, i, f, i, vp, f, f] + [vp] * 5,
     }
     for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
+def declare_selfpair(lib):
+    """argtypes of the plan's self-collision table (include/gpmp2mi.h "self-collision table in a plan")"""
+    vp, i = C.c_void_p, C.c_int
+    for name, args in {"gpmp2mi_plan_set_self_pairs": [vp, vp], "gpmp2mi_plan_self_pairs_count": [vp]}.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = i
 
@@ -602,6 +613,13 @@ def make_settings(setting):
         rng_ = mv.get("states") or (0, setting.total_step)
         o.moving_first, o.moving_last = int(rng_[0]), int(rng_[1])
         o.moving_epsilon, o.moving_sigma = float(mv["epsilon"]), float(mv["sigma"])
+    sp = getattr(setting, "self_pairs", None)
+    if sp is not None:
+        if not 0 <= int(sp["capacity"]) <= MAX_PLAN_SELF_PAIRS:
+            raise ValueError("self-collision table capacity outside 0..MAX_PLAN_SELF_PAIRS")
+        o.max_self_pairs = int(sp["capacity"])
+        rng_ = sp.get("states") or (0, setting.total_step)
+        o.self_pairs_first, o.self_pairs_last = int(rng_[0]), int(rng_[1])
     wp = getattr(setting, "workspace_path", None)
     if wp is not None:
         if int(wp["mode"]) not in (WORKSPACE_POSITION, WORKSPACE_ORIENTATION, WORKSPACE_POSE):

@@ -318,6 +318,16 @@ static int check_extras(const RobotDev& h, const gpmp2mi_graph_opts& o, int N, P
     ex.mv_eps = o.moving_epsilon;
     ex.mv_w = 1.0 / (o.moving_sigma * o.moving_sigma);
   }
+  G2_CHECK(o.max_self_pairs >= 0, GPMP2MI_ERR_INVALID, "max_self_pairs is negative");
+  G2_CHECK(o.max_self_pairs <= GPMP2MI_MAX_PLAN_SELF_PAIRS, GPMP2MI_ERR_INVALID,
+           "max_self_pairs above GPMP2MI_MAX_PLAN_SELF_PAIRS");
+  if (o.max_self_pairs > 0) {
+    G2_CHECK(o.self_pairs_first >= 0 && o.self_pairs_first <= o.self_pairs_last && o.self_pairs_last <= N,
+             GPMP2MI_ERR_INVALID, "self-collision table: bad state range");
+    ex.sp_cap = o.max_self_pairs;
+    ex.sp_first = o.self_pairs_first;
+    ex.sp_last = o.self_pairs_last;
+  }
   // the robot's radii in the caller's sphere order: read by the self-collision rows and the moving-sphere factor
   if (ex.n_sc > 0 || ex.mv_cap > 0)
     for (int sidx = 0; sidx < h.nr_spheres; sidx++) hx.radius[h.sph_orig[sidx]] = h.sph_r[sidx];
@@ -402,6 +412,13 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
     }
     G2_TRY(plan_alloc(p, &ex.mv_radius, (size_t)ex.mv_cap));
     G2_TRY(plan_alloc(p, &ex.mv_centers, (size_t)ex.mv_cap * (P.N + 1) * 3));
+  }
+  if (ex.sp_cap > 0) {   // the pair records; the centres and their Jacobians unless an extra above has them
+    if (ex.n_sc == 0 && ex.mv_cap == 0) {
+      G2_TRY(plan_alloc(p, &ex.cen, M * h.nr_spheres * 3));
+      G2_TRY(plan_alloc(p, &ex.Jc, M * h.nr_spheres * 3 * D));
+    }
+    G2_TRY(plan_alloc(p, &ex.sp_rec, (size_t)ex.sp_cap));
   }
   if (ex.wp_cap > 0) {   // the path and the list of its constrained states; no poses, Jacobians or rows
     G2_TRY(plan_alloc(p, &ex.wp_des, (size_t)(P.N + 1) * 16));
@@ -494,7 +511,7 @@ int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf
   if (s->Qc) std::copy(s->Qc, s->Qc + (size_t)D * D, p->Qc.begin());
   ExtrasHost hx;
   G2_TRY(check_extras(robot->h, o, p->hp.N, p->ex, hx));
-  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0 || p->ex.wp_cap > 0;
+  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0 || p->ex.wp_cap > 0 || p->ex.sp_cap > 0;
   p->h_xp_n.assign(B, 0);
   p->goal_removed.assign(B, 0);
   G2_TRY(alloc_buffers(p.get(), hx));

@@ -10,7 +10,8 @@ using namespace g2;
 // linearize `traj` into record buffer `bufsel` of every (active) trajectory: the fused obstacle / GP-prior kernel,
 // then -- only for plans that carry extra factors -- the workspace / self-collision factor kernels on the support
 // states and their accumulation into the unary records, and the moving-sphere factor of a non-empty resident set
-// (moving_kernels.hip) and the workspace-path factor of a resident path (path_kernels.hip), which add their terms to
+// (moving_kernels.hip), the self-collision factor of a non-empty resident pair table (selfpair_kernels.hip) and the
+// workspace-path factor of a resident path (path_kernels.hip), which add their terms to
 // the same records without storing rows
 // dst / pass: fused finish (launch_linearize); the extra-factor kernels then run on the NEW states in dst
 int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st, double* dst,
@@ -28,13 +29,15 @@ int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const in
       G2_TRY(launch_workspace_prior(ex.ws_mode[f], ex.ws_link[f], L, D, M, ex.des + 16 * f, ex.poses, ex.Jp,
                                     ex.ws_err + (size_t)f * M * 6, ex.ws_H + (size_t)f * M * 6 * D, st));
   }
-  // the sphere centres and their Jacobians: once, for the self-collision rows and the moving spheres alike
-  if (ex.n_sc > 0 || ex.mv_K > 0) G2_TRY(launch_sphere_centers(h, p->robot->d, M, traj, ex.cen, ex.Jc, st, 2 * D));
+  // the sphere centres and their Jacobians: once, for the self-collision rows, the moving spheres and the pair table
+  if (ex.n_sc > 0 || ex.mv_K > 0 || ex.sp_P > 0)
+    G2_TRY(launch_sphere_centers(h, p->robot->d, M, traj, ex.cen, ex.Jc, st, 2 * D));
   if (ex.n_sc > 0)
     G2_TRY(launch_self_collision(ex.n_sc, S, D, M, ex.sc_data, ex.radius, ex.cen, ex.Jc, ex.sc_err, ex.sc_H, st));
-  // the two accumulations follow each other on the stream: they never touch a record concurrently
+  // the accumulations follow each other on the stream: no two of them touch a record concurrently
   if (ex.n_ws > 0 || ex.n_sc > 0) G2_TRY(launch_extra_accumulate(P, p->pb, ex, L, S, bufsel, active, st));
   G2_TRY(launch_moving_accumulate(P, p->pb, ex, S, bufsel, active, st));   // nothing for an empty set
+  G2_TRY(launch_selfpair_accumulate(P, p->pb, ex, S, bufsel, active, st));   // nothing for an empty table
   // the workspace path (path_kernels.hip): nothing without a constrained state
   return launch_path_accumulate(h, p->robot->d, P, p->pb, ex, traj, bufsel, active, st);
 }

@@ -49,6 +49,13 @@ struct PlanParams {
 // ranges of support states.  They are unary in x_i, so their J^T J / sigma^2, J^T r / sigma^2, r^T r / sigma^2 are
 // added to the record of the state's unary evaluation point after k_linearize (launch_extra_factors); the solver
 // kernels never see them separately.
+// one row of a plan's self-collision table as k_selfpair_accumulate reads it, formed on the host when the table is set:
+// sphere indices in the order of PlanExtras::cen / Jc (the caller's), radius_A + radius_B + epsilon, 1 / sigma^2.  24 bytes.
+struct SelfPairRec {
+  double total_eps, w;
+  int a, b;
+};
+
 struct PlanExtras {
   int n_ws, n_sc, sc_first, sc_last;
   int ws_mode[GPMP2MI_MAX_WORKSPACE_FACTORS], ws_link[GPMP2MI_MAX_WORKSPACE_FACTORS];
@@ -82,6 +89,11 @@ struct PlanExtras {
   double* wp_sigma;      // [N+1], +inf: the state carries no factor
   int* wp_list;          // [N+1] the constrained states, ascending
   int* wp_count;         // [1] how many
+  // self-collision table (include/gpmp2mi.h "self-collision table in a plan"): the capacity, the range and the resident
+  // records.  sp_P is the table's current size, a host value that every launch takes as an argument
+  // (selfpair_kernels.hip)
+  int sp_cap, sp_P, sp_first, sp_last;
+  SelfPairRec* sp_rec;   // [sp_cap], the first sp_P rows in use
 };
 
 // Per-plan device buffers.
@@ -200,6 +212,10 @@ int launch_extra_accumulate(const PlanParams& hp, const PlanBuffers& pb, const P
 // set (ex.mv_K > 0), straight into the unary records
 int launch_moving_accumulate(const PlanParams& hp, const PlanBuffers& pb, const PlanExtras& ex, int S, int bufsel,
                              const int* active, hipStream_t st);
+// selfpair_kernels.hip: the self-collision factor of the states ex.sp_first..sp_last, from ex.cen / ex.Jc and the
+// resident table (ex.sp_P > 0), straight into the unary records
+int launch_selfpair_accumulate(const PlanParams& hp, const PlanBuffers& pb, const PlanExtras& ex, int S, int bufsel,
+                               const int* active, hipStream_t st);
 // path_kernels.hip: the workspace-path factor of the constrained states of the resident path (ex.wp_n > 0), from the
 // states in `traj` straight into the unary records
 int launch_path_accumulate(const RobotDev& h, const RobotDev* R, const PlanParams& hp, const PlanBuffers& pb,

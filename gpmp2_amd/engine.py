@@ -46,6 +46,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_motion(lib)
     _capi.declare_retime(lib)
     _capi.declare_moving(lib)
+    _capi.declare_selfpair(lib)
     _capi.declare_path(lib)
     _capi.declare_map(lib)
     _capi.declare_sensor(lib)
@@ -1687,6 +1688,17 @@ class Plan:
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
             None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, *rates, md,
             *args, C.c_void_p(stream or 0)))
+
+    # ---- a pair table of any size as a factor (include/gpmp2mi.h "self-collision table in a plan")
+    def set_self_pairs(self, pairs):
+        """The plan's self-collision table: a handle of Engine.self_pairs / generate_self_pairs, whose epsilon and sigma
+        columns are the factor's; None or an empty table clears it.  May be repeated between solves; the plan keeps its
+        own copy, and must have been created with room for the rows (TrajOptimizerSetting.set_self_pairs)."""
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_self_pairs(self.h.ptr, None if pairs is None else pairs.ptr))
+
+    def self_pairs_count(self):
+        """rows of the table resident in the plan"""
+        return int(self.eng.lib.gpmp2mi_plan_self_pairs_count(self.h.ptr))
 
     # ---- spheres that move with the support time (include/gpmp2mi.h "moving obstacles")
     def set_moving_spheres(self, radius, centers):

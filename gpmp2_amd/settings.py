@@ -54,6 +54,14 @@ class TrajOptimizerSetting:
         self.self_collision_states = None    # (first, last) support states, default all
         self.moving_spheres = None           # dict(capacity, epsilon, sigma, states): set_moving_spheres
         self.workspace_path = None           # dict(mode, link): set_workspace_path
+        self.self_pairs = None               # dict(capacity, states): set_self_pairs
+
+    def set_self_pairs(self, capacity, states=None):
+        """Room for a self-collision table of `capacity` pairs in the plan (include/gpmp2mi.h "self-collision table in a
+        plan"), a factor on the support states `states` = (first, last), default all; the table itself is data of
+        Plan.set_self_pairs.  capacity 0: none."""
+        self.self_pairs = dict(capacity=int(capacity),
+                               states=None if states is None else (int(states[0]), int(states[1])))
 
     def set_moving_spheres(self, capacity, epsilon, sigma, states=None):
         """Room for `capacity` moving spheres in the plan (include/gpmp2mi.h "moving obstacles") and the constants of

@@ -192,6 +192,8 @@ void gpmp2mi_settings_default(gpmp2mi_settings* s, int dof);
 #define GPMP2MI_MAX_WORKSPACE_FACTORS 4
 #define GPMP2MI_MAX_SELF_COLLISION_PAIRS 16
 #define GPMP2MI_MAX_MOVING_SPHERES 64
+/* all pairs of the largest sphere model: the largest table a plan takes ("self-collision table in a plan" below) */
+#define GPMP2MI_MAX_PLAN_SELF_PAIRS (GPMP2MI_MAX_SPHERES * (GPMP2MI_MAX_SPHERES - 1) / 2)
 /* A workspace factor carried by a plan: GaussianPriorWorkspace{Position,Orientation,Pose}<Arm>
  * (kinematics/GaussianPriorWorkspacePosition.h:52-67, ...Orientation.h:52-69, ...Pose.h:53-70) or GoalFactorArm
  * (kinematics/GoalFactorArm.h:58-77 = POSITION on the last link) on the support states first_state..last_state,
@@ -236,6 +238,10 @@ typedef struct gpmp2mi_graph_opts {
   int workspace_path;            /* 1: reserve the path at plan creation; 0: none */
   int workspace_path_mode;       /* GPMP2MI_WORKSPACE_POSITION / _ORIENTATION / _POSE */
   int workspace_path_link;       /* link index of the FK model */
+  /* ---- self-collision table ("self-collision table in a plan" below): room for a pair table of any size; the table
+   * itself is data of gpmp2mi_plan_set_self_pairs.  All default to 0 = none */
+  int max_self_pairs;            /* capacity reserved at plan creation, <= GPMP2MI_MAX_PLAN_SELF_PAIRS; 0: none */
+  int self_pairs_first, self_pairs_last;   /* inclusive range of support states that carry the factor */
   /* ---- moving spheres ("moving obstacles" below): the capacity and the factor's constants; the spheres themselves are
    * data of gpmp2mi_plan_set_moving_spheres.  Appended at the end of the struct; all default to 0 = none */
   int max_moving_spheres;        /* capacity reserved at plan creation, <= GPMP2MI_MAX_MOVING_SPHERES; 0: none */
@@ -871,6 +877,47 @@ int gpmp2mi_plan_select_moving_dev(gpmp2mi_plan* p, int inter_step, double requi
                                    const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
                                    double required_moving_clearance, int* best, int* n_eligible, double* traj_best,
                                    double* dense_best, void* stream);
+
+/* ---- self-collision table in a plan: a pair table of any size as a plan factor, on the device ----------------------
+ * The self-collision rows of gpmp2mi_graph_opts hold at most GPMP2MI_MAX_SELF_COLLISION_PAIRS pairs, while the check of
+ * "self-collision check" works with the full table.  A plan created with gpmp2mi_graph_opts::max_self_pairs > 0
+ * reserves room for that many pair records (all device memory is taken at gpmp2mi_plan_create: the records, and the
+ * sphere centres and their Jacobians if no other extra factor has them yet), carries the factor below on the support
+ * states self_pairs_first..self_pairs_last, and takes its table from gpmp2mi_plan_set_self_pairs, which may be
+ * repeated between solves.  One table per plan, shared by its B trajectories.
+ *
+ * Definitions, for row p = (A, B, epsilon_p, sigma_p) of the table (sphere ids in the order of the robot description):
+ *  - total_eps_p = radius_A + radius_B + epsilon_p, formed on the host in that order in fp64.
+ *  - The factor, at support state i in [self_pairs_first, self_pairs_last]: dist = |c_A(q_i) - c_B(q_i)|;
+ *    err = dist > total_eps_p ? 0 : total_eps_p - dist (obstacle/SelfCollision.h:66-128; a NaN distance keeps the hinge
+ *    on); the Jacobian row is -n^T (J_A - J_B) when active and zero otherwise, n = (c_A - c_B) / dist, J the
+ *    sphereCenters Jacobian as gpmp2mi_sphere_centers returns it (the Pose2 chart for the mobile kinds).  dist == 0:
+ *    err = total_eps_p, a zero row, no NaN -- the rule of "moving obstacles"; the n_self_collision rows of
+ *    gpmp2mi_graph_opts and gpmp2mi_self_collision_factor divide by the distance and make a NaN row there.
+ *    Weight w_p = 1 / sigma_p^2 (column 3 of the table, which the check does not read, is read here).  The P rows of a
+ *    state are never stored: one kernel adds sum w h h^T, sum w h r and sum w r^2 to the record of the state's unary
+ *    point, in table order, so a state's contribution is the same bits alone, in any batch and on any run.  A chunk of
+ *    64 rows without an active one is skipped; it would add exact zeros.  Every call that linearizes a plan carries
+ *    the factor: optimize, the queue runs (seeded ones included), plan_update, plan_linearize, plan_graph_error;
+ *    Gauss-Newton (without the early stop, as for the other extra factors), LM and Dogleg; narrow, wide and dense
+ *    blocks.  With an empty table nothing is launched for it.
+ *  - The two routes are independent: a plan may carry n_self_collision rows and a table; a pair in both is two factors.
+ * The factor on M evaluations is gpmp2mi_self_collision_factor, which takes any n_pairs.
+ * Errors: GPMP2MI_ERR_INVALID at gpmp2mi_plan_create for max_self_pairs < 0 or above GPMP2MI_MAX_PLAN_SELF_PAIRS, and
+ * with a capacity for a range outside 0..N or first > last.  The setter refuses with GPMP2MI_ERR_INVALID, before any
+ * device work and changing nothing: a NULL plan, a plan created without capacity, more rows than the capacity, a table
+ * made for another robot (sphere count / dof / kind), an epsilon that is not finite, a sigma that is not finite or
+ * <= 0.  GPMP2MI_ERR_TIMEOUT for a poisoned plan.
+ * gpmp2mi_multi_plan_create with a capacity creates shards that hold an empty table.
+ * Not here: the factor at GP-interpolated sub-states (the dense check is what looks between support states),
+ * gpmp2mi_multi_plan_* setters, C++ facade classes, per-trajectory tables, a self-collision term in the risk /
+ * collision-probability calls. */
+
+/* The plan's table.  Valid at any time between solves; NULL or an empty table clears it; a fresh plan holds none.  The
+ * plan keeps its own copy of the records (made before the call returns): the handle may be destroyed at once.  A later
+ * solve on any stream the plan uses sees the new table.  A refused call changes nothing. */
+int gpmp2mi_plan_set_self_pairs(gpmp2mi_plan* p, const gpmp2mi_self_pairs* pairs);
+int gpmp2mi_plan_self_pairs_count(const gpmp2mi_plan* p);   /* rows resident in the plan; -1 for NULL */
 
 /* ---- workspace path: time-indexed end-effector targets as a plan factor and a check, on the device ----------------
  * The workspace factors of gpmp2mi_graph_opts hold one constant des_pose over a range of states.  A workspace path is
