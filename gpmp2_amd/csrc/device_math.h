@@ -112,6 +112,25 @@ __device__ __forceinline__ double hinge_obstacle(const SdfDev& s, double px, dou
   return eps - d;
 }
 
+// The hinge between two spheres, SelfCollision.h:114-127 on (dx, dy, dz) = c_A - c_B (for a moving obstacle c_B is a
+// sphere outside the robot).  active: the hinge is on (a NaN distance keeps it on, as k_self_collision does); n: the
+// direction, zero when dist == 0 (no NaN is made)
+struct SphereHinge {
+  double err, n[3];
+  bool active;
+};
+__device__ __forceinline__ SphereHinge sphere_hinge(double dx, double dy, double dz, double total_eps) {
+  SphereHinge o;
+  const double dist = sqrt(dx * dx + dy * dy + dz * dz);
+  o.active = !(dist > total_eps);
+  o.err = o.active ? total_eps - dist : 0.0;
+  const bool dir = o.active && dist != 0.0;
+  o.n[0] = dir ? dx / dist : 0.0;
+  o.n[1] = dir ? dy / dist : 0.0;
+  o.n[2] = dir ? dz / dist : 0.0;
+  return o;
+}
+
 // hingeLossJointLimitCost  gpmp2/kinematics/JointLimitCost.h:16-31
 __device__ __forceinline__ double hinge_limit(double p, double lo, double hi, double th, double& H) {
   if (p < lo + th) {

@@ -3,9 +3,9 @@
 // inside its joint ranges, joint speeds, joint accelerations and a Cartesian speed at every state that is executed, and by
 // which factor must the duration be stretched if not?
 //
-//   k_motion         the tiling of k_score: a lane is a checked state, a workgroup covers SCORE_TILE consecutive states of
-//                    one trajectory, its `nsub` wavefronts share the spheres (s % nsub).  Every lane up-samples BOTH
-//                    halves of its state (score_dense_coord, score_select.h: the arithmetic of k_interpolate_traj);
+//   k_motion         tiled as k_score is (checked_grid, score_select.h): a lane is a checked state, a workgroup covers
+//                    SCORE_TILE consecutive states of one trajectory, its `nsub` wavefronts share the spheres (s % nsub).
+//                    Every lane up-samples BOTH halves of its state (score_dense_coord: the velocity is needed here);
 //                    wavefront 0 does the coordinate checks (position margin, velocity ratio) once per state, and its
 //                    lanes on a support state that opens an interval the two acceleration ends of that interval; then
 //                    every wavefront walks the chain and contracts each sphere's Jacobian with the velocity column by
@@ -185,12 +185,11 @@ __device__ __forceinline__ MotionRow motion_row(const MotionFinish& a, int b) {
 
 }  // namespace
 
-// Second stage, by the pattern of k_self_finish: rows are taken by thread.  With a.sel.select the grid is one workgroup
+// Second stage: rows are taken by thread (RowPick, score_select.h).  With a.sel.select the grid is one workgroup
 // and the rule reads, besides this stage's own results, the per-row scores k_score_finish and k_self_finish left.
 __global__ __launch_bounds__(256) void k_motion_finish(MotionFinish a) {
   const ScoreFinish& f = a.sel;
-  double my_err = HUGE_VAL;
-  int my_row = INT_MAX, my_cnt = 0;
+  RowPick mine;
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < f.B; b += gridDim.x * blockDim.x) {
     const MotionRow o = motion_row(a, b);
     if (a.pos_margin) a.pos_margin[b] = o.pos_margin;
@@ -208,19 +207,13 @@ __global__ __launch_bounds__(256) void k_motion_finish(MotionFinish a) {
     if (a.invalid) a.invalid[b] = o.invalid;
     if (!f.select) continue;
     const double fe = f.ferr[b];
-    bool ok = score_eligible(!f.status || f.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, a.clearance[b], f.required_clearance,
-                             f.require_in_range, a.oor[b]);
+    bool ok = row_eligible(f, b, fe, a.clearance[b], a.oor[b]);
     if (a.self_clearance) ok = ok && a.self_invalid[b] == 0 && a.self_clearance[b] >= a.required_self_clearance;
     ok = ok && o.invalid == 0 && o.pos_margin >= a.required_pos_margin && o.time_scale <= a.max_time_scale;
-    if (!ok) continue;
-    my_cnt++;
-    if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row
-      my_err = fe;
-      my_row = b;
-    }
+    if (ok) mine.take(fe, b);
   }
   if (!f.select) return;
-  select_finish(f, my_err, my_row, my_cnt);   // f.best is never null here (launch_motion_finish)
+  select_finish(f, mine);   // f.best is never null here (launch_motion_finish)
   if (threadIdx.x == 0 && a.time_scale_best) {
     const int best = *f.best;   // written by this thread
     if (best >= 0) *a.time_scale_best = motion_row(a, best).time_scale;
@@ -229,16 +222,10 @@ __global__ __launch_bounds__(256) void k_motion_finish(MotionFinish a) {
 
 int launch_motion(const RobotDev& h, const RobotDev* R, const MotionLimitsDev& lim, double dt, int inter, int B, int N,
                   const double* traj, MotionRec* recs, hipStream_t st) {
-  const long long Md = (long long)N * (inter + 1) + 1;
-  const long long nblk = (Md + SCORE_TILE - 1) / SCORE_TILE;
-  if (Md >= (1ll << 31) / GPMP2MI_MAX_DOF || nblk * B >= (1ll << 31)) {
-    set_error("too many checked states for one launch");
-    return GPMP2MI_ERR_INVALID;
-  }
-  // wavefronts that share the spheres of a tile: a function of the sphere count alone
-  const int nsub = h.nr_spheres >= 8 ? 4 : 1;
-  const dim3 grid((unsigned)(nblk * B)), block(64 * nsub);
-  G2_DISPATCH_ROBOT_H(h, (k_motion<KIND_, AD_, AD2_><<<grid, block, 0, st>>>(R, lim, dt, inter, N, (int)Md, (int)nblk, traj, recs)));
+  int Md, nblk;
+  if (const int rc = checked_grid(N, inter, SCORE_TILE, B, 1, Md, nblk)) return rc;
+  const dim3 grid((unsigned)(nblk * B)), block(64 * score_waves(h.nr_spheres));
+  G2_DISPATCH_ROBOT_H(h, (k_motion<KIND_, AD_, AD2_><<<grid, block, 0, st>>>(R, lim, dt, inter, N, Md, nblk, traj, recs)));
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
 }
@@ -248,10 +235,7 @@ int launch_motion_finish(const MotionFinish& a, hipStream_t st) {
     set_error("k_motion_finish: the selection needs a place for `best`");
     return GPMP2MI_ERR_INVALID;
   }
-  const int grid = a.sel.select ? 1 : (a.sel.B + 255) / 256;
-  k_motion_finish<<<dim3(grid), dim3(256), 0, st>>>(a);
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_finish(k_motion_finish, a, a.sel.select, a.sel.B, st);
 }
 
 }  // namespace g2

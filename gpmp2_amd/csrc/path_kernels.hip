@@ -8,9 +8,10 @@
 //                      the chain to the link (the walk is uniform over the wavefront, so it costs what one lane's walk
 //                      costs); lane k < D forms column k of the link's body Jacobian and of the <= 6 rows, and leaves it
 //                      in LDS beside the residual.  Every lane then adds the rows, in ascending order, to the record
-//                      entries it owns (entry e = lane, lane + 64, lane + 128 of the D (D + 1) / 2 + D + 1 <= 190 packed
-//                      entries G | g | e) and writes them once.  No poses, no Jacobians and no rows reach memory.
-//   k_path_deviation   the check of the executed trajectory: a lane is a checked state, ONE record per workgroup of 64.
+//                      entries it owns (RecAcc, record_entries.h) and writes them once.  No poses, no Jacobians and no
+//                      rows reach memory.
+//   k_path_deviation   the check of the executed trajectory: a lane is a checked state (checked_config, score_select.h),
+//                      ONE record per workgroup of 64.
 //   k_path_finish      reduces a row's records in index order to the outputs and, when asked, applies the selection rule
 //                      over the per-row scores of the obstacle stage.
 //
@@ -23,6 +24,7 @@
 #include "launch.h"
 #include "lie_log.h"
 #include "plan.h"
+#include "record_entries.h"
 #include "score_select.h"
 
 namespace g2 {
@@ -273,31 +275,10 @@ __global__ __launch_bounds__(64) void k_path_accumulate(const RobotDev* __restri
     if (lane < D) rows[r][lane] = h[r];
     if (lane == D) rows[r][D] = e[r];   // e is the same in every lane
   }
-  // the record entries of this lane as products rows[.][ea] * rows[.][eb]: G (k, k2) packed upper, g_k = h_k r, e = r r
-  const int NE = P.NG + D + 1;
-  int ea[3], eb[3];
-  double acc[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const int en = lane + 64 * j;
-    int k = 0, rem = en;
-    while (k < D && rem >= D - k) {
-      rem -= D - k;
-      k++;
-    }
-    ea[j] = en < P.NG ? k : en < P.NG + D ? en - P.NG : D;
-    eb[j] = en < P.NG ? k + rem : D;
-    if (en >= NE) ea[j] = eb[j] = 0;   // not an entry: reads stay inside the row, nothing is stored
-    acc[j] = 0.0;
-  }
+  RecAcc acc(D, P.NG);
   __syncthreads();
-  for (int r = 0; r < nrow; r++)   // rows in ascending order
-#pragma unroll
-    for (int j = 0; j < 3; j++) acc[j] += w * rows[r][ea[j]] * rows[r][eb[j]];
-  double* rec = rec_of(pb, pb.which[b], bufsel) + ((size_t)b * P.Ppad + (size_t)i * (P.I + 1)) * P.RECS;
-#pragma unroll
-  for (int j = 0; j < 3; j++)
-    if (lane + 64 * j < NE) rec[lane + 64 * j] += acc[j];
+  for (int r = 0; r < nrow; r++) acc.add(w, rows[r]);   // rows in ascending order
+  acc.store(pb, b, i, bufsel, P);
 }
 
 template <int KIND, int AD, int AD2>
@@ -331,26 +312,7 @@ __global__ __launch_bounds__(64) void k_path_deviation(const RobotDev* __restric
   if (chk) {
     const double* s0 = traj + ((size_t)b * (N + 1) + seg) * 2 * D;
     double q[D];
-    if (j == 0) {
-#pragma unroll
-      for (int k = 0; k < D; k++) q[k] = s0[k];
-    } else {   // the arithmetic of k_score / k_self_clearance / k_moving_clearance
-      const double* s1 = s0 + 2 * D;
-      const GpCoef gc = gp_coef_dev(dt, (double)j * (dt / (double)(inter + 1)));
-      if constexpr (Kn::MOBILE) {
-        double x0[3], w0[3], x1[3], w1[3], qp[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { x0[k] = s0[k]; w0[k] = s0[D + k]; x1[k] = s1[k]; w1[k] = s1[D + k]; }
-        lie_interpolate<3>(gc, x0, w0, x1, w1, qp, nullptr);
-#pragma unroll
-        for (int k = 0; k < 3; k++) q[k] = qp[k];
-#pragma unroll
-        for (int k = 3; k < D; k++) q[k] = s0[k] + (gc.l12 * s0[D + k] + gc.p11 * (s1[k] - s0[k]) + gc.p12 * s1[D + k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < D; k++) q[k] = gc.l11 * s0[k] + gc.l12 * s0[D + k] + gc.p11 * s1[k] + gc.p12 * s1[D + k];
-      }
-    }
+    checked_config<Kn>(s0, dt, inter, j, q);
     typename Kn::Axes A;   // filled by the walk, never read here
     Frame F;
     int nc, first;
@@ -416,12 +378,11 @@ __global__ __launch_bounds__(64) void k_path_deviation(const RobotDev* __restric
   if (lane == 0) recs[blockIdx.x] = PathRec{sup, dense, pos, rot, kp, kr, inv, 0};
 }
 
-// Second stage, by the pattern of k_moving_finish: rows are taken by thread.  With a.sel.select the grid is one
-// workgroup and the rule reads, besides this stage's own results, the per-row scores k_score_finish left.
+// Second stage: rows are taken by thread (RowPick, score_select.h).  With a.sel.select the grid is one workgroup and
+// the rule reads, besides this stage's own results, the per-row scores k_score_finish left.
 __global__ __launch_bounds__(256) void k_path_finish(PathFinish a) {
   const ScoreFinish& f = a.sel;
-  double my_err = HUGE_VAL;
-  int my_row = INT_MAX, my_cnt = 0;
+  RowPick mine;
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < f.B; b += gridDim.x * blockDim.x) {
     PathRec t = a.recs[(size_t)b * a.nblk];
     for (int i = 1; i < a.nblk; i++) {   // records in index order
@@ -445,18 +406,11 @@ __global__ __launch_bounds__(256) void k_path_finish(PathFinish a) {
     if (a.invalid) a.invalid[b] = t.inv;
     if (!f.select) continue;
     const double fe = f.ferr[b];
-    bool ok = score_eligible(!f.status || f.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, a.clearance[b], f.required_clearance,
-                             f.require_in_range, a.oor[b]);
-    ok = ok && t.inv == 0 && mp <= a.allowed_pos && mr <= a.allowed_rot;
-    if (!ok) continue;
-    my_cnt++;
-    if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row
-      my_err = fe;
-      my_row = b;
-    }
+    const bool ok = row_eligible(f, b, fe, a.clearance[b], a.oor[b]) && t.inv == 0 && mp <= a.allowed_pos && mr <= a.allowed_rot;
+    if (ok) mine.take(fe, b);
   }
   if (!f.select) return;
-  select_finish(f, my_err, my_row, my_cnt);
+  select_finish(f, mine);
 }
 
 int launch_path_factor(const RobotDev& h, const RobotDev* R, int mode, int link, int M, const double* conf,
@@ -493,24 +447,17 @@ int path_blocks(int Md) { return (Md + 63) / 64; }
 
 int launch_path_deviation(const RobotDev& h, const RobotDev* R, int mode, int link, const double* des, const double* sigma,
                           double dt, int inter, int B, int N, const double* traj, PathRec* recs, hipStream_t st) {
-  const long long Md = (long long)N * (inter + 1) + 1;
-  const long long nblk = (Md + 63) / 64;
-  if (Md >= (1ll << 31) / GPMP2MI_MAX_DOF || nblk * B >= (1ll << 31)) {
-    set_error("too many checked states for one launch");
-    return GPMP2MI_ERR_INVALID;
-  }
+  int Md, nblk;
+  if (const int rc = checked_grid(N, inter, 64, B, 1, Md, nblk)) return rc;
   const dim3 grid((unsigned)(nblk * B));
   G2_DISPATCH_ROBOT_H(h, (k_path_deviation<KIND_, AD_, AD2_><<<grid, dim3(64), 0, st>>>(R, mode, link, des, sigma, dt, inter, N,
-                                                                                      (int)Md, (int)nblk, traj, recs)));
+                                                                                      Md, nblk, traj, recs)));
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
 }
 
 int launch_path_finish(const PathFinish& a, hipStream_t st) {
-  const int grid = a.sel.select ? 1 : (a.sel.B + 255) / 256;
-  k_path_finish<<<dim3(grid), dim3(256), 0, st>>>(a);
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_finish(k_path_finish, a, a.sel.select, a.sel.B, st);
 }
 
 }  // namespace g2

@@ -3,9 +3,9 @@
 // sdot_k of planned against executed time at every checked state that makes the duration as short as the joint speeds,
 // joint accelerations and the Cartesian sphere speed allow.  The rule is retime_rule.h; these kernels spread it.
 //
-//   k_retime_caps    the tiling of k_motion: a lane is a checked state, a workgroup covers SCORE_TILE consecutive states
-//                    of one trajectory, its `nsub` wavefronts share the spheres.  Writes ps_k, the largest sphere speed
-//                    of the state (NaN when one of them is not finite).
+//   k_retime_caps    tiled as k_motion is (checked_grid, score_select.h): a lane is a checked state, a workgroup covers
+//                    SCORE_TILE consecutive states of one trajectory, its `nsub` wavefronts share the spheres.  Writes
+//                    ps_k, the largest sphere speed of the state (NaN when one of them is not finite).
 //   k_retime         one wavefront per row.  Caps X_k and the finiteness of the row, a lane per state.  Then the chain:
 //                    per stage, lanes < 2 D form the rows from the two support states of the interval (TRAJ) or from the
 //                    caller's arrays, lane 2 D the row of the next set; the (2 D + 1)^2 pairs are strided over the lanes
@@ -360,23 +360,16 @@ __global__ __launch_bounds__(64) void k_retime(RetimeArgs a) {
 // The selection of gpmp2mi_plan_select_retimed: one workgroup, rows by thread.
 __global__ __launch_bounds__(256) void k_retime_finish(RetimeFinish a) {
   const ScoreFinish& f = a.sel;
-  double my_err = HUGE_VAL;
-  int my_row = INT_MAX, my_cnt = 0;
+  RowPick mine;
   for (int b = threadIdx.x; b < f.B; b += blockDim.x) {
     const double fe = f.ferr[b];
-    bool ok = score_eligible(!f.status || f.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, a.clearance[b], f.required_clearance,
-                             f.require_in_range, a.oor[b]);
+    bool ok = row_eligible(f, b, fe, a.clearance[b], a.oor[b]);
     if (a.self_clearance) ok = ok && a.self_invalid[b] == 0 && a.self_clearance[b] >= a.required_self_clearance;
     ok = ok && a.motion_invalid[b] == 0 && a.pos_margin[b] >= a.required_pos_margin;
     ok = ok && a.rstatus[b] == RETIME_OK && a.duration[b] <= a.max_duration;
-    if (!ok) continue;
-    my_cnt++;
-    if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row
-      my_err = fe;
-      my_row = b;
-    }
+    if (ok) mine.take(fe, b);
   }
-  select_finish(f, my_err, my_row, my_cnt);   // f.best is never null here (launch_retime_finish)
+  select_finish(f, mine);   // f.best is never null here (launch_retime_finish)
   __syncthreads();   // best, and dense_best as interpolated
   const int best = *f.best;
   if (best < 0) return;
@@ -394,19 +387,14 @@ __global__ __launch_bounds__(256) void k_retime_finish(RetimeFinish a) {
 
 int launch_retime_caps(const RobotDev& h, const RobotDev* R, double dt, int inter, int B, int N, const double* traj,
                        double* ps, hipStream_t st) {
-  const long long Md = (long long)N * (inter + 1) + 1;
-  const long long nblk = (Md + SCORE_TILE - 1) / SCORE_TILE;
-  if (Md >= (1ll << 31) / GPMP2MI_MAX_DOF || nblk * B >= (1ll << 31)) {
-    set_error("too many checked states for one launch");
-    return GPMP2MI_ERR_INVALID;
-  }
-  const int nsub = h.nr_spheres >= 8 ? 4 : 1;   // as k_motion
-  const dim3 grid((unsigned)(nblk * B)), block(64 * nsub);
+  int Md, nblk;
+  if (const int rc = checked_grid(N, inter, SCORE_TILE, B, 1, Md, nblk)) return rc;
+  const dim3 grid((unsigned)(nblk * B)), block(64 * score_waves(h.nr_spheres));
   if (h.kind == GPMP2MI_ROBOT_POINT) {
-    k_retime_caps<GPMP2MI_ROBOT_POINT, 0, 0><<<grid, block, 0, st>>>(R, dt, inter, N, (int)Md, (int)nblk, traj, ps);
+    k_retime_caps<GPMP2MI_ROBOT_POINT, 0, 0><<<grid, block, 0, st>>>(R, dt, inter, N, Md, nblk, traj, ps);
   } else if (h.kind == GPMP2MI_ROBOT_ARM) {
     G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_retime_caps<GPMP2MI_ROBOT_ARM, AD_, 0><<<grid, block, 0, st>>>(
-                                              R, dt, inter, N, (int)Md, (int)nblk, traj, ps)));
+                                              R, dt, inter, N, Md, nblk, traj, ps)));
   } else {
     set_error("re-timing is not built for the Pose2 kinds: the acceleration of the tangent-space interpolation is missing");
     return GPMP2MI_ERR_UNSUPPORTED;
@@ -431,9 +419,7 @@ int launch_retime_finish(const RetimeFinish& a, hipStream_t st) {
     set_error("k_retime_finish: the selection needs a place for `best`");
     return GPMP2MI_ERR_INVALID;
   }
-  k_retime_finish<<<dim3(1), dim3(256), 0, st>>>(a);
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_finish(k_retime_finish, a, 1, a.sel.B, st);
 }
 
 }  // namespace g2

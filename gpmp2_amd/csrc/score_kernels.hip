@@ -2,11 +2,13 @@
 // (include/gpmp2mi.h "scoring"): which of these trajectories is executed, and is it collision-free between its
 // support states as well?
 //
-//   k_score         one lane per checked state of a trajectory: GP up-sampling (the arithmetic of k_interpolate_traj,
-//                   factor_kernels.hip) -> value-only walk of the kinematic chain -> field lookup per sphere -> hinge
-//                   sum, minimum clearance with its (state, sphere) and the out-of-range count; the up-sampled states
-//                   never reach memory.  A workgroup covers SCORE_TILE consecutive states; its `nsub` wavefronts share
-//                   the spheres of those states (s % nsub).  Wavefront butterfly -> LDS -> ONE record per workgroup.
+//   k_score         one lane per checked state of a trajectory: GP up-sampling -> value-only walk of the kinematic
+//                   chain -> field lookup per sphere -> hinge sum, minimum clearance with its (state, sphere) and the
+//                   out-of-range count; the up-sampled states never reach memory.  A workgroup covers SCORE_TILE
+//                   consecutive states; its `nsub` wavefronts share the spheres of those states (s % nsub).  ONE record
+//                   per workgroup (block_score_record, score_select.h).  The up-sampling is the text of checked_config
+//                   (score_select.h) written out: called from here, the same expressions are scheduled with up to ten
+//                   more VGPRs, which costs the 7- and 8-joint arm in a planar field a wavefront of occupancy.
 //   k_score_finish  reduces the records of every row in index order to the five per-row outputs, applies the
 //                   selection rule when asked and copies the chosen row and its up-sampled form.
 //
@@ -29,8 +31,6 @@ __global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, 
   using K = Kin<KIND, AD, AD2>;
   constexpr int D = K::DOF;
   __shared__ RobotDev R;
-  __shared__ double w_sup[4], w_den[4], w_clr[4];
-  __shared__ int w_k[4], w_s[4], w_oor[4];
   stage_robot(&R, Rg);
   const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk;
   const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6, nsub = blockDim.x >> 6;
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, 
     support = j == 0;
     const double* s0 = traj + ((size_t)b * (N + 1) + seg) * 2 * D;
     double q[D];
-    if (j == 0) {
+    if (j == 0) {   // checked_config, written out (see above)
 #pragma unroll
       for (int k = 0; k < D; k++) q[k] = s0[k];
     } else {
@@ -83,32 +83,7 @@ __global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, 
       if (key_less(key, best)) best = key;
     }, sub, nsub);
   }
-  double sup = support ? dense : 0.0;
-  // wavefront: butterfly (both partners add the same two numbers, so all 64 lanes end with the same bits)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    sup += __shfl_xor(sup, off);
-    dense += __shfl_xor(dense, off);
-    oor += __shfl_xor(oor, off);
-    const ScoreKey o{__shfl_xor(best.c, off), __shfl_xor(best.k, off), __shfl_xor(best.s, off)};
-    if (key_less(o, best)) best = o;
-  }
-  if (lane == 0) {
-    w_sup[sub] = sup; w_den[sub] = dense; w_clr[sub] = best.c;
-    w_k[sub] = best.k; w_s[sub] = best.s; w_oor[sub] = oor;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ScoreRec r{w_sup[0], w_den[0], w_clr[0], w_k[0], w_s[0], w_oor[0], 0};
-    for (int w = 1; w < nsub; w++) {   // wavefronts in index order
-      r.support += w_sup[w];
-      r.dense += w_den[w];
-      r.oor += w_oor[w];
-      const ScoreKey a{w_clr[w], w_k[w], w_s[w]}, c{r.clearance, r.k, r.s};
-      if (key_less(a, c)) { r.clearance = a.c; r.k = a.k; r.s = a.s; }
-    }
-    recs[blockIdx.x] = r;
-  }
+  block_score_record(support ? dense : 0.0, dense, oor, best, recs);
 }
 
 // Second stage.  Rows are taken by thread (row = thread id + multiple of the thread count): a row's records are summed
@@ -116,8 +91,7 @@ __global__ __launch_bounds__(256) void k_score(const RobotDev* __restrict__ Rg, 
 // the workgroup reduces them through LDS, then all its threads copy the chosen row (select_finish, score_select.h).
 // a.recs == nullptr: selection over given scores (gpmp2mi_select_best_dev).
 __global__ __launch_bounds__(256) void k_score_finish(ScoreFinish a) {
-  double my_err = HUGE_VAL;
-  int my_row = INT_MAX, my_cnt = 0;
+  RowPick mine;
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
     double clr;
     int oor;
@@ -140,46 +114,30 @@ __global__ __launch_bounds__(256) void k_score_finish(ScoreFinish a) {
     }
     if (!a.select) continue;
     const double fe = a.ferr[b];
-    const bool ok = score_eligible(!a.status || a.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, clr, a.required_clearance,
-                                   a.require_in_range, oor);
-    if (!ok) continue;
-    my_cnt++;
-    if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row
-      my_err = fe;
-      my_row = b;
-    }
+    if (row_eligible(a, b, fe, clr, oor)) mine.take(fe, b);
   }
   if (!a.select) return;
-  select_finish(a, my_err, my_row, my_cnt);
+  select_finish(a, mine);
 }
 
 int score_blocks(int Md) { return (Md + SCORE_TILE - 1) / SCORE_TILE; }
 
 int launch_score(const RobotDev& h, const RobotDev* R, const SdfDev& s, double dt, int inter, int B, int N,
                  const double* traj, ScoreRec* recs, hipStream_t st) {
-  const long long Md = (long long)N * (inter + 1) + 1;
-  const long long nblk = (Md + SCORE_TILE - 1) / SCORE_TILE;
-  if (Md >= (1ll << 31) / GPMP2MI_MAX_DOF || nblk * B >= (1ll << 31)) {
-    set_error("too many checked states for one launch");
-    return GPMP2MI_ERR_INVALID;
-  }
-  // wavefronts that share the spheres of a tile: a function of the sphere count alone
-  const int nsub = h.nr_spheres >= 8 ? 4 : 1;
-  const dim3 grid((unsigned)(nblk * B)), block(64 * nsub);
+  int Md, nblk;
+  if (const int rc = checked_grid(N, inter, SCORE_TILE, B, 1, Md, nblk)) return rc;
+  const dim3 grid((unsigned)(nblk * B)), block(64 * score_waves(h.nr_spheres));
   if (s.dim == 3) {
-    G2_DISPATCH_ROBOT_H(h, (k_score<KIND_, AD_, AD2_, 3><<<grid, block, 0, st>>>(R, s, dt, inter, N, (int)Md, (int)nblk, traj, recs)));
+    G2_DISPATCH_ROBOT_H(h, (k_score<KIND_, AD_, AD2_, 3><<<grid, block, 0, st>>>(R, s, dt, inter, N, Md, nblk, traj, recs)));
   } else {
-    G2_DISPATCH_ROBOT_H(h, (k_score<KIND_, AD_, AD2_, 2><<<grid, block, 0, st>>>(R, s, dt, inter, N, (int)Md, (int)nblk, traj, recs)));
+    G2_DISPATCH_ROBOT_H(h, (k_score<KIND_, AD_, AD2_, 2><<<grid, block, 0, st>>>(R, s, dt, inter, N, Md, nblk, traj, recs)));
   }
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
 }
 
 int launch_score_finish(const ScoreFinish& a, hipStream_t st) {
-  const int grid = a.select ? 1 : (a.B + 255) / 256;
-  k_score_finish<<<dim3(grid), dim3(256), 0, st>>>(a);
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_finish(k_score_finish, a, a.select, a.B, st);
 }
 
 }  // namespace g2

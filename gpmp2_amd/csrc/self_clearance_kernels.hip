@@ -2,13 +2,13 @@
 // gpmp2mi_plan_self_score / gpmp2mi_plan_select_checked (include/gpmp2mi.h "self-collision check"): does the robot
 // touch itself at any of the states that are executed, for any pair of a table far larger than the in-plan factor holds?
 //
-//   k_self_clearance  the tiling of k_score: a lane is a checked state, a workgroup covers self_tile(S) consecutive
-//                     states of one trajectory.  Phase 1: GP up-sampling (the arithmetic of k_score) -> value-only walk
+//   k_self_clearance  a lane is a checked state, a workgroup covers self_tile(S) consecutive states of one trajectory
+//                     (checked_grid, score_select.h).  Phase 1: GP up-sampling (checked_config) -> value-only walk
 //                     of the kinematic chain; the sphere centres go to LDS, lane-minor ([coord][sphere][state]), the
 //                     spheres dealt to the wavefronts (and, in a tile narrower than a wavefront, to the 64 / tile lanes
 //                     that share a state).  Barrier.  Phase 2: the pairs dealt the same way; per (state, pair) six
-//                     doubles from LDS -> distance, hinge, key (clearance, state, pair).  Wavefront butterfly -> LDS ->
-//                     ONE record per workgroup.
+//                     doubles from LDS -> distance, hinge, key (clearance, state, pair).  ONE record per workgroup
+//                     (block_score_record).
 //   k_self_finish     reduces the records of every row in index order to the five per-row outputs; when asked, reduces
 //                     the records of k_score for the same rows as well, applies the selection rule with both
 //                     clearances and copies the chosen row and its up-sampled form.
@@ -34,8 +34,6 @@ __global__ __launch_bounds__(256) void k_self_clearance(const RobotDev* __restri
   constexpr int D = K::DOF;
   extern __shared__ __attribute__((aligned(16))) double ctr[];   // [3][S][tile]
   __shared__ RobotDev R;
-  __shared__ double w_sup[4], w_den[4], w_clr[4];
-  __shared__ int w_k[4], w_p[4], w_inv[4];
   stage_robot(&R, Rg);
   const int S = R.nr_spheres;
   const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk;
@@ -48,27 +46,7 @@ __global__ __launch_bounds__(256) void k_self_clearance(const RobotDev* __restri
     const int seg = m / (inter + 1), j = m % (inter + 1);
     const double* s0 = traj + ((size_t)b * (N + 1) + seg) * 2 * D;
     double q[D];
-    if (j == 0) {
-#pragma unroll
-      for (int k = 0; k < D; k++) q[k] = s0[k];
-    } else {
-      const double* s1 = s0 + 2 * D;
-      const GpCoef gc = gp_coef_dev(dt, (double)j * (dt / (double)(inter + 1)));
-      if constexpr (K::MOBILE) {
-        // GaussianProcessInterpolatorPose2Vector: the Pose2 part through lie_interpolate, the rest as it does
-        double x0[3], w0[3], x1[3], w1[3], qp[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { x0[k] = s0[k]; w0[k] = s0[D + k]; x1[k] = s1[k]; w1[k] = s1[D + k]; }
-        lie_interpolate<3>(gc, x0, w0, x1, w1, qp, nullptr);
-#pragma unroll
-        for (int k = 0; k < 3; k++) q[k] = qp[k];
-#pragma unroll
-        for (int k = 3; k < D; k++) q[k] = s0[k] + (gc.l12 * s0[D + k] + gc.p11 * (s1[k] - s0[k]) + gc.p12 * s1[D + k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < D; k++) q[k] = gc.l11 * s0[k] + gc.l12 * s0[D + k] + gc.p11 * s1[k] + gc.p12 * s1[D + k];
-      }
-    }
+    checked_config<K>(s0, dt, inter, j, q);
     typename K::Axes A;   // filled by the walk, never read here: the Jacobian work is dead code
     K::walk(R, q, A, [&](int s, const double (&p)[3], auto) {
 #pragma unroll
@@ -102,41 +80,15 @@ __global__ __launch_bounds__(256) void k_self_clearance(const RobotDev* __restri
       for (int p = sub * slots + slot; p < P; p += nsub * slots) pair(p);
     }
   }
-  double sup = (live && m % (inter + 1) == 0) ? dense : 0.0;
-  // wavefront: butterfly (both partners add the same two numbers, so all 64 lanes end with the same bits)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    sup += __shfl_xor(sup, off);
-    dense += __shfl_xor(dense, off);
-    inv += __shfl_xor(inv, off);
-    const ScoreKey o{__shfl_xor(best.c, off), __shfl_xor(best.k, off), __shfl_xor(best.s, off)};
-    if (key_less(o, best)) best = o;
-  }
-  if (lane == 0) {
-    w_sup[sub] = sup; w_den[sub] = dense; w_clr[sub] = best.c;
-    w_k[sub] = best.k; w_p[sub] = best.s; w_inv[sub] = inv;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ScoreRec r{w_sup[0], w_den[0], w_clr[0], w_k[0], w_p[0], w_inv[0], 0};
-    for (int w = 1; w < nsub; w++) {   // wavefronts in index order
-      r.support += w_sup[w];
-      r.dense += w_den[w];
-      r.oor += w_inv[w];
-      const ScoreKey a{w_clr[w], w_k[w], w_p[w]}, c{r.clearance, r.k, r.s};
-      if (key_less(a, c)) { r.clearance = a.c; r.k = a.k; r.s = a.s; }
-    }
-    recs[blockIdx.x] = r;
-  }
+  block_score_record((live && m % (inter + 1) == 0) ? dense : 0.0, dense, inv, best, recs);
 }
 
-// Second stage, by the pattern of k_score_finish: rows are taken by thread, a row's records are summed in index order.
+// Second stage: rows are taken by thread, a row's records are summed in index order (RowPick, reduce_records).
 // With a.sel.select the grid is one workgroup and the rule reads both clearances of a row: the obstacle records of
 // k_score (a.sel.recs) are reduced here too, by the same function k_score_finish uses.
 __global__ __launch_bounds__(256) void k_self_finish(SelfFinish a) {
   const ScoreFinish& f = a.sel;
-  double my_err = HUGE_VAL;
-  int my_row = INT_MAX, my_cnt = 0;
+  RowPick mine;
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < f.B; b += gridDim.x * blockDim.x) {
     const ScoreRec t = reduce_records(a.recs + (size_t)b * a.nblk, a.nblk);
     const bool none = t.k == INT_MAX;
@@ -151,44 +103,28 @@ __global__ __launch_bounds__(256) void k_self_finish(SelfFinish a) {
     if (!f.select) continue;
     const ScoreRec o = reduce_records(f.recs + (size_t)b * f.nblk, f.nblk);
     const double fe = f.ferr[b];
-    const bool ok = score_eligible(!f.status || f.status[b] != GPMP2MI_TRAJ_NOT_SPD, fe, o.clearance,
-                                   f.required_clearance, f.require_in_range, o.oor) &&
-                    t.oor == 0 && t.clearance >= a.required_self_clearance;
-    if (!ok) continue;
-    my_cnt++;
-    if (fe < my_err) {   // rows ascend within a thread: a tie keeps the lower row
-      my_err = fe;
-      my_row = b;
-    }
+    const bool ok = row_eligible(f, b, fe, o.clearance, o.oor) && t.oor == 0 && t.clearance >= a.required_self_clearance;
+    if (ok) mine.take(fe, b);
   }
   if (!f.select) return;
-  select_finish(f, my_err, my_row, my_cnt);
+  select_finish(f, mine);
 }
 
 int launch_self_clearance(const RobotDev& h, const RobotDev* R, const SelfPair* pairs, int P, double dt, int inter, int B,
                           int N, const double* traj, ScoreRec* recs, hipStream_t st) {
   const int S = h.nr_spheres, tile = self_tile(S);
-  const long long Md = (long long)N * (inter + 1) + 1;
-  const long long nblk = (Md + tile - 1) / tile;
-  if (Md >= (1ll << 31) / GPMP2MI_MAX_DOF || nblk * B >= (1ll << 31) || Md * std::max(P, 1) >= (1ll << 31)) {
-    set_error("too many checked states for one launch");
-    return GPMP2MI_ERR_INVALID;
-  }
-  // wavefronts that share the spheres and the pairs of a tile: a function of the sphere count alone
-  const int nsub = S >= 8 ? 4 : 1;
+  int Md, nblk;
+  if (const int rc = checked_grid(N, inter, tile, B, P, Md, nblk)) return rc;
   const size_t lds = (size_t)3 * std::max(S, 1) * tile * sizeof(double);   // <= 48 KB by self_tile
-  const dim3 grid((unsigned)(nblk * B)), block(64 * nsub);
+  const dim3 grid((unsigned)(nblk * B)), block(64 * score_waves(S));
   G2_DISPATCH_ROBOT_H(h, (k_self_clearance<KIND_, AD_, AD2_><<<grid, block, lds, st>>>(R, pairs, P, tile, dt, inter, N,
-                                                                                      (int)Md, (int)nblk, traj, recs)));
+                                                                                      Md, nblk, traj, recs)));
   G2_HIP(hipGetLastError());
   return GPMP2MI_OK;
 }
 
 int launch_self_finish(const SelfFinish& a, hipStream_t st) {
-  const int grid = a.sel.select ? 1 : (a.sel.B + 255) / 256;
-  k_self_finish<<<dim3(grid), dim3(256), 0, st>>>(a);
-  G2_HIP(hipGetLastError());
-  return GPMP2MI_OK;
+  return launch_finish(k_self_finish, a, a.sel.select, a.sel.B, st);
 }
 
 }  // namespace g2
