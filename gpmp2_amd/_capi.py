@@ -222,6 +222,35 @@ def declare_retime(lib):
         getattr(lib, name).restype = i
 
 
+class DynamicsDescC(C.Structure):
+    """gpmp2mi_dynamics_desc (include/gpmp2mi.h "torque limits"): host arrays, gravity, and the limits or NULL."""
+    _fields_ = [("mass", c_double_p), ("com", c_double_p), ("inertia", c_double_p), ("gravity", C.c_double * 3),
+                ("torque", c_double_p)]
+
+
+def declare_torque(lib):
+    """argtypes of the torque-limit entry points (include/gpmp2mi.h "torque limits"); the description and `limits` are
+    host structs in every form, the `_dev` forms take device addresses for everything else."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    lp, dp = C.POINTER(MotionLimitsC), C.POINTER(DynamicsDescC)
+    decl = {
+        "gpmp2mi_dynamics_create": [vp, dp, vp],
+        "gpmp2mi_torque_score_traj": [vp, vp, f, i, i, i, d, d, d, d, ip, ip, d],
+        "gpmp2mi_torque_score_traj_dev": [vp, vp, f, i, i, i] + [vp] * 8,
+        "gpmp2mi_plan_torque_score": [vp, vp, i, d, d, d, ip, ip, d],
+        "gpmp2mi_plan_torque_score_dev": [vp, vp, i] + [vp] * 7,
+        "gpmp2mi_plan_select_dynamic": [vp, i, f, i, vp, f, lp, f, f, vp, ip, ip, d, d, d, d],
+        "gpmp2mi_plan_select_dynamic_dev": [vp, i, f, i, vp, f, lp, f, f, vp] + [vp] * 7,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+    lib.gpmp2mi_dynamics_desc_default.argtypes = [dp]
+    lib.gpmp2mi_dynamics_desc_default.restype = None
+    lib.gpmp2mi_dynamics_destroy.argtypes = [vp]
+    lib.gpmp2mi_dynamics_destroy.restype = None
+
+
 def declare_moving(lib):
     """argtypes of the moving-obstacle entry points (include/gpmp2mi.h "moving obstacles"); the `_dev` forms take device
     addresses."""

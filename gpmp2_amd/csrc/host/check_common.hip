@@ -1,5 +1,6 @@
 // check_common.hip -- the host-side driver that the check stages of the executed trajectory share (score.hip,
-// self_score.hip, motion_score.hip, moving.hip, path.hip, retime.hip; group.hip takes the parts that fit): the preamble
+// self_score.hip, motion_score.hip, moving.hip, path.hip, retime.hip, torque.hip; group.hip takes the parts that fit): the
+// preamble
 // of a plan form, the shape and the selection of its finish kernel, the earlier stages a later one's rule reads, the
 // closing read-back of a host form, and the preamble of a caller-buffer `_dev` form.  The layouts and the staging rule
 // are in staging.h; the kernels and what they compute stay with the stages.

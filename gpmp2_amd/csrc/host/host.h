@@ -200,6 +200,23 @@ struct gpmp2mi_self_pairs {
   }
 };
 
+// The inertial table of a fixed-base arm (torque.hip; include/gpmp2mi.h "torque limits"), bound to the kinematics of
+// the robot it was made for: the table on the device, the limits and gravity on the host (they travel as a kernel
+// argument).
+struct gpmp2mi_dynamics {
+  g2::RobotDev robot;          // the kinematics the table belongs to, as the robot handle had them at creation
+  g2::TorqueLimitsDev lim;     // +inf: no limit
+  int device = -1;             // the device `d` lives on
+  g2::DynDev* d = nullptr;
+  // records (and nothing else) of gpmp2mi_torque_score_traj(_dev) calls with this handle, by the rules of
+  // gpmp2mi_robot::score_ws: mu guards the pointer, the calls themselves must be in stream order
+  mutable std::mutex mu;
+  mutable g2::Workspace ws;
+  ~gpmp2mi_dynamics() {
+    if (d) (void)hipFree(d);
+  }
+};
+
 // A scene (scene.hip; include/gpmp2mi.h "scene"): the objects on the host as they were given (poses and enabled flags
 // change in place), the meshes' vertices and triangles on the device, and the workspace of a rasterisation.
 struct gpmp2mi_scene {
@@ -380,8 +397,9 @@ struct gpmp2mi_plan {
   //   GROUP    the bit matrix of k_traj_pairs, the per-row scores the rule reads, what k_group_rule leaves, the staging
   //   MOTION, MOVING, PATH   CheckWs with the stage's records and the per-row scores of the earlier stages its rule reads
   //   RETIME   ps, the caps and the sets of k_retime, the profile, the scores of the earlier stages, the staging
+  //   TORQUE   the records of k_torque, the scores of the earlier stages, the staging with the torques, the pick
   enum Ws { WS_QUEUE, WS_SCORE, WS_POST, WS_SEED, WS_RISK, WS_SAMPLED, WS_SELF, WS_GROUP, WS_MOTION, WS_MOVING, WS_PATH,
-            WS_RETIME, WS_COUNT };
+            WS_RETIME, WS_TORQUE, WS_COUNT };
   g2::Workspace ws[WS_COUNT];
   // seeding (seed.hip): H_seed of the plan's linear prior graph on the host (built at the first seeded call or read-out)
   std::vector<double> seed_Hd, seed_Ho;

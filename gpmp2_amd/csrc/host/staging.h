@@ -229,6 +229,46 @@ inline RetimeWs carve_retime(char* base, RowOut* rows, const Shape& s) {
   return w;
 }
 
+// torque limits: tau [B][Md][D] is the last row, which a selection needs room for whoever asks (the chosen row's torques
+// are copied out of it)
+struct TorqueOut {
+  double *torque_ratio = nullptr, *static_ratio = nullptr, *time_scale = nullptr;
+  int *worst = nullptr, *invalid = nullptr;   // worst: [B][3][2]
+  double* tau = nullptr;
+};
+constexpr int TORQUE_ROWS = 6;
+inline void rows_of(const TorqueOut& o, size_t Md, size_t D, RowOut* r) {
+  r[0] = row(o.torque_ratio), r[1] = row(o.static_ratio), r[2] = row(o.time_scale), r[3] = row(o.worst, 6);
+  r[4] = row(o.invalid), r[5] = row(o.tau, Md * D);
+}
+inline TorqueOut torque_out(const RowOut* r, bool host) {
+  TorqueOut o;
+  o.torque_ratio = target<double>(r[0], host), o.static_ratio = target<double>(r[1], host);
+  o.time_scale = target<double>(r[2], host), o.worst = target<int>(r[3], host), o.invalid = target<int>(r[4], host);
+  o.tau = target<double>(r[5], host);
+  return o;
+}
+// the stage's records, the scores of all three earlier stages with the motion stage's time_scale [B] behind them, the
+// staged outputs, and the pick with the chosen row's torques [Md][D] behind it
+struct TorqueWs {
+  char* recs;
+  PriorRows prior;
+  double* motion_time_scale;
+  PickRows sel;
+  size_t bytes;
+};
+inline TorqueWs carve_torque(char* base, size_t rec_bytes, RowOut* rows, const Shape& s) {
+  TorqueWs w;
+  Carver c{base};
+  w.recs = c(rec_bytes);
+  w.prior = carve_priors(c, s.B, 3);
+  w.motion_time_scale = c.take<double>(s.B);
+  carve_rows(c, rows, TORQUE_ROWS, s.B);
+  w.sel = carve_pick(c, s, true, s.Md * s.D * sizeof(double));
+  w.bytes = c.off;
+  return w;
+}
+
 // distinct alternatives: the bit matrix of k_traj_pairs ([B][words] 64-bit words), the per-row scores the rule reads,
 // what the rule leaves, then the staging of the host form (`alt_cap` slots of indices, sizes and errors; max_alt slabs)
 struct GroupWs {

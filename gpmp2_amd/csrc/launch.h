@@ -264,6 +264,46 @@ struct RetimeFinish {
 };
 int launch_retime_finish(const RetimeFinish& a, hipStream_t st);
 
+// torque_kernels.hip (include/gpmp2mi.h "torque limits")
+// the inertial table of a fixed-base arm as k_torque reads it: lives in HBM once per dynamics handle, staged into LDS
+// by every workgroup as RobotDev is.  Link j carries mass[j], its centre of mass com[3 j ..] in the link frame and
+// inertia[6 j ..] = ixx iyy izz ixy ixz iyz about that centre, link frame.
+constexpr int TORQUE_MAX_AD = 8;   // k_torque is instantiated for fixed-base arms of 1..8 joints
+struct DynDev {
+  double mass[TORQUE_MAX_AD], com[TORQUE_MAX_AD * 3], inertia[TORQUE_MAX_AD * 6];
+};
+// the torque limits and gravity as k_torque reads them, a kernel argument: +inf where there is no limit
+struct TorqueLimitsDev {
+  double limit[TORQUE_MAX_AD], gravity[3];
+};
+// What one workgroup of k_torque leaves for k_torque_finish: MINUS the largest |tau| / L, |tau_g| / L and r of its tile
+// of SCORE_TILE checked states (minima under key_less, exact ties to the lowest indices), each with its (state, joint),
+// and the count of non-finite torques.  ij = INT_MAX: none.  56 bytes.
+struct TorqueRec {
+  double v[3];
+  int ij[3][2];
+  int invalid, pad;
+};
+// arguments of k_torque_finish; every output may be null.  `sel` carries the selection (sel.select) and the shape of the
+// trajectories; the rule reads the per-row scores the existing stages left, as RetimeFinish does, and the motion stage's
+// time_scale.  tau: what k_torque wrote, [B][Md][D], the source of tau_best.
+struct TorqueFinish {
+  ScoreFinish sel;
+  const TorqueRec* recs;   // [B][nblk]
+  int nblk;
+  double *torque_ratio, *static_ratio, *time_scale;
+  int *worst, *invalid;    // [B][3][2], [B]
+  const double *clearance, *self_clearance, *pos_margin, *motion_time_scale;
+  const int *oor, *self_invalid, *motion_invalid;
+  double required_self_clearance, required_pos_margin, max_time_scale;
+  const double* tau;
+  double *time_scale_best, *tau_best;
+};
+// records per row: score_blocks.  tau: [B][Md][D] or null
+int launch_torque(const RobotDev& h, const RobotDev* R, const DynDev* dyn, const TorqueLimitsDev& lim, double dt, int inter,
+                  int B, int N, const double* traj, TorqueRec* recs, double* tau, hipStream_t st);
+int launch_torque_finish(const TorqueFinish& a, hipStream_t st);
+
 // moving_kernels.hip (include/gpmp2mi.h "moving obstacles"; the in-plan factor's launcher is in plan.h)
 // the factor on M evaluations: cen / Jc from launch_sphere_centers, robot_radius [S] in the caller's sphere order,
 // centers [M][K][3] -> err [M][S][K], H [M][S][K][D] or null

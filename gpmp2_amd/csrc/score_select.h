@@ -1,5 +1,6 @@
 // score_select.h -- the one copy of every stage the checks of the executed trajectory share (score_kernels.hip,
-// self_clearance_kernels.hip, motion_kernels.hip, moving_kernels.hip, path_kernels.hip, retime_kernels.hip):
+// self_clearance_kernels.hip, motion_kernels.hip, moving_kernels.hip, path_kernels.hip, retime_kernels.hip,
+// torque_kernels.hip):
 //
 //   first stage    checked_config: the configuration of checked state m; score_dense_coord: one coordinate of its
 //                  up-sampled form with the velocity.  ScoreKey / key_less: the (clearance, state, index) key and its

@@ -45,6 +45,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_self(lib)
     _capi.declare_motion(lib)
     _capi.declare_retime(lib)
+    _capi.declare_torque(lib)
     _capi.declare_moving(lib)
     _capi.declare_selfpair(lib)
     _capi.declare_path(lib)
@@ -139,6 +140,11 @@ def _motion_ptrs(o):
             dptr(o["time_scale"]), iptr(o["worst"]), iptr(o["invalid"]))
 
 
+def _torque_ptrs(o):
+    return (dptr(o["torque_ratio"]), dptr(o["static_ratio"]), dptr(o["torque_time_scale"]), iptr(o["worst"]),
+            iptr(o["invalid"]), dptr(o["tau"]))
+
+
 def _retime_ptrs(o):
     return (dptr(o["sdot"]), dptr(o["u"]), dptr(o["stamps"]), dptr(o["duration"]), iptr(o["status"]),
             dptr(o["achieved"])) + ((dptr(o["dense_retimed"]),) if "dense_retimed" in o else ())
@@ -166,6 +172,31 @@ class MotionLimits:
 def _limits_arg(limits, dof):
     """limits: a MotionLimits, or None = no limit at all"""
     return (limits if limits is not None else MotionLimits(dof)).ref(dof)
+
+
+class Dynamics:
+    """gpmp2mi_dynamics for `robot` (include/gpmp2mi.h "torque limits"): the inertial table of a fixed-base arm on the
+    device, bound to the robot's kinematics.  mass [L], com [L][3] in the link frames, inertia [L][6] = ixx iyy izz ixy
+    ixz iyz about the centres of mass, gravity [3] in the world frame, torque [dof] limits (a scalar is spread over the
+    joints; inf: none for that joint) or None = no limit.  Validated as the C side validates (ValueError) before the
+    library is called."""
+
+    def __init__(self, eng, robot, mass, com, inertia, gravity=(0.0, 0.0, -9.81), torque=None):
+        self.L, self.dof = int(robot.L), int(robot.dof)
+        self.mass, self.com, self.inertia, self.gravity, self.torque = scoring.dynamics_table(
+            self.L, self.dof, mass, com, inertia, gravity, torque)
+        desc = _capi.DynamicsDescC(dptr(self.mass), dptr(self.com), dptr(self.inertia), (C.c_double * 3)(*self.gravity),
+                                   dptr(self.torque))
+        out = C.c_void_p()
+        eng._ck(eng.lib.gpmp2mi_dynamics_create(robot.ptr, C.byref(desc), C.byref(out)))
+        self._h = _Handle(out, eng.lib.gpmp2mi_dynamics_destroy)
+
+    @property
+    def ptr(self):
+        return self._h.ptr
+
+    def close(self):
+        self._h.close()
 
 
 def _kappa_arg(kappa):
@@ -678,6 +709,25 @@ class Engine:
         lim = _limits_arg(limits, robot.dof)
         self._ck(self.lib.gpmp2mi_motion_score_traj(robot.ptr, lim, float(delta_t), inter_step, B, N, dptr(t),
                                                     *_motion_ptrs(o)))
+        return o
+
+    # ---------------------------------------------------------------- torque limits (include/gpmp2mi.h)
+    def dynamics(self, robot, mass, com, inertia, gravity=(0.0, 0.0, -9.81), torque=None):
+        """A Dynamics handle for `robot`."""
+        return Dynamics(self, robot, mass, com, inertia, gravity, torque)
+
+    def torque_score_traj(self, robot, dynamics, delta_t, inter_step, traj, out=None, tau=True):
+        """traj [B][N+1][2D] (or one [N+1][2D]) -> dict(torque_ratio [B], static_ratio [B], torque_time_scale [B], worst
+        [B][3][2], invalid [B], tau [B][Md][D]) of the inter_step-up-sampled trajectories by inverse dynamics against the
+        limits of `dynamics` (a Dynamics).  tau = False: the torques themselves are not fetched (tau: None)."""
+        t = scoring.traj_rows(traj, robot.dof)
+        inter_step = _score_args(inter_step)
+        if not float(delta_t) > 0:
+            raise ValueError("delta_t must be > 0")
+        B, N = t.shape[0], t.shape[1] - 1
+        o = scoring.torque_outputs(B, scoring.checked_states(N, inter_step), robot.dof, out, tau)
+        self._ck(self.lib.gpmp2mi_torque_score_traj(robot.ptr, dynamics.ptr, float(delta_t), inter_step, B, N, dptr(t),
+                                                    *_torque_ptrs(o)))
         return o
 
     # ---------------------------------------------------------------- re-timing (include/gpmp2mi.h)
@@ -1623,6 +1673,63 @@ class Plan:
         self.eng._ck(self.eng.lib.gpmp2mi_plan_select_feasible_dev(
             self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
             None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts,
+            *args, C.c_void_p(stream or 0)))
+
+    # ---- can the drives produce it (include/gpmp2mi.h "torque limits")
+    def torque_score(self, dynamics, inter_step, out=None, tau=True):
+        """dict(torque_ratio, static_ratio, torque_time_scale, worst, invalid, tau) of the plan's result, B rows."""
+        inter_step = _score_args(inter_step)
+        o = scoring.torque_outputs(self.B, scoring.checked_states(self.N, inter_step), self.D, out, tau)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_torque_score(self.h.ptr, dynamics.ptr, inter_step, *_torque_ptrs(o)))
+        return o
+
+    def torque_score_dev(self, dynamics, inter_step, torque_ratio=None, static_ratio=None, torque_time_scale=None,
+                         worst=None, invalid=None, tau=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        inter_step = _score_args(inter_step)
+        B, Md = self.B, scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("torque_ratio", torque_ratio, (B,)), _dev_arg("static_ratio", static_ratio, (B,)),
+                _dev_arg("torque_time_scale", torque_time_scale, (B,)), _dev_arg("worst", worst, (B, 3, 2), True),
+                _dev_arg("invalid", invalid, (B,), True), _dev_arg("tau", tau, (B, Md, self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_torque_score_dev(self.h.ptr, dynamics.ptr, inter_step, *args,
+                                                                C.c_void_p(stream or 0)))
+
+    def select_dynamic(self, inter_step, limits, dynamics, required_pos_margin=0.0, max_time_scale=1.0,
+                       required_clearance=0.0, require_in_range=False, pairs=None, required_self_clearance=0.0):
+        """select_feasible() with max(time_scale, torque_time_scale) <= max_time_scale in place of its time-scale test
+        and no non-finite torque: dict(best, n_eligible, time_scale_best, tau_best, traj_best, dense_best); best = -1:
+        the last four are None.  time_scale_best is that maximum; tau_best [Md][D] are the torques at planned timing."""
+        inter_step = _score_args(inter_step)
+        rpm, mts = scoring.feasible_thresholds(required_pos_margin, max_time_scale)
+        lim = _limits_arg(limits, self.D)
+        Md = scoring.checked_states(self.N, inter_step)
+        tb, db, ub = np.zeros((self.N + 1, 2 * self.D)), np.zeros((Md, 2 * self.D)), np.zeros((Md, self.D))
+        best, n, ts = C.c_int(-1), C.c_int(0), C.c_double(0.0)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_dynamic(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts, dynamics.ptr,
+            C.byref(best), C.byref(n), C.cast(C.byref(ts), _capi.c_double_p), dptr(ub), dptr(tb), dptr(db)))
+        hit = best.value >= 0
+        return dict(best=best.value, n_eligible=n.value, time_scale_best=ts.value if hit else None,
+                    tau_best=ub if hit else None, traj_best=tb if hit else None, dense_best=db if hit else None)
+
+    def select_dynamic_dev(self, inter_step, limits, dynamics, required_pos_margin=0.0, max_time_scale=1.0,
+                           required_clearance=0.0, require_in_range=False, pairs=None, required_self_clearance=0.0,
+                           best=None, n_eligible=None, time_scale_best=None, tau_best=None, traj_best=None,
+                           dense_best=None, stream=None):
+        """The same with device outputs, as select_feasible_dev, plus tau_best float64 [Md][D].  One enqueue on `stream`,
+        no host synchronisation once the plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        rpm, mts = scoring.feasible_thresholds(required_pos_margin, max_time_scale)
+        lim = _limits_arg(limits, self.D)
+        Md = scoring.checked_states(self.N, inter_step)
+        args = [_dev_arg("best", best, (1,), True), _dev_arg("n_eligible", n_eligible, (1,), True),
+                _dev_arg("time_scale_best", time_scale_best, (1,)), _dev_arg("tau_best", tau_best, (Md, self.D)),
+                _dev_arg("traj_best", traj_best, (self.N + 1, 2 * self.D)),
+                _dev_arg("dense_best", dense_best, (Md, 2 * self.D))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_select_dynamic_dev(
+            self.h.ptr, inter_step, float(required_clearance), int(bool(require_in_range)),
+            None if pairs is None else pairs.ptr, float(required_self_clearance), lim, rpm, mts, dynamics.ptr,
             *args, C.c_void_p(stream or 0)))
 
     # ---- how fast can the robot run it (include/gpmp2mi.h "re-timing")

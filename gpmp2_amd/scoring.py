@@ -266,6 +266,84 @@ def retimed_thresholds(required_pos_margin, max_duration):
     return required_pos_margin, max_duration
 
 
+# ---- torque limits (include/gpmp2mi.h "torque limits"): the inertial table, the outputs and the rule of its selection
+TORQUE_NAMES = ("torque_ratio", "static_ratio", "torque_time_scale", "worst", "invalid", "tau")
+TORQUE_MAX_JOINTS = 8       # k_torque is instantiated for fixed-base arms of 1..8 joints
+
+
+def dynamics_table(L, dof, mass, com, inertia, gravity=(0.0, 0.0, -9.81), torque=None):
+    """The description of gpmp2mi_dynamics_create as the C side takes it: contiguous float64 mass [L], com [L][3],
+    inertia [L][6] (ixx iyy izz ixy ixz iyz), gravity [3], torque [dof] or None (a scalar is spread over the joints),
+    checked as the C side checks them; ValueError otherwise."""
+    def arr(name, x, shape):
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{name}: expected {list(shape)}, got {list(a.shape)}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name}: every entry must be finite")
+        return a
+    m, c, i, g = arr("mass", mass, (L,)), arr("com", com, (L, 3)), arr("inertia", inertia, (L, 6)), arr("gravity", gravity, (3,))
+    if (m < 0).any():
+        raise ValueError("mass: entries must be >= 0")
+    if (i[:, :3] < 0).any():
+        raise ValueError("inertia: the diagonal entries must be >= 0")
+    t = None
+    if torque is not None:
+        t = np.asarray(torque, dtype=np.float64)
+        t = np.full(dof, float(t)) if t.ndim == 0 else np.ascontiguousarray(t)
+        if t.shape != (dof,) or not (t > 0).all():          # False for NaN
+            raise ValueError(f"torque: expected [{dof}] limits > 0 (inf: none), got {list(np.shape(torque))}")
+    return m, c, i, g, t
+
+
+def torque_outputs(B, Md, D, out=None, tau=True):
+    """The per-row outputs of a torque-score call: fresh arrays, or the caller's (checked as score_outputs does).
+    tau = False: no [B][Md][D] torques unless the caller brings the array."""
+    f, i = np.float64, np.int32
+    want = dict(zip(TORQUE_NAMES, (((B,), f), ((B,), f), ((B,), f), ((B, 3, 2), i), ((B,), i), ((B, Md, D), f))))
+    res = {}
+    out = out or {}
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"unknown torque outputs: {sorted(unknown)}")
+    for name, (shape, dt) in want.items():
+        x = out.get(name)
+        if x is None:
+            x = np.zeros(shape, dtype=dt) if (tau or name != "tau") else None
+        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
+            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
+                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
+        res[name] = x
+    return res
+
+
+def dynamic_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+                 min_self_clearance=None, invalid=None, required_self_clearance=0.0, pos_margin=None, time_scale=None,
+                 motion_invalid=None, required_pos_margin=0.0, max_time_scale=np.inf, torque_time_scale=None,
+                 torque_invalid=None):
+    """(best, n_eligible) by feasible_rule with max(time_scale, torque_time_scale) <= max_time_scale in place of its
+    time-scale test, and no non-finite torque."""
+    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
+    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+                  invalid, required_self_clearance)
+    if motion_invalid is not None:
+        ok &= np.asarray(motion_invalid).reshape(-1) == 0
+    if torque_invalid is not None:
+        ok &= np.asarray(torque_invalid).reshape(-1) == 0
+    with np.errstate(invalid="ignore"):
+        if pos_margin is not None:
+            ok &= np.asarray(pos_margin, dtype=np.float64).reshape(-1) >= required_pos_margin
+        scale = np.zeros(fe.size)
+        for s in (time_scale, torque_time_scale):
+            if s is not None:
+                scale = np.maximum(scale, np.asarray(s, dtype=np.float64).reshape(-1))
+        ok &= scale <= max_time_scale
+    rows = np.flatnonzero(ok)
+    if rows.size == 0:
+        return -1, 0
+    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+
+
 # ---- moving obstacles (include/gpmp2mi.h "moving obstacles"): the output names, the extended rule, the sphere set
 MOVING_NAMES = ("moving_support_cost", "moving_dense_cost", "min_moving_clearance", "worst", "invalid")
 MAX_MOVING_SPHERES = 64     # GPMP2MI_MAX_MOVING_SPHERES

@@ -797,6 +797,109 @@ int gpmp2mi_plan_select_retimed_dev(gpmp2mi_plan* p, int inter_step, double requ
                                     int* n_eligible, double* duration_best, double* stamps_best, double* traj_best,
                                     double* dense_best, void* stream);
 
+/* ---- torque limits: the joint torques the executed trajectory asks for, by inverse dynamics on the device -----------
+ * acc[d] of "motion limits" is a stand-in for what saturates an arm, which is joint torque: the acceleration a joint can
+ * deliver depends on the configuration (gravity, the inertia seen at the joint), on what the other joints do (the
+ * velocity products) and on how much torque is already spent holding the arm up.  These calls compute the joint torques
+ * of a fixed-base arm at every checked state of "scoring", compare them with per-joint limits, say how much of each limit
+ * gravity alone takes, give the factor by which a row's duration must be stretched for the drives to follow, and let the
+ * selection ask for it.
+ *
+ * The dynamics handle (gpmp2mi_dynamics) carries the inertial parameters of the arm on the device and is bound to the
+ * kinematics of the robot handle it was made for (kind, joint count, DH table, base pose).  L = gpmp2mi_robot_nr_links.
+ * The link frame of link j is the frame gpmp2mi_forward_kinematics returns for it: the DH frame behind joint j's
+ * transform.  Joint j turns about the z axis of the frame in front of it.  mass [L] in kg; com [L][3], the centre of mass
+ * in the link frame; inertia [L][6] = ixx iyy izz ixy ixz iyz, the entries of the symmetric inertia matrix about the
+ * centre of mass in the link frame (the off-diagonal ones with the sign they have in the matrix); gravity in the world
+ * frame; torque [dof], the limits L_d > 0, +inf = none for that joint, NULL = none at all.  All HOST pointers, read
+ * before gpmp2mi_dynamics_create returns.  gpmp2mi_dynamics_desc_default: NULL arrays, gravity (0, 0, -9.81).
+ *
+ * Definitions, for one trajectory traj [N+1][2D], delta_t = dt and inter_step = J >= 0:
+ *  - Checked states: exactly those of "scoring", Md = N (J+1) + 1 states, with q_k and q'_k as in "motion limits" and
+ *    q''_k as in "re-timing": linear between a_i,0 and a_i,1 inside interval i, the two ends exact.  A support state
+ *    between two intervals has a left and a right acceleration and is evaluated for both ("sides"); the first state has
+ *    the right one only, the last the left one only.
+ *  - tau = ID(q, q', q'') is the inverse dynamics of the rigid chain; tau_g = ID(q, 0, 0) holds the arm still against
+ *    gravity; m = tau - tau_g is what the motion asks for.  The device accumulates tau_g and m apart and forms
+ *    tau = tau_g + m (the dynamics are affine in gravity), so a row at rest has m == 0 exactly.
+ *  - torque_ratio [B]: max over (state, side, joint with a finite limit) of |tau_d| / L_d; 0 if nothing is limited.
+ *  - static_ratio [B]: max over (state, joint with a finite limit) of |tau_g,d| / L_d.  At >= 1 no timing helps.
+ *  - torque_time_scale [B]: the smallest uniform stretch c of the duration that meets every limit.  Under a stretch
+ *    q' scales by 1/c and q'' by 1/c^2, so m scales by exactly 1/c^2 while tau_g stays: c^2 = max over (state, side,
+ *    joint with a finite limit) of r, with r = m / (L - tau_g) for m > 0, r = -m / (L + tau_g) for m < 0 and r = 0 for
+ *    m == 0 (a quotient whose denominator is <= 0 is left out: static_ratio >= 1 says it).  0 when every m is 0; +inf
+ *    when static_ratio >= 1.  Consistency: given static_ratio < 1, torque_ratio <= 1 <=> torque_time_scale <= 1 (up to
+ *    rounding at the boundary itself).
+ *  - worst [B][3][2]: the (state, joint) attaining torque_ratio, static_ratio and c^2, on exact ties the lowest state, then
+ *    the lowest joint; (-1, -1) if none.
+ *  - invalid [B]: the number of (state, side, joint) whose tau is not finite, limited or not.  Such a value joins no
+ *    extremum; a non-finite tau_g joins none either.
+ *  - tau [B][Md][dof], optional: the torques at planned timing, the controller's feed-forward term.  At a support state
+ *    the right-sided value, at the last state the left-sided one.
+ *  - SAMPLED, NOT BOUNDED: the torque between two checked states is not bounded by its values at them (tau is not linear
+ *    in time), unlike acc_ratio of "motion limits", whose interval ends are exact.  Raise inter_step for a finer check.
+ *  - Determinism: every per-row output is an extremum with an index key or an integer count: no floating-point sum across
+ *    states, no atomics.  A row's results are a function of the row, the two handles, delta_t and J alone: bit-identical
+ *    alone, anywhere in any batch, through the trajectory form or the plan form.
+ *  - Selection (gpmp2mi_plan_select_dynamic): the rule of gpmp2mi_plan_select_feasible with
+ *      max(time_scale[b], torque_time_scale[b]) <= max_time_scale
+ *    in place of its time-scale test, and the torque invalid[b] == 0 besides.  Ranking and ties are unchanged.
+ *    time_scale_best is that maximum for the chosen row, tau_best [Md][dof] its torques (both untouched when none is).
+ *    With every torque limit +inf, the row gpmp2mi_plan_select_feasible chooses (for rows without a non-finite torque).
+ * Errors, before any device work: GPMP2MI_ERR_INVALID for a NULL argument, a non-finite entry of the description, a
+ * negative mass or diagonal inertia, a torque limit that is NaN or <= 0, the argument errors of "scoring" and "motion
+ * limits", and a dynamics handle made for another robot or living on another device; GPMP2MI_ERR_UNSUPPORTED, the reason
+ * in the message, for any kind but GPMP2MI_ROBOT_ARM and for an arm of more than 8 joints; GPMP2MI_ERR_TIMEOUT for a
+ * poisoned plan.  A refused call writes nothing and leaves the plan usable.
+ * Memory: one 56-byte record per 64 checked states of every row.  A plan takes the records, the scores of the earlier
+ * stages, the staging of its host-pointer forms and the torques of every row ([B][Md][dof]) at the first call and keeps
+ * them (grown when a later call needs more).  gpmp2mi_torque_score_traj_dev keeps its records with the dynamics handle,
+ * under the stream-order rule of gpmp2mi_score_traj_dev.  The `_dev` forms enqueue and return.  The plan forms read the
+ * plan's resident result and delta_t, have the preconditions of gpmp2mi_plan_score and leave the optimizer's state and
+ * every existing call's outputs untouched.
+ * Not here: the mobile kinds (a moving base in the recursion); friction, rotor inertia, payload changes at run time and
+ * external wrenches; torque rows inside gpmp2mi_plan_retime (they carry the offset tau_g, the rule knows symmetric rows
+ * only); the torques of an already re-timed row; a torque factor inside the optimisation; gpmp2mi_multi_plan_* twins. */
+typedef struct gpmp2mi_dynamics gpmp2mi_dynamics;   /* device-resident inertial table, bound to the robot's kinematics */
+typedef struct gpmp2mi_dynamics_desc {
+  const double* mass;     /* [L]     kg, >= 0                                             */
+  const double* com;      /* [L][3]  centre of mass in the link frame                     */
+  const double* inertia;  /* [L][6]  ixx iyy izz ixy ixz iyz about the COM, link frame    */
+  double gravity[3];      /* world frame; default (0, 0, -9.81)                           */
+  const double* torque;   /* [dof] limits, > 0, +inf: none; NULL: none at all             */
+} gpmp2mi_dynamics_desc;
+void gpmp2mi_dynamics_desc_default(gpmp2mi_dynamics_desc* desc);
+int gpmp2mi_dynamics_create(const gpmp2mi_robot* robot, const gpmp2mi_dynamics_desc* desc, gpmp2mi_dynamics** out);
+void gpmp2mi_dynamics_destroy(gpmp2mi_dynamics* dynamics);   /* NULL: no-op */
+
+/* caller buffers; traj [B][total_step+1][2D].  The device of the two handles must be current.  Any output may be NULL. */
+int gpmp2mi_torque_score_traj(const gpmp2mi_robot* robot, const gpmp2mi_dynamics* dynamics, double delta_t,
+                              int inter_step, int B, int total_step, const double* traj, double* torque_ratio,
+                              double* static_ratio, double* torque_time_scale, int* worst, int* invalid, double* tau);
+int gpmp2mi_torque_score_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_dynamics* dynamics, double delta_t,
+                                  int inter_step, int B, int total_step, const double* traj, double* torque_ratio,
+                                  double* static_ratio, double* torque_time_scale, int* worst, int* invalid, double* tau,
+                                  void* stream);
+/* The plan's resident result; preconditions and errors as gpmp2mi_plan_score. */
+int gpmp2mi_plan_torque_score(gpmp2mi_plan* p, const gpmp2mi_dynamics* dynamics, int inter_step, double* torque_ratio,
+                              double* static_ratio, double* torque_time_scale, int* worst, int* invalid, double* tau);
+int gpmp2mi_plan_torque_score_dev(gpmp2mi_plan* p, const gpmp2mi_dynamics* dynamics, int inter_step,
+                                  double* torque_ratio, double* static_ratio, double* torque_time_scale, int* worst,
+                                  int* invalid, double* tau, void* stream);
+/* gpmp2mi_plan_select_feasible with the torque rule, one enqueue: the existing score stages, the motion scores, the
+ * torques, then one finish that reads them all.  Outputs as gpmp2mi_plan_select_feasible, plus tau_best. */
+int gpmp2mi_plan_select_dynamic(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                const gpmp2mi_motion_limits* limits, double required_pos_margin, double max_time_scale,
+                                const gpmp2mi_dynamics* dynamics, int* best, int* n_eligible, double* time_scale_best,
+                                double* tau_best, double* traj_best, double* dense_best);
+int gpmp2mi_plan_select_dynamic_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                    const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                    const gpmp2mi_motion_limits* limits, double required_pos_margin,
+                                    double max_time_scale, const gpmp2mi_dynamics* dynamics, int* best,
+                                    int* n_eligible, double* time_scale_best, double* tau_best, double* traj_best,
+                                    double* dense_best, void* stream);
+
 /* ---- moving obstacles: time-indexed spheres as a plan factor and a check, on the device ---------------------------
  * Every obstacle of "scoring" lives in one static signed-distance field.  A person or another robot crossing the
  * workspace is a set of K spheres whose centres are indexed by the support time: radius [K], centers [K][N+1][3],

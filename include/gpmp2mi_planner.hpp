@@ -1054,6 +1054,95 @@ inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int
   return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
 }
 
+/// The inertial table of a fixed-base arm on the device (include/gpmp2mi.h "torque limits"), bound to the kinematics of
+/// the robot it was made for: mass [L], com [L][3] in the link frames, inertia [L][6] = ixx iyy izz ixy ixz iyz about the
+/// centres of mass, gravity in the world frame, and the torque limits [dof] (empty: none; +infinity: none for that joint).
+/// ROBOT: a fixed-base arm of at most 8 joints (anything else throws, the reason in the message).
+class ArmDynamics {
+ public:
+  template <class ROBOT>
+  ArmDynamics(const ROBOT& robot, const Vector& mass, const Vector& com, const Vector& inertia, const Vector& torque = {},
+              const std::array<double, 3>& gravity = {0.0, 0.0, -9.81}) {
+    const std::size_t L = static_cast<std::size_t>(gpmp2mi_robot_nr_links(robot.handle()));
+    if (mass.size() != L || com.size() != 3 * L || inertia.size() != 6 * L)
+      throw std::runtime_error("[ArmDynamics] mass / com / inertia do not fit the number of links");
+    if (!torque.empty() && torque.size() != robot.dof()) throw std::runtime_error("[ArmDynamics] torque does not fit the dof");
+    gpmp2mi_dynamics_desc d;
+    gpmp2mi_dynamics_desc_default(&d);
+    d.mass = mass.data();
+    d.com = com.data();
+    d.inertia = inertia.data();
+    d.torque = torque.empty() ? nullptr : torque.data();
+    for (int i = 0; i < 3; i++) d.gravity[i] = gravity[i];
+    check(gpmp2mi_dynamics_create(robot.handle(), &d, &h_), "gpmp2mi_dynamics_create");
+  }
+  ArmDynamics(ArmDynamics&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ArmDynamics& operator=(ArmDynamics&& o) noexcept {
+    if (this != &o) {
+      gpmp2mi_dynamics_destroy(h_);
+      h_ = o.h_;
+      o.h_ = nullptr;
+    }
+    return *this;
+  }
+  ArmDynamics(const ArmDynamics&) = delete;
+  ArmDynamics& operator=(const ArmDynamics&) = delete;
+  ~ArmDynamics() { gpmp2mi_dynamics_destroy(h_); }
+  const gpmp2mi_dynamics* handle() const { return h_; }
+
+ private:
+  gpmp2mi_dynamics* h_ = nullptr;
+};
+/// Whether the drives can produce the up-sampled trajectory: the largest joint torque and the largest gravity torque
+/// relative to their limits, the factor by which the duration must be stretched to meet every torque limit (<= 1: as
+/// planned; +infinity: gravity alone is too much), each with the (state, joint) where it occurs ((-1, -1) if nothing is
+/// limited), the number of torques that are not finite, and the torques themselves, [Md][dof] at planned timing (the
+/// feed-forward term).  The torque between checked states is sampled, not bounded.
+struct TrajectoryTorqueScore {
+  double torque_ratio = 0.0, static_ratio = 0.0, time_scale = 0.0;
+  int torque_state = -1, torque_joint = -1, static_state = -1, static_joint = -1, scale_state = -1, scale_joint = -1,
+      invalid = 0;
+  Vector tau;
+};
+template <class ROBOT>
+inline TrajectoryTorqueScore TorqueScore(const ROBOT& robot, const ArmDynamics& dynamics, const Trajectory& result,
+                                         const TrajOptimizerSetting& setting, std::size_t inter_step) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[TorqueScore] result does not match dof / total_step");
+  TrajectoryTorqueScore sc;
+  sc.tau.assign((result.total_step * (inter_step + 1) + 1) * result.dof, 0.0);
+  int worst[6] = {-1, -1, -1, -1, -1, -1};
+  check(gpmp2mi_torque_score_traj(robot.handle(), dynamics.handle(), setting.total_time / static_cast<double>(setting.total_step),
+                                  static_cast<int>(inter_step), 1, static_cast<int>(result.total_step), result.data.data(),
+                                  &sc.torque_ratio, &sc.static_ratio, &sc.time_scale, worst, &sc.invalid, sc.tau.data()),
+        "gpmp2mi_torque_score_traj");
+  sc.torque_state = worst[0]; sc.torque_joint = worst[1]; sc.static_state = worst[2]; sc.static_joint = worst[3];
+  sc.scale_state = worst[4]; sc.scale_joint = worst[5];
+  return sc;
+}
+/// The SelectBestTrajectory of the motion scores with the torques: the LARGER of the two stretches (motion limits, torque
+/// limits) must not exceed max_time_scale, and no torque may be non-finite.  Host code.
+inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int>& status,
+                                const std::vector<TrajectoryScore>& scores,
+                                const std::vector<TrajectoryMotionScore>& motion_scores,
+                                const std::vector<TrajectoryTorqueScore>& torque_scores, double required_pos_margin,
+                                double max_time_scale, double required_clearance = 0.0, bool require_in_range = false,
+                                std::size_t* n_eligible = nullptr) {
+  if (motion_scores.size() != scores.size() || torque_scores.size() != scores.size())
+    throw std::runtime_error("[SelectBestTrajectory] scores, motion_scores and torque_scores differ in length");
+  if (required_pos_margin != required_pos_margin || max_time_scale != max_time_scale)
+    throw std::runtime_error("[SelectBestTrajectory] required_pos_margin / max_time_scale is NaN");
+  std::vector<TrajectoryScore> both(scores);
+  for (std::size_t b = 0; b < both.size(); b++) {
+    const TrajectoryMotionScore& m = motion_scores[b];
+    const TrajectoryTorqueScore& t = torque_scores[b];
+    const double scale = t.time_scale > m.time_scale ? t.time_scale : m.time_scale;
+    const bool ok = m.invalid == 0 && t.invalid == 0 && m.pos_margin >= required_pos_margin && scale <= max_time_scale;
+    if (!ok) both[b].min_clearance = std::nan("");   // a NaN clearance is never eligible
+  }
+  return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
+}
+
 namespace internal {
 inline Trajectory interpolateTraj(const Trajectory& opt_values, const Vector& Qc, double delta_t, std::size_t inter_step,
                                   std::size_t start_index, std::size_t end_index, bool lie) {

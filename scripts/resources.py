@@ -1,6 +1,7 @@
 """Build-time resource table of every shipped kernel: VGPRs, SGPRs, spills, scratch, LDS, occupancy, as the compiler
 reports them (hipcc -Rpass-analysis=kernel-resource-usage on the product sources with the product flags).
-usage: python scripts/resources.py > profiles/rNN_resources.txt        (compiles the .hip files with kernels, a few minutes)"""
+usage: python scripts/resources.py > profiles/rNN_resources.txt        (compiles the .hip files with kernels, a few minutes)
+       python scripts/resources.py torque_kernels.hip > profiles/torque_resources.txt      (the named units only)"""
 import concurrent.futures
 import os
 import re
@@ -10,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "gpmp2_amd", "csrc")
 FILES = ["host/debug.hip", "sdf_kernels.hip", "map_kernels.hip", "sensor_kernels.hip", "scene_kernels.hip", "factor_kernels.hip", "linearize_kernels.hip", "plan_kernels.hip", "cr_kernels.hip", "dense_kernels.hip",
-         "score_kernels.hip", "self_clearance_kernels.hip", "motion_kernels.hip", "retime_kernels.hip", "moving_kernels.hip", "selfpair_kernels.hip", "path_kernels.hip", "group_kernels.hip", "posterior_kernels.hip", "seed_kernels.hip", "risk_kernels.hip", "sample_clearance_kernels.hip", "ik_kernels.hip"]
+         "score_kernels.hip", "self_clearance_kernels.hip", "motion_kernels.hip", "retime_kernels.hip", "torque_kernels.hip", "moving_kernels.hip", "selfpair_kernels.hip", "path_kernels.hip", "group_kernels.hip", "posterior_kernels.hip", "seed_kernels.hip", "risk_kernels.hip", "sample_clearance_kernels.hip", "ik_kernels.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage", "-c"]
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]",
         "Occupancy [waves/SIMD]"]
@@ -33,16 +34,17 @@ def demangle(names):
 
 
 def main():
-    only = sys.argv[1:]          # optional substrings: print only kernels whose name contains one of them
+    only = [a for a in sys.argv[1:] if not a.endswith(".hip")]   # optional substrings: only kernels whose name has one
+    files = [a for a in sys.argv[1:] if a.endswith(".hip")] or FILES   # optional units: only these are compiled
     with concurrent.futures.ThreadPoolExecutor(max_workers=3) as ex:
-        logs = dict(ex.map(compile_one, FILES))
+        logs = dict(ex.map(compile_one, files))
     try:
         head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     except Exception:
         head = "?"
     print(f"# kernel resource usage, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; commit {head}")
     print(f"# {'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'sSpill':>6s} {'vSpill':>6s} {'scratch':>7s} {'LDS':>6s} {'occ':>4s}")
-    for f in FILES:
+    for f in files:
         rows, cur = [], None
         for line in logs[f].splitlines():
             m = re.search(r"remark:\s+Function Name: (\S+)", line)
