@@ -1,9 +1,11 @@
-"""The score-and-select stage in numpy terms: the selection rule of include/gpmp2mi.h ("scoring") stated once, and the
-shape checks of the wrappers in engine.py.  The scores themselves come from the device (k_score); nothing here computes
-a collision cost."""
+"""The score-and-select stage in numpy terms: the selection rules of include/gpmp2mi.h ("scoring" and the stages after
+it) stated once, and the shape checks of the wrappers in checks.py and plan.py.  The per-row outputs of every stage are
+the table of stages.py.  The scores themselves come from the device (k_score); nothing here computes a collision cost."""
 from __future__ import annotations
 
 import numpy as np
+
+from . import stages
 
 TRAJ_NOT_SPD = 3   # GPMP2MI_TRAJ_NOT_SPD
 
@@ -27,24 +29,55 @@ def eligible(final_error, status, min_clearance, out_of_range, required_clearanc
         ok &= clr >= required_clearance          # False for a NaN clearance
     if require_in_range and out_of_range is not None:
         ok &= np.asarray(out_of_range).reshape(-1) == 0
-    if min_self_clearance is not None:
-        with np.errstate(invalid="ignore"):
-            ok &= np.asarray(min_self_clearance, dtype=np.float64).reshape(-1) >= required_self_clearance
-    if invalid is not None:
-        ok &= np.asarray(invalid).reshape(-1) == 0
+    _at_least(ok, min_self_clearance, required_self_clearance)
+    _none_set(ok, invalid)
     return ok
 
 
 def select_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
                 min_self_clearance=None, invalid=None, required_self_clearance=0.0):
     """(best, n_eligible): the eligible row with the smallest final_error, the lowest row on ties; (-1, 0) if none."""
+    ok = eligible(final_error, status, min_clearance, out_of_range, required_clearance, require_in_range,
+                  min_self_clearance, invalid, required_self_clearance)
+    return pick(final_error, ok)
+
+
+def pick(final_error, ok):
+    """(best, n_eligible) of the mask `ok` [B]: the row with the smallest final_error, the lowest row on ties."""
     fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
-                  invalid, required_self_clearance)
     rows = np.flatnonzero(ok)
     if rows.size == 0:
         return -1, 0
     return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+
+
+def _none_set(ok, flags):
+    """ok &= no flag set (flags None: not asked)"""
+    if flags is not None:
+        ok &= np.asarray(flags).reshape(-1) == 0
+
+
+def _at_least(ok, x, bound):
+    """ok &= x >= bound (x None: not asked); False for a NaN"""
+    if x is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= np.asarray(x, dtype=np.float64).reshape(-1) >= bound
+
+
+def _at_most(ok, x, bound):
+    """ok &= x <= bound (x None: not asked); False for a NaN"""
+    if x is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= np.asarray(x, dtype=np.float64).reshape(-1) <= bound
+
+
+def _motion_eligible(base, motion_invalid, pos_margin, required_pos_margin):
+    """The mask of `eligible` (its arguments: base) with the motion conditions the three motion-based rules share: no
+    non-finite motion quantity and pos_margin >= required_pos_margin (each None: not asked)."""
+    ok = eligible(*base)
+    _none_set(ok, motion_invalid)
+    _at_least(ok, pos_margin, required_pos_margin)
+    return ok
 
 
 def select_inputs(final_error, status, min_clearance, out_of_range, require_in_range):
@@ -73,8 +106,7 @@ def traj_rows(traj, D, total_step=None):
     return t
 
 
-SCORE_NAMES = ("support_cost", "dense_cost", "min_clearance", "worst", "out_of_range")
-SELF_NAMES = ("self_support_cost", "self_dense_cost", "min_self_clearance", "worst", "invalid")
+SCORE_NAMES, SELF_NAMES = stages.names(stages.SCORE), stages.names(stages.SELF)
 
 
 def pair_table(data, S=None):
@@ -95,31 +127,8 @@ def pair_table(data, S=None):
     return np.ascontiguousarray(full)
 
 
-def score_outputs(B, out=None, names=SCORE_NAMES):
-    """The five per-row outputs of a score call: fresh arrays, or the caller's (a dict with any of the five names),
-    checked for dtype, contiguity and length.  names: SCORE_NAMES, SELF_NAMES for the self-collision check, or
-    MOVING_NAMES for the moving obstacles (worst [B][3])."""
-    nw = 3 if names is MOVING_NAMES else 2
-    shapes = (((B,), np.float64), ((B,), np.float64), ((B,), np.float64), ((B, nw), np.int32), ((B,), np.int32))
-    want = dict(zip(names, shapes))
-    res = {}
-    out = out or {}
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"unknown score outputs: {sorted(unknown)}")
-    for name, (shape, dt) in want.items():
-        x = out.get(name)
-        if x is None:
-            x = np.zeros(shape, dtype=dt)
-        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
-            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
-                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
-        res[name] = x
-    return res
-
-
 # ---- motion limits (include/gpmp2mi.h "motion limits"): the extended rule and the checks of its wrappers
-MOTION_NAMES = ("pos_margin", "vel_ratio", "acc_ratio", "point_speed", "time_scale", "worst", "invalid")
+MOTION_NAMES = stages.names(stages.MOTION)
 
 
 def feasible_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
@@ -127,20 +136,11 @@ def feasible_rule(final_error, status, min_clearance, out_of_range, required_cle
                   motion_invalid=None, required_pos_margin=0.0, max_time_scale=np.inf):
     """(best, n_eligible) by the rule of select_rule with three more conditions: no non-finite motion quantity,
     pos_margin >= required_pos_margin, time_scale <= max_time_scale (each None: not asked)."""
-    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
-                  invalid, required_self_clearance)
-    if motion_invalid is not None:
-        ok &= np.asarray(motion_invalid).reshape(-1) == 0
-    with np.errstate(invalid="ignore"):
-        if pos_margin is not None:
-            ok &= np.asarray(pos_margin, dtype=np.float64).reshape(-1) >= required_pos_margin
-        if time_scale is not None:
-            ok &= np.asarray(time_scale, dtype=np.float64).reshape(-1) <= max_time_scale
-    rows = np.flatnonzero(ok)
-    if rows.size == 0:
-        return -1, 0
-    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+    base = (final_error, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+            invalid, required_self_clearance)
+    ok = _motion_eligible(base, motion_invalid, pos_margin, required_pos_margin)
+    _at_most(ok, time_scale, max_time_scale)
+    return pick(final_error, ok)
 
 
 def motion_limits(D, pos_down=None, pos_up=None, vel=None, acc=None, point_speed=np.inf):
@@ -169,23 +169,8 @@ def motion_limits(D, pos_down=None, pos_up=None, vel=None, acc=None, point_speed
 
 
 def motion_outputs(B, out=None):
-    """The seven per-row outputs of a motion-score call: fresh arrays, or the caller's (checked as score_outputs does)."""
-    f, i = np.float64, np.int32
-    want = dict(zip(MOTION_NAMES, (((B,), f), ((B,), f), ((B,), f), ((B,), f), ((B,), f), ((B, 4, 2), i), ((B,), i))))
-    res = {}
-    out = out or {}
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"unknown motion outputs: {sorted(unknown)}")
-    for name, (shape, dt) in want.items():
-        x = out.get(name)
-        if x is None:
-            x = np.zeros(shape, dtype=dt)
-        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
-            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
-                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
-        res[name] = x
-    return res
+    """The seven per-row outputs of a motion-score call: fresh arrays, or the caller's (checked by stages.outputs)."""
+    return stages.outputs(stages.MOTION, B, out=out)
 
 
 def feasible_thresholds(required_pos_margin, max_time_scale):
@@ -197,31 +182,13 @@ def feasible_thresholds(required_pos_margin, max_time_scale):
 
 # ---- re-timing (include/gpmp2mi.h "re-timing"): the status values, the outputs, the rates and the rule of its selection
 RETIME_OK, RETIME_BOUNDARY, RETIME_EMPTY, RETIME_INVALID = range(4)
-RETIME_NAMES = ("sdot", "u", "stamps", "duration", "status", "achieved", "dense_retimed")
+RETIME_NAMES = stages.names(stages.RETIME)
 
 
 def retime_outputs(B, Md, D=None, out=None):
-    """The per-row outputs of a re-timing call: fresh arrays, or the caller's (checked as score_outputs does).
+    """The per-row outputs of a re-timing call: fresh arrays, or the caller's (checked by stages.outputs).
     D = None: the path form, which has no dense_retimed."""
-    f, i = np.float64, np.int32
-    want = dict(sdot=((B, Md), f), u=((B, Md), f), stamps=((B, Md), f), duration=((B,), f), status=((B,), i),
-                achieved=((B, 4), f))
-    if D is not None:
-        want["dense_retimed"] = ((B, Md, 2 * D), f)
-    res = {}
-    out = out or {}
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"unknown retime outputs: {sorted(unknown)}")
-    for name, (shape, dt) in want.items():
-        x = out.get(name)
-        if x is None:
-            x = np.zeros(shape, dtype=dt)
-        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
-            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
-                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
-        res[name] = x
-    return res
+    return stages.outputs(stages.RETIME, B, Md, D, out, absent=("dense_retimed",) if D is None else ())
 
 
 def retime_rates(max_rate=1.0, rate_start=None, rate_end=None):
@@ -243,20 +210,13 @@ def retimed_rule(final_error, status, min_clearance, out_of_range, required_clea
                  motion_invalid=None, required_pos_margin=0.0, retime_status=None, duration=None, max_duration=np.inf):
     """(best, n_eligible) by feasible_rule without its time_scale test, and then status == RETIME_OK and
     duration <= max_duration."""
-    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
-                  invalid, required_self_clearance)
-    if motion_invalid is not None:
-        ok &= np.asarray(motion_invalid).reshape(-1) == 0
+    base = (final_error, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+            invalid, required_self_clearance)
+    ok = _motion_eligible(base, motion_invalid, pos_margin, required_pos_margin)
+    ok &= np.asarray(retime_status).reshape(-1) == RETIME_OK
     with np.errstate(invalid="ignore"):
-        if pos_margin is not None:
-            ok &= np.asarray(pos_margin, dtype=np.float64).reshape(-1) >= required_pos_margin
-        ok &= np.asarray(retime_status).reshape(-1) == RETIME_OK
         ok &= np.asarray(duration, dtype=np.float64).reshape(-1) <= max_duration
-    rows = np.flatnonzero(ok)
-    if rows.size == 0:
-        return -1, 0
-    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+    return pick(final_error, ok)
 
 
 def retimed_thresholds(required_pos_margin, max_duration):
@@ -267,7 +227,7 @@ def retimed_thresholds(required_pos_margin, max_duration):
 
 
 # ---- torque limits (include/gpmp2mi.h "torque limits"): the inertial table, the outputs and the rule of its selection
-TORQUE_NAMES = ("torque_ratio", "static_ratio", "torque_time_scale", "worst", "invalid", "tau")
+TORQUE_NAMES = stages.names(stages.TORQUE)
 TORQUE_MAX_JOINTS = 8       # k_torque is instantiated for fixed-base arms of 1..8 joints
 
 
@@ -297,24 +257,9 @@ def dynamics_table(L, dof, mass, com, inertia, gravity=(0.0, 0.0, -9.81), torque
 
 
 def torque_outputs(B, Md, D, out=None, tau=True):
-    """The per-row outputs of a torque-score call: fresh arrays, or the caller's (checked as score_outputs does).
+    """The per-row outputs of a torque-score call: fresh arrays, or the caller's (checked by stages.outputs).
     tau = False: no [B][Md][D] torques unless the caller brings the array."""
-    f, i = np.float64, np.int32
-    want = dict(zip(TORQUE_NAMES, (((B,), f), ((B,), f), ((B,), f), ((B, 3, 2), i), ((B,), i), ((B, Md, D), f))))
-    res = {}
-    out = out or {}
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"unknown torque outputs: {sorted(unknown)}")
-    for name, (shape, dt) in want.items():
-        x = out.get(name)
-        if x is None:
-            x = np.zeros(shape, dtype=dt) if (tau or name != "tau") else None
-        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
-            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
-                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
-        res[name] = x
-    return res
+    return stages.outputs(stages.TORQUE, B, Md, D, out, absent=() if tau else ("tau",))
 
 
 def dynamic_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
@@ -322,30 +267,22 @@ def dynamic_rule(final_error, status, min_clearance, out_of_range, required_clea
                  motion_invalid=None, required_pos_margin=0.0, max_time_scale=np.inf, torque_time_scale=None,
                  torque_invalid=None):
     """(best, n_eligible) by feasible_rule with max(time_scale, torque_time_scale) <= max_time_scale in place of its
-    time-scale test, and no non-finite torque."""
-    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
-                  invalid, required_self_clearance)
-    if motion_invalid is not None:
-        ok &= np.asarray(motion_invalid).reshape(-1) == 0
-    if torque_invalid is not None:
-        ok &= np.asarray(torque_invalid).reshape(-1) == 0
+    time-scale test, and no non-finite torque.  The maximum starts from 0, and is tested even when neither scale is given."""
+    base = (final_error, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
+            invalid, required_self_clearance)
+    ok = _motion_eligible(base, motion_invalid, pos_margin, required_pos_margin)
+    _none_set(ok, torque_invalid)
+    scale = np.zeros(ok.size)
     with np.errstate(invalid="ignore"):
-        if pos_margin is not None:
-            ok &= np.asarray(pos_margin, dtype=np.float64).reshape(-1) >= required_pos_margin
-        scale = np.zeros(fe.size)
         for s in (time_scale, torque_time_scale):
             if s is not None:
                 scale = np.maximum(scale, np.asarray(s, dtype=np.float64).reshape(-1))
-        ok &= scale <= max_time_scale
-    rows = np.flatnonzero(ok)
-    if rows.size == 0:
-        return -1, 0
-    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+    _at_most(ok, scale, max_time_scale)
+    return pick(final_error, ok)
 
 
 # ---- moving obstacles (include/gpmp2mi.h "moving obstacles"): the output names, the extended rule, the sphere set
-MOVING_NAMES = ("moving_support_cost", "moving_dense_cost", "min_moving_clearance", "worst", "invalid")
+MOVING_NAMES = stages.names(stages.MOVING)
 MAX_MOVING_SPHERES = 64     # GPMP2MI_MAX_MOVING_SPHERES
 
 
@@ -354,18 +291,11 @@ def moving_rule(final_error, status, min_clearance, out_of_range, required_clear
                 moving_invalid=None, required_moving_clearance=-np.inf):
     """(best, n_eligible) by the rule of select_rule with two more conditions: no invalid (state, sphere, moving sphere)
     and min_moving_clearance >= required_moving_clearance (each None: not asked)."""
-    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range, min_self_clearance,
-                  invalid, required_self_clearance)
-    if moving_invalid is not None:
-        ok &= np.asarray(moving_invalid).reshape(-1) == 0
-    if min_moving_clearance is not None:
-        with np.errstate(invalid="ignore"):
-            ok &= np.asarray(min_moving_clearance, dtype=np.float64).reshape(-1) >= required_moving_clearance
-    rows = np.flatnonzero(ok)
-    if rows.size == 0:
-        return -1, 0
-    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+    ok = eligible(final_error, status, min_clearance, out_of_range, required_clearance, require_in_range,
+                  min_self_clearance, invalid, required_self_clearance)
+    _none_set(ok, moving_invalid)
+    _at_least(ok, min_moving_clearance, required_moving_clearance)
+    return pick(final_error, ok)
 
 
 def moving_set(radius, centers, states, capacity=MAX_MOVING_SPHERES):
@@ -382,28 +312,7 @@ def moving_set(radius, centers, states, capacity=MAX_MOVING_SPHERES):
 
 
 # ---- workspace path (include/gpmp2mi.h "workspace path"): the output names, the extended rule, a straight-line path
-PATH_NAMES = ("max_pos_dev", "max_rot_dev", "worst", "support_cost", "dense_cost", "invalid")
-
-
-def path_outputs(B, out=None):
-    """The six per-row outputs of a path score call: fresh arrays, or the caller's (a dict with any of PATH_NAMES),
-    checked for dtype, contiguity and shape."""
-    want = dict(zip(PATH_NAMES, (((B,), np.float64), ((B,), np.float64), ((B, 2), np.int32), ((B,), np.float64),
-                                 ((B,), np.float64), ((B,), np.int32))))
-    res = {}
-    out = out or {}
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"unknown path outputs: {sorted(unknown)}")
-    for name, (shape, dt) in want.items():
-        x = out.get(name)
-        if x is None:
-            x = np.zeros(shape, dtype=dt)
-        elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags["C_CONTIGUOUS"] or x.shape != shape:
-            raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of shape {list(shape)}, got "
-                             f"{getattr(x, 'dtype', type(x).__name__)} {list(np.shape(x))}")
-        res[name] = x
-    return res
+PATH_NAMES = stages.names(stages.PATH)
 
 
 def path_arrays(des, sigma, states):
@@ -428,19 +337,11 @@ def path_rule(final_error, status, min_clearance, out_of_range, required_clearan
               max_rot_dev_allowed=np.inf):
     """(best, n_eligible) by the rule of select_rule with one more condition: no invalid checked state,
     max_pos_dev <= max_pos_dev_allowed and max_rot_dev <= max_rot_dev_allowed (each None: not asked)."""
-    fe = np.asarray(final_error, dtype=np.float64).reshape(-1)
-    ok = eligible(fe, status, min_clearance, out_of_range, required_clearance, require_in_range)
-    if path_invalid is not None:
-        ok &= np.asarray(path_invalid).reshape(-1) == 0
-    with np.errstate(invalid="ignore"):
-        if max_pos_dev is not None:
-            ok &= np.asarray(max_pos_dev, dtype=np.float64).reshape(-1) <= max_pos_dev_allowed
-        if max_rot_dev is not None:
-            ok &= np.asarray(max_rot_dev, dtype=np.float64).reshape(-1) <= max_rot_dev_allowed
-    rows = np.flatnonzero(ok)
-    if rows.size == 0:
-        return -1, 0
-    return int(rows[np.argmin(fe[rows])]), int(rows.size)   # argmin returns the first of equal minima
+    ok = eligible(final_error, status, min_clearance, out_of_range, required_clearance, require_in_range)
+    _none_set(ok, path_invalid)
+    _at_most(ok, max_pos_dev, max_pos_dev_allowed)
+    _at_most(ok, max_rot_dev, max_rot_dev_allowed)
+    return pick(final_error, ok)
 
 
 def _rot_log(R):
