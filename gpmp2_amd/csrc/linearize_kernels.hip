@@ -10,6 +10,7 @@
 #include "plan.h"
 #include "tiles.h"
 #include "cr_schedule.h"
+#include "rec_pieces.h"
 #include "plan_device.h"
 
 namespace g2 {
@@ -282,11 +283,18 @@ __global__ __launch_bounds__(64 * NSPLIT, KIND == GPMP2MI_ROBOT_ARM ? 2 : 1) voi
 //            sin / cos of the joints j % NW == its index -> LDS
 //   phase 2  wavefront 0 walks the chain once (AD dependent frame advances) and leaves, per link, the columns c0, c2
 //            and the origin t of its frame in LDS (9 doubles per lane and link; c1 = c2 x c0 is recomputed where a
-//            sphere centre needs it).  Axis and origin of joint k are c2 and t of frame k - 1 (the base frame for k = 0)
+//            sphere centre needs it).  Axis and origin of joint k are c2 and t of frame k - 1 (the base frame for k = 0).
+//            Meanwhile wavefront 1 forms the prior / limit share and wavefront 2 evaluates the GP prior of the chunk's
+//            support states (states in LDS and the plan's constants: nothing of it waits for the chain)
 //   phase 3  wavefront w visits the spheres s % NW == w: centre from its link's frame, SDF lookup, hinge, and for the
 //            active lanes the Jacobian columns z_k x (p - o_k) of the joints below the link, accumulated as before
-//   phase 4  partial records summed over the wavefronts in a fixed tree order through LDS (the frames' bytes), wavefront
-//            0 stores the record while the last wavefront evaluates the GP prior
+//   phase 4  partial records summed over the wavefronts in a fixed tree order (w0 + w2) + (w1 + w3) through LDS (the
+//            frames' bytes): wavefronts 0 and 1 leave w0 + w2 and w1 + w3 there, and all four wavefronts form the last
+//            add and the scaling and store the chunk's 64 records -- one run of memory -- in 16-B pieces in memory order
+//            (rec_pieces.h): 1 KiB per wavefront and store instruction.  (Wavefront 0 alone, each lane its own record at a
+//            stride of 288 B, was 18 store instructions of 64 partial-line requests at the very end of the longest
+//            wavefront; the GP prior sat behind the last barrier on wavefront 3.  Linearization of passes 1 - 4 of the
+//            flagship: 20.9 / 26.3 / 26.0 / 25.6 -> 18.7 / 24.5 / 24.6 / 24.0 us)
 // Against the two-wavefront split above (both wavefronts walk the chain and keep all joint axes in registers, 252
 // VGPRs, two wavefronts per SIMD) the dependent chain of a wavefront is sin/cos of two joints + 4 spheres instead of
 // 7 joints + 8 spheres, and 168 VGPRs leave room for three wavefronts per SIMD: 640 workgroups x 4 wavefronts of the
@@ -300,7 +308,7 @@ __global__ __launch_bounds__(64 * NSPLIT, KIND == GPMP2MI_ROBOT_ARM ? 2 : 1) voi
 // two state buffers of a plan (cur / last) swap roles from pass to pass: `last` is the buffer the step started from.
 // Error shares (linearization at `cur`: bufsel == 0, not `trial`): the kernel holds every term of the graph error
 // 0.5 (sum of point errors + sum of GP energies + prior / limit terms), so each workgroup leaves its chunk's three sums in
-// pb.cshare -- obstacle (wavefront 0, the values it stores in the records), GP prior (last wavefront), and the prior /
+// pb.cshare -- obstacle (wavefront 0, the values that are stored in the records), GP prior (wavefront 2), and the prior /
 // limit / state-prior terms of the states it owns (wavefront 1, from the states in LDS, while wavefront 0 walks the chain).
 // The Gauss-Newton step control reads them (error_from_shares) instead of a sum over k_assemble's blocks.
 template <int AD, int SDIM, int NW>
@@ -313,7 +321,7 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
   constexpr int D = AD, n = 2 * D, NG = D * (D + 1) / 2, RV = NG + D + 1;
   constexpr int FR = 9;                                  // doubles per lane and link: c0, c2, t
   constexpr int ROWS_F = FR * AD, ROWS_SC = 2 * AD;
-  constexpr int ROWS_P = (NW / 2) * RV;                  // partial records: NW / 2 buffers
+  constexpr int ROWS_P = (NW / 2) * rec_lds_stride(RV);  // partial records: NW / 2 buffers of 64 points (rec_pieces.h)
   constexpr int ROWS = (ROWS_F + ROWS_SC > ROWS_P) ? ROWS_F + ROWS_SC : ROWS_P;
   const PlanParams& P = *pp;
   const int nchunk = P.Ppad / 64;
@@ -342,6 +350,7 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     j = t - (i - 1) * (I + 1);
   }
   const bool unary = (j == I);
+  const bool store_ok = p_raw < P.P;
   // ---- the states this workgroup reads: [s0, s1]; through LDS (zn), with the pending step applied in the fused form
   double (*fx)[16] = reinterpret_cast<double (*)[16]>(&buf[0][0]);   // step of the blocks w0 .. w0 + 39 (buf is not in use yet)
   static_assert(FXS * 16 <= ROWS * 64, "the step window lives in the frame buffer");
@@ -368,7 +377,9 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     }
     __syncthreads();
     // Task t of a level (the t-th needed block) belongs to wavefront t % NW.  (Requesting the factor tiles ahead -- all twelve
-    // of a wavefront at once, or one level ahead -- was slower: 21.0 / 20.2 against 19.5 us; 2 560 wavefronts x 21 KB.)
+    // of a wavefront at once, or one level ahead -- was slower: 21.0 / 20.2 against 19.5 us; 2 560 wavefronts x 21 KB.  Touching
+    // one 8-byte word of each of their lines at this point, only when few trajectories are live, was slower as well, down to a
+    // plan of 4 trajectories: DESIGN.md section 4.)
     auto level = [&](u64 need, int h) {
       int t = 0;
       for (u64 m = need; m; m &= m - 1, t++) {
@@ -485,6 +496,44 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     }
     acc = wave_sum(acc);
     if (lane == 0) cshare[2] = acc;
+  } else if (wv == 2) {
+    // GP prior of the interval ending at state i: GaussianProcessPriorLinear (gp/GaussianProcessPriorLinear.h:57-83),
+    // r = Phi z_{i-1} - z_i, u = Q^-1 r (Q^-1 = B(dt) (x) Qc^-1), energy r^T u.  It needs the states in LDS and the plan's
+    // constants only, so it runs here, while wavefront 0 walks the chain, and not behind the sphere loop
+    double en = 0.0;
+    if (unary && i > 0 && store_ok) {
+      double rx[D], rv[D], sx[D], sv[D];
+      double* gb = gpu + ((size_t)b * P.Npad + i) * P.GPS;
+#pragma unroll
+      for (int k = 0; k < D; k++) {
+        rx[k] = z0[k] + P.delta_t * z0[D + k] - z1[k];
+        rv[k] = z0[D + k] - z1[D + k];
+      }
+#pragma unroll
+      for (int k = 0; k < D; k++) {
+        double ax = 0, av = 0;
+#pragma unroll
+        for (int m = 0; m < D; m++) {
+          ax += P.Qc_inv[k * D + m] * rx[m];
+          av += P.Qc_inv[k * D + m] * rv[m];
+        }
+        sx[k] = ax;
+        sv[k] = av;
+      }
+#pragma unroll
+      for (int k = 0; k < D; k++) {
+        const double ux = P.Winv[0] * sx[k] + P.Winv[1] * sv[k];
+        const double uv = P.Winv[2] * sx[k] + P.Winv[3] * sv[k];
+        gb[k] = ux;
+        gb[D + k] = uv;
+        en += rx[k] * ux + rv[k] * uv;
+      }
+      gb[n] = en;
+    }
+    if (shares) {   // GP share: the energies as stored
+      const double gs = wave_sum(en);
+      if (lane == 0) cshare[1] = gs;
+    }
   }
   __syncthreads();
   G2_LSTAMP(2);
@@ -540,87 +589,60 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     });
   }
   G2_LSTAMP(3);
-  // partial records -> wavefront 0, fixed order: (w0 + w2) + (w1 + w3)
+  // partial records, fixed order: (w0 + w2) + (w1 + w3).  The two slots are point-major with an odd stride (rec_pieces.h)
   __syncthreads();   // every wavefront is done with the frames: their bytes now take the partial records
+  constexpr int RECL = RV, RVP = rec_lds_stride(RECL), SLOT = 64 * RVP;
+  static_assert(2 * SLOT <= ROWS * 64, "two partial records fit in the frame buffer");
+  double* const part = &buf[0][0];
   auto put = [&](int slot) {
+    double* q = part + slot * SLOT + lane * RVP;
 #pragma unroll
-    for (int k = 0; k < NG; k++) buf[slot * RV + k][lane] = G[k];
+    for (int k = 0; k < NG; k++) q[k] = G[k];
 #pragma unroll
-    for (int k = 0; k < D; k++) buf[slot * RV + NG + k][lane] = gv[k];
-    buf[slot * RV + NG + D][lane] = e;
+    for (int k = 0; k < D; k++) q[NG + k] = gv[k];
+    q[NG + D] = e;
   };
   auto add = [&](int slot) {
+    const double* q = part + slot * SLOT + lane * RVP;
 #pragma unroll
-    for (int k = 0; k < NG; k++) G[k] += buf[slot * RV + k][lane];
+    for (int k = 0; k < NG; k++) G[k] += q[k];
 #pragma unroll
-    for (int k = 0; k < D; k++) gv[k] += buf[slot * RV + NG + k][lane];
-    e += buf[slot * RV + NG + D][lane];
+    for (int k = 0; k < D; k++) gv[k] += q[NG + k];
+    e += q[NG + D];
   };
   if (wv >= 2) put(wv - 2);
   __syncthreads();
-  if (wv < 2) add(wv);
-  if (wv == 1) put(1);      // (slot 1 was read by wavefront 1 alone)
+  if (wv < 2) {             // w0 + w2 back into slot 0, w1 + w3 into slot 1: each slot is read and rewritten by one wavefront
+    add(wv);
+    put(wv);
+  }
   __syncthreads();
-  if (wv == 0) add(1);
-  const bool store_ok = p_raw < P.P;
   G2_LSTAMP(13);
-  if (wv == 0) {
-    // point-major record: this lane's REC values are one contiguous run, stored in 16-B pieces
-    const double w = P.obs_w;
-    constexpr int RECL = NG + D + 1;
-    double rv[RECL + 1];
+  // The record is (slot 0 + slot 1) * obs_w, the last add of the tree and the scaling.  All four wavefronts form and store it,
+  // in 16-B pieces in memory order (rec_pieces.h): the chunk's records are one run of memory, a wavefront stores 1 KiB of it
+  // per instruction.  (Wavefront 0 alone, each lane its own record, issued 18 stores of 64 separate 16-B requests.)
+  const double w = P.obs_w;
+  {
+    const int npc = rec_piece_count(rec_live_points(P.P, p_lo), RECL);   // points at or beyond P.P are not written
+    double* rchunk = rec + ((size_t)b * P.Ppad + p_lo) * P.RECS;
+    constexpr int NIT = (64 * rec_npieces(RECL) + 64 * NW - 1) / (64 * NW);
 #pragma unroll
-    for (int k = 0; k < NG; k++) rv[k] = G[k] * w;
-#pragma unroll
-    for (int k = 0; k < D; k++) rv[NG + k] = gv[k] * w;
-    rv[NG + D] = e * w;
-    rv[RECL] = 0.0;
-    double2* rb = reinterpret_cast<double2*>(rec + ((size_t)b * P.Ppad + p) * P.RECS);
-#pragma unroll
-    for (int k = 0; k < (RECL + 1) / 2; k++)
-      if (store_ok) rb[k] = double2{rv[2 * k], rv[2 * k + 1]};
-    if (shares) {   // obstacle share: the point errors as stored
-      const double es = wave_sum(store_ok ? rv[NG + D] : 0.0);
-      if (lane == 0) cshare[0] = es;
+    for (int it = 0; it < NIT; it++) {
+      const int pe = threadIdx.x + 64 * NW * it;
+      if (pe < npc) {
+        const RecPiece pc = rec_piece(pe, RECL, P.RECS);
+        const double* a = part + pc.src;
+        const double v0 = (a[0] + a[SLOT]) * w;
+        const double v1 = pc.padded ? 0.0 : (a[1] + a[SLOT + 1]) * w;
+        *reinterpret_cast<double2*>(rchunk + pc.dst) = double2{v0, v1};
+      }
     }
+  }
+  if (wv == 0 && shares) {   // obstacle share: the point errors as stored
+    const double es = wave_sum(store_ok ? (e + part[SLOT + lane * RVP + NG + D]) * w : 0.0);
+    if (lane == 0) cshare[0] = es;
   }
   G2_LSTAMP(14);
-  // GP prior of the interval ending at state i: GaussianProcessPriorLinear (gp/GaussianProcessPriorLinear.h:57-83),
-  // r = Phi z_{i-1} - z_i, u = Q^-1 r (Q^-1 = B(dt) (x) Qc^-1), energy r^T u
-  double en = 0.0;
-  if (unary && i > 0 && store_ok && wv == NW - 1) {
-    double rx[D], rv[D], sx[D], sv[D];
-    double* gb = gpu + ((size_t)b * P.Npad + i) * P.GPS;
-#pragma unroll
-    for (int k = 0; k < D; k++) {
-      rx[k] = z0[k] + P.delta_t * z0[D + k] - z1[k];
-      rv[k] = z0[D + k] - z1[D + k];
-    }
-#pragma unroll
-    for (int k = 0; k < D; k++) {
-      double ax = 0, av = 0;
-#pragma unroll
-      for (int m = 0; m < D; m++) {
-        ax += P.Qc_inv[k * D + m] * rx[m];
-        av += P.Qc_inv[k * D + m] * rv[m];
-      }
-      sx[k] = ax;
-      sv[k] = av;
-    }
-#pragma unroll
-    for (int k = 0; k < D; k++) {
-      const double ux = P.Winv[0] * sx[k] + P.Winv[1] * sv[k];
-      const double uv = P.Winv[2] * sx[k] + P.Winv[3] * sv[k];
-      gb[k] = ux;
-      gb[D + k] = uv;
-      en += rx[k] * ux + rv[k] * uv;
-    }
-    gb[n] = en;
-  }
-  if (wv == NW - 1 && shares) {   // GP share: the energies as stored
-    const double gs = wave_sum(en);
-    if (lane == 0) cshare[1] = gs;
-  }
   G2_LSTAMP(15);
 }
 
