@@ -429,20 +429,40 @@ __device__ __forceinline__ P2 pose2_between(const P2& a, const P2& b) {
   sincos(b.th - a.th, &sd, &cd);
   return P2{ca * dx + sa * dy, -sa * dx + ca * dy, wrap_angle(cd, sd)};
 }
-// Pose2::Logmap
-__device__ __forceinline__ void pose2_logmap(const P2& p, double (&v)[3]) {
-  const double w = p.th;
-  if (fabs(w) < 1e-10) {
-    v[0] = p.x; v[1] = p.y; v[2] = w;
-  } else {
-    double s, c;
-    sincos(w, &s, &c);
-    const double c_1 = c - 1.0, det = c_1 * c_1 + s * s;
-    const double ux = c * p.x + s * p.y - p.x, uy = -s * p.x + c * p.y - p.y;
-    v[0] = (w / det) * (-uy);
-    v[1] = (w / det) * ux;
-    v[2] = w;
+// The Pose2 maps below are the exact maps in forms without cancellation, not GTSAM's expressions (SURVEY.md appendix
+// B, DESIGN.md "Pose2 maps"): GTSAM switches to first order below |w| < 1e-10 (maps) and |w| <= 1e-5 (derivatives) and
+// divides by 1 - cos w above; that loses |t| 2e-16 / w^3 in the log derivative (3e-2 at w = 1e-5).  With a = w / 2:
+//   sin w / w = sin a cos a / a      (1 - cos w) / w = sin^2 a / a      h = a cot a      g = 1 / w - cot(a) / 2
+// h and the two quotients have no cancellation at any w in (-pi, pi]; g and (1 - sin w / w) / w cancel like u / w and
+// take their series below POSE2_SERIES_BELOW, where the closed forms are still good to 1e-14 (measured: 7e-15,
+// profiles/pose2_maps_error.txt) and the omitted series terms are below 1e-17 relative.
+constexpr double POSE2_SERIES_BELOW = 1e-2;
+struct P2Half {
+  double a, sa, ca;   // a = w / 2, sin a, cos a
+  double sa_a;        // sin(a) / a, 1 at 0
+};
+__device__ __forceinline__ P2Half pose2_half(double w) {
+  P2Half q;
+  q.a = 0.5 * w;
+  sincos(q.a, &q.sa, &q.ca);
+  q.sa_a = (q.a == 0.0) ? 1.0 : q.sa / q.a;
+  return q;
+}
+// g(w) = 1 / w - cot(w / 2) / 2 = w / 12 + w^3 / 720 + w^5 / 30240 + w^7 / 1209600 + ...
+__device__ __forceinline__ double pose2_g(double w, const P2Half& q) {
+  if (fabs(w) < POSE2_SERIES_BELOW) {
+    const double w2 = w * w;
+    return w * (1.0 / 12.0 + w2 * (1.0 / 720.0 + w2 * (1.0 / 30240.0 + w2 * (1.0 / 1209600.0))));
   }
+  return 1.0 / w - 0.5 * q.ca / q.sa;
+}
+// Pose2::Logmap: v = (h x + a y, -a x + h y, w), h = a cot a
+__device__ __forceinline__ void pose2_logmap(const P2& p, double (&v)[3]) {
+  const P2Half q = pose2_half(p.th);
+  const double h = q.ca / q.sa_a;
+  v[0] = h * p.x + q.a * p.y;
+  v[1] = -q.a * p.x + h * p.y;
+  v[2] = p.th;
 }
 // Pose2::AdjointMap (row-major 3x3)
 __device__ __forceinline__ void pose2_adjoint(const P2& p, double (&A)[9]) {
@@ -459,38 +479,34 @@ __device__ __forceinline__ P2 pose2_inverse(const P2& a) {
 __device__ __forceinline__ void pose2_logmap_derivative(const P2& p, double (&J)[9]) {
   double v[3];
   pose2_logmap(p, v);
-  const double alpha = v[2];
-  if (fabs(alpha) > 1e-5) {
-    const double ai = 1 / alpha, hc = 0.5 * sin(alpha) / (1 - cos(alpha));
-    J[0] = alpha * hc; J[1] = -0.5 * alpha; J[2] = v[0] * ai - v[0] * hc + 0.5 * v[1];
-    J[3] = 0.5 * alpha; J[4] = alpha * hc; J[5] = v[1] * ai - 0.5 * v[0] - v[1] * hc;
-    J[6] = 0; J[7] = 0; J[8] = 1;
-  } else {
-    J[0] = 1; J[1] = 0; J[2] = 0.5 * v[1]; J[3] = 0; J[4] = 1; J[5] = -0.5 * v[0]; J[6] = 0; J[7] = 0; J[8] = 1;
-  }
+  const P2Half q = pose2_half(p.th);
+  const double h = q.ca / q.sa_a, g = pose2_g(p.th, q);
+  J[0] = h; J[1] = -q.a; J[2] = v[0] * g + 0.5 * v[1];
+  J[3] = q.a; J[4] = h; J[5] = v[1] * g - 0.5 * v[0];
+  J[6] = 0; J[7] = 0; J[8] = 1;
 }
-// Pose2::Expmap
+// Pose2::Expmap: t = [A -B; B A] (v0, v1), A = sin w / w, B = (1 - cos w) / w
 __device__ __forceinline__ P2 pose2_expmap(const double (&v)[3]) {
-  const double w = v[2];
-  if (fabs(w) < 1e-10) return P2{v[0], v[1], v[2]};
-  double s, c;
-  sincos(w, &s, &c);
-  const double ox = -v[1], oy = v[0];
-  const double rx = c * ox - s * oy, ry = s * ox + c * oy;
-  return P2{(ox - rx) / w, (oy - ry) / w, wrap_angle(c, s)};
+  const P2Half q = pose2_half(v[2]);
+  const double A = q.sa_a * q.ca, B = q.sa_a * q.sa;
+  return P2{A * v[0] - B * v[1], B * v[0] + A * v[1], wrap_angle((q.ca - q.sa) * (q.ca + q.sa), 2.0 * q.sa * q.ca)};
 }
-// Pose2::ExpmapDerivative
+// Pose2::ExpmapDerivative: [A B k1 v0 - k2 v1; -B A k2 v0 + k1 v1; 0 0 1],
+// k1 = (1 - A) / w = w / 6 - w^3 / 120 + w^5 / 5040 - w^7 / 362880 + ...,  k2 = (1 - cos w) / w^2
 __device__ __forceinline__ void pose2_expmap_derivative(const double (&v)[3], double (&J)[9]) {
-  const double alpha = v[2];
-  if (fabs(alpha) > 1e-5) {
-    const double sZ = sin(alpha) / alpha, c1Z = (cos(alpha) - 1) / alpha;
-    const double v1Z = v[0] / alpha, v2Z = v[1] / alpha;
-    J[0] = sZ; J[1] = -c1Z; J[2] = v1Z + v2Z * c1Z - v1Z * sZ;
-    J[3] = c1Z; J[4] = sZ; J[5] = -v1Z * c1Z + v2Z - v2Z * sZ;
-    J[6] = 0; J[7] = 0; J[8] = 1;
+  const double w = v[2];
+  const P2Half q = pose2_half(w);
+  const double A = q.sa_a * q.ca, B = q.sa_a * q.sa, k2 = 0.5 * q.sa_a * q.sa_a;
+  double k1;
+  if (fabs(w) < POSE2_SERIES_BELOW) {
+    const double w2 = w * w;
+    k1 = w * (1.0 / 6.0 + w2 * (-1.0 / 120.0 + w2 * (1.0 / 5040.0 + w2 * (-1.0 / 362880.0))));
   } else {
-    J[0] = 1; J[1] = 0; J[2] = -0.5 * v[1]; J[3] = 0; J[4] = 1; J[5] = 0.5 * v[0]; J[6] = 0; J[7] = 0; J[8] = 1;
+    k1 = (1.0 - A) / w;
   }
+  J[0] = A; J[1] = B; J[2] = k1 * v[0] - k2 * v[1];
+  J[3] = -B; J[4] = A; J[5] = k2 * v[0] + k1 * v[1];
+  J[6] = 0; J[7] = 0; J[8] = 1;
 }
 __device__ __forceinline__ P2 pose2_compose(const P2& a, const P2& b) {
   double s, c, sb, cb;

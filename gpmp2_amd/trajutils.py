@@ -59,24 +59,23 @@ def pose2_compose(a, b):
     return np.array([a[0] + c * b[0] - s * b[1], a[1] + s * b[0] + c * b[1], _wrap(a[2] + b[2])])
 
 
+def _sin_over(a):
+    return 1.0 if a == 0.0 else float(np.sin(a) / a)
+
+
 def pose2_logmap(p):
+    """the exact map in the cancellation-free form of csrc/device_math.h: h = (w/2) cot(w/2), no small-angle branch"""
     w = _wrap(p[2])
-    if abs(w) < 1e-10:
-        return np.array([p[0], p[1], w])
-    c, s = np.cos(p[2]), np.sin(p[2])
-    det = (c - 1.0) ** 2 + s * s
-    ux, uy = c * p[0] + s * p[1] - p[0], -s * p[0] + c * p[1] - p[1]
-    return np.array([(w / det) * -uy, (w / det) * ux, w])
+    a = 0.5 * w
+    h = float(np.cos(a)) / _sin_over(a)
+    return np.array([h * p[0] + a * p[1], -a * p[0] + h * p[1], w])
 
 
 def pose2_expmap(v):
-    w = v[2]
-    if abs(w) < 1e-10:
-        return np.array([v[0], v[1], v[2]])
-    c, s = np.cos(w), np.sin(w)
-    ox, oy = -v[1], v[0]
-    rx, ry = c * ox - s * oy, s * ox + c * oy
-    return np.array([(ox - rx) / w, (oy - ry) / w, _wrap(w)])
+    a = 0.5 * v[2]
+    q = _sin_over(a)
+    A, B = q * float(np.cos(a)), q * float(np.sin(a))      # sin w / w, (1 - cos w) / w
+    return np.array([A * v[0] - B * v[1], B * v[0] + A * v[1], _wrap(v[2])])
 
 
 def pose2_interpolate(a, b, t):

@@ -149,38 +149,32 @@ Pose2 pose2_inverse(const Pose2& a) {
   return r;
 }
 Pose2 pose2_between(const Pose2& a, const Pose2& b) { return pose2_compose(pose2_inverse(a), b); }
-void pose2_logmap(const Pose2& p, double v[3]) {
-  const double c = std::cos(p.th), s = std::sin(p.th);
-  const double w = wrap_theta(c, s);
-  if (std::fabs(w) < 1e-10) {
-    v[0] = p.x;
-    v[1] = p.y;
-    v[2] = w;
-  } else {
-    const double c_1 = c - 1.0, det = c_1 * c_1 + s * s;
-    // R.unrotate(t) - t, then rotate by +90 deg
-    const double ux = c * p.x + s * p.y - p.x, uy = -s * p.x + c * p.y - p.y;
-    const double px = -uy, py = ux;
-    v[0] = (w / det) * px;
-    v[1] = (w / det) * py;
-    v[2] = w;
+// The four maps below are the exact maps in cancellation-free forms, as in gpmp2_amd/csrc/device_math.h, and no longer
+// GTSAM's branch structure: with a = w / 2,
+//   sin w / w = sin a cos a / a,  (1 - cos w) / w = sin^2 a / a,  h = a cot a,  g = 1 / w - cot(a) / 2 (series below 1e-2)
+static const double kPose2SeriesBelow = 1e-2;
+static inline double sin_over(double a, double sa) { return a == 0.0 ? 1.0 : sa / a; }
+static inline double pose2_g(double w) {
+  if (std::fabs(w) < kPose2SeriesBelow) {
+    const double w2 = w * w;
+    return w * (1.0 / 12.0 + w2 * (1.0 / 720.0 + w2 * (1.0 / 30240.0 + w2 * (1.0 / 1209600.0))));
   }
+  return 1.0 / w - 0.5 * std::cos(0.5 * w) / std::sin(0.5 * w);
+}
+void pose2_logmap(const Pose2& p, double v[3]) {
+  const double w = wrap_theta(std::cos(p.th), std::sin(p.th));
+  const double a = 0.5 * w, h = std::cos(a) / sin_over(a, std::sin(a));
+  v[0] = h * p.x + a * p.y;
+  v[1] = -a * p.x + h * p.y;
+  v[2] = w;
 }
 Pose2 pose2_expmap(const double v[3]) {
-  const double w = v[2];
+  const double a = 0.5 * v[2], sa = std::sin(a), ca = std::cos(a), q = sin_over(a, sa);
+  const double A = q * ca, B = q * sa;
   Pose2 r;
-  if (std::fabs(w) < 1e-10) {
-    r.x = v[0];
-    r.y = v[1];
-    r.th = v[2];
-  } else {
-    const double c = std::cos(w), s = std::sin(w);
-    const double ox = -v[1], oy = v[0];  // v_ortho = R_PI_2 * v
-    const double rx = c * ox - s * oy, ry = s * ox + c * oy;
-    r.x = (ox - rx) / w;
-    r.y = (oy - ry) / w;
-    r.th = wrap_theta(c, s);
-  }
+  r.x = A * v[0] - B * v[1];
+  r.y = B * v[0] + A * v[1];
+  r.th = wrap_theta((ca - sa) * (ca + sa), 2.0 * sa * ca);
   return r;
 }
 Pose2 pose2_retract(const Pose2& p, const double v[3]) {
@@ -196,32 +190,24 @@ void pose2_adjoint(const Pose2& p, double A[9]) {
   std::memcpy(A, M, sizeof(M));
 }
 void pose2_expmap_derivative(const double v[3], double J[9]) {
-  const double alpha = v[2];
-  if (std::fabs(alpha) > 1e-5) {
-    const double sZ = std::sin(alpha) / alpha, c1Z = (std::cos(alpha) - 1) / alpha;
-    const double v1Z = v[0] / alpha, v2Z = v[1] / alpha;
-    const double M[9] = {sZ, -c1Z, v1Z + v2Z * c1Z - v1Z * sZ, c1Z, sZ,
-                         -v1Z * c1Z + v2Z - v2Z * sZ, 0, 0, 1};
-    std::memcpy(J, M, sizeof(M));
+  const double w = v[2], a = 0.5 * w, sa = std::sin(a), ca = std::cos(a), q = sin_over(a, sa);
+  const double A = q * ca, B = q * sa, k2 = 0.5 * q * q;
+  double k1;  // (1 - sin w / w) / w
+  if (std::fabs(w) < kPose2SeriesBelow) {
+    const double w2 = w * w;
+    k1 = w * (1.0 / 6.0 + w2 * (-1.0 / 120.0 + w2 * (1.0 / 5040.0 + w2 * (-1.0 / 362880.0))));
   } else {
-    const double M[9] = {1, 0, -0.5 * v[1], 0, 1, 0.5 * v[0], 0, 0, 1};
-    std::memcpy(J, M, sizeof(M));
+    k1 = (1.0 - A) / w;
   }
+  const double M[9] = {A, B, k1 * v[0] - k2 * v[1], -B, A, k2 * v[0] + k1 * v[1], 0, 0, 1};
+  std::memcpy(J, M, sizeof(M));
 }
 void pose2_logmap_derivative(const Pose2& p, double J[9]) {
   double v[3];
   pose2_logmap(p, v);
-  const double alpha = v[2];
-  if (std::fabs(alpha) > 1e-5) {
-    const double ai = 1 / alpha, hc = 0.5 * std::sin(alpha) / (1 - std::cos(alpha));
-    const double v1 = v[0], v2 = v[1];
-    const double M[9] = {alpha * hc, -0.5 * alpha, v1 * ai - v1 * hc + 0.5 * v2,
-                         0.5 * alpha, alpha * hc, v2 * ai - 0.5 * v1 - v2 * hc, 0, 0, 1};
-    std::memcpy(J, M, sizeof(M));
-  } else {
-    const double M[9] = {1, 0, 0.5 * v[1], 0, 1, -0.5 * v[0], 0, 0, 1};
-    std::memcpy(J, M, sizeof(M));
-  }
+  const double w = v[2], a = 0.5 * w, h = std::cos(a) / sin_over(a, std::sin(a)), g = pose2_g(w);
+  const double M[9] = {h, -a, v[0] * g + 0.5 * v[1], a, h, v[1] * g - 0.5 * v[0], 0, 0, 1};
+  std::memcpy(J, M, sizeof(M));
 }
 
 // =============================================================================== SO(3) / SE(3) logs

@@ -94,21 +94,21 @@ def _pose2_interpolate(x0, v0, x1, v1, l12, p11, p12, l22, p21, p22):
     bx, by = c1 * dx + s1 * dy, -s1 * dx + c1 * dy
     dth = x1[..., 2] - x0[..., 2]
     w = np.arctan2(np.sin(dth), np.cos(dth))
-    small = np.abs(w) < 1e-10
-    ws = np.where(small, 1.0, w)
-    c, s = np.cos(ws), np.sin(ws)
-    det = (c - 1) ** 2 + s ** 2
-    ux, uy = c * bx + s * by - bx, -s * bx + c * by - by
-    lg = np.stack([np.where(small, bx, (ws / det) * (-uy)), np.where(small, by, (ws / det) * ux), w], axis=-1)
+    one = np.ones_like(w)
+
+    def half(w):        # a = w / 2, sin a, cos a, sin(a) / a: the cancellation-free forms of csrc/device_math.h
+        a = w / 2
+        z = a == 0
+        return a, np.sin(a), np.cos(a), np.where(z, one, np.sin(a) / np.where(z, one, a))
+
+    a, _, ca, q = half(w)
+    h = ca / q
+    lg = np.stack([h * bx + a * by, -a * bx + h * by, w], axis=-1)
     xi = l12 * v0 + p11 * lg + p12 * v1
-    w = xi[..., 2]
-    small = np.abs(w) < 1e-10
-    ws = np.where(small, 1.0, w)
-    c, s = np.cos(ws), np.sin(ws)
-    ox, oy = -xi[..., 1], xi[..., 0]
-    rx, ry = c * ox - s * oy, s * ox + c * oy
-    ex, ey = np.where(small, xi[..., 0], (ox - rx) / ws), np.where(small, xi[..., 1], (oy - ry) / ws)
-    eth = np.where(small, w, np.arctan2(s, c))
+    a, sa, ca, q = half(xi[..., 2])
+    A, Bq = q * ca, q * sa
+    ex, ey = A * xi[..., 0] - Bq * xi[..., 1], Bq * xi[..., 0] + A * xi[..., 1]
+    eth = np.arctan2(2 * sa * ca, (ca - sa) * (ca + sa))
     ce, se = np.cos(eth), np.sin(eth)
     pose = np.stack([x0[..., 0] + c1 * ex - s1 * ey, x0[..., 1] + s1 * ex + c1 * ey,
                      np.arctan2(s1 * ce + c1 * se, c1 * ce - s1 * se)], axis=-1)
