@@ -47,6 +47,7 @@ class Settings(C.Structure):
 
 MAX_WORKSPACE_FACTORS, MAX_SELF_COLLISION_PAIRS = 4, 16
 MAX_MOVING_SPHERES = 64
+MAX_CARRIED_SPHERES = 256    # GPMP2MI_MAX_CARRIED_SPHERES
 HEADER_MAX_SPHERES = 96   # GPMP2MI_MAX_SPHERES
 MAX_PLAN_SELF_PAIRS = HEADER_MAX_SPHERES * (HEADER_MAX_SPHERES - 1) // 2   # GPMP2MI_MAX_PLAN_SELF_PAIRS
 WORKSPACE_POSITION, WORKSPACE_ORIENTATION, WORKSPACE_POSE = 0, 1, 2
@@ -68,6 +69,8 @@ class GraphOpts(C.Structure):
                 ("workspace", WorkspaceFactor * MAX_WORKSPACE_FACTORS),
                 ("n_self_collision", C.c_int), ("self_collision_first", C.c_int), ("self_collision_last", C.c_int),
                 ("self_collision", (C.c_double * 4) * MAX_SELF_COLLISION_PAIRS),
+                ("max_carried_spheres", C.c_int), ("carried_first", C.c_int), ("carried_last", C.c_int),
+                ("carried_epsilon", C.c_double), ("carried_sigma", C.c_double),
                 ("workspace_path", C.c_int), ("workspace_path_mode", C.c_int), ("workspace_path_link", C.c_int),
                 ("max_self_pairs", C.c_int), ("self_pairs_first", C.c_int), ("self_pairs_last", C.c_int),
                 ("max_moving_spheres", C.c_int), ("moving_first", C.c_int), ("moving_last", C.c_int),
@@ -265,6 +268,27 @@ def declare_moving(lib):
         "gpmp2mi_plan_moving_score_dev": [vp, i] + [vp] * 6,
         "gpmp2mi_plan_select_moving": [vp, i, f, i, vp, f, f, ip, ip, d, d],
         "gpmp2mi_plan_select_moving_dev": [vp, i, f, i, vp, f, f] + [vp] * 5,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
+def declare_carried(lib):
+    """argtypes of the carried-object entry points (include/gpmp2mi.h "carried object"); the `_dev` forms take device
+    addresses."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    decl = {
+        "gpmp2mi_plan_set_carried": [vp, i, i, d, d],
+        "gpmp2mi_plan_set_carried_dev": [vp, i, i, vp, vp, vp],
+        "gpmp2mi_plan_carried_count": [vp],
+        "gpmp2mi_carried_sphere_factor": [vp, vp, i, i, d, d, f, i, d, d, d],
+        "gpmp2mi_carried_score_traj": [vp, vp, i, i, d, d, f, i, i, i, d, d, d, d, ip, ip],
+        "gpmp2mi_carried_score_traj_dev": [vp, vp, i, i, vp, vp, f, i, i, i] + [vp] * 7,
+        "gpmp2mi_plan_carried_score": [vp, i, d, d, d, ip, ip],
+        "gpmp2mi_plan_carried_score_dev": [vp, i] + [vp] * 6,
+        "gpmp2mi_plan_select_carried": [vp, i, f, i, vp, f, f, ip, ip, d, d],
+        "gpmp2mi_plan_select_carried_dev": [vp, i, f, i, vp, f, f] + [vp] * 5,
     }
     for name, args in decl.items():
         getattr(lib, name).argtypes = args
@@ -642,6 +666,14 @@ def make_settings(setting):
         rng_ = mv.get("states") or (0, setting.total_step)
         o.moving_first, o.moving_last = int(rng_[0]), int(rng_[1])
         o.moving_epsilon, o.moving_sigma = float(mv["epsilon"]), float(mv["sigma"])
+    cr = getattr(setting, "carried_spheres", None)
+    if cr is not None:
+        if not 0 <= int(cr["capacity"]) <= MAX_CARRIED_SPHERES:
+            raise ValueError("carried-sphere capacity outside 0..MAX_CARRIED_SPHERES")
+        o.max_carried_spheres = int(cr["capacity"])
+        rng_ = cr.get("states") or (0, setting.total_step)
+        o.carried_first, o.carried_last = int(rng_[0]), int(rng_[1])
+        o.carried_epsilon, o.carried_sigma = float(cr["epsilon"]), float(cr["sigma"])
     sp = getattr(setting, "self_pairs", None)
     if sp is not None:
         if not 0 <= int(sp["capacity"]) <= MAX_PLAN_SELF_PAIRS:

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import scoring, stages
 from ._capi import dptr, f64, iptr
-from .marshalling import Dynamics, _dev_arg, _Handle, _limits_arg, out_ptrs, traj_args
+from .marshalling import Dynamics, _dev_arg, _Handle, _limits_arg, dev_args, out_ptrs, traj_args
 
 
 class TrajChecks:
@@ -143,6 +143,29 @@ class TrajChecks:
         self._ck(self.lib.gpmp2mi_moving_score_traj(robot.ptr, K, dptr(r), dptr(c), float(epsilon), delta_t,
                                                     inter_step, B, N, dptr(t), *out_ptrs(stages.MOVING, o)))
         return o
+
+    # ---------------------------------------------------------------- carried object (include/gpmp2mi.h)
+    def carried_score_traj(self, robot, sdf, link, radius, centers, delta_t, inter_step, traj, out=None):
+        """traj [B][N+1][2D] (or one [N+1][2D]) with the spheres radius [A], centers [A][3] attached to `link`, against
+        the field -> dict(carried_support_cost [B], carried_dense_cost [B], min_carried_clearance [B], worst [B][2] =
+        (checked state, carried sphere), out_of_range [B]) of the inter_step-up-sampled trajectories."""
+        t, inter_step, delta_t, B, N = traj_args(traj, robot.dof, delta_t, inter_step)
+        A, r, c = scoring.carried_set(radius, centers)
+        o = stages.outputs(stages.CARRIED, B, out=out)
+        self._ck(self.lib.gpmp2mi_carried_score_traj(robot.ptr, sdf.ptr, int(link), A, dptr(r), dptr(c), delta_t,
+                                                     inter_step, B, N, dptr(t), *out_ptrs(stages.CARRIED, o)))
+        return o
+
+    def carried_score_traj_dev(self, robot, sdf, link, A, radius, centers, delta_t, inter_step, B, N, traj,
+                               carried_support_cost=None, carried_dense_cost=None, min_carried_clearance=None,
+                               worst=None, out_of_range=None, stream=None):
+        """The same on device buffers (torch tensors or raw pointers; any output may be None); no host synchronisation."""
+        A, B, N = int(A), int(B), int(N)
+        lead = [_dev_arg("radius", radius, (A,)), _dev_arg("centers", centers, (A, 3))]
+        t = _dev_arg("traj", traj, (B, N + 1, 2 * robot.dof))
+        args = dev_args(stages.CARRIED, B, None, None, locals())
+        self._ck(self.lib.gpmp2mi_carried_score_traj_dev(robot.ptr, sdf.ptr, int(link), A, *lead, float(delta_t),
+                                                         int(inter_step), B, N, t, *args, C.c_void_p(stream or 0)))
 
     # ---------------------------------------------------------------- workspace path (include/gpmp2mi.h)
     def workspace_path_factor(self, robot, mode, link, conf, des, jac=True):

@@ -143,6 +143,8 @@ struct gpmp2mi_robot {
   mutable g2::Workspace moving_ws;
   // the records of gpmp2mi_path_score_traj(_dev) calls on this handle (path.hip), under the same guard and rule
   mutable g2::Workspace path_ws;
+  // the records of gpmp2mi_carried_score_traj(_dev) calls on this handle (carried.hip), under the same guard and rule
+  mutable g2::Workspace carried_ws;
   // the workspace of gpmp2mi_retime_traj(_dev) calls on this handle (retime.hip), under the same guard and rule
   mutable g2::Workspace retime_ws;
   ~gpmp2mi_robot() {
@@ -395,11 +397,11 @@ struct gpmp2mi_plan {
   //   SAMPLED  a chunk of delta, its records, the carried counts and ok
   //   SELF     CheckWs with the records of k_self_clearance and those of k_score for select_checked
   //   GROUP    the bit matrix of k_traj_pairs, the per-row scores the rule reads, what k_group_rule leaves, the staging
-  //   MOTION, MOVING, PATH   CheckWs with the stage's records and the per-row scores of the earlier stages its rule reads
+  //   MOTION, MOVING, PATH, CARRIED   CheckWs with the stage's records and the per-row scores of the earlier stages its rule reads
   //   RETIME   ps, the caps and the sets of k_retime, the profile, the scores of the earlier stages, the staging
   //   TORQUE   the records of k_torque, the scores of the earlier stages, the staging with the torques, the pick
   enum Ws { WS_QUEUE, WS_SCORE, WS_POST, WS_SEED, WS_RISK, WS_SAMPLED, WS_SELF, WS_GROUP, WS_MOTION, WS_MOVING, WS_PATH,
-            WS_RETIME, WS_TORQUE, WS_COUNT };
+            WS_RETIME, WS_TORQUE, WS_CARRIED, WS_COUNT };
   g2::Workspace ws[WS_COUNT];
   // seeding (seed.hip): H_seed of the plan's linear prior graph on the host (built at the first seeded call or read-out)
   std::vector<double> seed_Hd, seed_Ho;

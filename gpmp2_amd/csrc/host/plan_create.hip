@@ -328,6 +328,20 @@ static int check_extras(const RobotDev& h, const gpmp2mi_graph_opts& o, int N, P
     ex.sp_first = o.self_pairs_first;
     ex.sp_last = o.self_pairs_last;
   }
+  G2_CHECK(o.max_carried_spheres >= 0 && o.max_carried_spheres <= GPMP2MI_MAX_CARRIED_SPHERES, GPMP2MI_ERR_INVALID,
+           "max_carried_spheres outside 0..GPMP2MI_MAX_CARRIED_SPHERES");
+  if (o.max_carried_spheres > 0) {   // without capacity the other four fields are not read
+    G2_CHECK(o.carried_sigma > 0 && std::isfinite(o.carried_sigma), GPMP2MI_ERR_INVALID, "carried object: sigma must be positive");
+    G2_CHECK(std::isfinite(o.carried_epsilon), GPMP2MI_ERR_INVALID, "carried object: epsilon must be finite");
+    G2_CHECK(o.carried_first >= 0 && o.carried_first <= o.carried_last && o.carried_last <= N, GPMP2MI_ERR_INVALID,
+             "carried object: bad state range");
+    G2_DISPATCH_ROBOT_H(h, (void)0);   // a (kind, dof) the chain kernels are not instantiated for: GPMP2MI_ERR_UNSUPPORTED
+    ex.cr_cap = o.max_carried_spheres;
+    ex.cr_first = o.carried_first;
+    ex.cr_last = o.carried_last;
+    ex.cr_eps = o.carried_epsilon;
+    ex.cr_w = 1.0 / (o.carried_sigma * o.carried_sigma);
+  }
   // the robot's radii in the caller's sphere order: read by the self-collision rows and the moving-sphere factor
   if (ex.n_sc > 0 || ex.mv_cap > 0)
     for (int sidx = 0; sidx < h.nr_spheres; sidx++) hx.radius[h.sph_orig[sidx]] = h.sph_r[sidx];
@@ -426,6 +440,10 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
     G2_TRY(plan_alloc(p, &ex.wp_list, (size_t)P.N + 1));
     G2_TRY(plan_alloc(p, &ex.wp_count, 1));
   }
+  if (ex.cr_cap > 0) {   // the set alone: no poses, Jacobians or rows
+    G2_TRY(plan_alloc(p, &ex.cr_radius, (size_t)ex.cr_cap));
+    G2_TRY(plan_alloc(p, &ex.cr_centers, (size_t)ex.cr_cap * 3));
+  }
   G2_TRY(plan_alloc(p, &pb.n_active, p->n_active_len));
   G2_TRY(plan_alloc(p, &pb.stamps, (size_t)B * 128));   // rows 0..B-1: kernel phases, rows B..2B-1: one CR task per level
   G2_TRY(flags_acquire(p->n_active_len, &p->flagbuf));
@@ -511,7 +529,8 @@ int gpmp2mi_debug_plan_create(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf
   if (s->Qc) std::copy(s->Qc, s->Qc + (size_t)D * D, p->Qc.begin());
   ExtrasHost hx;
   G2_TRY(check_extras(robot->h, o, p->hp.N, p->ex, hx));
-  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0 || p->ex.wp_cap > 0 || p->ex.sp_cap > 0;
+  p->has_extras = p->ex.n_ws > 0 || p->ex.n_sc > 0 || p->ex.mv_cap > 0 || p->ex.wp_cap > 0 || p->ex.sp_cap > 0 ||
+                  p->ex.cr_cap > 0;
   p->h_xp_n.assign(B, 0);
   p->goal_removed.assign(B, 0);
   G2_TRY(alloc_buffers(p.get(), hx));

@@ -11,8 +11,8 @@ using namespace g2;
 // then -- only for plans that carry extra factors -- the workspace / self-collision factor kernels on the support
 // states and their accumulation into the unary records, and the moving-sphere factor of a non-empty resident set
 // (moving_kernels.hip), the self-collision factor of a non-empty resident pair table (selfpair_kernels.hip) and the
-// workspace-path factor of a resident path (path_kernels.hip), which add their terms to
-// the same records without storing rows
+// workspace-path factor of a resident path (path_kernels.hip) and the carried-object factor of a non-empty resident set
+// (carried_kernels.hip), which add their terms to the same records without storing rows
 // dst / pass: fused finish (launch_linearize); the extra-factor kernels then run on the NEW states in dst
 int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const int* active, hipStream_t st, double* dst,
                        int pass, bool trial) {
@@ -39,7 +39,9 @@ int g2::plan_linearize(gpmp2mi_plan* p, const double* traj, int bufsel, const in
   G2_TRY(launch_moving_accumulate(P, p->pb, ex, S, bufsel, active, st));   // nothing for an empty set
   G2_TRY(launch_selfpair_accumulate(P, p->pb, ex, S, bufsel, active, st));   // nothing for an empty table
   // the workspace path (path_kernels.hip): nothing without a constrained state
-  return launch_path_accumulate(h, p->robot->d, P, p->pb, ex, traj, bufsel, active, st);
+  G2_TRY(launch_path_accumulate(h, p->robot->d, P, p->pb, ex, traj, bufsel, active, st));
+  // the carried object (carried_kernels.hip), last: nothing for an empty set
+  return launch_carried_accumulate(h, p->robot->d, p->sdf->h, P, p->pb, ex, traj, bufsel, active, st);
 }
 
 // Active-trajectory count of a finished pass.  The closing kernel of every pass publishes it to a pinned,

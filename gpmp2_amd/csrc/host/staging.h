@@ -85,7 +85,7 @@ inline PickRows carve_pick(Carver& c, const Shape& s, bool extra, size_t extra_r
 // ---- the per-row outputs of the stages, each stated once: the typed face, its list, and the list resolved by the
 // staging rule back into the typed face (what the stage's finish kernel gets)
 
-// score, self check (oor: invalid) and moving obstacles (oor: invalid) share a face; `worst` is [B][worst_w]
+// score, self check (oor: invalid), moving obstacles (oor: invalid) and the carried object share a face; `worst` is [B][worst_w]
 struct ScoreOut {
   double *support = nullptr, *dense = nullptr, *clearance = nullptr;
   int *worst = nullptr, *oor = nullptr;
@@ -95,7 +95,7 @@ inline ScoreOut make_out(double* support, double* dense, double* clearance, int*
   o.support = support, o.dense = dense, o.clearance = clearance, o.worst = worst, o.oor = oor;
   return o;
 }
-constexpr int SCORE_ROWS = 5, SCORE_WORST = 2, SELF_WORST = 2, MOVING_WORST = 3;
+constexpr int SCORE_ROWS = 5, SCORE_WORST = 2, SELF_WORST = 2, MOVING_WORST = 3, CARRIED_WORST = 2;
 inline void rows_of(const ScoreOut& o, size_t worst_w, RowOut* r) {
   r[0] = row(o.support), r[1] = row(o.dense), r[2] = row(o.clearance), r[3] = row(o.worst, worst_w), r[4] = row(o.oor);
 }
@@ -180,8 +180,8 @@ inline CheckWs carve_check(char* base, size_t rec_bytes, size_t rec2_bytes, int 
   w.bytes = c.off;
   return w;
 }
-// the five stages that keep a CheckWs (rows: the stage's rows_of).  The self check keeps the records of k_score for
-// select_checked as its second set; motion limits and moving obstacles read the obstacle stage and the self check, the
+// the six stages that keep a CheckWs (rows: the stage's rows_of).  The self check keeps the records of k_score for
+// select_checked as its second set; motion limits, moving obstacles and the carried object read the obstacle stage and the self check, the
 // workspace path the obstacle stage alone; the motion limits carry time_scale in the pick.
 inline CheckWs carve_score(char* base, size_t rec_bytes, RowOut* rows, const Shape& s) {
   return carve_check(base, rec_bytes, 0, 0, rows, SCORE_ROWS, s, false);
@@ -193,6 +193,9 @@ inline CheckWs carve_motion(char* base, size_t rec_bytes, RowOut* rows, const Sh
   return carve_check(base, rec_bytes, 0, 2, rows, MOTION_ROWS, s, true);
 }
 inline CheckWs carve_moving(char* base, size_t rec_bytes, RowOut* rows, const Shape& s) {
+  return carve_check(base, rec_bytes, 0, 2, rows, SCORE_ROWS, s, false);
+}
+inline CheckWs carve_carried(char* base, size_t rec_bytes, RowOut* rows, const Shape& s) {
   return carve_check(base, rec_bytes, 0, 2, rows, SCORE_ROWS, s, false);
 }
 inline CheckWs carve_path(char* base, size_t rec_bytes, RowOut* rows, const Shape& s) {

@@ -330,6 +330,31 @@ int launch_moving_clearance(const RobotDev& h, const RobotDev* R, int K, const d
                             hipStream_t st);
 int launch_moving_finish(const MovingFinish& a, hipStream_t st);
 
+// carried_kernels.hip (include/gpmp2mi.h "carried object"; the in-plan factor's launcher is in plan.h)
+// the factor on M evaluations: radius [A], centers [A][3] in the frame of `link`, conf [M][D] -> err [M][A],
+// H [M][A][D] or null
+int launch_carried_factor(const RobotDev& h, const RobotDev* R, const SdfDev& s, int link, int A, const double* radius,
+                          const double* centers, double eps, int M, const double* conf, double* err, double* H,
+                          hipStream_t st);
+// arguments of k_carried_finish.  The records of k_carried_clearance are ScoreRecs by the tiling of k_score
+// (score_blocks): s is the carried sphere, oor the number of out-of-range (state, sphere)s.  `sel` carries the selection
+// (sel.select) and the shape of the trajectories; the rule reads the per-row scores the existing stages left, as
+// MovingFinish does (obs_oor: the obstacle stage's out-of-range count).
+struct CarriedFinish {
+  ScoreFinish sel;
+  const ScoreRec* recs;   // [B][nblk]
+  int nblk;
+  double *support, *dense, *min_clearance;
+  int *worst, *oor;       // [B][2], [B]
+  const double *clearance, *self_clearance;
+  const int *obs_oor, *self_invalid;
+  double required_self_clearance, required_carried_clearance;
+};
+int launch_carried_clearance(const RobotDev& h, const RobotDev* R, const SdfDev& s, int link, int A, const double* radius,
+                             const double* centers, double dt, int inter, int B, int N, const double* traj,
+                             ScoreRec* recs, hipStream_t st);
+int launch_carried_finish(const CarriedFinish& a, hipStream_t st);
+
 // path_kernels.hip (include/gpmp2mi.h "workspace path"; the in-plan factor's launcher is in plan.h)
 // the factor on M evaluations, one target per evaluation: conf [M][D], des [M][16] -> err [M][rows], H [M][rows][D] or
 // null (rows = 6 for the POSE mode, else 3)

@@ -94,6 +94,12 @@ struct PlanExtras {
   // (selfpair_kernels.hip)
   int sp_cap, sp_P, sp_first, sp_last;
   SelfPairRec* sp_rec;   // [sp_cap], the first sp_P rows in use
+  // carried object (include/gpmp2mi.h "carried object"): the capacity, the range, the factor's constants and the resident
+  // set.  cr_A and cr_link are host values that every launch takes as arguments (carried_kernels.hip)
+  int cr_cap, cr_A, cr_link, cr_first, cr_last;
+  double cr_eps, cr_w;   // epsilon, 1 / sigma^2
+  double* cr_radius;     // [cr_cap]
+  double* cr_centers;    // [cr_cap][3] in the frame of link cr_link, the first cr_A spheres in use
 };
 
 // Per-plan device buffers.
@@ -220,6 +226,11 @@ int launch_selfpair_accumulate(const PlanParams& hp, const PlanBuffers& pb, cons
 // states in `traj` straight into the unary records
 int launch_path_accumulate(const RobotDev& h, const RobotDev* R, const PlanParams& hp, const PlanBuffers& pb,
                            const PlanExtras& ex, const double* traj, int bufsel, const int* active, hipStream_t st);
+// carried_kernels.hip: the carried-object factor of the states ex.cr_first..cr_last, from the states in `traj`, the field
+// and the resident set (ex.cr_A > 0), straight into the unary records
+int launch_carried_accumulate(const RobotDev& h, const RobotDev* R, const SdfDev& s, const PlanParams& hp,
+                              const PlanBuffers& pb, const PlanExtras& ex, const double* traj, int bufsel,
+                              const int* active, hipStream_t st);
 int launch_set_mode(const PlanBuffers& pb, int opt_type, int fixed_iters, hipStream_t st);
 int launch_error_parts(const PlanParams& hp, const PlanBuffers& pb, const double* traj, int bufsel, const int* active,
                        hipStream_t st);

@@ -1,5 +1,5 @@
 // record_entries.h -- the packed unary record G | g | e of a support state as a sum of row products, for the factors that
-// add rows [h | r] (weight w) straight into it: k_moving_accumulate, k_selfpair_accumulate, k_path_accumulate.
+// add rows [h | r] (weight w) straight into it: k_moving_accumulate, k_selfpair_accumulate, k_path_accumulate, k_carried_accumulate.
 //
 // The map from an entry to its two row positions is a pure function: no buffer, no thread index, and a plain host
 // compiler builds the same text for the CPU tests (tests/cpp/record_entries_shim.cpp), which run every D up to MAXD.

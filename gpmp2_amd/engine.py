@@ -58,6 +58,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_retime(lib)
     _capi.declare_torque(lib)
     _capi.declare_moving(lib)
+    _capi.declare_carried(lib)
     _capi.declare_selfpair(lib)
     _capi.declare_path(lib)
     _capi.declare_map(lib)
@@ -207,6 +208,17 @@ class Engine(FieldCalls, TrajChecks):
         err, H = np.zeros((M, S, K)), (np.zeros((M, S, K, robot.dof)) if jac else None)
         self._ck(self.lib.gpmp2mi_moving_sphere_factor(robot.ptr, K, dptr(r), float(epsilon), M, dptr(q), dptr(c),
                                                        dptr(err), dptr(H)))
+        return err, H
+
+    def carried_sphere_factor(self, robot, sdf, link, radius, centers, epsilon, conf, jac=True):
+        """The carried-object hinge (include/gpmp2mi.h "carried object"): radius [A], centers [A][3] in the frame of
+        `link`, conf [M][D] -> err [M][A], H [M][A][D]"""
+        q = f64(conf).reshape(-1, robot.dof)
+        M = q.shape[0]
+        A, r, c = scoring.carried_set(radius, centers)
+        err, H = np.zeros((M, A)), (np.zeros((M, A, robot.dof)) if jac else None)
+        self._ck(self.lib.gpmp2mi_carried_sphere_factor(robot.ptr, sdf.ptr, int(link), A, dptr(r), dptr(c),
+                                                        float(epsilon), M, dptr(q), dptr(err), dptr(H)))
         return err, H
 
     def vehicle_dynamics_factor(self, lie, conf, vel):

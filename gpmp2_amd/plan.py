@@ -476,6 +476,59 @@ class Plan:
         lead.append(float(required_moving_clearance))
         selection_dev(self, "gpmp2mi_plan_select_moving_dev", inter_step, lead, locals())
 
+    # ---- spheres rigidly attached to one link (include/gpmp2mi.h "carried object")
+    def set_carried(self, link, radius, centers):
+        """The plan's carried set: radius [A], centers [A][3] in the frame of `link`; None / empty clears it.  May be
+        repeated between solves; the plan must have been created with room for A
+        (TrajOptimizerSetting.set_carried_spheres)."""
+        A, r, c = scoring.carried_set(radius, centers)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_carried(self.h.ptr, int(link), A, dptr(r), dptr(c)))
+
+    def set_carried_dev(self, link, A, radius, centers, stream=None):
+        """The same from device buffers (torch tensors or raw pointers); the copies are enqueued on `stream`."""
+        A = int(A)
+        args = [_dev_arg("radius", radius, (A,)), _dev_arg("centers", centers, (A, 3))]
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_set_carried_dev(self.h.ptr, int(link), A, *args, C.c_void_p(stream or 0)))
+
+    def carried_count(self):
+        """spheres of the set resident in the plan"""
+        return int(self.eng.lib.gpmp2mi_plan_carried_count(self.h.ptr))
+
+    def carried_score(self, inter_step, out=None):
+        """dict(carried_support_cost, carried_dense_cost, min_carried_clearance, worst [B][2], out_of_range) of the
+        plan's result with its resident carried set against the plan's field, B rows."""
+        inter_step = _score_args(inter_step)
+        o = stages.outputs(stages.CARRIED, self.B, out=out)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_carried_score(self.h.ptr, inter_step, *out_ptrs(stages.CARRIED, o)))
+        return o
+
+    def carried_score_dev(self, inter_step, carried_support_cost=None, carried_dense_cost=None,
+                          min_carried_clearance=None, worst=None, out_of_range=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        args = dev_args(stages.CARRIED, self.B, None, None, locals())
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_carried_score_dev(self.h.ptr, _score_args(inter_step), *args,
+                                                                 C.c_void_p(stream or 0)))
+
+    def select_carried(self, inter_step, required_carried_clearance=0.0, required_clearance=0.0, require_in_range=False,
+                       pairs=None, required_self_clearance=0.0):
+        """select() (select_checked() when `pairs` is given) with the rule that also asks for
+        required_carried_clearance of the plan's carried set and, with require_in_range, for no carried sphere out of
+        the field: dict(best, n_eligible, traj_best, dense_best); best = -1: the two trajectories are None."""
+        inter_step = _score_args(inter_step)
+        lead = threshold_args(required_clearance, require_in_range, pairs, required_self_clearance)
+        lead.append(float(required_carried_clearance))
+        return selection_host(self, "gpmp2mi_plan_select_carried", inter_step, lead)
+
+    def select_carried_dev(self, inter_step, required_carried_clearance=0.0, required_clearance=0.0,
+                           require_in_range=False, pairs=None, required_self_clearance=0.0, best=None, n_eligible=None,
+                           traj_best=None, dense_best=None, stream=None):
+        """The same with device outputs, as select_dev.  One enqueue on `stream`, no host synchronisation once the
+        plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        lead = threshold_args(required_clearance, require_in_range, pairs, required_self_clearance)
+        lead.append(float(required_carried_clearance))
+        selection_dev(self, "gpmp2mi_plan_select_carried_dev", inter_step, lead, locals())
+
     # ---- one target pose per support state (include/gpmp2mi.h "workspace path")
     def set_workspace_path(self, des, sigma=None):
         """The plan's path: des [N+1][4][4], sigma [N+1] (or a scalar; +inf: the state carries no factor); des None

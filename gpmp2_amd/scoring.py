@@ -311,6 +311,37 @@ def moving_set(radius, centers, states, capacity=MAX_MOVING_SPHERES):
     return K, r, c
 
 
+# ---- carried object (include/gpmp2mi.h "carried object"): the output names, the extended rule, the sphere set
+CARRIED_NAMES = stages.names(stages.CARRIED)
+MAX_CARRIED_SPHERES = 256   # GPMP2MI_MAX_CARRIED_SPHERES
+
+
+def carried_rule(final_error, status, min_clearance, out_of_range, required_clearance=0.0, require_in_range=False,
+                 min_self_clearance=None, invalid=None, required_self_clearance=0.0, min_carried_clearance=None,
+                 carried_out_of_range=None, required_carried_clearance=-np.inf):
+    """(best, n_eligible) by the rule of select_rule with two more conditions: no carried sphere out of range when
+    require_in_range, and min_carried_clearance >= required_carried_clearance (each None: not asked)."""
+    ok = eligible(final_error, status, min_clearance, out_of_range, required_clearance, require_in_range,
+                  min_self_clearance, invalid, required_self_clearance)
+    if require_in_range:
+        _none_set(ok, carried_out_of_range)
+    _at_least(ok, min_carried_clearance, required_carried_clearance)
+    return pick(final_error, ok)
+
+
+def carried_set(radius, centers, capacity=MAX_CARRIED_SPHERES):
+    """A carried set as contiguous float64 (radius [A], centers [A][3]); None / empty: A = 0.  ValueError for another
+    shape or more than `capacity` spheres."""
+    r = np.zeros(0) if radius is None else np.ascontiguousarray(radius, dtype=np.float64).reshape(-1)
+    A = r.size
+    c = np.zeros((0, 3)) if centers is None or A == 0 else np.ascontiguousarray(centers, dtype=np.float64)
+    if c.shape != (A, 3):
+        raise ValueError(f"centers: expected [{A}][3], got {list(c.shape)}")
+    if A > capacity:
+        raise ValueError(f"{A} carried spheres, room for {capacity}")
+    return A, r, c
+
+
 # ---- workspace path (include/gpmp2mi.h "workspace path"): the output names, the extended rule, a straight-line path
 PATH_NAMES = stages.names(stages.PATH)
 

@@ -54,6 +54,7 @@ class TrajOptimizerSetting:
         self.self_collision_states = None    # (first, last) support states, default all
         self.moving_spheres = None           # dict(capacity, epsilon, sigma, states): set_moving_spheres
         self.workspace_path = None           # dict(mode, link): set_workspace_path
+        self.carried_spheres = None          # dict(capacity, epsilon, sigma, states): set_carried_spheres
         self.self_pairs = None               # dict(capacity, states): set_self_pairs
 
     def set_self_pairs(self, capacity, states=None):
@@ -69,6 +70,13 @@ class TrajOptimizerSetting:
         Plan.set_moving_spheres.  capacity 0: none."""
         self.moving_spheres = dict(capacity=int(capacity), epsilon=float(epsilon), sigma=float(sigma),
                                    states=None if states is None else (int(states[0]), int(states[1])))
+
+    def set_carried_spheres(self, capacity, epsilon, sigma, states=None):
+        """Room for `capacity` carried spheres in the plan (include/gpmp2mi.h "carried object") and the constants of
+        their factor on the support states `states` = (first, last), default all; the spheres themselves and their link
+        are data of Plan.set_carried.  capacity 0: none."""
+        self.carried_spheres = dict(capacity=int(capacity), epsilon=float(epsilon), sigma=float(sigma),
+                                    states=None if states is None else (int(states[0]), int(states[1])))
 
     def set_workspace_path(self, mode, link):
         """Room for a workspace path in the plan (include/gpmp2mi.h "workspace path"): one target pose and one sigma

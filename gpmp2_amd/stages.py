@@ -1,5 +1,5 @@
-"""The check stages of include/gpmp2mi.h (scoring, self-collision check, moving obstacles, workspace path, motion limits,
-torque limits, re-timing) as one table: each stage's word in error messages and its per-row outputs in C argument
+"""The check stages of include/gpmp2mi.h (scoring, self-collision check, moving obstacles, carried object, workspace path,
+motion limits, torque limits, re-timing) as one table: each stage's word in error messages and its per-row outputs in C argument
 order.  The *_NAMES tuples of scoring.py, the validation of caller-supplied outputs, the pointer tuple of a host call
 and the argument list of a `_dev` call (marshalling.py) all follow from it."""
 from __future__ import annotations
@@ -33,6 +33,9 @@ SELF = _stage("score", ("self_support_cost", _F, _row), ("self_dense_cost", _F, 
               ("worst", _I, _tail(2)), ("invalid", _I, _row))
 MOVING = _stage("score", ("moving_support_cost", _F, _row), ("moving_dense_cost", _F, _row),
                 ("min_moving_clearance", _F, _row), ("worst", _I, _tail(3)), ("invalid", _I, _row))
+# not in STAGES: a stage of the same face as SCORE, against the carried set
+CARRIED = _stage("score", ("carried_support_cost", _F, _row), ("carried_dense_cost", _F, _row),
+                 ("min_carried_clearance", _F, _row), ("worst", _I, _tail(2)), ("out_of_range", _I, _row))
 PATH = _stage("path", ("max_pos_dev", _F, _row), ("max_rot_dev", _F, _row), ("worst", _I, _tail(2)),
               ("support_cost", _F, _row), ("dense_cost", _F, _row), ("invalid", _I, _row))
 MOTION = _stage("motion", ("pos_margin", _F, _row), ("vel_ratio", _F, _row), ("acc_ratio", _F, _row),

@@ -192,6 +192,7 @@ void gpmp2mi_settings_default(gpmp2mi_settings* s, int dof);
 #define GPMP2MI_MAX_WORKSPACE_FACTORS 4
 #define GPMP2MI_MAX_SELF_COLLISION_PAIRS 16
 #define GPMP2MI_MAX_MOVING_SPHERES 64
+#define GPMP2MI_MAX_CARRIED_SPHERES 256
 /* all pairs of the largest sphere model: the largest table a plan takes ("self-collision table in a plan" below) */
 #define GPMP2MI_MAX_PLAN_SELF_PAIRS (GPMP2MI_MAX_SPHERES * (GPMP2MI_MAX_SPHERES - 1) / 2)
 /* A workspace factor carried by a plan: GaussianPriorWorkspace{Position,Orientation,Pose}<Arm>
@@ -232,6 +233,12 @@ typedef struct gpmp2mi_graph_opts {
                                     self_collision_first..last; <= GPMP2MI_MAX_SELF_COLLISION_PAIRS rows */
   int self_collision_first, self_collision_last;
   double self_collision[GPMP2MI_MAX_SELF_COLLISION_PAIRS][4];  /* sphere A, sphere B, epsilon, sigma */
+  /* ---- carried object ("carried object" below): the capacity and the factor's constants; the spheres themselves and
+   * their link are data of gpmp2mi_plan_set_carried.  All default to 0 = none; without capacity the other four fields
+   * are not read.  (They stand ahead of the workspace-path block; fill the struct by field name.) */
+  int max_carried_spheres;       /* capacity reserved at plan creation, <= GPMP2MI_MAX_CARRIED_SPHERES; 0: none */
+  int carried_first, carried_last;   /* inclusive range of support states that carry the factor */
+  double carried_epsilon, carried_sigma;
   /* ---- workspace path ("workspace path" below): room for one target pose and one sigma per support state; the path
    * itself is data of gpmp2mi_plan_set_workspace_path.  All default to 0 = none.  (They stand ahead of the moving-sphere
    * block, which stays the struct's tail; fill the struct by field name.) */
@@ -980,6 +987,100 @@ int gpmp2mi_plan_select_moving_dev(gpmp2mi_plan* p, int inter_step, double requi
                                    const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
                                    double required_moving_clearance, int* best, int* n_eligible, double* traj_best,
                                    double* dense_best, void* stream);
+
+/* ---- carried object: spheres rigidly attached to one link as a plan factor and a check, on the device --------------
+ * The robot's collision geometry is the sphere table of the robot handle, fixed when the handle is made.  What the robot
+ * holds after a grasp is a set of A spheres rigidly attached to one link: radius [A], centers [A][3] in the frame of
+ * link `link`.  One set per plan, shared by its B trajectories; it is replaced or cleared between solves without
+ * touching the plan (grasp, release, regrasp on another link).  A plan created with
+ * gpmp2mi_graph_opts::max_carried_spheres > 0 reserves room for that many spheres (all device memory is taken at
+ * gpmp2mi_plan_create), carries the factor below on the support states carried_first..carried_last, and takes its data
+ * from gpmp2mi_plan_set_carried.  The spheres are extra body spheres of ObstacleSDFFactor<ROBOT>
+ * (gpmp2/obstacle/ObstacleSDFFactor-inl.h:18-56, kinematics/RobotModel-inl.h:12-40) with their own epsilon and sigma.
+ *
+ * Definitions, for carried sphere a (radius r_a, centre o_a in the frame of link l) and configuration q:
+ *  - Centre: c_a(q) = T_l(q) o_a, T_l the frame gpmp2mi_forward_kinematics returns for link l.  In a planar field the
+ *    first two coordinates are used, as for body spheres.
+ *  - Derivative: d c_a / d q_k = R_l (v_k + omega_k x o_a), [omega_k; v_k] column k of the link's body Jacobian as
+ *    gpmp2mi_forward_kinematics returns it (the Pose2 chart for the mobile kinds).
+ *  - The factor, at support state i in [carried_first, carried_last]: d and grad d are the field's value and gradient
+ *    at c_a.  If c_a is inside the field and !(d > r_a + carried_epsilon): err = (r_a + carried_epsilon) - d and the
+ *    Jacobian row is -grad d^T d c_a / d q; otherwise err = 0 with a zero row (what obstacle/ObstacleCost.h:31-38 does
+ *    for a query out of range).  Noise: isotropic carried_sigma.  The terms go to the configuration block of the
+ *    state's unary record only.  In a plan the A rows of a state are never stored: one kernel adds sum w h h^T,
+ *    sum w h r and sum w r^2 (w = 1 / sigma^2) to the record, in sphere order, so a state's contribution is the same
+ *    bits alone, in any batch and on any run.  Every call that linearizes a plan carries the factor: optimize, the
+ *    queue runs, plan_update, plan_linearize, plan_graph_error; Gauss-Newton, LM and Dogleg; narrow, wide and dense
+ *    blocks.  With A == 0 nothing is launched for it.
+ *  - Range test before any lookup: inside means x >= origin && x <= upper on every axis of the field, written as that
+ *    conjunction, so a NaN centre fails it, counts as out of range and is never turned into a cell index.  The _dev
+ *    setters take unvalidated device data; this test is what keeps a bad centre from becoming a wild read.
+ *  - The check: the checked states of "scoring" (Md = N (J+1) + 1), with epsilon 0 as there.
+ *    carried_support_cost [B] / carried_dense_cost [B]: the sums of max(0, r_a - d) over the support / all checked
+ *    states.  min_carried_clearance [B]: the minimum of d - r_a over the in-range (state, sphere), +inf if there is none
+ *    (or A = 0).  worst [B][2]: the (checked state, carried sphere) attaining it; on exact ties the lowest state, then
+ *    the lowest sphere; (-1, -1) if none.  out_of_range [B].  Any output may be NULL.
+ *  - Determinism as in "moving obstacles": an inactive sphere adds an exact zero; active rows are added in ascending
+ *    sphere order into one accumulator per record entry, without atomics; a row's check outputs are a function of the
+ *    row, the handles, the set, delta_t and inter_step alone.
+ *  - Selection: the rule of gpmp2mi_plan_select (of gpmp2mi_plan_select_checked when pairs != NULL) with two more
+ *    conditions,
+ *      eligible(b) = <that rule> && (!require_in_range || carried_out_of_range[b] == 0)
+ *                    && min_carried_clearance[b] >= required_carried_clearance;
+ *    ranking and ties unchanged.  With A == 0 and required_carried_clearance = -inf it answers what the existing call
+ *    does.
+ * Errors: GPMP2MI_ERR_INVALID (checked before any device work) for a NULL plan or handle, a link outside 0..L-1, A < 0,
+ * A above the capacity (the plan forms) or above GPMP2MI_MAX_CARRIED_SPHERES (the others), NULL arrays with A > 0, a
+ * radius that is NaN or negative and a non-finite centre (host forms), carried_sigma <= 0 or a non-finite epsilon when
+ * there is capacity, a bad state range, the argument errors of "scoring"; the plan forms of the check also for a plan
+ * created without capacity, and with the preconditions of gpmp2mi_plan_score.  GPMP2MI_ERR_TIMEOUT for a poisoned plan.
+ * A refused call writes nothing and leaves the resident set in place.
+ * Memory: the workspace rules of "scoring"; the records (one 40-byte record per tile of 64 checked states) are kept
+ * with the plan, and by gpmp2mi_carried_score_traj_dev with the robot handle.
+ * Not here: the factor at GP-interpolated sub-states (the dense check is what looks between support states, as for the
+ * self-collision table); carried spheres against the robot's own spheres, the moving spheres, the posterior-risk and
+ * collision-probability calls and the live map's self-filter; more than one link per set, per-trajectory sets;
+ * gpmp2mi_multi_plan_* setters (shards pass the capacity through and hold an empty set); C++ facade classes. */
+
+/* The plan's carried set.  Valid at any time between solves; A = 0 clears the set; a fresh plan holds A = 0.  Host form:
+ * the data is copied before the call returns.  _dev: device pointers, the copies are enqueued on `stream`, the values
+ * are not inspected.  A set call is two copies and two host values (link, A).  A refused call changes nothing. */
+int gpmp2mi_plan_set_carried(gpmp2mi_plan* p, int link, int A, const double* radius /*[A]*/,
+                             const double* centers /*[A][3]*/);
+int gpmp2mi_plan_set_carried_dev(gpmp2mi_plan* p, int link, int A, const double* radius, const double* centers,
+                                 void* stream);
+/* the size of the resident set; -1 for a NULL plan */
+int gpmp2mi_plan_carried_count(const gpmp2mi_plan* p);
+/* The factor, batched over M evaluations: conf [M][D] -> err [M][A] (unwhitened), H [M][A][D] (NULL ok). */
+int gpmp2mi_carried_sphere_factor(const gpmp2mi_robot* r, const gpmp2mi_sdf* sdf, int link, int A, const double* radius,
+                                  const double* centers, double epsilon, int M, const double* conf, double* err,
+                                  double* H);
+/* The check for caller buffers; traj [B][total_step+1][2D].  The device of the robot handle must be current. */
+int gpmp2mi_carried_score_traj(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, int link, int A, const double* radius,
+                               const double* centers, double delta_t, int inter_step, int B, int total_step,
+                               const double* traj, double* carried_support_cost, double* carried_dense_cost,
+                               double* min_carried_clearance, int* worst, int* out_of_range);
+int gpmp2mi_carried_score_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_sdf* sdf, int link, int A,
+                                   const double* radius, const double* centers, double delta_t, int inter_step, int B,
+                                   int total_step, const double* traj, double* carried_support_cost,
+                                   double* carried_dense_cost, double* min_carried_clearance, int* worst,
+                                   int* out_of_range, void* stream);
+/* The plan's resident result against the plan's resident set, with its field and delta_t. */
+int gpmp2mi_plan_carried_score(gpmp2mi_plan* p, int inter_step, double* carried_support_cost, double* carried_dense_cost,
+                               double* min_carried_clearance, int* worst, int* out_of_range);
+int gpmp2mi_plan_carried_score_dev(gpmp2mi_plan* p, int inter_step, double* carried_support_cost,
+                                   double* carried_dense_cost, double* min_carried_clearance, int* worst,
+                                   int* out_of_range, void* stream);
+/* One enqueue: the existing score stages, the carried scores, then one finish that reads them all.  Outputs as
+ * gpmp2mi_plan_select. */
+int gpmp2mi_plan_select_carried(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                double required_carried_clearance, int* best, int* n_eligible, double* traj_best,
+                                double* dense_best);
+int gpmp2mi_plan_select_carried_dev(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                    const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                    double required_carried_clearance, int* best, int* n_eligible, double* traj_best,
+                                    double* dense_best, void* stream);
 
 /* ---- self-collision table in a plan: a pair table of any size as a plan factor, on the device ----------------------
  * The self-collision rows of gpmp2mi_graph_opts hold at most GPMP2MI_MAX_SELF_COLLISION_PAIRS pairs, while the check of
