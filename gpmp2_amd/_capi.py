@@ -254,6 +254,26 @@ def declare_torque(lib):
     lib.gpmp2mi_dynamics_destroy.restype = None
 
 
+def declare_retime_dynamic(lib):
+    """argtypes of the entry points of include/gpmp2mi.h "re-timing under torque limits"; `limits`, `acc` and `bound` are
+    host data in every form, the `_dev` forms take device addresses for everything else."""
+    vp, i, d, ip, f = C.c_void_p, C.c_int, c_double_p, c_int_p, C.c_double
+    lp = C.POINTER(MotionLimitsC)
+    decl = {
+        "gpmp2mi_retime_path_affine": [i, i, i, d, d, d, d, d, i, d, d, d, d, d, f, f, f, f, d, d, d, d, ip, d],
+        "gpmp2mi_retime_path_affine_dev": [i, i, i, vp, vp, vp, vp, d, i, vp, vp, vp, vp, d, f, f, f, f] + [vp] * 8,
+        "gpmp2mi_retime_dynamic_traj": [vp, vp, lp, f, i, i, i, d, f, f, f, d, d, d, d, ip, d, d, d, d],
+        "gpmp2mi_retime_dynamic_traj_dev": [vp, vp, lp, f, i, i, i, vp, f, f, f] + [vp] * 10,
+        "gpmp2mi_plan_retime_dynamic": [vp, vp, lp, i, f, f, f, d, d, d, d, ip, d, d, d, d],
+        "gpmp2mi_plan_retime_dynamic_dev": [vp, vp, lp, i, f, f, f] + [vp] * 10,
+        "gpmp2mi_plan_select_retimed_dynamic": [vp, i, f, i, vp, f, lp, f, f, f, f, f, vp, ip, ip, d, d, d, d, d],
+        "gpmp2mi_plan_select_retimed_dynamic_dev": [vp, i, f, i, vp, f, lp, f, f, f, f, f, vp] + [vp] * 8,
+    }
+    for name, args in decl.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = i
+
+
 def declare_moving(lib):
     """argtypes of the moving-obstacle entry points (include/gpmp2mi.h "moving obstacles"); the `_dev` forms take device
     addresses."""

@@ -132,6 +132,45 @@ class TrajChecks:
                                               *out_ptrs(stages.RETIME, o)))
         return o
 
+    # ---------------------------------------------------------------- re-timing under torque limits (include/gpmp2mi.h)
+    def retime_path_affine(self, qd, qdd_left, qdd_right, cap, acc, cx_left, cx_right, cu, off, bound, h, max_rate=1.0,
+                           rate_start=None, rate_end=None, out=None):
+        """retime_path() with R affine rows |cx x + cu u + off| <= bound per state next to its own: cx_left, cx_right, cu,
+        off [B][Md][R] (or one [Md][R]), bound [R] (inf: none; None or empty: R = 0) -> dict(sdot, u, stamps [B][Md],
+        duration [B], status [B], achieved [B][6])."""
+        q = np.ascontiguousarray(qd, dtype=np.float64)
+        q = q[None] if q.ndim == 2 else q
+        if q.ndim != 3 or q.shape[1] < 2:
+            raise ValueError(f"qd: expected [B][Md][D] with Md >= 2, got {list(np.shape(qd))}")
+        B, Md, D = q.shape
+        ql, qr = (np.ascontiguousarray(x, dtype=np.float64).reshape(q.shape) for x in (qdd_left, qdd_right))
+        c = np.ascontiguousarray(cap, dtype=np.float64).reshape(B, Md)
+        a = None if acc is None else scoring.motion_limits(D, acc=acc)[3]
+        R, cxl, cxr, ccu, cof, b = scoring.affine_rows(B, Md, cx_left, cx_right, cu, off, bound)
+        if not (np.isfinite(float(h)) and float(h) > 0):
+            raise ValueError("h must be finite and > 0")
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        o = scoring.retime_affine_outputs(B, Md, out)
+        rows = [dptr(x) if R else None for x in (cxl, cxr, ccu, cof, b)]
+        self._ck(self.lib.gpmp2mi_retime_path_affine(B, Md, D, dptr(q), dptr(ql), dptr(qr), dptr(c), dptr(a), R, *rows,
+                                                     float(h), *rates, *out_ptrs(stages.RETIME_AFFINE, o)))
+        return o
+
+    def retime_dynamic_traj(self, robot, dynamics, limits, delta_t, inter_step, traj, max_rate=1.0, rate_start=None,
+                            rate_end=None, out=None, tau=True, coef=True):
+        """traj [B][N+1][2D] (or one [N+1][2D]) -> dict(sdot, u, stamps [B][Md], duration [B], status [B], achieved
+        [B][6], dense_retimed [B][Md][2D], tau_retimed [B][Md][D], coef [B][Md][4][D]): the fastest speed profile along
+        the unchanged path under the torque limits of `dynamics` (a Dynamics) and the rate limits of `limits` (a
+        MotionLimits; None: max_rate alone), with the torques the re-timed row asks for and the coefficients p, m_left,
+        m_right, tau_g of tau = p u + m x + tau_g.  tau / coef = False: not fetched (None)."""
+        t, inter_step, delta_t, B, N = traj_args(traj, robot.dof, delta_t, inter_step)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        o = scoring.retime_dynamic_outputs(B, scoring.checked_states(N, inter_step), robot.dof, out, tau, coef)
+        lim = _limits_arg(limits, robot.dof)
+        self._ck(self.lib.gpmp2mi_retime_dynamic_traj(robot.ptr, dynamics.ptr, lim, delta_t, inter_step, B, N, dptr(t),
+                                                      *rates, *out_ptrs(stages.RETIME_DYNAMIC, o)))
+        return o
+
     # ---------------------------------------------------------------- moving obstacles (include/gpmp2mi.h)
     def moving_score_traj(self, robot, radius, centers, epsilon, delta_t, inter_step, traj, out=None):
         """traj [B][N+1][2D] (or one [N+1][2D]) against the spheres radius [K], centers [K][N+1][3] -> dict(

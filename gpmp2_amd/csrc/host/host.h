@@ -214,6 +214,9 @@ struct gpmp2mi_dynamics {
   // gpmp2mi_robot::score_ws: mu guards the pointer, the calls themselves must be in stream order
   mutable std::mutex mu;
   mutable g2::Workspace ws;
+  // the workspace of gpmp2mi_retime_dynamic_traj(_dev) calls with this handle (retime_dynamic.hip), under the same guard
+  // and rule
+  mutable g2::Workspace retime_ws;
   ~gpmp2mi_dynamics() {
     if (d) (void)hipFree(d);
   }
@@ -400,8 +403,9 @@ struct gpmp2mi_plan {
   //   MOTION, MOVING, PATH, CARRIED   CheckWs with the stage's records and the per-row scores of the earlier stages its rule reads
   //   RETIME   ps, the caps and the sets of k_retime, the profile, the scores of the earlier stages, the staging
   //   TORQUE   the records of k_torque, the scores of the earlier stages, the staging with the torques, the pick
+  //   RETIME_DYN   what RETIME keeps, the coefficients, the stage rows of k_retime_rows and the torques of every row
   enum Ws { WS_QUEUE, WS_SCORE, WS_POST, WS_SEED, WS_RISK, WS_SAMPLED, WS_SELF, WS_GROUP, WS_MOTION, WS_MOVING, WS_PATH,
-            WS_RETIME, WS_TORQUE, WS_CARRIED, WS_COUNT };
+            WS_RETIME, WS_TORQUE, WS_CARRIED, WS_RETIME_DYN, WS_COUNT };
   g2::Workspace ws[WS_COUNT];
   // seeding (seed.hip): H_seed of the plan's linear prior graph on the host (built at the first seeded call or read-out)
   std::vector<double> seed_Hd, seed_Ho;
@@ -570,6 +574,16 @@ int records_ready(const gpmp2mi_robot* r, const gpmp2mi_self_pairs* t, Workspace
 // itself and its scalar), and its arrays [dof] as the kernels read them (+-inf where there is no limit)
 int check_limits_head(const gpmp2mi_motion_limits* l);
 int read_limits(const gpmp2mi_motion_limits* l, int dof, MotionLimitsDev* out);
+// retime.hip and torque.hip, shared with retime_dynamic.hip: the rules of the three rates and of the arrays of
+// gpmp2mi_retime_path (acc [D] or null -> acc_out [GPMP2MI_MAX_DOF], +inf: none), and the binding of a dynamics handle to
+// the robot it was made for
+struct RetimeRates {
+  double max_rate, rate_start, rate_end;
+};
+int check_retime_rates(const RetimeRates& r);
+int check_retime_path_call(int B, int Md, int dof, const double* qd, const double* ql, const double* qr, const double* cap,
+                           const double* acc, double h, const RetimeRates& rt, double* acc_out);
+int check_dynamics_binding(const gpmp2mi_robot* r, const gpmp2mi_dynamics* y);
 // B comparisons on the host: the rule of gpmp2mi_select_best
 void select_rule_host(int B, const double* ferr, const int* status, const double* clearance, const int* oor,
                       double required_clearance, int require_in_range, int* best, int* n_eligible);

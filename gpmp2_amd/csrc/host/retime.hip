@@ -180,6 +180,13 @@ RetimeSel make_sel(double required_clearance, int require_in_range, const gpmp2m
 
 }  // namespace
 
+// what retime_dynamic.hip shares (host.h)
+int g2::check_retime_rates(const RetimeRates& r) { return check_rates(Rates{r.max_rate, r.rate_start, r.rate_end}); }
+int g2::check_retime_path_call(int B, int Md, int dof, const double* qd, const double* ql, const double* qr,
+                               const double* cap, const double* acc, double h, const RetimeRates& rt, double* acc_out) {
+  return check_path_call(B, Md, dof, qd, ql, qr, cap, acc, h, Rates{rt.max_rate, rt.rate_start, rt.rate_end}, acc_out);
+}
+
 extern "C" {
 
 int gpmp2mi_retime_path_dev(int B, int Md, int dof, const double* qd, const double* qdd_left, const double* qdd_right,

@@ -272,6 +272,57 @@ inline TorqueWs carve_torque(char* base, size_t rec_bytes, RowOut* rows, const S
   return w;
 }
 
+// re-timing under torque limits: the outputs of re-timing (achieved is [B][6] here), the torques of the re-timed row
+// [B][Md][D] and the coefficients [B][Md][4][D].  The last two have room whoever asks: the chain reads the coefficients,
+// and a selection copies the chosen row's torques.
+struct RetimeDynOut : RetimeOut {
+  double *tau = nullptr, *coef = nullptr;
+};
+constexpr int RETIME_DYN_ROWS = 9;
+inline void rows_of(const RetimeDynOut& o, size_t Md, size_t D, RowOut* r) {
+  rows_of(static_cast<const RetimeOut&>(o), Md, D, r);
+  r[4] = row(o.achieved, 6);
+  r[7] = row(o.tau, Md * D), r[8] = row(o.coef, Md * 4 * D);
+}
+inline RetimeDynOut retime_dyn_out(const RowOut* r, bool host) {
+  RetimeDynOut o;
+  static_cast<RetimeOut&>(o) = retime_out(r, host);
+  o.tau = target<double>(r[7], host), o.coef = target<double>(r[8], host);
+  return o;
+}
+// what k_retime needs, the rows of k_retime_rows ([B][Md][4 D][4]: 2 D acceleration and 2 D torque rows per stage) and a
+// flag per row (a coefficient is not finite); a caller's trajectory call carves this alone
+struct RetimeDynCore {
+  RetimeCore core;
+  double* stage_rows;
+  int* nonfinite;
+};
+inline RetimeDynCore carve_retime_dyn_core(Carver& c, RowOut* rows, size_t B, size_t Md, size_t D) {
+  RetimeDynCore w;
+  w.core = carve_retime_core(c, rows, B, Md);
+  w.stage_rows = c.take<double>(B * Md * 4 * D * 4);
+  w.nonfinite = c.take<int>(B);
+  carve_rows(c, rows + 7, 2, B);
+  return w;
+}
+// the scores of all three earlier stages behind them, and the chosen row's stamps [Md] and torques [Md][D] behind the pick
+struct RetimeDynWs {
+  RetimeDynCore core;
+  PriorRows prior;
+  PickRows sel;
+  size_t bytes;
+};
+inline RetimeDynWs carve_retime_dyn(char* base, RowOut* rows, const Shape& s) {
+  RetimeDynWs w;
+  Carver c{base};
+  w.core = carve_retime_dyn_core(c, rows, s.B, s.Md, s.D);
+  carve_rows(c, rows + RETIME_CORE_ROWS, RETIME_ROWS - RETIME_CORE_ROWS, s.B);
+  w.prior = carve_priors(c, s.B, 3);
+  w.sel = carve_pick(c, s, true, s.Md * (1 + s.D) * sizeof(double));
+  w.bytes = c.off;
+  return w;
+}
+
 // distinct alternatives: the bit matrix of k_traj_pairs ([B][words] 64-bit words), the per-row scores the rule reads,
 // what the rule leaves, then the staging of the host form (`alt_cap` slots of indices, sizes and errors; max_alt slabs)
 struct GroupWs {

@@ -143,6 +143,9 @@ DynamicSel make_sel(double required_clearance, int require_in_range, const gpmp2
 
 }  // namespace
 
+// what retime_dynamic.hip shares (host.h)
+int g2::check_dynamics_binding(const gpmp2mi_robot* r, const gpmp2mi_dynamics* y) { return check_dynamics(r, y); }
+
 extern "C" {
 
 void gpmp2mi_dynamics_desc_default(gpmp2mi_dynamics_desc* d) {

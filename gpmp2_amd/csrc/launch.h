@@ -304,6 +304,35 @@ int launch_torque(const RobotDev& h, const RobotDev* R, const DynDev* dyn, const
                   int B, int N, const double* traj, TorqueRec* recs, double* tau, hipStream_t st);
 int launch_torque_finish(const TorqueFinish& a, hipStream_t st);
 
+// retime_dynamic_kernels.hip (include/gpmp2mi.h "re-timing under torque limits")
+constexpr int RETIME_DYN_MAX_ROWS = 8;   // affine rows per state and side: one per joint of k_torque's arms
+// coef [B][Md][4][D] = p, m_left, m_right, tau_g of every checked state: tau = p u + m x + tau_g along the path
+int launch_retime_coef(const RobotDev& h, const RobotDev* R, const DynDev* dyn, const TorqueLimitsDev& lim, double dt,
+                       int inter, int B, int N, const double* traj, double* coef, hipStream_t st);
+// arguments of k_retime_rows and k_retime_dynamic: those of k_retime, and R affine rows |cx x + cu u + off| <= bound per
+// state.  cxl / cxr / cu / off: element r of state k of row b at [(b Md + k) stride + r] (the caller's arrays: stride R;
+// the four blocks of coef: stride 4 D).  rows [B][Md][2 D + 2 R][4] is workspace; tau [B][Md][D] or null (trajectory
+// form: the affine rows are the torques).  achieved is [B][6].  nonfinite [B] or null: 1 where one of a row's
+// coefficients is not finite, whether its row has a bound or not.
+struct RetimeDynArgs {
+  RetimeArgs rt;
+  int R, stride;
+  double bound[RETIME_DYN_MAX_ROWS];
+  const double *cxl, *cxr, *cu, *off;
+  double *rows, *tau;
+  int* nonfinite;
+};
+int launch_retime_dynamic(const RetimeDynArgs& a, bool traj, hipStream_t st);
+// arguments of k_retime_dynamic_finish (one workgroup): RetimeFinish, and the coefficients' flag and the torques of
+// every re-timed row, the source of tau_best
+struct RetimeDynFinish {
+  RetimeFinish rt;
+  const int* nonfinite;   // [B]
+  const double* tau;      // [B][Md][D]
+  double* tau_best;
+};
+int launch_retime_dynamic_finish(const RetimeDynFinish& a, hipStream_t st);
+
 // moving_kernels.hip (include/gpmp2mi.h "moving obstacles"; the in-plan factor's launcher is in plan.h)
 // the factor on M evaluations: cen / Jc from launch_sphere_centers, robot_radius [S] in the caller's sphere order,
 // centers [M][K][3] -> err [M][S][K], H [M][S][K][D] or null

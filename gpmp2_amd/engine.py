@@ -57,6 +57,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     _capi.declare_motion(lib)
     _capi.declare_retime(lib)
     _capi.declare_torque(lib)
+    _capi.declare_retime_dynamic(lib)
     _capi.declare_moving(lib)
     _capi.declare_carried(lib)
     _capi.declare_selfpair(lib)

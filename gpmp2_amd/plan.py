@@ -26,8 +26,9 @@ def threshold_args(required_clearance, require_in_range, *self_check):
 def _selected(N, D, Md, scalar, row):
     """(name, shape, integer) of the outputs of a selection, in C argument order: best, n_eligible, the optional extra
     scalar and extra row ((name, shape per checked state)) of the chosen row, traj_best, dense_best."""
+    rows = [] if row is None else [row] if isinstance(row[0], str) else list(row)      # one extra row, or several
     return ([("best", (1,), True), ("n_eligible", (1,), True)] + ([] if scalar is None else [(scalar, (1,), False)])
-            + ([] if row is None else [(row[0], (Md,) + tuple(row[1]), False)])
+            + [(name, (Md,) + tuple(tail), False) for name, tail in rows]
             + [("traj_best", (N + 1, 2 * D), False), ("dense_best", (Md, 2 * D), False)])
 
 
@@ -416,6 +417,59 @@ class Plan:
         lead += [_limits_arg(limits, self.D), rpm, *rates, md]
         selection_dev(self, "gpmp2mi_plan_select_retimed_dev", inter_step, lead, locals(), "duration_best",
                       ("stamps_best", ()))
+
+    # ---- how fast can the drives run it (include/gpmp2mi.h "re-timing under torque limits")
+    def retime_dynamic(self, dynamics, limits, inter_step, max_rate=1.0, rate_start=None, rate_end=None, out=None,
+                       tau=True, coef=True):
+        """dict(sdot, u, stamps, duration, status, achieved [B][6], dense_retimed, tau_retimed, coef) of the plan's
+        result, B rows: retime() with the torque limits of `dynamics` in the profile."""
+        inter_step = _score_args(inter_step)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        o = scoring.retime_dynamic_outputs(self.B, scoring.checked_states(self.N, inter_step), self.D, out, tau, coef)
+        lim = _limits_arg(limits, self.D)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_retime_dynamic(self.h.ptr, dynamics.ptr, lim, inter_step, *rates,
+                                                              *out_ptrs(stages.RETIME_DYNAMIC, o)))
+        return o
+
+    def retime_dynamic_dev(self, dynamics, limits, inter_step, max_rate=1.0, rate_start=None, rate_end=None, sdot=None,
+                           u=None, stamps=None, duration=None, status=None, achieved=None, dense_retimed=None,
+                           tau_retimed=None, coef=None, stream=None):
+        """The same into device buffers (torch tensors or raw pointers, any may be None); no host synchronisation."""
+        inter_step = _score_args(inter_step)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        args = dev_args(stages.RETIME_DYNAMIC, self.B, scoring.checked_states(self.N, inter_step), self.D, locals())
+        lim = _limits_arg(limits, self.D)
+        self.eng._ck(self.eng.lib.gpmp2mi_plan_retime_dynamic_dev(self.h.ptr, dynamics.ptr, lim, inter_step, *rates, *args,
+                                                                  C.c_void_p(stream or 0)))
+
+    def select_retimed_dynamic(self, inter_step, limits, dynamics, required_pos_margin=0.0, max_duration=np.inf,
+                               max_rate=1.0, rate_start=None, rate_end=None, required_clearance=0.0,
+                               require_in_range=False, pairs=None, required_self_clearance=0.0):
+        """select_retimed() on the profile under the torque limits of `dynamics`, and no coefficient that is not finite:
+        dict(best, n_eligible, duration_best, stamps_best, tau_best, traj_best, dense_best); best = -1: the last five are
+        None.  tau_best [Md][D] are the torques the re-timed row asks for."""
+        inter_step = _score_args(inter_step)
+        rpm, md = scoring.retimed_thresholds(required_pos_margin, max_duration)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        lead = threshold_args(required_clearance, require_in_range, pairs, required_self_clearance)
+        lead += [_limits_arg(limits, self.D), rpm, *rates, md, dynamics.ptr]
+        return selection_host(self, "gpmp2mi_plan_select_retimed_dynamic", inter_step, lead, "duration_best",
+                              (("stamps_best", ()), ("tau_best", (self.D,))))
+
+    def select_retimed_dynamic_dev(self, inter_step, limits, dynamics, required_pos_margin=0.0, max_duration=np.inf,
+                                   max_rate=1.0, rate_start=None, rate_end=None, required_clearance=0.0,
+                                   require_in_range=False, pairs=None, required_self_clearance=0.0, best=None,
+                                   n_eligible=None, duration_best=None, stamps_best=None, tau_best=None, traj_best=None,
+                                   dense_best=None, stream=None):
+        """The same with device outputs, as select_retimed_dev, plus tau_best float64 [Md][D].  One enqueue on `stream`,
+        no host synchronisation once the plan's workspaces hold the shape."""
+        inter_step = _score_args(inter_step)
+        rpm, md = scoring.retimed_thresholds(required_pos_margin, max_duration)
+        rates = scoring.retime_rates(max_rate, rate_start, rate_end)
+        lead = threshold_args(required_clearance, require_in_range, pairs, required_self_clearance)
+        lead += [_limits_arg(limits, self.D), rpm, *rates, md, dynamics.ptr]
+        selection_dev(self, "gpmp2mi_plan_select_retimed_dynamic_dev", inter_step, lead, locals(), "duration_best",
+                      (("stamps_best", ()), ("tau_best", (self.D,))))
 
     # ---- a pair table of any size as a factor (include/gpmp2mi.h "self-collision table in a plan")
     def set_self_pairs(self, pairs):

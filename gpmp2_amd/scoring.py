@@ -281,6 +281,52 @@ def dynamic_rule(final_error, status, min_clearance, out_of_range, required_clea
     return pick(final_error, ok)
 
 
+# ---- re-timing under torque limits (include/gpmp2mi.h): the extra status, the outputs, the affine rows and the rule
+RETIME_STATIC = 4
+RETIME_DYNAMIC_NAMES = stages.names(stages.RETIME_DYNAMIC)
+RETIME_MAX_AFFINE = 8       # affine rows per state of gpmp2mi_retime_path_affine
+
+
+def retime_affine_outputs(B, Md, out=None):
+    """The per-row outputs of the path form: those of re-timing with achieved [B][6]."""
+    return stages.outputs(stages.RETIME_AFFINE, B, Md, None, out)
+
+
+def retime_dynamic_outputs(B, Md, D, out=None, tau=True, coef=True):
+    """The per-row outputs of a trajectory or plan call: fresh arrays, or the caller's (checked by stages.outputs).
+    tau / coef = False: no tau_retimed [B][Md][D] / coef [B][Md][4][D] unless the caller brings the array."""
+    absent = (() if tau else ("tau_retimed",)) + (() if coef else ("coef",))
+    return stages.outputs(stages.RETIME_DYNAMIC, B, Md, D, out, absent=absent)
+
+
+def affine_rows(B, Md, cx_left, cx_right, cu, off, bound):
+    """The R affine rows |cx x + cu u + off| <= bound of the path form as the C side takes them: (R, cx_left, cx_right,
+    cu, off contiguous float64 [B][Md][R], bound [R]); ValueError for R outside 0..8, a shape that does not fit or a bound
+    that is NaN or <= 0 (inf: none)."""
+    b = np.ascontiguousarray([] if bound is None else bound, dtype=np.float64).reshape(-1)
+    R = b.shape[0]
+    if R > RETIME_MAX_AFFINE:
+        raise ValueError(f"at most {RETIME_MAX_AFFINE} affine rows per state, got {R}")
+    if not (b > 0).all():          # False for NaN
+        raise ValueError("bound: every entry must be > 0 (inf: none)")
+    rows = []
+    for name, x in (("cx_left", cx_left), ("cx_right", cx_right), ("cu", cu), ("off", off)):
+        a = np.ascontiguousarray(np.zeros((B, Md, 0)) if x is None else x, dtype=np.float64)
+        if a.size != B * Md * R:
+            raise ValueError(f"{name}: expected [{B}][{Md}][{R}], got {list(a.shape)}")
+        rows.append(a.reshape(B, Md, R))
+    return (R, *rows, b)
+
+
+def retimed_dynamic_rule(*args, coef_finite=None, **kw):
+    """(best, n_eligible) by retimed_rule on the profile under torque limits, and no coefficient of the row that is not
+    finite (coef_finite: bool [B])."""
+    if coef_finite is None:
+        return retimed_rule(*args, **kw)
+    status = np.where(np.asarray(coef_finite, dtype=bool).reshape(-1), np.asarray(kw["retime_status"]).reshape(-1), -1)
+    return retimed_rule(*args, **dict(kw, retime_status=status))
+
+
 # ---- moving obstacles (include/gpmp2mi.h "moving obstacles"): the output names, the extended rule, the sphere set
 MOVING_NAMES = stages.names(stages.MOVING)
 MAX_MOVING_SPHERES = 64     # GPMP2MI_MAX_MOVING_SPHERES

@@ -1,5 +1,5 @@
 """The check stages of include/gpmp2mi.h (scoring, self-collision check, moving obstacles, carried object, workspace path,
-motion limits, torque limits, re-timing) as one table: each stage's word in error messages and its per-row outputs in C argument
+motion limits, torque limits, re-timing, re-timing under torque limits) as one table: each stage's word in error messages and its per-row outputs in C argument
 order.  The *_NAMES tuples of scoring.py, the validation of caller-supplied outputs, the pointer tuple of a host call
 and the argument list of a `_dev` call (marshalling.py) all follow from it."""
 from __future__ import annotations
@@ -47,6 +47,11 @@ TORQUE = _stage("torque", ("torque_ratio", _F, _row), ("static_ratio", _F, _row)
 RETIME = _stage("retime", ("sdot", _F, lambda Md, D: (Md,)), ("u", _F, lambda Md, D: (Md,)),
                 ("stamps", _F, lambda Md, D: (Md,)), ("duration", _F, _row), ("status", _I, _row),
                 ("achieved", _F, _tail(4)), ("dense_retimed", _F, lambda Md, D: (Md, 2 * D)), dense_retimed="dropped")
+# not in STAGES: re-timing under torque limits.  RETIME_AFFINE is the path form (gpmp2mi_retime_path_affine), which has no
+# robot; RETIME_DYNAMIC the trajectory and plan forms, whose tau_retimed and coef take NULL when they are not wanted
+RETIME_AFFINE = _stage("retime", *RETIME.outputs[:5], ("achieved", _F, _tail(6)))
+RETIME_DYNAMIC = _stage("retime", *RETIME_AFFINE.outputs, RETIME.outputs[6], ("tau_retimed", _F, lambda Md, D: (Md, D)),
+                        ("coef", _F, lambda Md, D: (Md, 4, D)), tau_retimed="null", coef="null")
 
 STAGES = dict(score=SCORE, self=SELF, moving=MOVING, path=PATH, motion=MOTION, torque=TORQUE, retime=RETIME)
 

@@ -761,7 +761,8 @@ enum {
   GPMP2MI_RETIME_OK = 0,
   GPMP2MI_RETIME_BOUNDARY = 1,
   GPMP2MI_RETIME_EMPTY = 2,
-  GPMP2MI_RETIME_INVALID = 3
+  GPMP2MI_RETIME_INVALID = 3,
+  GPMP2MI_RETIME_STATIC = 4   /* "re-timing under torque limits" only */
 };
 /* The bare rule on any joint-space path: qd, qdd_left, qdd_right [B][Md][D] (qdd_left of state 0 and qdd_right of state
  * Md-1 are not read), cap [B][Md] (a bound on x = sdot^2, +inf: none), acc HOST [D] or NULL, rate_start / rate_end < 0:
@@ -865,8 +866,8 @@ int gpmp2mi_plan_select_retimed_dev(gpmp2mi_plan* p, int inter_step, double requ
  * plan's resident result and delta_t, have the preconditions of gpmp2mi_plan_score and leave the optimizer's state and
  * every existing call's outputs untouched.
  * Not here: the mobile kinds (a moving base in the recursion); friction, rotor inertia, payload changes at run time and
- * external wrenches; torque rows inside gpmp2mi_plan_retime (they carry the offset tau_g, the rule knows symmetric rows
- * only); the torques of an already re-timed row; a torque factor inside the optimisation; gpmp2mi_multi_plan_* twins. */
+ * external wrenches; a torque factor inside the optimisation; gpmp2mi_multi_plan_* twins.  Torque rows inside the speed
+ * profile and the torques of the re-timed row: "re-timing under torque limits" below. */
 typedef struct gpmp2mi_dynamics gpmp2mi_dynamics;   /* device-resident inertial table, bound to the robot's kinematics */
 typedef struct gpmp2mi_dynamics_desc {
   const double* mass;     /* [L]     kg, >= 0                                             */
@@ -906,6 +907,112 @@ int gpmp2mi_plan_select_dynamic_dev(gpmp2mi_plan* p, int inter_step, double requ
                                     double max_time_scale, const gpmp2mi_dynamics* dynamics, int* best,
                                     int* n_eligible, double* time_scale_best, double* tau_best, double* traj_best,
                                     double* dense_best, void* stream);
+
+/* ---- re-timing under torque limits: a speed profile that the drives can follow, on the device ------------------------
+ * gpmp2mi_plan_retime knows the drives by a per-joint acceleration box, and gpmp2mi_plan_torque_score can only answer with
+ * one uniform stretch of the whole row: one demanding stage slows the whole trajectory.  These calls find the fastest speed
+ * profile along the unchanged path under the joint torque limits of a gpmp2mi_dynamics handle, with gravity taken off each
+ * limit state by state, next to the speed, acceleration and Cartesian-speed limits of "re-timing", which stay in force.
+ * They give the feed-forward torques of the re-timed row, and a selection that asks for the re-timed duration.
+ *
+ * Along a fixed path, with x = sdot^2 and u = sddot, the torque is affine: tau = p u + m x + tau_g, with p = M(q) q' (the
+ * inverse dynamics of (q, 0, q') without gravity), m = ID(q, q', q'') without gravity and tau_g = ID(q, 0, 0), all of
+ * "torque limits".  The rule is that of "re-timing" with rows that carry an offset (csrc/retime_affine_rule.h states it
+ * for host and device; every operation is rounded once in the order written):
+ *  - The row |cx x + cu u + off| <= A, with lo = -A - off and hi = A - off: A = +inf bounds nothing; cu > 0 gives
+ *    lo/cu - (cx/cu) x <= u <= hi/cu - (cx/cu) x; cu < 0 gives hi/cu - (cx/cu) x <= u <= lo/cu - (cx/cu) x; cu == 0 bounds
+ *    no u and caps x at hi/cx for cx > 0, at lo/cx for cx < 0.  With off == 0 this is the two-sided row of "re-timing", bit
+ *    for bit.
+ *  - Rows of stage k, for every affine constraint r with a finite bound: at the start of the stage
+ *    (cx, cu, off) = (cx_right_k, cu_k, off_k); at its end (cx_left_{k+1}, cu_{k+1} + 2 h cx_left_{k+1}, off_{k+1}), the
+ *    constraint at state k+1 seen from the left, written in (x_k, u_k).  For the torque of joint d:
+ *    (m_{k+}[d], p_k[d], tau_g,k[d]) and (m_{(k+1)-}[d], p_{k+1}[d] + 2 h m_{(k+1)-}[d], tau_g,k+1[d]) against L_d.  They
+ *    join the 2 D acceleration rows and the row of the next set: n = 2 D + 2 R + 1 rows per stage, R <= 8.
+ *  - Backward pass, forward pass, time and the statuses of "re-timing" are unchanged.  GPMP2MI_RETIME_INVALID also for a
+ *    non-finite cx, cu or off of a constraint with a finite bound (cx_left of state 0 and cx_right of state Md-1 are not
+ *    read; a constraint without a bound is not looked at).  GPMP2MI_RETIME_STATIC: some constraint with a finite bound
+ *    has |off| >= bound at a checked state (gravity alone takes the limit: static_ratio >= 1 of "torque limits"); no
+ *    timing helps.  It is tested after INVALID and before everything else.  With |off| < bound everywhere x = 0, u = 0
+ *    meets every affine row, and GPMP2MI_RETIME_EMPTY keeps its meaning.
+ *  - achieved [B][6]: [0..3] as "re-timing"; [4] the largest |cx x_k + cu u_k + off| / bound over the start and end rows
+ *    of every stage (the torque ratio of the re-timed row at the checked states), <= 1 up to rounding; [5] the largest
+ *    |off| / bound over the states (static_ratio).  NaN in a row that is not OK.
+ *  - coef [B][Md][4][dof] = p, m_left, m_right, tau_g of every checked state; a state with one side carries that side
+ *    twice.  Where q'_k == 0 exactly, p_k == 0 exactly, and where q'' == 0 as well, m == 0: a state at rest gives rows that
+ *    cap x, not rows with a rounding-level cu.
+ *  - tau_retimed [B][Md][dof] = m_{k+} x_k + p_k u_k + tau_g,k, the torques the re-timed row asks for at its checked
+ *    states; the last state uses m_- and u_{Md-2}.  NaN in a row that is not OK.
+ *  - With R == 0, or with every bound (every torque limit) +inf, sdot, u, stamps, duration, status, achieved[0..3] and
+ *    dense_retimed have the bits of gpmp2mi_retime_path / gpmp2mi_retime_traj.
+ *  - Determinism as for "re-timing": a row's outputs are bit-identical alone, in any batch and through every entry point.
+ *  - Selection (gpmp2mi_plan_select_retimed_dynamic): the rule of gpmp2mi_plan_select_retimed on the profile of these
+ *    calls, and no coefficient of the row that is not finite (whether its joint has a limit or not).  Outputs as
+ *    gpmp2mi_plan_select_retimed, plus tau_best [Md][dof], the chosen row of tau_retimed (untouched when none is chosen).
+ * Re-timing changes WHEN the robot is where: the moving-obstacle and workspace-path checks of a row, which index their
+ * spheres and targets by planned time, are not valid for the re-timed row.
+ * Errors, before any device work: those of "re-timing" and of "torque limits" (a dynamics handle made for another robot or
+ * living on another device; GPMP2MI_ERR_UNSUPPORTED for any kind but GPMP2MI_ROBOT_ARM and for more than 8 joints);
+ * GPMP2MI_ERR_INVALID for R outside 0..8, a NULL array of the R > 0 constraints, or a bound that is NaN or <= 0.  A
+ * refused call writes nothing.
+ * Memory: beyond the seven doubles per checked state of "re-timing", 4 D for the coefficients (room for them is kept
+ * whoever asks: the chain reads them), 4 (2 D + 2 R) for the rows of the stages, which are formed ahead of the chain,
+ * and D for the torques, with the dynamics handle for gpmp2mi_retime_dynamic_traj_dev (under the stream-order rule of
+ * gpmp2mi_score_traj_dev), with the plan for the plan forms, taken at the first call and grown on demand.
+ * gpmp2mi_retime_path_affine_dev has no handle: the caller gives `workspace`, B Md (3 + 4 (2 dof + 2 R)) doubles on the
+ * device, and none of its sdot / u / stamps may be NULL.  Any other output may be NULL.  The `_dev` forms enqueue and
+ * return.
+ * Not here: torque rows between checked states (SAMPLED, NOT BOUNDED, as in "torque limits": raise inter_step), jerk
+ * limits, the Pose2 and the mobile kinds, gpmp2mi_multi_plan_* twins. */
+/* The bare rule: the arguments of gpmp2mi_retime_path, and R constraints per state cx_left, cx_right, cu, off
+ * [B][Md][R] with bound HOST [R] (> 0, +inf: none); NULL arrays are fine for R == 0.  achieved [B][6]. */
+int gpmp2mi_retime_path_affine(int B, int Md, int dof, const double* qd, const double* qdd_left, const double* qdd_right,
+                               const double* cap, const double* acc, int R, const double* cx_left,
+                               const double* cx_right, const double* cu, const double* off, const double* bound, double h,
+                               double max_rate, double rate_start, double rate_end, double* sdot, double* u,
+                               double* stamps, double* duration, int* status, double* achieved);
+int gpmp2mi_retime_path_affine_dev(int B, int Md, int dof, const double* qd, const double* qdd_left,
+                                   const double* qdd_right, const double* cap, const double* acc, int R,
+                                   const double* cx_left, const double* cx_right, const double* cu, const double* off,
+                                   const double* bound, double h, double max_rate, double rate_start, double rate_end,
+                                   double* sdot, double* u, double* stamps, double* duration, int* status,
+                                   double* achieved, double* workspace, void* stream);
+/* caller buffers; traj [B][total_step+1][2D].  The device of the two handles must be current.  Any output may be NULL. */
+int gpmp2mi_retime_dynamic_traj(const gpmp2mi_robot* robot, const gpmp2mi_dynamics* dynamics,
+                                const gpmp2mi_motion_limits* limits, double delta_t, int inter_step, int B,
+                                int total_step, const double* traj, double max_rate, double rate_start, double rate_end,
+                                double* sdot, double* u, double* stamps, double* duration, int* status, double* achieved,
+                                double* dense_retimed, double* tau_retimed, double* coef);
+int gpmp2mi_retime_dynamic_traj_dev(const gpmp2mi_robot* robot, const gpmp2mi_dynamics* dynamics,
+                                    const gpmp2mi_motion_limits* limits, double delta_t, int inter_step, int B,
+                                    int total_step, const double* traj, double max_rate, double rate_start,
+                                    double rate_end, double* sdot, double* u, double* stamps, double* duration,
+                                    int* status, double* achieved, double* dense_retimed, double* tau_retimed,
+                                    double* coef, void* stream);
+/* The plan's resident result; preconditions and errors as gpmp2mi_plan_score. */
+int gpmp2mi_plan_retime_dynamic(gpmp2mi_plan* p, const gpmp2mi_dynamics* dynamics, const gpmp2mi_motion_limits* limits,
+                                int inter_step, double max_rate, double rate_start, double rate_end, double* sdot,
+                                double* u, double* stamps, double* duration, int* status, double* achieved,
+                                double* dense_retimed, double* tau_retimed, double* coef);
+int gpmp2mi_plan_retime_dynamic_dev(gpmp2mi_plan* p, const gpmp2mi_dynamics* dynamics,
+                                    const gpmp2mi_motion_limits* limits, int inter_step, double max_rate,
+                                    double rate_start, double rate_end, double* sdot, double* u, double* stamps,
+                                    double* duration, int* status, double* achieved, double* dense_retimed,
+                                    double* tau_retimed, double* coef, void* stream);
+/* gpmp2mi_plan_select_retimed with the torque rows in the profile, one enqueue. */
+int gpmp2mi_plan_select_retimed_dynamic(gpmp2mi_plan* p, int inter_step, double required_clearance, int require_in_range,
+                                        const gpmp2mi_self_pairs* pairs /*NULL ok*/, double required_self_clearance,
+                                        const gpmp2mi_motion_limits* limits, double required_pos_margin, double max_rate,
+                                        double rate_start, double rate_end, double max_duration,
+                                        const gpmp2mi_dynamics* dynamics, int* best, int* n_eligible,
+                                        double* duration_best, double* stamps_best, double* tau_best, double* traj_best,
+                                        double* dense_best);
+int gpmp2mi_plan_select_retimed_dynamic_dev(gpmp2mi_plan* p, int inter_step, double required_clearance,
+                                            int require_in_range, const gpmp2mi_self_pairs* pairs /*NULL ok*/,
+                                            double required_self_clearance, const gpmp2mi_motion_limits* limits,
+                                            double required_pos_margin, double max_rate, double rate_start,
+                                            double rate_end, double max_duration, const gpmp2mi_dynamics* dynamics,
+                                            int* best, int* n_eligible, double* duration_best, double* stamps_best,
+                                            double* tau_best, double* traj_best, double* dense_best, void* stream);
 
 /* ---- moving obstacles: time-indexed spheres as a plan factor and a check, on the device ---------------------------
  * Every obstacle of "scoring" lives in one static signed-distance field.  A person or another robot crossing the

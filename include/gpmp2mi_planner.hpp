@@ -1143,6 +1143,68 @@ inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int
   return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
 }
 
+/// The speed profile of a trajectory under the joint torque limits of an ArmDynamics, next to the rate limits of
+/// RetimeTrajectory (include/gpmp2mi.h "re-timing under torque limits"): the members of RetimedTrajectory, with two more
+/// entries of achieved (the largest torque ratio of the re-timed result at its checked states, <= 1 up to rounding, and
+/// the largest share gravity alone takes of a limit), the torques the re-timed result asks for, tau [Md][dof] (the
+/// feed-forward term), and the coefficients coef [Md][4][dof] = p, m_left, m_right, tau_g of tau = p u + m sdot^2 + tau_g.
+/// status may also be GPMP2MI_RETIME_STATIC: gravity alone exceeds a limit, no timing helps.  The torque between checked
+/// states is sampled, not bounded.
+struct DynamicRetimedTrajectory {
+  Vector sdot, u, stamps;
+  double duration = 0.0, achieved[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int status = GPMP2MI_RETIME_INVALID;
+  Trajectory dense;   // total_step * (inter_step + 1) intervals
+  Vector tau, coef;
+};
+/// ROBOT: a fixed-base arm of at most 8 joints (anything else throws, the reason in the message).
+template <class ROBOT>
+inline DynamicRetimedTrajectory RetimeTrajectory(const ROBOT& robot, const ArmDynamics& dynamics, const MotionLimits& limits,
+                                                 const Trajectory& result, const TrajOptimizerSetting& setting,
+                                                 std::size_t inter_step, double max_rate = 1.0, double rate_start = -1.0,
+                                                 double rate_end = -1.0) {
+  if (result.dof != robot.dof() || result.total_step != setting.total_step)
+    throw std::runtime_error("[RetimeTrajectory] result does not match dof / total_step");
+  const gpmp2mi_motion_limits l = limits.c(robot.dof());
+  DynamicRetimedTrajectory rt;
+  rt.dense = Trajectory(result.dof, result.total_step * (inter_step + 1));
+  const std::size_t Md = rt.dense.total_step + 1;
+  rt.sdot.assign(Md, 0.0);
+  rt.u.assign(Md, 0.0);
+  rt.stamps.assign(Md, 0.0);
+  rt.tau.assign(Md * result.dof, 0.0);
+  rt.coef.assign(Md * 4 * result.dof, 0.0);
+  check(gpmp2mi_retime_dynamic_traj(robot.handle(), dynamics.handle(), &l,
+                                    setting.total_time / static_cast<double>(setting.total_step), static_cast<int>(inter_step),
+                                    1, static_cast<int>(result.total_step), result.data.data(), max_rate, rate_start, rate_end,
+                                    rt.sdot.data(), rt.u.data(), rt.stamps.data(), &rt.duration, &rt.status, rt.achieved,
+                                    rt.dense.data.data(), rt.tau.data(), rt.coef.data()),
+        "gpmp2mi_retime_dynamic_traj");
+  return rt;
+}
+/// The SelectBestTrajectory of the re-timed results, with the torque rows in the profile: the result must re-time
+/// (GPMP2MI_RETIME_OK) within max_duration, and none of its coefficients may be non-finite.  Host code.
+inline int SelectBestTrajectory(const Vector& final_error, const std::vector<int>& status,
+                                const std::vector<TrajectoryScore>& scores,
+                                const std::vector<TrajectoryMotionScore>& motion_scores,
+                                const std::vector<DynamicRetimedTrajectory>& retimed, double required_pos_margin,
+                                double max_duration, double required_clearance = 0.0, bool require_in_range = false,
+                                std::size_t* n_eligible = nullptr) {
+  if (motion_scores.size() != scores.size() || retimed.size() != scores.size())
+    throw std::runtime_error("[SelectBestTrajectory] scores, motion_scores and retimed differ in length");
+  if (required_pos_margin != required_pos_margin || max_duration != max_duration)
+    throw std::runtime_error("[SelectBestTrajectory] required_pos_margin / max_duration is NaN");
+  std::vector<TrajectoryScore> both(scores);
+  for (std::size_t b = 0; b < both.size(); b++) {
+    const TrajectoryMotionScore& m = motion_scores[b];
+    bool ok = m.invalid == 0 && m.pos_margin >= required_pos_margin && retimed[b].status == GPMP2MI_RETIME_OK &&
+              retimed[b].duration <= max_duration;
+    for (double c : retimed[b].coef) ok = ok && std::isfinite(c);
+    if (!ok) both[b].min_clearance = std::nan("");   // a NaN clearance is never eligible
+  }
+  return SelectBestTrajectory(final_error, status, both, required_clearance, require_in_range, n_eligible);
+}
+
 namespace internal {
 inline Trajectory interpolateTraj(const Trajectory& opt_values, const Vector& Qc, double delta_t, std::size_t inter_step,
                                   std::size_t start_index, std::size_t end_index, bool lie) {

@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "gpmp2_amd", "csrc")
 FILES = ["host/debug.hip", "sdf_kernels.hip", "map_kernels.hip", "sensor_kernels.hip", "scene_kernels.hip", "factor_kernels.hip", "linearize_kernels.hip", "plan_kernels.hip", "cr_kernels.hip", "dense_kernels.hip",
-         "score_kernels.hip", "self_clearance_kernels.hip", "motion_kernels.hip", "retime_kernels.hip", "torque_kernels.hip", "moving_kernels.hip", "selfpair_kernels.hip", "path_kernels.hip", "carried_kernels.hip", "group_kernels.hip", "posterior_kernels.hip", "seed_kernels.hip", "risk_kernels.hip", "sample_clearance_kernels.hip", "ik_kernels.hip"]
+         "score_kernels.hip", "self_clearance_kernels.hip", "motion_kernels.hip", "retime_kernels.hip", "torque_kernels.hip", "retime_dynamic_kernels.hip", "moving_kernels.hip", "selfpair_kernels.hip", "path_kernels.hip", "carried_kernels.hip", "group_kernels.hip", "posterior_kernels.hip", "seed_kernels.hip", "risk_kernels.hip", "sample_clearance_kernels.hip", "ik_kernels.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage", "-c"]
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]",
         "Occupancy [waves/SIMD]"]
