@@ -5,8 +5,8 @@
 // kernels spread it.  ps comes from k_retime_caps (retime_kernels.hip), unchanged.
 //
 //   k_retime_coef     tiled as k_torque is: one wavefront, a lane per checked state, SCORE_TILE states per workgroup.
-//                     One outward walk in the world frame (the walk of k_torque, torque_kernels.hip, a second copy of
-//                     it) with three accelerations per lane: (q', q''_right), (q', q''_left) and (0, q').  The third has
+//                     One outward walk in the world frame (the walk of k_torque, described in dyn_walk.h with what the
+//                     two share) with three accelerations per lane: (q', q''_right), (q', q''_left) and (0, q').  The third has
 //                     no velocity terms and gives p = M(q) q'.  Writes coef [B][Md][4][D] = p, m_left, m_right, tau_g; a
 //                     state with one side carries that side twice.  Where q' == 0 exactly p == 0 exactly (every term of
 //                     the third walk is a product with a q'), and where q'' == 0 as well m == 0: the rule branches on
@@ -14,7 +14,8 @@
 //   k_retime_rows     a lane per (stage, row): (pl, pu, r, xcap) of the 2 D + 2 R rows of every stage that do not
 //                     depend on the chain, into the workspace.  Forming rows inside the chain is what k_retime pays per
 //                     dependent stage.
-//   k_retime_dynamic  one wavefront per row, the structure of k_retime: caps, finiteness and the static test, a lane per
+//   k_retime_dynamic  one wavefront per row, the chain of k_retime (the stages of retime_chain.h, which both kernels
+//                     call): caps, finiteness and the static test, a lane per
 //                     state; the chain reads a stage's rows from the workspace (the next stage's are in flight
 //                     meanwhile), lane 2 D + 2 R forms the row of the next set, the n^2 pairs are strided over the
 //                     lanes; the forward pass; `achieved` [6], the rates, the stamps in index order, the re-timed
@@ -30,35 +31,16 @@
 
 #include "device_math.h"
 #include "dispatch.h"
+#include "dyn_walk.h"
 #include "launch.h"
 #include "retime_affine_rule.h"
+#include "retime_chain.h"
 #include "score_select.h"
 
 namespace g2 {
 
 static_assert(2 * GPMP2MI_MAX_DOF + 2 * 8 + 1 <= 64, "the rows of a stage are one per lane");
 static_assert(RETIME_DYN_MAX_ROWS == RETIME_MAX_EXTRA && TORQUE_MAX_AD <= RETIME_MAX_EXTRA, "one affine row per joint");
-
-namespace {
-
-__device__ __forceinline__ void cross3(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-
-// per lane (column): the axis and the origin of every joint reached so far, and per joint m of the right side, m of the
-// left side, p and tau_g (TorqueLds of torque_kernels.hip with a fourth slot; profiles/torque_resources.txt says why
-// not registers)
-template <int AD>
-struct CoefLds {
-  double ax[6 * AD][SCORE_TILE], tq[4 * AD][SCORE_TILE];
-};
-
-}  // namespace
 
 template <int AD>
 __global__ __launch_bounds__(64) void k_retime_coef(const RobotDev* __restrict__ Rg, const DynDev* __restrict__ Dg,
@@ -67,12 +49,8 @@ __global__ __launch_bounds__(64) void k_retime_coef(const RobotDev* __restrict__
   constexpr int D = AD;
   __shared__ RobotDev R;
   __shared__ DynDev Dn;
-  __shared__ CoefLds<AD> S;
-  {
-    const int* s = reinterpret_cast<const int*>(Dg);
-    int* d = reinterpret_cast<int*>(&Dn);
-    for (int i = threadIdx.x; i < (int)(sizeof(DynDev) / 4); i += blockDim.x) d[i] = s[i];
-  }
+  __shared__ DynLds<AD, 3> S;   // per joint: m of the right side, m of the left side, p and tau_g
+  stage_dyn(&Dn, Dg);
   stage_robot(&R, Rg);   // its barrier closes both copies
   const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk;
   const int lane = threadIdx.x;
@@ -187,43 +165,6 @@ __global__ __launch_bounds__(64) void k_retime_coef(const RobotDev* __restrict__
 
 namespace {
 
-// q'_k, q''_{k-} and q''_{k+} of coordinate d at checked state k of row b (qL: k > 0, qR: k < Md - 1; else 0): the
-// expressions of retime_state in retime_kernels.hip, which that unit keeps to itself
-template <bool TRAJ>
-__device__ __forceinline__ void dyn_state(const RetimeArgs& a, int b, int k, int d, double& v, double& qL, double& qR) {
-  const int D = a.D;
-  if constexpr (!TRAJ) {
-    const size_t at = ((size_t)b * a.Md + k) * D + d;
-    v = a.qd[at];
-    qL = k > 0 ? a.ql[at] : 0.0;
-    qR = k < a.Md - 1 ? a.qr[at] : 0.0;
-  } else {
-    const int J1 = a.inter + 1, seg = k / J1, j = k % J1;
-    const double* s0 = a.traj + ((size_t)b * (a.N + 1) + seg) * 2 * D;
-    qL = qR = 0.0;
-    if (j == 0) {
-      v = s0[D + d];
-    } else {   // the velocity half of score_dense_coord (score_select.h), vector coordinates
-      const double* s1 = s0 + 2 * D;
-      const GpCoef gc = gp_coef_dev(a.dt, (double)j * (a.dt / (double)J1));
-      v = gc.l21 * s0[d] + gc.l22 * s0[D + d] + gc.p21 * s1[d] + gc.p22 * s1[D + d];
-    }
-    if (seg < a.N) {
-      const double* s1 = s0 + 2 * D;
-      double a0, a1;
-      retime_acc_ends(a.dt, s1[d] - s0[d], s0[D + d], s1[D + d], a0, a1);
-      qR = retime_acc_at(a0, a1, j, J1);
-      if (j > 0) qL = qR;
-    }
-    if (j == 0 && seg > 0) {
-      const double* sp = s0 - 2 * D;
-      double a0, a1;
-      retime_acc_ends(a.dt, s0[d] - sp[d], sp[D + d], s0[D + d], a0, a1);
-      qL = a1;
-    }
-  }
-}
-
 // the four coefficients of affine row r at checked state k of row b
 struct AffineAt {
   double cxl, cxr, cu, off;
@@ -231,23 +172,6 @@ struct AffineAt {
 __device__ __forceinline__ AffineAt affine_at(const RetimeDynArgs& a, int b, int k, int r) {
   const size_t at = ((size_t)b * a.rt.Md + k) * a.stride + r;
   return AffineAt{a.cxl[at], a.cxr[at], a.cu[at], a.off[at]};
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(v, off);
-    if (o < v) v = o;
-  }
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(v, off);
-    if (o > v) v = o;
-  }
-  return v;
 }
 
 // row `lane` of stage k as k_retime_rows left it; lanes behind the stored rows hold a row that bounds nothing
@@ -280,10 +204,10 @@ __global__ __launch_bounds__(256) void k_retime_rows(RetimeDynArgs a) {
   RetimeRow row;
   double v, qL, qR;
   if (i < D) {
-    dyn_state<TRAJ>(a.rt, b, k, i, v, qL, qR);
+    retime_state<TRAJ>(a.rt, b, k, i, v, qL, qR);
     row = retime_row_start(qR, v, s_acc[i]);
   } else if (i < 2 * D) {
-    dyn_state<TRAJ>(a.rt, b, k + 1, i - D, v, qL, qR);
+    retime_state<TRAJ>(a.rt, b, k + 1, i - D, v, qL, qR);
     row = retime_row_end(qL, v, s_acc[i - D], h2);
   } else if (i < 2 * D + R) {
     const AffineAt c = affine_at(a, b, k, i - 2 * D);
@@ -315,51 +239,29 @@ __global__ __launch_bounds__(64) void k_retime_dynamic(RetimeDynArgs g) {
   for (int r = 0; r < RETIME_DYN_MAX_ROWS; r++)
     if (lane == 32 + r) s_bound[r] = g.bound[r];
   __syncthreads();
-  double* X = a.X + (size_t)b * Md;
-  double* Kw = a.K + (size_t)b * Md * 2;
-  double* x = a.sdot + (size_t)b * Md;   // x_k until the rates replace it
-  double* u = a.u + (size_t)b * Md;
-  double* stamps = a.stamps + (size_t)b * Md;
+  const RetimeMem w = retime_mem(a, b);
+  const double* x = w.x;
+  const double* u = w.u;
   const double* rows = g.rows + (size_t)b * Md * nr * 4;
   int status = RETIME_OK;
   double ach[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
   // caps, finiteness and what the offsets alone take, a lane per state
   {
-    const double X0 = a.max_rate * a.max_rate;
-    int bad = 0, stat = 0, inf = 0;
-    for (int k = lane; k < Md; k += 64) {
-      double c = X0;
-      for (int d = 0; d < D; d++) {
-        double v, qL, qR;
-        dyn_state<TRAJ>(a, b, k, d, v, qL, qR);
-        bad |= !isfinite(v) || !isfinite(qL) || !isfinite(qR);
-        if constexpr (TRAJ) {
-          const double cv = retime_cap(s_vel[d], v);
-          if (cv < c) c = cv;
-        }
-      }
-      if constexpr (TRAJ) {
-        const double p = a.ps[(size_t)b * Md + k];
-        bad |= !isfinite(p);
-        const double cp = retime_cap(a.point_speed, p);
-        if (cp < c) c = cp;
-      } else {
-        const double cc = a.cap[(size_t)b * Md + k];
-        bad |= !(cc >= 0.0);
-        if (cc < c) c = cc;
-      }
+    int stat = 0, inf = 0;
+    const int bad = retime_caps_pass<TRAJ>(a, s_vel, w, b, lane, [&](int k) {
+      int inv = 0;
       for (int r = 0; r < R; r++) {
         const AffineAt q = affine_at(g, b, k, r);
         const int what = retime_affine_check(k > 0, q.cxl, k < Md - 1, q.cxr, q.cu, q.off, s_bound[r]);
-        bad |= what == 1;
+        inv |= what == 1;
         stat |= what == 2;
         inf |= retime_affine_check(k > 0, q.cxl, k < Md - 1, q.cxr, q.cu, q.off, 1.0) == 1;
         const double s = retime_static_ratio(q.off, s_bound[r]);
         if (s > ach[5]) ach[5] = s;
       }
-      X[k] = c;
-    }
+      return inv;
+    });
     if (__any(bad)) status = RETIME_INVALID;
     else if (__any(stat)) status = RETIME_STATIC;
     inf = __any(inf);
@@ -367,92 +269,31 @@ __global__ __launch_bounds__(64) void k_retime_dynamic(RetimeDynArgs g) {
   }
   __syncthreads();
 
-  // backward: the controllable sets
-  double lo = 0.0, hi = 0.0;
-  if (status == RETIME_OK) {
-    hi = X[Md - 1];
-    if (a.rate_end >= 0.0) {
-      lo = a.rate_end * a.rate_end;
-      if (lo > hi) status = RETIME_BOUNDARY;
-      hi = lo;
-    }
-  }
-  if (status == RETIME_OK) {
-    if (lane == 0) { Kw[2 * (Md - 1)] = lo; Kw[2 * (Md - 1) + 1] = hi; }
-    const int q64 = 64 / n, r64 = 64 % n;
-    RetimeRow ahead = stored_row(rows, Md - 2, nr, lane);
-    for (int k = Md - 2; k >= 0; k--) {
-      RetimeRow row = ahead;
-      if (k > 0) ahead = stored_row(rows, k - 1, nr, lane);   // in flight while this stage is eliminated
-      if (lane == nr) row = retime_row_next(lo, hi, h2);
-      s_pl[lane] = row.pl;
-      s_pu[lane] = row.pu;
-      s_r[lane] = row.r;
-      __syncthreads();
-      double l = 0.0, t = X[k];
-      if (row.xcap < t) t = row.xcap;
-      int empty = 0;
-      int i = lane / n, j = lane % n;
-      for (int p = lane; p < n * n; p += 64) {
-        retime_pair(RetimeRow{s_pl[i], 0.0, s_r[i], 0.0}, RetimeRow{0.0, s_pu[j], s_r[j], 0.0}, l, t, empty);
-        i += q64;
-        j += r64;
-        if (j >= n) { j -= n; i++; }
-      }
-      __syncthreads();   // the rows of this stage are read
-      l = wave_max(l);
-      t = wave_min(t);
-      if (__any(empty) || l > t) {
-        status = RETIME_EMPTY;
-        break;
-      }
-      lo = l;
-      hi = t;
-      if (lane == 0) { Kw[2 * k] = lo; Kw[2 * k + 1] = hi; }
-    }
-  }
+  // backward: the controllable sets; forward: greedy.  Both read a stage's rows from the workspace while the next
+  // stage's are in flight (`ahead`); lane nr forms the row of the next set.
+  RetimeRow ahead;
+  double lo, hi;
+  if (status == RETIME_OK) ahead = stored_row(rows, Md - 2, nr, lane);
+  retime_backward(a, w, s_pl, s_pu, s_r, n, lane, status, lo, hi, [&](int k, double klo, double khi) {
+    RetimeRow row = ahead;
+    if (k > 0) ahead = stored_row(rows, k - 1, nr, lane);   // in flight while this stage is eliminated
+    if (lane == nr) row = retime_row_next(klo, khi, h2);
+    return row;
+  });
   __syncthreads();   // K is read below by every lane
-
-  // forward: greedy
-  double xk = hi;
-  if (status == RETIME_OK && a.rate_start >= 0.0) {
-    xk = a.rate_start * a.rate_start;
-    if (xk < lo || xk > hi) status = RETIME_BOUNDARY;
-  }
-  if (status == RETIME_OK) {
-    if (lane == 0) x[0] = xk;
-    RetimeRow ahead = stored_row(rows, 0, nr, lane);
-    for (int k = 0; k < Md - 1; k++) {
-      const double nlo = Kw[2 * k + 2], nhi = Kw[2 * k + 3];
-      RetimeRow row = ahead;
-      if (k < Md - 2) ahead = stored_row(rows, k + 1, nr, lane);
-      if (lane == nr) row = retime_row_next(nlo, nhi, h2);
-      const double uh = wave_min(retime_upper_at(row, xk));
-      double x1, uk;
-      retime_step(xk, uh, nlo, nhi, h2, x1, uk);
-      if (lane == 0) { x[k + 1] = x1; u[k] = uk; }
-      xk = x1;
-    }
-    if (lane == 0) u[Md - 1] = 0.0;
-  }
+  if (status == RETIME_OK) ahead = stored_row(rows, 0, nr, lane);
+  retime_forward(a, w, lane, status, lo, hi, h2, [&](int k, double nlo, double nhi) {
+    RetimeRow row = ahead;
+    if (k < Md - 2) ahead = stored_row(rows, k + 1, nr, lane);
+    if (lane == nr) row = retime_row_next(nlo, nhi, h2);
+    return row;
+  });
   __syncthreads();   // x and u are read below by every lane
 
   double duration = HUGE_VAL;
   if (status == RETIME_OK) {
     // achieved: the accelerations, a lane per (stage, joint), and the affine rows, a lane per (stage, row)
-    for (int e = lane; e < (Md - 1) * D; e += 64) {
-      const int k = e / D, d = e % D;
-      double v0, v1, l0, r0, l1, r1;
-      dyn_state<TRAJ>(a, b, k, d, v0, l0, r0);
-      dyn_state<TRAJ>(a, b, k + 1, d, v1, l1, r1);
-      const double xs = x[k], us = u[k], A = s_acc[d];
-      const double e0 = retime_acc_ratio(r0, v0, xs, us, A);
-      const double e1 = retime_acc_ratio(l1, retime_end_b(l1, v1, h2), xs, us, A);
-      const double m = retime_mid_ratio(v0, r0, l1, xs, us, a.h, A);
-      if (e0 > ach[1]) ach[1] = e0;
-      if (e1 > ach[1]) ach[1] = e1;
-      if (m > ach[2]) ach[2] = m;
-    }
+    retime_achieved_acc<TRAJ>(a, s_acc, w, b, lane, h2, ach);
     for (int e = lane; e < (Md - 1) * R; e += 64) {
       const int k = e / R, r = e % R;
       const AffineAt c0 = affine_at(g, b, k, r), c1 = affine_at(g, b, k + 1, r);
@@ -474,60 +315,18 @@ __global__ __launch_bounds__(64) void k_retime_dynamic(RetimeDynArgs g) {
       }
     }
     __syncthreads();   // x is read; the rates take its place
-    for (int k = lane; k < Md; k += 64) {
-      const double s = sqrt(x[k]);
-      x[k] = s;
-      if constexpr (TRAJ) {
-        for (int d = 0; d < D; d++) {
-          if (!(s_vel[d] < HUGE_VAL)) continue;
-          double v, qL, qR;
-          dyn_state<TRAJ>(a, b, k, d, v, qL, qR);
-          const double r = fabs(v) * s / s_vel[d];
-          if (r > ach[0]) ach[0] = r;
-        }
-        if (a.point_speed < HUGE_VAL) {
-          const double r = a.ps[(size_t)b * Md + k] * s / a.point_speed;
-          if (r > ach[3]) ach[3] = r;
-        }
-      } else {
-        const double c = a.cap[(size_t)b * Md + k];
-        if (c < HUGE_VAL && c > 0.0) {
-          const double r = s / sqrt(c);
-          if (r > ach[0]) ach[0] = r;
-        }
-      }
-    }
+    retime_rates<TRAJ>(a, s_vel, w, b, lane, ach);
 #pragma unroll
     for (int c = 0; c < 6; c++) ach[c] = wave_max(ach[c]);
     __syncthreads();   // the rates are read by the neighbouring lanes
-    // the stage times, a lane per stage; then one sum in index order, the same in every lane
-    int zero = 0;
-    for (int k = lane; k < Md - 1; k += 64) {
-      const double s0 = x[k], s1 = x[k + 1];
-      zero |= s0 + s1 == 0.0;
-      stamps[k + 1] = retime_stage_time(s0, s1, h2);
-    }
-    if (__any(zero)) status = RETIME_EMPTY;
+    if (retime_stage_times(Md, w, lane, h2)) status = RETIME_EMPTY;
   }
   __syncthreads();
   if (status == RETIME_OK) {
-    double t = 0.0;
-    if (lane == 0) stamps[0] = 0.0;
-    for (int base = 0; base < Md - 1; base += 64) {
-      const int k = base + lane;
-      const double v = k < Md - 1 ? stamps[k + 1] : 0.0;
-      double mine = 0.0;
-#pragma unroll
-      for (int i = 0; i < 64; i++) {
-        t = t + __shfl(v, i);   // t + 0 behind the last stage leaves t as it is
-        if (lane == i) mine = t;
-      }
-      if (k < Md - 1) stamps[k + 1] = mine;
-    }
-    duration = t;
+    duration = retime_stamp_sum(Md, w.stamps, lane);
   } else {
     const double nn = nan("");
-    for (int k = lane; k < Md; k += 64) x[k] = u[k] = stamps[k] = nn;
+    for (int k = lane; k < Md; k += 64) w.x[k] = w.u[k] = w.stamps[k] = nn;
 #pragma unroll
     for (int c = 0; c < 6; c++) ach[c] = nn;
     if constexpr (TRAJ) {
@@ -541,19 +340,7 @@ __global__ __launch_bounds__(64) void k_retime_dynamic(RetimeDynArgs g) {
     if (a.achieved)
       for (int c = 0; c < 6; c++) a.achieved[6 * b + c] = ach[c];
   }
-  if constexpr (TRAJ) {
-    if (a.dense) {
-      __syncthreads();   // the rates (or the NaNs) of every state
-      double* out = a.dense + (size_t)b * Md * 2 * D;
-      const double* row = a.traj + (size_t)b * (a.N + 1) * 2 * D;
-      for (int e = lane; e < Md * D; e += 64) {
-        const int m = e / D, k = e % D;
-        double* o = out + (size_t)m * 2 * D;
-        score_dense_coord(false, a.dt, a.inter, D, m % (a.inter + 1), k, row + (size_t)(m / (a.inter + 1)) * 2 * D, o);
-        o[D + k] = o[D + k] * x[m];
-      }
-    }
-  }
+  retime_dense<TRAJ>(a, w.x, b, lane);
 }
 
 // The selection of gpmp2mi_plan_select_retimed_dynamic: one workgroup, rows by thread; the rule of k_retime_finish and
@@ -564,28 +351,15 @@ __global__ __launch_bounds__(256) void k_retime_dynamic_finish(RetimeDynFinish g
   RowPick mine;
   for (int b = threadIdx.x; b < f.B; b += blockDim.x) {
     const double fe = f.ferr[b];
-    bool ok = row_eligible(f, b, fe, a.clearance[b], a.oor[b]);
-    if (a.self_clearance) ok = ok && a.self_invalid[b] == 0 && a.self_clearance[b] >= a.required_self_clearance;
-    ok = ok && a.motion_invalid[b] == 0 && a.pos_margin[b] >= a.required_pos_margin;
-    ok = ok && a.rstatus[b] == RETIME_OK && g.nonfinite[b] == 0 && a.duration[b] <= a.max_duration;
-    if (ok) mine.take(fe, b);
+    if (retime_row_ok(a, f, b, fe) && g.nonfinite[b] == 0) mine.take(fe, b);
   }
   select_finish(f, mine);   // f.best is never null here (launch_retime_dynamic_finish)
   __syncthreads();   // best, and dense_best as interpolated
   const int best = *f.best;
   if (best < 0) return;
-  const double* sd = a.sdot + (size_t)best * f.Md;
-  if (threadIdx.x == 0 && a.duration_best) *a.duration_best = a.duration[best];
-  if (a.stamps_best)
-    for (int m = threadIdx.x; m < f.Md; m += blockDim.x) a.stamps_best[m] = a.stamps[(size_t)best * f.Md + m];
+  retime_copy_best(a, f, best);
   if (g.tau_best)
     for (int e = threadIdx.x; e < f.Md * f.D; e += blockDim.x) g.tau_best[e] = g.tau[(size_t)best * f.Md * f.D + e];
-  if (f.dense_best)
-    for (int e = threadIdx.x; e < f.Md * f.D; e += blockDim.x) {   // the elements this thread wrote in select_finish
-      const int m = e / f.D, k = e % f.D;
-      double* o = f.dense_best + (size_t)m * 2 * f.D + f.D + k;
-      *o = *o * sd[m];
-    }
 }
 
 int launch_retime_coef(const RobotDev& h, const RobotDev* R, const DynDev* dyn, const TorqueLimitsDev& lim, double dt,

@@ -6,7 +6,8 @@
 //   k_retime_caps    tiled as k_motion is (checked_grid, score_select.h): a lane is a checked state, a workgroup covers
 //                    SCORE_TILE consecutive states of one trajectory, its `nsub` wavefronts share the spheres.  Writes
 //                    ps_k, the largest sphere speed of the state (NaN when one of them is not finite).
-//   k_retime         one wavefront per row.  Caps X_k and the finiteness of the row, a lane per state.  Then the chain:
+//   k_retime         one wavefront per row; its stages are retime_chain.h's, shared with k_retime_dynamic
+//                    (retime_dynamic_kernels.hip).  Caps X_k and the finiteness of the row, a lane per state.  Then the chain:
 //                    per stage, lanes < 2 D form the rows from the two support states of the interval (TRAJ) or from the
 //                    caller's arrays, lane 2 D the row of the next set; the (2 D + 1)^2 pairs are strided over the lanes
 //                    and the two ends reduced by butterflies.  K goes to the workspace.  The forward pass takes the
@@ -22,7 +23,7 @@
 #include "device_math.h"
 #include "dispatch.h"
 #include "launch.h"
-#include "retime_rule.h"
+#include "retime_chain.h"
 #include "score_select.h"
 
 namespace g2 {
@@ -74,42 +75,6 @@ __global__ __launch_bounds__(256) void k_retime_caps(const RobotDev* __restrict_
 
 namespace {
 
-// q'_k, q''_{k-} and q''_{k+} of coordinate d at checked state k of row b (qL: k > 0, qR: k < Md - 1; else 0)
-template <bool TRAJ>
-__device__ __forceinline__ void retime_state(const RetimeArgs& a, int b, int k, int d, double& v, double& qL, double& qR) {
-  const int D = a.D;
-  if constexpr (!TRAJ) {
-    const size_t at = ((size_t)b * a.Md + k) * D + d;
-    v = a.qd[at];
-    qL = k > 0 ? a.ql[at] : 0.0;
-    qR = k < a.Md - 1 ? a.qr[at] : 0.0;
-  } else {
-    const int J1 = a.inter + 1, seg = k / J1, j = k % J1;
-    const double* s0 = a.traj + ((size_t)b * (a.N + 1) + seg) * 2 * D;
-    qL = qR = 0.0;
-    if (j == 0) {
-      v = s0[D + d];
-    } else {   // the velocity half of score_dense_coord (score_select.h), vector coordinates
-      const double* s1 = s0 + 2 * D;
-      const GpCoef gc = gp_coef_dev(a.dt, (double)j * (a.dt / (double)J1));
-      v = gc.l21 * s0[d] + gc.l22 * s0[D + d] + gc.p21 * s1[d] + gc.p22 * s1[D + d];
-    }
-    if (seg < a.N) {
-      const double* s1 = s0 + 2 * D;
-      double a0, a1;
-      retime_acc_ends(a.dt, s1[d] - s0[d], s0[D + d], s1[D + d], a0, a1);
-      qR = retime_acc_at(a0, a1, j, J1);
-      if (j > 0) qL = qR;
-    }
-    if (j == 0 && seg > 0) {
-      const double* sp = s0 - 2 * D;
-      double a0, a1;
-      retime_acc_ends(a.dt, s0[d] - sp[d], sp[D + d], s0[D + d], a0, a1);
-      qL = a1;
-    }
-  }
-}
-
 // row `lane` of stage k: lanes < D the start rows, < 2 D the end rows, 2 D the next set [lo, hi]; the others nothing
 template <bool TRAJ>
 __device__ __forceinline__ RetimeRow retime_lane_row(const RetimeArgs& a, const double* s_acc, int b, int k, int lane,
@@ -128,23 +93,6 @@ __device__ __forceinline__ RetimeRow retime_lane_row(const RetimeArgs& a, const 
   return RetimeRow{-HUGE_VAL, HUGE_VAL, 0.0, HUGE_VAL};
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(v, off);
-    if (o < v) v = o;
-  }
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(v, off);
-    if (o > v) v = o;
-  }
-  return v;
-}
-
 }  // namespace
 
 template <bool TRAJ>
@@ -159,180 +107,38 @@ __global__ __launch_bounds__(64) void k_retime(RetimeArgs a) {
   for (int d = 0; d < GPMP2MI_MAX_DOF; d++)   // static indices into the kernel argument
     if (lane == d) { s_acc[d] = a.acc[d]; s_vel[d] = a.vel[d]; }
   __syncthreads();
-  double* X = a.X + (size_t)b * Md;
-  double* Kw = a.K + (size_t)b * Md * 2;
-  double* x = a.sdot + (size_t)b * Md;   // x_k until the rates replace it
-  double* u = a.u + (size_t)b * Md;
-  double* stamps = a.stamps + (size_t)b * Md;
+  const RetimeMem w = retime_mem(a, b);
   int status = RETIME_OK;
 
   // caps and finiteness, a lane per state
-  {
-    const double X0 = a.max_rate * a.max_rate;
-    int bad = 0;
-    for (int k = lane; k < Md; k += 64) {
-      double c = X0;
-      for (int d = 0; d < D; d++) {
-        double v, qL, qR;
-        retime_state<TRAJ>(a, b, k, d, v, qL, qR);
-        bad |= !isfinite(v) || !isfinite(qL) || !isfinite(qR);
-        if constexpr (TRAJ) {
-          const double cv = retime_cap(s_vel[d], v);
-          if (cv < c) c = cv;
-        }
-      }
-      if constexpr (TRAJ) {
-        const double p = a.ps[(size_t)b * Md + k];
-        bad |= !isfinite(p);
-        const double cp = retime_cap(a.point_speed, p);
-        if (cp < c) c = cp;
-      } else {
-        const double cc = a.cap[(size_t)b * Md + k];
-        bad |= !(cc >= 0.0);
-        if (cc < c) c = cc;
-      }
-      X[k] = c;
-    }
-    if (__any(bad)) status = RETIME_INVALID;
-  }
+  if (__any(retime_caps_pass<TRAJ>(a, s_vel, w, b, lane, [](int) { return 0; }))) status = RETIME_INVALID;
   __syncthreads();
 
-  // backward: the controllable sets
-  double lo = 0.0, hi = 0.0;
-  if (status == RETIME_OK) {
-    hi = X[Md - 1];
-    if (a.rate_end >= 0.0) {
-      lo = a.rate_end * a.rate_end;
-      if (lo > hi) status = RETIME_BOUNDARY;
-      hi = lo;
-    }
-  }
-  if (status == RETIME_OK) {
-    if (lane == 0) { Kw[2 * (Md - 1)] = lo; Kw[2 * (Md - 1) + 1] = hi; }
-    const int q64 = 64 / n, r64 = 64 % n;
-    for (int k = Md - 2; k >= 0; k--) {
-      const RetimeRow row = retime_lane_row<TRAJ>(a, s_acc, b, k, lane, lo, hi, h2);
-      s_pl[lane] = row.pl;
-      s_pu[lane] = row.pu;
-      s_r[lane] = row.r;
-      __syncthreads();
-      double l = 0.0, t = X[k];
-      if (row.xcap < t) t = row.xcap;
-      int empty = 0;
-      int i = lane / n, j = lane % n;
-      for (int p = lane; p < n * n; p += 64) {
-        retime_pair(RetimeRow{s_pl[i], 0.0, s_r[i], 0.0}, RetimeRow{0.0, s_pu[j], s_r[j], 0.0}, l, t, empty);
-        i += q64;
-        j += r64;
-        if (j >= n) { j -= n; i++; }
-      }
-      __syncthreads();   // the rows of this stage are read
-      l = wave_max(l);
-      t = wave_min(t);
-      if (__any(empty) || l > t) {
-        status = RETIME_EMPTY;
-        break;
-      }
-      lo = l;
-      hi = t;
-      if (lane == 0) { Kw[2 * k] = lo; Kw[2 * k + 1] = hi; }
-    }
-  }
+  // backward: the controllable sets; forward: greedy.  Both form the rows of a stage in its lanes.
+  const auto rowfn = [&](int k, double klo, double khi) { return retime_lane_row<TRAJ>(a, s_acc, b, k, lane, klo, khi, h2); };
+  double lo, hi;
+  retime_backward(a, w, s_pl, s_pu, s_r, n, lane, status, lo, hi, rowfn);
   __syncthreads();   // K is read below by every lane
-
-  // forward: greedy
-  double xk = hi;
-  if (status == RETIME_OK && a.rate_start >= 0.0) {
-    xk = a.rate_start * a.rate_start;
-    if (xk < lo || xk > hi) status = RETIME_BOUNDARY;
-  }
-  if (status == RETIME_OK) {
-    if (lane == 0) x[0] = xk;
-    for (int k = 0; k < Md - 1; k++) {
-      const double nlo = Kw[2 * k + 2], nhi = Kw[2 * k + 3];
-      const RetimeRow row = retime_lane_row<TRAJ>(a, s_acc, b, k, lane, nlo, nhi, h2);
-      const double uh = wave_min(retime_upper_at(row, xk));
-      double x1, uk;
-      retime_step(xk, uh, nlo, nhi, h2, x1, uk);
-      if (lane == 0) { x[k + 1] = x1; u[k] = uk; }
-      xk = x1;
-    }
-    if (lane == 0) u[Md - 1] = 0.0;
-  }
+  retime_forward(a, w, lane, status, lo, hi, h2, rowfn);
   __syncthreads();   // x and u are read below by every lane
 
   double duration = HUGE_VAL;
   double ach[4] = {0.0, 0.0, 0.0, 0.0};
   if (status == RETIME_OK) {
-    // achieved: the accelerations, a lane per (stage, joint)
-    for (int e = lane; e < (Md - 1) * D; e += 64) {
-      const int k = e / D, d = e % D;
-      double v0, v1, l0, r0, l1, r1;
-      retime_state<TRAJ>(a, b, k, d, v0, l0, r0);
-      retime_state<TRAJ>(a, b, k + 1, d, v1, l1, r1);
-      const double xs = x[k], us = u[k], A = s_acc[d];
-      const double e0 = retime_acc_ratio(r0, v0, xs, us, A);
-      const double e1 = retime_acc_ratio(l1, retime_end_b(l1, v1, h2), xs, us, A);
-      const double m = retime_mid_ratio(v0, r0, l1, xs, us, a.h, A);
-      if (e0 > ach[1]) ach[1] = e0;
-      if (e1 > ach[1]) ach[1] = e1;
-      if (m > ach[2]) ach[2] = m;
-    }
+    retime_achieved_acc<TRAJ>(a, s_acc, w, b, lane, h2, ach);
     __syncthreads();   // x is read; the rates take its place
-    for (int k = lane; k < Md; k += 64) {
-      const double s = sqrt(x[k]);
-      x[k] = s;
-      if constexpr (TRAJ) {
-        for (int d = 0; d < D; d++) {
-          if (!(s_vel[d] < HUGE_VAL)) continue;
-          double v, qL, qR;
-          retime_state<TRAJ>(a, b, k, d, v, qL, qR);
-          const double r = fabs(v) * s / s_vel[d];
-          if (r > ach[0]) ach[0] = r;
-        }
-        if (a.point_speed < HUGE_VAL) {
-          const double r = a.ps[(size_t)b * Md + k] * s / a.point_speed;
-          if (r > ach[3]) ach[3] = r;
-        }
-      } else {
-        const double c = a.cap[(size_t)b * Md + k];
-        if (c < HUGE_VAL && c > 0.0) {
-          const double r = s / sqrt(c);
-          if (r > ach[0]) ach[0] = r;
-        }
-      }
-    }
+    retime_rates<TRAJ>(a, s_vel, w, b, lane, ach);
 #pragma unroll
     for (int c = 0; c < 4; c++) ach[c] = wave_max(ach[c]);
     __syncthreads();   // the rates are read by the neighbouring lanes
-    // the stage times, a lane per stage; then one sum in index order, the same in every lane
-    int zero = 0;
-    for (int k = lane; k < Md - 1; k += 64) {
-      const double s0 = x[k], s1 = x[k + 1];
-      zero |= s0 + s1 == 0.0;
-      stamps[k + 1] = retime_stage_time(s0, s1, h2);
-    }
-    if (__any(zero)) status = RETIME_EMPTY;
+    if (retime_stage_times(Md, w, lane, h2)) status = RETIME_EMPTY;
   }
   __syncthreads();
   if (status == RETIME_OK) {
-    double t = 0.0;
-    if (lane == 0) stamps[0] = 0.0;
-    for (int base = 0; base < Md - 1; base += 64) {
-      const int k = base + lane;
-      const double v = k < Md - 1 ? stamps[k + 1] : 0.0;
-      double mine = 0.0;
-#pragma unroll
-      for (int i = 0; i < 64; i++) {
-        t = t + __shfl(v, i);   // t + 0 behind the last stage leaves t as it is
-        if (lane == i) mine = t;
-      }
-      if (k < Md - 1) stamps[k + 1] = mine;
-    }
-    duration = t;
+    duration = retime_stamp_sum(Md, w.stamps, lane);
   } else {
     const double nn = nan("");
-    for (int k = lane; k < Md; k += 64) x[k] = u[k] = stamps[k] = nn;
+    for (int k = lane; k < Md; k += 64) w.x[k] = w.u[k] = w.stamps[k] = nn;
 #pragma unroll
     for (int c = 0; c < 4; c++) ach[c] = nn;
   }
@@ -342,19 +148,7 @@ __global__ __launch_bounds__(64) void k_retime(RetimeArgs a) {
     if (a.achieved)
       for (int c = 0; c < 4; c++) a.achieved[4 * b + c] = ach[c];
   }
-  if constexpr (TRAJ) {
-    if (a.dense) {
-      __syncthreads();   // the rates (or the NaNs) of every state
-      double* out = a.dense + (size_t)b * Md * 2 * D;
-      const double* row = a.traj + (size_t)b * (a.N + 1) * 2 * D;
-      for (int e = lane; e < Md * D; e += 64) {
-        const int m = e / D, k = e % D;
-        double* o = out + (size_t)m * 2 * D;
-        score_dense_coord(false, a.dt, a.inter, D, m % (a.inter + 1), k, row + (size_t)(m / (a.inter + 1)) * 2 * D, o);
-        o[D + k] = o[D + k] * x[m];
-      }
-    }
-  }
+  retime_dense<TRAJ>(a, w.x, b, lane);
 }
 
 // The selection of gpmp2mi_plan_select_retimed: one workgroup, rows by thread.
@@ -363,26 +157,13 @@ __global__ __launch_bounds__(256) void k_retime_finish(RetimeFinish a) {
   RowPick mine;
   for (int b = threadIdx.x; b < f.B; b += blockDim.x) {
     const double fe = f.ferr[b];
-    bool ok = row_eligible(f, b, fe, a.clearance[b], a.oor[b]);
-    if (a.self_clearance) ok = ok && a.self_invalid[b] == 0 && a.self_clearance[b] >= a.required_self_clearance;
-    ok = ok && a.motion_invalid[b] == 0 && a.pos_margin[b] >= a.required_pos_margin;
-    ok = ok && a.rstatus[b] == RETIME_OK && a.duration[b] <= a.max_duration;
-    if (ok) mine.take(fe, b);
+    if (retime_row_ok(a, f, b, fe)) mine.take(fe, b);
   }
   select_finish(f, mine);   // f.best is never null here (launch_retime_finish)
   __syncthreads();   // best, and dense_best as interpolated
   const int best = *f.best;
   if (best < 0) return;
-  const double* sd = a.sdot + (size_t)best * f.Md;
-  if (threadIdx.x == 0 && a.duration_best) *a.duration_best = a.duration[best];
-  if (a.stamps_best)
-    for (int m = threadIdx.x; m < f.Md; m += blockDim.x) a.stamps_best[m] = a.stamps[(size_t)best * f.Md + m];
-  if (f.dense_best)
-    for (int e = threadIdx.x; e < f.Md * f.D; e += blockDim.x) {   // the elements this thread wrote in select_finish
-      const int m = e / f.D, k = e % f.D;
-      double* o = f.dense_best + (size_t)m * 2 * f.D + f.D + k;
-      *o = *o * sd[m];
-    }
+  retime_copy_best(a, f, best);
 }
 
 int launch_retime_caps(const RobotDev& h, const RobotDev* R, double dt, int inter, int B, int N, const double* traj,

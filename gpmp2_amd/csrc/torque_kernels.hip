@@ -16,19 +16,9 @@
 //                    selection rule over the per-row scores the existing stages left and copies the chosen row
 //                    (select_finish, score_select.h) with its torques.
 //
-// The walk: inverse dynamics in the world frame during one outward pass, without a backward pass.  It carries the
-// angular velocity w, the angular acceleration wd and the acceleration ao of the current joint origin.  When link i is
-// reached it forms the link's force f = m a(c) and moment n = I wd + w x I w about its centre of mass c (I = R Ibar R^T,
-// applied in the link frame), and adds z_k . (n + (c - o_k) x f) to the torque of every joint k <= i at once: O(AD^2)
-// small products, and nothing per link is kept but the joint axes and origins and the torque vectors.  The motion part
-// m = ID(q, v, a) with gravity off and the gravity part tau_g = ID(q, 0, 0) are accumulated apart (the dynamics are
-// affine in gravity, tau = tau_g + m): a row at rest has m == 0 exactly, and m is what a stretch of the duration scales.
-//
-// Where the per-joint state lives: in LDS, one column per lane (TorqueLds), and the walk is a loop, not an unrolled
-// chain as Kin::walk_links is.  Unrolled with everything in registers (6 AD doubles of axes, 3 AD of torques, the state
-// of the joints still ahead) the compiler needed 100 VGPRs per joint and spilled from five joints on, whatever the
-// register budget and however the links were fenced (profiles/torque_resources.txt has the table).  A lane's column is
-// its own: no barrier, and [slot][lane] has no bank conflict.
+// The walk itself and where its per-joint state lives (LDS columns DynLds, not registers) are described in dyn_walk.h,
+// which holds what this walk and k_retime_coef's (retime_dynamic_kernels.hip) share; here NS = 2: per joint m of side 0,
+// m of side 1 and tau_g.
 //
 // Determinism: every output is an extremum with an index key (key_less: exact ties go to the lowest indices), an integer
 // count, or a per-state value; no sums of floating-point numbers across lanes, no atomics.  A row's results do not depend
@@ -37,29 +27,11 @@
 
 #include "device_math.h"
 #include "dispatch.h"
-#include "launch.h"
-#include "retime_rule.h"
-#include "score_select.h"
+#include "dyn_walk.h"
 
 namespace g2 {
 
 namespace {
-
-__device__ __forceinline__ void cross3(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-
-// per lane (column): the axis and the origin of every joint reached so far, and per joint m of side 0, m of side 1
-// and tau_g
-template <int AD>
-struct TorqueLds {
-  double ax[6 * AD][SCORE_TILE], tq[3 * AD][SCORE_TILE];
-};
 
 __device__ __forceinline__ void torque_key(ScoreKey& best, double value, int i, int j) {
   const ScoreKey key{value, i, j};
@@ -102,12 +74,8 @@ __global__ __launch_bounds__(64) void k_torque(const RobotDev* __restrict__ Rg, 
   constexpr int D = AD;
   __shared__ RobotDev R;
   __shared__ DynDev Dn;
-  __shared__ TorqueLds<AD> S;
-  {
-    const int* s = reinterpret_cast<const int*>(Dg);
-    int* d = reinterpret_cast<int*>(&Dn);
-    for (int i = threadIdx.x; i < (int)(sizeof(DynDev) / 4); i += blockDim.x) d[i] = s[i];
-  }
+  __shared__ DynLds<AD, 2> S;
+  stage_dyn(&Dn, Dg);
   stage_robot(&R, Rg);   // its barrier closes both copies
   const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk;
   const int lane = threadIdx.x;
