@@ -412,7 +412,8 @@ __global__ void k_interpolate_traj(double dt, int inter, int B, int N, int start
 // (kinematics/GaussianPriorWorkspacePosition.h:52-67, ...Orientation.h:52-69, ...Pose.h:53-70,
 // kinematics/GoalFactorArm.h:58-77) on the link poses / pose Jacobians k_fk produced:
 // poses [M][L][16], Jp [M][L][6][D]; err [M][rows], H [M][rows][D] (may be null)
-__global__ void k_workspace_prior(int mode, int joint, int L, int D, int M, const double* __restrict__ des,
+// launched by G2_GRID with 64 threads a block: the bound keeps the log maps' 3x3 temporaries in registers
+__global__ void __launch_bounds__(64) k_workspace_prior(int mode, int joint, int L, int D, int M, const double* __restrict__ des,
                                   const double* __restrict__ poses, const double* __restrict__ Jp,
                                   double* __restrict__ err, double* __restrict__ H) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -471,7 +472,7 @@ __global__ void k_workspace_prior(int mode, int joint, int L, int D, int M, cons
   for (int i = 0; i < 6; i++) e[i] = xi[i];
   if (Hm) {
     double Hep[36];
-    pose3_logmap_derivative(Rrel, trel, Hep);
+    pose3_logmap_derivative(xi, Hep);
     for (int i = 0; i < 6; i++)
       for (int k = 0; k < D; k++) {
         double a = 0;

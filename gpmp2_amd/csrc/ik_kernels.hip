@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64) void k_ik(const RobotDev* __restrict__ Rg, IkAr
 #pragma unroll
         for (int i = 0; i < 6 * D; i++) s_J[i][threadIdx.x] = J6[i / D][i % D];
         double Hep[36];
-        pose3_logmap_derivative(Rrel, trel, Hep);
+        pose3_logmap_derivative(e, Hep);   // e == et here: the accepted point's log map
 #pragma unroll
         for (int i = 0; i < 36; i++) Hm[i / 6][i % 6] = Hep[i];
 #pragma unroll

@@ -101,7 +101,7 @@ __device__ __forceinline__ void path_rows(int mode, const Frame& F, const double
   for (int i = 0; i < 6; i++) e[i] = xi[i];
   if (!jac) return;
   double Hep[36];
-  pose3_logmap_derivative(Rrel, trel, Hep);
+  pose3_logmap_derivative(xi, Hep);
 #pragma unroll
   for (int i = 0; i < 6; i++) {
     double a = 0;

@@ -222,65 +222,54 @@ static void m3mul(const double* A, const double* B, double* C) {
     for (int j = 0; j < 3; j++) T[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
   std::memcpy(C, T, sizeof(T));
 }
-// gtsam SO3::Logmap (4.0): trace based, special branch near pi, series near 0
+// What gtsam's SO3::Logmap computes, not how (the forms of csrc/lie_log.h, restated): theta = atan2(|v|, c) of the skew
+// part v = vee(R - R^T) / 2 and c = (tr - 1) / 2; the axis from v while c > -1/2, beyond from the symmetric part
+// (R + R^T) / 2 = c I + (1 - c) a a^T through its largest diagonal entry, signed so that a . v >= 0.
 void rot3_logmap(const double R[9], double w[3]) {
-  const double R11 = R[0], R12 = R[1], R13 = R[2], R21 = R[3], R22 = R[4], R23 = R[5], R31 = R[6], R32 = R[7], R33 = R[8];
-  const double tr = R11 + R22 + R33;
-  if (std::fabs(tr + 1.0) < 1e-10) {
-    if (std::fabs(R33 + 1.0) > 1e-10) {
-      const double k = M_PI / std::sqrt(2.0 + 2.0 * R33);
-      w[0] = k * R13; w[1] = k * R23; w[2] = k * (1.0 + R33);
-    } else if (std::fabs(R22 + 1.0) > 1e-10) {
-      const double k = M_PI / std::sqrt(2.0 + 2.0 * R22);
-      w[0] = k * R12; w[1] = k * (1.0 + R22); w[2] = k * R32;
-    } else {
-      const double k = M_PI / std::sqrt(2.0 + 2.0 * R11);
-      w[0] = k * (1.0 + R11); w[1] = k * R21; w[2] = k * R31;
-    }
-  } else {
-    double magnitude;
-    const double tr_3 = tr - 3.0;
-    if (tr_3 < -1e-7) {
-      const double theta = std::acos((tr - 1.0) / 2.0);
-      magnitude = theta / (2.0 * std::sin(theta));
-    } else {
-      magnitude = 0.5 - tr_3 * tr_3 / 12.0;
-    }
-    w[0] = magnitude * (R32 - R23);
-    w[1] = magnitude * (R13 - R31);
-    w[2] = magnitude * (R21 - R12);
+  const double v[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+  const double s = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+  const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+  double theta = std::atan2(s, c);
+  if (c > -0.5) {
+    const double m = s > 0.0 ? theta / s : 1.0;
+    for (int j = 0; j < 3; j++) w[j] = m * v[j];
+    return;
   }
+  int i = 0;
+  if (R[4] > R[0]) i = 1;
+  if (R[8] > R[i * 4]) i = 2;
+  const double d = 1.0 - c;
+  const double ai = std::sqrt((R[i * 4] - c) / d), f = 1.0 / (2.0 * d * ai);
+  double a[3];
+  for (int j = 0; j < 3; j++) a[j] = (R[i * 3 + j] + R[j * 3 + i]) * f;
+  a[i] = ai;
+  if ((a[0] * v[0] + a[1] * v[1]) + a[2] * v[2] < 0.0) theta = -theta;
+  for (int j = 0; j < 3; j++) w[j] = theta * a[j];
 }
-// gtsam SO3::LogmapDerivative
+// k = (1 - (t / 2) cot(t / 2)) / t^2: the [w]x^2 coefficient of the inverse right Jacobian and of Pose3's log
+static double so3_k(double theta2) {
+  if (theta2 <= std::numeric_limits<double>::epsilon()) return 1.0 / 12.0;
+  const double theta = std::sqrt(theta2), h = 0.5 * theta;
+  return (1.0 - h * std::cos(h) / std::sin(h)) / theta2;
+}
+// SO3::LogmapDerivative: I + [w]x / 2 + k [w]x^2 at every angle
 void rot3_logmap_derivative(const double w[3], double H[9]) {
   const double theta2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  for (int i = 0; i < 9; i++) H[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  if (theta2 <= std::numeric_limits<double>::epsilon()) return;
-  const double theta = std::sqrt(theta2);
   double W[9], WW[9];
   skew(w, W);
   m3mul(W, W, WW);
-  const double k = 1.0 / (theta * theta) - (1.0 + std::cos(theta)) / (2.0 * theta * std::sin(theta));
-  for (int i = 0; i < 9; i++) H[i] += 0.5 * W[i] + k * WW[i];
+  const double k = so3_k(theta2);
+  for (int i = 0; i < 9; i++) H[i] = ((i % 4 == 0) ? 1.0 : 0.0) + (0.5 * W[i] + k * WW[i]);
 }
-// gtsam Pose3::Logmap: xi = [omega; u]
+// Pose3::Logmap: xi = [omega; u], u = T - w x T / 2 + k w x (w x T) at every angle
 void pose3_logmap(const double R[9], const double T[3], double xi[6]) {
   double w[3];
   rot3_logmap(R, w);
-  const double t = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   xi[0] = w[0]; xi[1] = w[1]; xi[2] = w[2];
-  if (t < 1e-10) {
-    xi[3] = T[0]; xi[4] = T[1]; xi[5] = T[2];
-    return;
-  }
-  const double wn[3] = {w[0] / t, w[1] / t, w[2] / t};
-  double W[9];
-  skew(wn, W);
-  const double Tan = std::tan(0.5 * t);
-  double WT[3], WWT[3];
-  for (int i = 0; i < 3; i++) WT[i] = W[i * 3] * T[0] + W[i * 3 + 1] * T[1] + W[i * 3 + 2] * T[2];
-  for (int i = 0; i < 3; i++) WWT[i] = W[i * 3] * WT[0] + W[i * 3 + 1] * WT[1] + W[i * 3 + 2] * WT[2];
-  for (int i = 0; i < 3; i++) xi[3 + i] = T[i] - (0.5 * t) * WT[i] + (1.0 - t / (2.0 * Tan)) * WWT[i];
+  const double k = so3_k(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  const double WT[3] = {w[1] * T[2] - w[2] * T[1], w[2] * T[0] - w[0] * T[2], w[0] * T[1] - w[1] * T[0]};
+  const double WWT[3] = {w[1] * WT[2] - w[2] * WT[1], w[2] * WT[0] - w[0] * WT[2], w[0] * WT[1] - w[1] * WT[0]};
+  for (int i = 0; i < 3; i++) xi[3 + i] = T[i] - 0.5 * WT[i] + k * WWT[i];
 }
 // gtsam Pose3::computeQforExpmapDerivative (Barfoot eq. 102 with the sign convention of gtsam)
 static void pose3_Q(const double xi[6], double Q[9]) {
@@ -300,16 +289,18 @@ static void pose3_Q(const double xi[6], double Q[9]) {
   m3mul(W, WVW, WWVW);
   const double phi = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   double c1, c2, c3;
-  if (std::fabs(phi) > 1e-5) {
-    const double s = std::sin(phi), c = std::cos(phi);
-    const double phi2 = phi * phi, phi3 = phi2 * phi, phi4 = phi3 * phi, phi5 = phi4 * phi;
-    c1 = (phi - s) / phi3;
-    c2 = (1.0 - phi2 / 2.0 - c) / phi4;
-    c3 = -0.5 * ((1.0 - phi2 / 2.0 - c) / phi4 - 3.0 * (phi - s - phi3 / 6.0) / phi5);
+  const double x = phi * phi;
+  if (phi < 0.25) {   // LIE_Q_SERIES_BELOW of csrc/lie_log.h: five terms of each series in phi^2
+    c1 = 1.0 / 6.0 - x * (1.0 / 120.0 - x * (1.0 / 5040.0 - x * (1.0 / 362880.0 - x * (1.0 / 39916800.0))));
+    c2 = -(1.0 / 24.0 - x * (1.0 / 720.0 - x * (1.0 / 40320.0 - x * (1.0 / 3628800.0 - x * (1.0 / 479001600.0)))));
+    const double d = -(1.0 / 120.0 - x * (1.0 / 5040.0 - x * (1.0 / 362880.0 - x * (1.0 / 39916800.0 - x * (1.0 / 6227020800.0)))));
+    c3 = -0.5 * (c2 - 3.0 * d);
   } else {
-    c1 = 1.0 / 6.0;
-    c2 = 1.0 / 24.0;
-    c3 = -0.5 * (1.0 / 24.0 + 3.0 / 120.0);
+    const double s = std::sin(phi), c = std::cos(phi);
+    const double phi3 = x * phi, phi4 = x * x, phi5 = phi4 * phi;
+    c1 = (phi - s) / phi3;
+    c2 = (1.0 - x / 2.0 - c) / phi4;
+    c3 = -0.5 * (c2 - 3.0 * (phi - s - phi3 / 6.0) / phi5);
   }
   for (int i = 0; i < 9; i++)
     Q[i] = -0.5 * V[i] + c1 * (WV[i] + VW[i] - WVW[i]) + c2 * (WWV[i] + VWW[i] - 3.0 * WVW[i]) + c3 * (WVWW[i] + WWVW[i]);

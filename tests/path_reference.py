@@ -35,34 +35,41 @@ def rot_exp(w):
     return np.eye(3) + (np.sin(th) / th) * W + ((1.0 - np.cos(th)) / th2) * (W @ W)
 
 
+def so3_k(th2):
+    """k = (1 - (t / 2) cot(t / 2)) / t^2, the coefficient of [w]x^2 in the inverse Jacobians and in Pose3's Log; 1/12 at
+    theta^2 <= 2.22e-16"""
+    if th2 <= EPS2:
+        return 1.0 / 12.0
+    th = np.sqrt(th2)
+    return (1.0 - 0.5 * th * np.cos(0.5 * th) / np.sin(0.5 * th)) / th2
+
+
 def rot_log(R):
-    """SO3::Logmap of GTSAM 4.0 (the branches of the factor's log map)"""
+    """the factor's SO(3) log map (csrc/lie_log.h): theta = atan2(|v|, c) of the skew part v and c = (tr - 1) / 2; the
+    axis from v while c > -1/2, from the symmetric part (largest diagonal entry) beyond, its sign from v"""
     R = np.asarray(R, dtype=np.float64)
-    tr = R[0, 0] + R[1, 1] + R[2, 2]
-    if abs(tr + 1.0) < 1e-10:
-        if abs(R[2, 2] + 1.0) > 1e-10:
-            return (np.pi / np.sqrt(2.0 + 2.0 * R[2, 2])) * np.array([R[0, 2], R[1, 2], 1.0 + R[2, 2]])
-        if abs(R[1, 1] + 1.0) > 1e-10:
-            return (np.pi / np.sqrt(2.0 + 2.0 * R[1, 1])) * np.array([R[0, 1], 1.0 + R[1, 1], R[2, 1]])
-        return (np.pi / np.sqrt(2.0 + 2.0 * R[0, 0])) * np.array([1.0 + R[0, 0], R[1, 0], R[2, 0]])
-    tr_3 = tr - 3.0
-    if tr_3 < -1e-7:
-        th = np.arccos((tr - 1.0) / 2.0)
-        mag = th / (2.0 * np.sin(th))
-    else:
-        mag = 0.5 - tr_3 * tr_3 / 12.0
-    return mag * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    c = 0.5 * (((R[0, 0] + R[1, 1]) + R[2, 2]) - 1.0)
+    th = np.arctan2(s, c)
+    if c > -0.5:
+        return v * (th / s) if s > 0.0 else v
+    i = int(np.argmax([R[0, 0], R[1, 1], R[2, 2]]))
+    d = 1.0 - c
+    ai = np.sqrt((R[i, i] - c) / d)
+    a = np.array([(R[i, j] + R[j, i]) / (2.0 * d * ai) for j in range(3)])
+    a[i] = ai
+    if (a[0] * v[0] + a[1] * v[1]) + a[2] * v[2] < 0.0:
+        th = -th
+    return th * a
 
 
 def pose_log(R, t):
-    """Pose3::Logmap of GTSAM 4.0: [omega; u]"""
+    """the factor's SE(3) log map: [omega; u], u = t - w x t / 2 + k w x (w x t)"""
     w = rot_log(R)
-    th = np.linalg.norm(w)
-    if th < 1e-10:
-        return np.concatenate([w, t])
-    W = skew(w / th)
+    W = skew(w)
     Wt = W @ t
-    return np.concatenate([w, t - (0.5 * th) * Wt + (1.0 - th / (2.0 * np.tan(0.5 * th))) * (W @ Wt)])
+    return np.concatenate([w, t - 0.5 * Wt + so3_k(float(w @ w)) * (W @ Wt)])
 
 
 def pose(R=None, t=(0.0, 0.0, 0.0)):
