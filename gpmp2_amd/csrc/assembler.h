@@ -48,6 +48,15 @@ struct Assembler {
   __device__ __forceinline__ Slot make_slot(double* smem, int which) const {
     return Slot{smem + which * slot_doubles(P.I, P.RECS, P.GPS), P.RECS, P.I + 1, P.GPS};
   }
+  // The sizes staging needs, for a kernel that holds them in its arguments (PassConsts) and must not wait for *pp
+  // before it can form an address.
+  struct StageDims {
+    int I, RECS, GPS, N, Ppad, Npad;
+  };
+  __device__ __forceinline__ StageDims stage_dims() const { return StageDims{P.I, P.RECS, P.GPS, P.N, P.Ppad, P.Npad}; }
+  __device__ __forceinline__ static Slot make_slot(double* smem, int which, const StageDims& d) {
+    return Slot{smem + which * slot_doubles(d.I, d.RECS, d.GPS), d.RECS, d.I + 1, d.GPS};
+  }
 
   const PlanParams& P;
   const PlanBuffers& pb;
@@ -90,7 +99,15 @@ struct Assembler {
   static constexpr int NLD2 = (D <= 7) ? 6 : (D <= 11) ? 9 : 14;
   // count = 1 stages interval iv only (kernels whose wavefronts share their slots)
   __device__ __forceinline__ void stage2(int iv, const Slot& s0, const Slot& s1, int count = 2) const {
-    const int I = P.I, RECS = P.RECS, GPS = P.GPS;
+    stage2(stage_dims(), iv, s0, s1, count, [] { return false; });
+  }
+  // `between` runs once the loads are issued and before the first LDS store, i.e. while they fly; when it returns true
+  // nothing is stored and stage2 returns true (k_assemble: the step control, whose outcome may be that the trajectory
+  // builds nothing -- the loads then complete into registers nobody reads).
+  template <class Between>
+  __device__ __forceinline__ bool stage2(const StageDims& dm, int iv, const Slot& s0, const Slot& s1, int count,
+                                         Between between) const {
+    const int I = dm.I, RECS = dm.RECS, GPS = dm.GPS;
     double2 val[2][NLD2];
 #pragma unroll
     for (int w = 0; w < 2; w++) {
@@ -99,9 +116,9 @@ struct Assembler {
       const int npt = (ivw == 0) ? 1 : I + 1;
       const int nd2 = (npt * RECS) >> 1, ng2 = GPS >> 1, nc2 = (CQ / 2) * I;
       const int p0 = (ivw == 0) ? 0 : 1 + (ivw - 1) * (I + 1);
-      const bool in_range = ivw <= P.N;
-      const double2* src = reinterpret_cast<const double2*>(rec + ((size_t)b * P.Ppad + p0) * RECS);
-      const double2* gsrc = reinterpret_cast<const double2*>(gpu + ((size_t)b * P.Npad + ivw) * GPS);
+      const bool in_range = ivw <= dm.N;
+      const double2* src = reinterpret_cast<const double2*>(rec + ((size_t)b * dm.Ppad + p0) * RECS);
+      const double2* gsrc = reinterpret_cast<const double2*>(gpu + ((size_t)b * dm.Npad + ivw) * GPS);
       const double2* csrc = reinterpret_cast<const double2*>(P.coefq);
 #pragma unroll
       for (int m = 0; m < NLD2; m++) {
@@ -117,6 +134,7 @@ struct Assembler {
         val[w][m] = x;
       }
     }
+    if (between()) return true;
 #pragma unroll
     for (int w = 0; w < 2; w++) {
       if (w >= count) break;
@@ -133,6 +151,7 @@ struct Assembler {
         else if (v < nd2 + ng2 + nc2) dgp[v - nd2] = val[w][m];
       }
     }
+    return false;
   }
 
   // (Hint^T g)[kr]

@@ -135,26 +135,31 @@ constexpr int ASM_WT_MAX_B = 256;
 #define G2_ASM_MINW 5
 #endif
 template <int D, bool LIE, StorePolicy ASM_OUT>
-__global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assemble(const PlanParams* __restrict__ pp, PlanBuffers pb,
+__global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assemble(PassConsts pc, const PlanParams* __restrict__ pp, PlanBuffers pb,
                                                               const double* __restrict__ traj, int bufsel,
                                                               double* __restrict__ tiles,
                                                               const int* __restrict__ active, int early_stop) {
   constexpr int n = 2 * D;
   using Asm = Assembler<D, LIE>;
   const PlanParams& P = *pp;
-  const int N = P.N;
+  // Head: everything up to the record loads is formed from the kernel arguments (pc) and ONE batch of the trajectory's
+  // own words -- active, which, phase, and for the early stop iters, prev_err and the error shares -- requested together
+  // before the first of them is tested.  (Through *pp and one array after the other this was six dependent round trips
+  // to words that kernels on other XCDs wrote)
+  const int N = pc.N;
   const int groups = crr_groups(N, ASM_WAVES);     // tree indices 0 .. N + 1 in fours
   const int b = blockIdx.x / groups, q = blockIdx.x - b * groups;
-  if (active && !active[b]) return;
-  // Early stop (Gauss-Newton fast driver): the graph error at these states is already known -- k_linearize_arm left its
-  // shares -- so the step control of k_gn_step_cr is evaluated here, on the same inputs: a trajectory that stops in this
-  // pass (converged, rolled back, out of iterations) builds and eliminates nothing and leaves the hand-over tiles alone.
-  if (early_stop) {
-    int status;
-    if (gn_decide(P.rules, pb.iters[b], pb.prev_err[b], error_from_shares(P, pb, b), status) != 0) return;
-  }
+  const int nchunk = pc.Ppad / 64;
+  int act = (active ? active : pb.active)[b];   // (every load of the batch is unconditional: no branch between them)
+  int wh = pb.which[b];
+  int ph = pb.phase[b];
+  int it = pb.iters[b];
+  const double prev = pb.prev_err[b];
+  const ShareHead sh = shares_request(pb, b, nchunk, threadIdx.x & 63);
+  head_batch_end(act, wh, ph, it);
+  if (active && !act) return;
   // Dogleg retries (phase 1: same linearization, smaller trust region) need no new factorisation
-  if (active && dogleg_retry(P, pb, b)) return;
+  if (active && pc.rules.opt_type == GPMP2MI_OPT_DOGLEG && ph != 0) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int v = ASM_WAVES * q + wv, i = v - 1;   // tree index, state
   const bool live = v >= 1 && i <= N;   // the last group may be partly empty; v = 0 does not exist
@@ -166,15 +171,25 @@ __global__ __launch_bounds__(64 * ASM_WAVES, LIE ? 2 : G2_ASM_MINW) void k_assem
   // interval 0 into the slot nobody else reads.)
   // hand-over tiles: [0] W_l, [1] W_r of block 4q+1; [2] W_l, [3] W_r of block 4q+3; S of block 4q goes where only its
   // own wavefront has read -- record slot 0 -- when a slot holds a tile, otherwise into a fifth tile
-  const int slotd = Asm::slot_doubles(P.I, P.RECS, P.GPS);
+  const typename Asm::StageDims dm{pc.I, pc.RECS, pc.GPS, pc.N, pc.Ppad, pc.Npad};
+  const int slotd = Asm::slot_doubles(dm.I, dm.RECS, dm.GPS);
   double* xch = asm_smem + (size_t)(ASM_WAVES + 1) * slotd;
   double* xs0 = (slotd >= TILE_DBL) ? asm_smem : xch + 4 * TILE_DBL;
-  const double* rec = rec_of(pb, pb.which[b], bufsel);
-  const double* gpu = gpu_of(pb, pb.which[b], bufsel);
+  const double* rec = rec_of(pb, wh, bufsel);
+  const double* gpu = gpu_of(pb, wh, bufsel);
   Asm as(P, pb, rec, gpu, b, lane);
   G2_ASTAMP(0);
-  const typename Asm::Slot slot0 = as.make_slot(asm_smem, wv), slot1 = as.make_slot(asm_smem, wv + 1);
-  as.stage2(max(i, 0), slot0, slot1, wv == ASM_WAVES - 1 ? 2 : 1);
+  const typename Asm::Slot slot0 = Asm::make_slot(asm_smem, wv, dm), slot1 = Asm::make_slot(asm_smem, wv + 1, dm);
+  // Early stop (Gauss-Newton fast driver): the graph error at these states is already known -- k_linearize_arm left its
+  // shares -- so the step control of k_gn_step_cr is evaluated here, on the same inputs: a trajectory that stops in this
+  // pass (converged, rolled back, out of iterations) builds and eliminates nothing and leaves the hand-over tiles alone.
+  // The decision is computed while the record loads are in flight; no record load is issued for an inactive trajectory.
+  const bool stops = as.stage2(dm, max(i, 0), slot0, slot1, wv == ASM_WAVES - 1 ? 2 : 1, [&] {
+    if (!early_stop) return false;
+    int status;
+    return gn_decide(pc.rules, it, prev, error_from_shares(sh, pb, b, nchunk), status) != 0;
+  });
+  if (stops) return;
   __syncthreads();
   G2_ASTAMP(1);
   const bool odd = (v & 1) != 0;
@@ -307,10 +322,11 @@ int launch_assemble(const PlanParams& hp, const PlanBuffers& pb, const double* t
     constexpr int D = decltype(d)::value;
     constexpr StorePolicy WT = StorePolicy::WriteThrough, PL = StorePolicy::Plain;
     const bool wt = hp.B <= ASM_WT_MAX_B;
-    if (hp.lie && wt) k_assemble<D, true, WT><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
-    else if (hp.lie) k_assemble<D, true, PL><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
-    else if (wt) k_assemble<D, false, WT><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
-    else k_assemble<D, false, PL><<<grid, block, shmem, st>>>(pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    const PassConsts pc = pass_consts(hp);
+    if (hp.lie && wt) k_assemble<D, true, WT><<<grid, block, shmem, st>>>(pc, pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else if (hp.lie) k_assemble<D, true, PL><<<grid, block, shmem, st>>>(pc, pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else if (wt) k_assemble<D, false, WT><<<grid, block, shmem, st>>>(pc, pb.params, pb, traj, bufsel, pb.tiles, active, es);
+    else k_assemble<D, false, PL><<<grid, block, shmem, st>>>(pc, pb.params, pb, traj, bufsel, pb.tiles, active, es);
   });
 }
 
@@ -467,16 +483,26 @@ __device__ __forceinline__ void cr_backward(const PlanBuffers& pb, int b, int N,
 
 }
 
+// Returns 1 when the trajectory keeps iterating (uniform over the workgroup): its share of the pass's count.
 template <int D>
-__device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuffers& pb, int pass, int early_stop) {
+__device__ __forceinline__ int gn_step_body(const PassConsts& pc, const PlanParams& P, const PlanBuffers& pb, int pass,
+                                            int early_stop) {
   constexpr int n = 2 * D;
   const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
-  if (!pb.active[b]) return;
-  const int N = P.N;
+  // head: the sizes and rules come with the kernel arguments (pc); the trajectory's own words -- active, iters, prev_err
+  // and the error shares -- are requested in one batch before `active` is tested
+  const int N = pc.N, nchunk = pc.Ppad / 64;
+  int act = pb.active[b];
+  int it = pb.iters[b];
+  const double prev = pb.prev_err[b];
+  const ShareHead sh = shares_request(pb, b, nchunk, lane);
+  int prev_hi = __double2hiint(prev);   // (names prev_err's arrival; the value itself is `prev`)
+  head_batch_end(act, it, prev_hi);
+  if (!act) return 0;
   const size_t tsz = (size_t)(N + 1) * n;
   // fused finish (plan.h: fuse_finish): the states of pass k live in pb.cur for even k, pb.last for odd k, and the other
   // buffer holds the states the last step started from
-  const bool odd = P.fuse_finish && (pass & 1);
+  const bool odd = pc.fuse_finish && (pass & 1);
   double* cur = (odd ? pb.last : pb.cur) + b * tsz;
   double* last = (odd ? pb.cur : pb.last) + b * tsz;
   double* result = pb.result + b * tsz;
@@ -487,9 +513,6 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
   G2_STAMP_DECL;
 
   G2_STAMP(0);
-  // what the step control below needs from HBM is requested before the error sum, not after its barrier
-  const int it = pb.iters[b];
-  const double prev = pb.prev_err[b];
   // ---- graph error at `cur`, then the gpmp2::optimize control flow (gn_decide): every thread evaluates it on the same
   // values, thread 0 records the outcome.
   // Early stop: the error is the fixed-order sum of the per-chunk shares of k_linearize_arm -- uniform loads, no
@@ -497,7 +520,7 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
   // trajectory that stops.  Otherwise: the per-block partials of k_assemble (or the sum k_error_parts left in block 0).
   double new_err;
   if (early_stop) {
-    new_err = error_from_shares(P, pb, b);
+    new_err = error_from_shares(sh, pb, b, nchunk);
     if (tid == 0) flags[1] = 0;   // (set only behind the barriers of cr_forward)
   } else {
     if (w == 0) {
@@ -513,9 +536,9 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
     new_err = red[0];
   }
   int status;
-  const int decision = gn_decide(P.rules, it, prev, new_err, status);  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
+  const int decision = gn_decide(pc.rules, it, prev, new_err, status);  // 0 iterate, 1 stop(result = cur), 2 stop(result = last)
   if (tid == 0) {
-    if (it <= P.rules.max_iter) pb.trace[(size_t)b * (P.rules.max_iter + 1) + it] = new_err;
+    if (it <= pc.rules.max_iter) pb.trace[(size_t)b * (pc.rules.max_iter + 1) + it] = new_err;
     pb.cur_err[b] = new_err;
     if (decision != 0) {
       pb.status[b] = status;
@@ -524,7 +547,7 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
   }
   // prev_err and active are inputs of this very decision: they are written only behind a barrier that every wavefront
   // reaches after it has read them
-  const bool keep_err = it == 0 || (decision == 0 && P.rules.fixed_iters == 0);   // currentError = the error just found
+  const bool keep_err = it == 0 || (decision == 0 && pc.rules.fixed_iters == 0);   // currentError = the error just found
   if (decision != 0) {
     const double* src = (decision == 2) ? last : cur;
     for (size_t k = tid; k < tsz; k += blockDim.x) result[k] = src[k];
@@ -533,7 +556,7 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
       if (keep_err) pb.prev_err[b] = new_err;
       pb.active[b] = 0;
     }
-    return;
+    return 0;
   }
 
   G2_STAMP(1);
@@ -550,10 +573,10 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
       pb.final_err[b] = pb.cur_err[b];
       pb.active[b] = 0;
     }
-    return;
+    return 0;
   }
 
-  if (P.split_back) {
+  if (pc.split_back) {
     // the three widest back-substitution levels (88 of the 101 blocks) and the retract run chip-wide in
     // k_finish_step; this kernel only solves the blocks whose tree index is a multiple of 8 and hands them over
     cr_backward<n>(pb, b, N, tid, xs, FIN_BLOCKS);
@@ -568,9 +591,8 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
       pb.stepped[b] = pass + 1;
       pb.last_err[b] = pb.cur_err[b];
       pb.iters[b] += 1;
-      atomicAdd(pb.n_active + pass, 1);
     }
-    return;
+    return 1;
   }
   cr_backward<n>(pb, b, N, tid, xs);
   G2_STAMP(3);
@@ -581,20 +603,20 @@ __device__ __forceinline__ void gn_step_body(const PlanParams& P, const PlanBuff
     const int i = (int)(k / n), rho = (int)(k - (size_t)i * n);
     const double* zs = last + (size_t)i * n;
     const double* dz = xs + i * 16;
-    cur[k] = (rho < D) ? retract_coord(P.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
+    cur[k] = (rho < D) ? retract_coord(pc.lie != 0, rho, zs, dz) : zs[rho] + dz[rho];
   }
   G2_STAMP(4);
   if (tid == 0) {
     pb.last_err[b] = pb.cur_err[b];
     pb.iters[b] += 1;
-    atomicAdd(pb.n_active + pass, 1);
   }
+  return 1;
 }
 template <int D>
-__global__ __launch_bounds__(64 * CR_WAVES) void k_gn_step_cr(const PlanParams* __restrict__ pp,
+__global__ __launch_bounds__(64 * CR_WAVES) void k_gn_step_cr(PassConsts pc, const PlanParams* __restrict__ pp,
                                                                PlanBuffers pb, int pass, int early_stop) {
-  gn_step_body<D>(*pp, pb, pass, early_stop);
-  if (threadIdx.x == 0) publish_pass_count(pb, pass);
+  const int continues = gn_step_body<D>(pc, *pp, pb, pass, early_stop);
+  if (threadIdx.x == 0) publish_pass_count(pb, pass, continues);
 }
 
 // Chip-wide tail of a Gauss-Newton pass (split path): one workgroup of 8 wavefronts per (trajectory, tree blocks
@@ -751,7 +773,7 @@ int launch_gn_step_cr(const PlanParams& hp, const PlanBuffers& pb, int pass, hip
     return GPMP2MI_ERR_UNSUPPORTED;
   }
   return launch_for_dof(TILE_DOFS, hp.D, [&](auto d) {
-    k_gn_step_cr<decltype(d)::value><<<grid, block, shmem, st>>>(pb.params, pb, pass, early_stop ? 1 : 0);
+    k_gn_step_cr<decltype(d)::value><<<grid, block, shmem, st>>>(pass_consts(hp), pb.params, pb, pass, early_stop ? 1 : 0);
   });
 }
 

@@ -449,7 +449,7 @@ static int alloc_buffers(gpmp2mi_plan* p, const ExtrasHost& hx) {
   G2_TRY(flags_acquire(p->n_active_len, &p->flagbuf));
   p->h_flags = p->flagbuf.host;
   pb.host_flags = p->flagbuf.dev;
-  G2_TRY(plan_alloc(p, &pb.done, p->n_active_len));
+  G2_TRY(plan_alloc(p, &pb.pass_word, p->n_active_len));
   return GPMP2MI_OK;
 }
 

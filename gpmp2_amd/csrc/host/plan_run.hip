@@ -288,10 +288,11 @@ static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* pas
   G2_CHECK(cap_l <= (1L << 26), GPMP2MI_ERR_UNSUPPORTED, "too many problems for one queue run");
   const int cap = (int)cap_l;
 
-  // workspace: busy counter, job / next / act / fresh / qpass [B], head, then the step kernels' n_active / done /
-  // host_flags [cap] (device memory: the host reads k_queue_scan's counts instead)
-  const size_t ints = 5 * (size_t)B + 1 + 3 * (size_t)cap;
-  const size_t bytes = sizeof(long long) + ints * sizeof(int);
+  // workspace: busy counter, job / next / act / fresh / qpass [B], head, then (from the next 8-byte boundary) the step
+  // kernels' pass_word [cap] (64-bit words), n_active / host_flags [cap] (device memory: the host reads k_queue_scan's
+  // counts instead)
+  const size_t slot_ints = (5 * (size_t)B + 1 + 1) & ~(size_t)1;
+  const size_t bytes = sizeof(long long) + slot_ints * sizeof(int) + (size_t)cap * (sizeof(unsigned long long) + 2 * sizeof(int));
   G2_TRY(p->ws[p->WS_QUEUE].reserve(bytes));
   if (p->qflags.cap < cap) {
     flags_release(p->qflags);
@@ -307,12 +308,12 @@ static int plan_queue_impl(gpmp2mi_plan* p, hipStream_t st, QueueRun q, int* pas
   q.qpass = w + 4 * B;
   q.head = w + 5 * B;
   PlanBuffers qb = p->pb;
-  qb.n_active = q.head + 1;
-  qb.done = qb.n_active + cap;
-  qb.host_flags = qb.done + cap;
+  qb.pass_word = (unsigned long long*)(w + slot_ints);
+  qb.n_active = (int*)(qb.pass_word + cap);
+  qb.host_flags = qb.n_active + cap;
   q.flags = p->qflags.dev;
   for (int k = 0; k < cap; k++) p->qflags.host[k] = -1;   // the previous run has drained
-  G2_HIP(hipMemsetAsync(qb.n_active, 0, 3 * (size_t)cap * sizeof(int), st));
+  G2_HIP(hipMemsetAsync(qb.pass_word, 0, (size_t)cap * (sizeof(unsigned long long) + 2 * sizeof(int)), st));
 
   const PlanBuffers& pb = p->pb;
   p->timer.reset();

@@ -312,7 +312,7 @@ __global__ __launch_bounds__(64 * NSPLIT, KIND == GPMP2MI_ROBOT_ARM ? 2 : 1) voi
 // limit / state-prior terms of the states it owns (wavefront 1, from the states in LDS, while wavefront 0 walks the chain).
 // The Gauss-Newton step control reads them (error_from_shares) instead of a sum over k_assemble's blocks.
 template <int AD, int SDIM, int NW>
-__global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __restrict__ Rg, SdfDev sdf,
+__global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(PassConsts pc, const RobotDev* __restrict__ Rg, SdfDev sdf,
                                                                const PlanParams* __restrict__ pp, PlanBuffers pb,
                                                                const double* __restrict__ traj, int bufsel,
                                                                const int* __restrict__ active, double* __restrict__ dst,
@@ -324,12 +324,18 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
   constexpr int ROWS_P = (NW / 2) * rec_lds_stride(RV);  // partial records: NW / 2 buffers of 64 points (rec_pieces.h)
   constexpr int ROWS = (ROWS_F + ROWS_SC > ROWS_P) ? ROWS_F + ROWS_SC : ROWS_P;
   const PlanParams& P = *pp;
-  const int nchunk = P.Ppad / 64;
+  // head: the sizes come with the kernel arguments (pc), and the trajectory's own words -- active, which, stepped -- are
+  // requested together before `active` is tested; the model, the states and the step stay behind that test
+  const int nchunk = pc.Ppad / 64;
   const int b = blockIdx.x / nchunk, chunk = blockIdx.x - b * nchunk;
-  if (active && !active[b]) return;
+  int act = (active ? active : pb.active)[b];
+  int wh = pb.which[b];
+  int stp = pb.stepped[b];
+  head_batch_end(act, wh, stp);
+  if (active && !act) return;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  double* __restrict__ rec = rec_of(pb, pb.which[b], bufsel);
-  double* __restrict__ gpu = gpu_of(pb, pb.which[b], bufsel);
+  double* __restrict__ rec = rec_of(pb, wh, bufsel);
+  double* __restrict__ gpu = gpu_of(pb, wh, bufsel);
   G2_LSTAMP(0);
   __shared__ RobotDev R;
   __shared__ double buf[ROWS][64];                       // [0, ROWS_F) frames, [ROWS_F, ROWS_F + ROWS_SC) sin / cos; later the partial records
@@ -341,8 +347,8 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     rtmp[u] = idx < RN ? reinterpret_cast<const int*>(Rg)[idx] : 0;
   }
   const int p_raw = chunk * 64 + lane;
-  const int p = min(p_raw, P.P - 1);  // tail lanes shadow the last point, their stores are predicated
-  const int N = P.N, I = P.I;
+  const int p = min(p_raw, pc.P - 1);  // tail lanes shadow the last point, their stores are predicated
+  const int N = pc.N, I = pc.I;
   int i = 0, j = I;
   if (p > 0) {
     const int t = p - 1;
@@ -350,15 +356,15 @@ __global__ __launch_bounds__(64 * NW, 3) void k_linearize_arm(const RobotDev* __
     j = t - (i - 1) * (I + 1);
   }
   const bool unary = (j == I);
-  const bool store_ok = p_raw < P.P;
+  const bool store_ok = p_raw < pc.P;
   // ---- the states this workgroup reads: [s0, s1]; through LDS (zn), with the pending step applied in the fused form
   double (*fx)[16] = reinterpret_cast<double (*)[16]>(&buf[0][0]);   // step of the blocks w0 .. w0 + 39 (buf is not in use yet)
   static_assert(FXS * 16 <= ROWS * 64, "the step window lives in the frame buffer");
   __shared__ double zn[ZNS][n];       // states s0 .. s0 + ZNS - 1 (ZNS, FXS: cr_schedule.h)
-  const int p_lo = chunk * 64, p_hi = min(p_lo + 63, P.P - 1);
+  const int p_lo = chunk * 64, p_hi = min(p_lo + 63, pc.P - 1);
   auto state_of = [&](int pt) { return pt == 0 ? 0 : 1 + (pt - 1) / (I + 1); };
   const int s1 = state_of(p_hi), s0 = max(0, state_of(p_lo) - 1), ns = s1 - s0 + 1;   // ns <= ZNS: launch_linearize checks
-  const bool apply = dst != nullptr && pb.stepped[b] == pass;
+  const bool apply = dst != nullptr && stp == pass;
   const bool shares = bufsel == 0 && !trial;
   double* __restrict__ cshare = pb.cshare + ((size_t)b * nchunk + chunk) * 3;
   if (apply) {
@@ -665,9 +671,9 @@ int launch_linearize(const RobotDev& h, const RobotDev* robot, const SdfDev& sdf
   if (hp.lin_split == 4) {
     const dim3 block(256);
     if (sdf.dim == 3) {
-      G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize_arm<AD_, 3, 4><<<grid, block, 0, st>>>(robot, sdf, pb.params, pb, traj, bufsel, active, dst, pass, trial ? 1 : 0)));
+      G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize_arm<AD_, 3, 4><<<grid, block, 0, st>>>(pass_consts(hp), robot, sdf, pb.params, pb, traj, bufsel, active, dst, pass, trial ? 1 : 0)));
     } else {
-      G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize_arm<AD_, 2, 4><<<grid, block, 0, st>>>(robot, sdf, pb.params, pb, traj, bufsel, active, dst, pass, trial ? 1 : 0)));
+      G2_DISPATCH_ROBOT_ARM_ONLY(h.arm_dof, (k_linearize_arm<AD_, 2, 4><<<grid, block, 0, st>>>(pass_consts(hp), robot, sdf, pb.params, pb, traj, bufsel, active, dst, pass, trial ? 1 : 0)));
     }
   } else if (hp.lin_split == 2) {
     const dim3 block(128);

@@ -45,6 +45,20 @@ struct PlanParams {
   double KA[4 * MAXD * MAXD], KB[4 * MAXD * MAXD], KO[4 * MAXD * MAXD];
 };
 
+// What a workgroup of the three pass kernels (k_linearize_arm, k_assemble, k_gn_step_cr) needs before its first
+// data-dependent load, passed BY VALUE in the kernel arguments: the sizes that turn a workgroup index into a trajectory
+// and into addresses, the step rules and the form switches.  Read through `pp`, each of them is a dependent load (kernel
+// arguments -> *pp -> the word) in front of everything else at the head of the kernel.  The launcher fills it from the
+// host copy of PlanParams it is handed; everything else still comes from *pp.
+struct PassConsts {
+  int N, Ppad, P, I, RECS, GPS, Npad;
+  int fuse_finish, split_back, lie;
+  StepRules rules;
+};
+inline PassConsts pass_consts(const PlanParams& hp) {
+  return PassConsts{hp.N, hp.Ppad, hp.P, hp.I, hp.RECS, hp.GPS, hp.Npad, hp.fuse_finish, hp.split_back, hp.lie, hp.rules};
+}
+
 // Extra factors a plan carries as data (gpmp2mi_graph_opts): workspace priors / goal factor and self collision on
 // ranges of support states.  They are unary in x_i, so their J^T J / sigma^2, J^T r / sigma^2, r^T r / sigma^2 are
 // added to the record of the state's unary evaluation point after k_linearize (launch_extra_factors); the solver
@@ -166,7 +180,7 @@ struct PlanBuffers {
   double* cshare;          // [B][Ppad/64][3] per-chunk share of the graph error at `cur`: obstacle, GP prior, priors / limits
                            // (k_linearize_arm, buffer 0 only; summed by error_from_shares)
   int* n_active;           // [max_pass] trajectories that iterated in each pass
-  int* done;               // [max_pass] workgroups of the pass-closing kernel that have finished
+  unsigned long long* pass_word;  // [max_pass] arrivals of the pass-closing kernel's workgroups and their count (pass_counter.h)
   int* host_flags;         // [max_pass] pinned, device-mapped: n_active[pass] once the pass is complete, else -1
   unsigned long long* stamps;  // [B][64] s_memtime stamps (diagnostic builds only)
 };

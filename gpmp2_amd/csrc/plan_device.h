@@ -2,6 +2,7 @@
 // a trial step.  The step-control rules themselves are in step_control.h.
 #pragma once
 #include "device_math.h"
+#include "pass_counter.h"
 #include "plan.h"
 #include "tiles.h"
 
@@ -117,16 +118,50 @@ __device__ __forceinline__ bool dogleg_retry(const PlanParams& P, const PlanBuff
   return P.rules.opt_type == GPMP2MI_OPT_DOGLEG && pb.phase[b] != 0;
 }
 
-// Graph error of trajectory b from the per-chunk shares k_linearize_arm left (pb.cshare): chunks in ascending order,
-// obstacle + GP + misc of each, halved.  Uniform loads, every lane forms the same value: no cross-lane step, no barrier.
-__device__ __forceinline__ double error_from_shares(const PlanParams& P, const PlanBuffers& pb, int b) {
-  const int nchunk = P.Ppad / 64;
-  const double* __restrict__ cs = pb.cshare + (size_t)b * nchunk * 3;
-  double acc = 0.0;
-  for (int q = 0; q < nchunk; q++) acc += (cs[3 * q] + cs[3 * q + 1]) + cs[3 * q + 2];
-  return 0.5 * acc;
+// End of the batch of loads at the head of a pass kernel.  The loads written above this line are issued above it (the
+// compiler may not sink a load past what might be a store), and the uniform words named here pass through this point
+// together: every use of one of them comes after the arrival of all, so the batch costs one round trip and one wait,
+// whatever order the tests below come in.  (Left to itself the scheduler put the test of `active`, and with it a wait,
+// in front of the request for `which`.)  No instruction of its own.
+__device__ __forceinline__ void head_batch_end(int& a, int& b, int& c) {
+  asm volatile("" : "+s"(a), "+s"(b), "+s"(c)::"memory");
+}
+__device__ __forceinline__ void head_batch_end(int& a, int& b, int& c, int& d) {
+  asm volatile("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d)::"memory");
 }
 
+// Graph error of trajectory b from the per-chunk shares k_linearize_arm left (pb.cshare): chunks in ascending order,
+// (obstacle + GP) + misc of each, halved -- acc = 0; acc += t_q for q = 0 .. nchunk - 1.  In two halves, for the head of a
+// pass kernel.  shares_request: lane q of the calling wavefront asks for the three shares of chunk q -- one batch of
+// vector loads, issued together with the trajectory's other scalars and before any of them is tested.  (As uniform
+// loads in one batch the row took 60 scalar registers and pushed k_gn_step_cr into scratch; as the loop it was before, a
+// chain of dependent loads behind `active`.)  error_from_shares forms t_q in lane q and adds the lanes' values in that
+// order, so every lane holds the same value, with the bits of the plain loop: no barrier.  Chunks past the 64th finish
+// from memory.
+struct ShareHead {
+  double a, g, m;
+};
+__device__ __forceinline__ ShareHead shares_request(const PlanBuffers& pb, int b, int nchunk, int lane) {
+  const double* __restrict__ cs = pb.cshare + ((size_t)b * nchunk + lane) * 3;
+  ShareHead h{0.0, 0.0, 0.0};
+  if (lane < nchunk) {
+    h.a = cs[0];
+    h.g = cs[1];
+    h.m = cs[2];
+  }
+  return h;
+}
+__device__ __forceinline__ double error_from_shares(const ShareHead& h, const PlanBuffers& pb, int b, int nchunk) {
+  const double t = (h.a + h.g) + h.m;
+  const int lo = __double2loint(t), hi = __double2hiint(t);
+  double acc = 0.0;
+  const int nq = min(nchunk, 64);
+  for (int q = 0; q < nq; q++)
+    acc += __hiloint2double(__builtin_amdgcn_readlane(hi, q), __builtin_amdgcn_readlane(lo, q));
+  const double* __restrict__ cs = pb.cshare + (size_t)b * nchunk * 3;
+  for (int q = 64; q < nchunk; q++) acc += (cs[3 * q] + cs[3 * q + 1]) + cs[3 * q + 2];
+  return 0.5 * acc;
+}
 
 // block-wide deterministic sum over the WAVES wavefronts of a workgroup (a wave sum, then the per-wave partials in
 // wave order); every thread returns the total.  red: WAVES doubles of LDS.
@@ -222,12 +257,20 @@ __device__ __forceinline__ void trial_step_tail(const PlanParams& P, const PlanB
 
 // Called by one thread of every workgroup of the kernel that closes a pass, after its own work: the last
 // workgroup to arrive publishes the pass's active count to the host-mapped flag array, so the host
-// driver learns it without a copy command or an event in the stream.
-__device__ __forceinline__ void publish_pass_count(const PlanBuffers& pb, int pass) {
-  __threadfence();
-  if (atomicAdd(pb.done + pass, 1) == (int)gridDim.x - 1) {
-    const int v = atomicAdd(pb.n_active + pass, 0);
-    __hip_atomic_store(pb.host_flags + pass, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+// driver learns it without a copy command or an event in the stream.  `continues`: 1 when the workgroup's trajectory
+// keeps iterating.
+// Arrival and count travel in one word (pass_counter.h), added to with one relaxed device-scope atomic: the add that
+// returns grid - 1 earlier arrivals also returns their counts, so there is a single location and nothing to order --
+// no fence in any workgroup.  The flag store is system scope because the host polls it, but it releases no data: the
+// host uses the count only to decide what to enqueue next on the same stream, where stream order makes this kernel's
+// writes visible to the next one, and it reads results only after hipStreamSynchronize.
+__device__ __forceinline__ void publish_pass_count(const PlanBuffers& pb, int pass, int continues) {
+  const unsigned long long before = __hip_atomic_fetch_add(pb.pass_word + pass, (unsigned long long)pass_arrival(continues),
+                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (pass_arrived_last(before, (int)gridDim.x)) {
+    const int v = pass_count(before, continues);
+    pb.n_active[pass] = v;
+    __hip_atomic_store(pb.host_flags + pass, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 

@@ -149,7 +149,10 @@ __global__ __launch_bounds__(256) void k_plan_reset(const PlanParams* __restrict
     const size_t tot = B * (size_t)(P.N + 1) * P.n;
     for (size_t k = tid; k < tot; k += nth) pb.cur[k] = start[k];
   }
-  for (size_t k = tid; k < (size_t)P.max_pass; k += nth) pb.n_active[k] = pb.done[k] = 0;
+  for (size_t k = tid; k < (size_t)P.max_pass; k += nth) {
+    pb.n_active[k] = 0;
+    pb.pass_word[k] = 0;
+  }
   for (size_t k = tid; k < B * SC_COUNT; k += nth) pb.scal[k] = 0.0;
   for (size_t k = tid; k < B * (size_t)(P.rules.max_iter + 1); k += nth) pb.trace[k] = __longlong_as_double(0x7ff8000000000000LL);
   for (size_t b = tid; b < B; b += nth) reset_slot(P, pb, b);
@@ -173,14 +176,15 @@ int launch_plan_reset(const PlanParams& hp, const PlanBuffers& pb, const double*
 // followed by the do/while of gpmp2::optimize (checkConvergence, max_iter, no-increase rollback).
 // The rules themselves are the pure functions of step_control.h; the first lane loads the trajectory's scalars, calls
 // them and stores what changed.
-__device__ __forceinline__ void decide_body(const PlanParams& P, const PlanBuffers& pb, int pass, int init) {
+// Returns 1 when the trajectory keeps iterating (uniform over the workgroup): its share of the pass's count.
+__device__ __forceinline__ int decide_body(const PlanParams& P, const PlanBuffers& pb, int pass, int init) {
   // 4 wavefronts: all of them sum the graph error of the point in question (fixed-order block reduction),
   // the first thread takes the decision, all four wavefronts then move the trajectories
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const bool w0 = tid < 64;
   __shared__ int dec[2];
   __shared__ double red[4];
-  if (!pb.active[b]) return;
+  if (!pb.active[b]) return 0;
   const int N = P.N, n = P.n;
   const size_t tsz = (size_t)(N + 1) * n;
   double* cur = pb.cur + b * tsz;
@@ -339,14 +343,12 @@ __device__ __forceinline__ void decide_body(const PlanParams& P, const PlanBuffe
   } else if (action == 2) {
     for (size_t k = tid; k < tsz; k += blockDim.x) result[k] = last[k];
   }
-  if (tid == 0) {
-    if (action != 0) pb.active[b] = 0;
-    else atomicAdd(pb.n_active + pass, 1);
-  }
+  if (tid == 0 && action != 0) pb.active[b] = 0;
+  return action == 0;
 }
 __global__ __launch_bounds__(256) void k_decide(const PlanParams* __restrict__ pp, PlanBuffers pb, int pass, int init) {
-  decide_body(*pp, pb, pass, init);
-  if (threadIdx.x == 0) publish_pass_count(pb, pass);
+  const int continues = decide_body(*pp, pb, pass, init);
+  if (threadIdx.x == 0) publish_pass_count(pb, pass, continues);
 }
 
 int launch_decide(const PlanParams& hp, const PlanBuffers& pb, int pass, bool init, hipStream_t st) {
